@@ -21,6 +21,9 @@ Prints ONE JSON line (rank 0) with the contract fields plus
   step_ms      median / min / max of the K timed steps (HIP events between steps) and value_median = the metric on the median
   clock_mhz    shader clock sampled from sysfs during the timed region (the convolution phase runs power-limited)
   at N > 1: rank_ms_per_step (min / max over ranks) and no_gather (the same loop without the RCCL all_gather of the outputs)
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, for output-for-output comparisons of two
+builds: inputs and weights come from fixed seeds, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -38,6 +41,7 @@ sys.path.insert(0, ROOT)
 FP32_MATRIX_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 BF16_MATRIX_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: v_mfma_f32_32x32x16_bf16, dense
 HBM_PEAK_GBS = 8000.0
+DUMP_BYTES = 64_000_000           # --dump-outputs: bytes of all .npy files together, headers included
 
 
 def synth_batch(b, k, lr, seed):
@@ -195,6 +199,35 @@ def train_step_figure(args, dist_on, rank):
                 workload=f'configs[2] per-GPU shape: 5-ref training step (extractor + matching frozen, net_g fwd + L1 + bwd + 4-group Adam), '
                          f'B=4 per GPU, LR 40x40 -> 160x160, fp32{", DistributedDataParallel(net_g) over RCCL" if dist_on else ""}',
                 parallelism=f'ddp{world}' if dist_on else 'dp1')
+
+
+def last_step_outputs(model, args):
+    """what a caller of the timed step receives, copied to the host: infer -> the 4x output and the match indices of
+    model.test(); train -> the same of the step's forward, its L1 loss and net_g's parameters after the Adam step (concatenated
+    in state-dict order).  float32 stays float32; indices and the loss as float64 (exact)."""
+    out = dict(output=model.output.detach().float().cpu().numpy(),
+               match_idx=model.max_idx.detach().double().cpu().numpy())
+    if args.mode == 'train':
+        import numpy as np
+        out['loss'] = np.array(model.get_current_log()['l_g_pix'], dtype=np.float64)
+        params = model.get_bare_model(model.net_g).parameters()
+        out['net_g_params'] = torch.cat([p.detach().reshape(-1).float() for p in params]).cpu().numpy()
+    return out
+
+
+def dump_outputs(arrays, out_dir):
+    """DIR/<name>.npy per array.  When they do not fit in DUMP_BYTES together, each keeps the same share of its flattened
+    elements, at positions drawn once from a fixed seed (sorted): the same arguments give the same sample."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_BYTES - 256 * len(arrays)   # (an .npy header is 128 bytes)
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > budget:
+            keep = max(1, a.size * budget // total)
+            pos = np.sort(np.random.default_rng(i).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def spawn_ranks_if_needed(args):
@@ -507,7 +540,11 @@ def main():
     ap.add_argument('--no-train-step', action='store_true', help='skip the training-step figure (train_step on the JSON line) after the inference loop')
     ap.add_argument('--train-steps', type=int, default=10, help='timed training steps of the train_step figure')
     ap.add_argument('--no-gather', action='store_true', help='N > 1: leave the RCCL all_gather of the outputs out of the step (the line then carries only that figure)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed (rank 0) as DIR/<name>.npy, '
+                                                          f'float32 / float64, {DUMP_BYTES // 10**6} MB at most (a fixed sample beyond that)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     spawn_ranks_if_needed(args)   # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (before any GPU call)
     if args.graph:
         os.environ['MREFSR_TRAIN_GRAPH' if args.mode == 'train' else 'MREFSR_GRAPH'] = '1'
@@ -586,6 +623,8 @@ def main():
     hip.set_kernel_timing(True)
     with ClockSampler(local_rank) as clock:
         elapsed, elapsed_mine, step_ms = timed_region(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:   # now: the passes below overwrite model.output
+        dump_outputs(last_step_outputs(model, args), args.dump_outputs)
     rank_elapsed = None
     if dist_on:
         t = torch.tensor([elapsed_mine], device='cuda', dtype=torch.float64)

@@ -217,65 +217,89 @@ def test_state_dict_keys_match_reference(golden):
         assert mine == spec_from(g, name + '_'), name  # same keys, same shapes, same order
 
 
-def test_compat_installs_into_reference_registries():
-    """with the reference importable (build container only): our classes replace the registry slots
-    train.py / test.py resolve by name"""
-    import _refimport as R
-    if not R.available():
-        pytest.skip('reference tree not present on this machine')
-    R.install()
-    import mrefsr_amd.compat as compat
-    from basicsr.utils.registry import ARCH_REGISTRY as REF
-    assert compat.install_into_basicsr(ops=False, mmcv=False)
-    from mrefsr_amd.archs.ref_mrapa_restoration_arch import MRAPARestorationNet
-    assert REF.get('MRAPARestorationNet') is MRAPARestorationNet
+_HOST_ARCHS = ('MRAPARestorationNet', 'RestorationNet', 'CorrespondenceGenerationArch', 'ContrasMultiExtractorSep',
+               'ContrasExtractorSep', 'VGGFeatureExtractor')
+_HOST_MODELS = ('MultiRefRestorationModel', 'RefRestorationModel')
+
+
+@pytest.fixture
+def host_basicsr():
+    """a stand-in for the ``basicsr`` package compat installs into (the reference's; not part of this repository): its two
+    registries with the reference's lookup contract (mrefsr_amd/utils/registry.py restates it), every slot compat replaces
+    already taken -- the host's arch / model modules register their classes at import --, no mmcv; sys.modules restored after"""
     import sys
-    net = sys.modules['basicsr.archs'].build_network(dict(type='MRAPARestorationNet', ngf=64, n_blocks=16, groups=8))
+    import types
+    from mrefsr_amd.utils.registry import Registry
+
+    def host_keys():
+        return [k for k in sys.modules if k.split('.')[0] in ('basicsr', 'mmcv')]
+    saved = {k: sys.modules.pop(k) for k in host_keys()}
+    reg = types.ModuleType('basicsr.utils.registry')
+    reg.ARCH_REGISTRY, reg.MODEL_REGISTRY = Registry('arch'), Registry('model')
+    for registry, names in ((reg.ARCH_REGISTRY, _HOST_ARCHS), (reg.MODEL_REGISTRY, _HOST_MODELS)):
+        for name in names:
+            registry.register(type(name, (), {}))
+    for name in ('basicsr', 'basicsr.utils', 'basicsr.ops'):
+        sys.modules[name] = types.ModuleType(name)
+        sys.modules[name].__path__ = []
+    sys.modules['basicsr.utils.registry'] = reg
+    try:
+        yield reg
+    finally:
+        for k in host_keys():
+            del sys.modules[k]
+        sys.modules.update(saved)
+
+
+def test_compat_installs_into_reference_registries(host_basicsr):
+    """our classes replace the registry slots train.py / test.py resolve by name"""
+    import mrefsr_amd.compat as compat
+    from mrefsr_amd.archs import ARCH_REGISTRY
+    from mrefsr_amd.archs.ref_mrapa_restoration_arch import MRAPARestorationNet
+    from mrefsr_amd.models import MODEL_REGISTRY
+    assert compat.install_into_basicsr(ops=False, mmcv=False)
+    REF = host_basicsr.ARCH_REGISTRY
+    assert REF.get('MRAPARestorationNet') is MRAPARestorationNet
+    for name in _HOST_ARCHS:
+        assert REF.get(name) is ARCH_REGISTRY.get(name), name
+    for name in _HOST_MODELS:
+        assert host_basicsr.MODEL_REGISTRY.get(name) is MODEL_REGISTRY.get(name), name
+    net = REF.get('MRAPARestorationNet')(ngf=64, n_blocks=16, groups=8)   # what the host's build_network does with the type name
     assert isinstance(net, MRAPARestorationNet)
 
 
-def test_compat_mmcv_shim_builds_the_reference_dynagg():
-    """install_into_basicsr(ops=True, mmcv=True): the REFERENCE's own DynAgg (a subclass of mmcv.ops.ModulatedDeformConv2d,
-    ref_mrapa_restoration_arch.py:11-43) constructs on the shim and finds every attribute it reads (deform_groups, ...)"""
-    import importlib
+def test_compat_mmcv_shim_builds_the_reference_dynagg(host_basicsr):
+    """install_into_basicsr(ops=True, mmcv=True): the import the reference's arch files make (``from mmcv.ops import
+    ModulatedDeformConv2d, modulated_deform_conv2d``) resolves to the shim, and a DynAgg-style subclass (mmcv's DCNv2 pack
+    pattern: the super().__init__ signature, a zero-initialised conv_offset_mask sized from deform_groups and kernel_size)
+    constructs on it and finds every attribute it reads; basicsr.ops.* are the mrefsr_amd modules"""
     import sys
-    import _refimport as R
-    if not R.available():
-        pytest.skip('reference tree not present on this machine')
-    R.install()
+    from torch import nn
     import mrefsr_amd.compat as compat
-    saved = {k: sys.modules.pop(k) for k in list(sys.modules) if k == 'mmcv' or k.startswith('mmcv.')}
-    saved_ops = {k: sys.modules.get(k) for k in ('basicsr.ops.dcn', 'basicsr.ops.fused_act', 'basicsr.ops.upfirdn2d', 'basicsr.ops.dcn.deform_conv_ext')}
-    ref_arch = sys.modules.pop('basicsr.archs.ref_mrapa_restoration_arch', None)
-    try:
-        assert compat.install_into_basicsr(models=False, ops=True, mmcv=True)
-        assert sys.modules['mmcv.ops'].ModulatedDeformConv2d is compat.ModulatedDeformConv2d
-        from basicsr.utils.registry import ARCH_REGISTRY as REF
-        REF._obj_map.pop('MRAPARestorationNet', None)        # the reference module registers its classes at import
-        m = importlib.import_module('basicsr.archs.ref_mrapa_restoration_arch')
-        agg = m.DynAgg(64, 64, 3, stride=1, padding=1, dilation=1, deform_groups=8, extra_offset_mask=True)
-        assert isinstance(agg, compat.ModulatedDeformConv2d) and agg.deform_groups == 8
-        assert tuple(agg.conv_offset_mask.weight.shape) == (216, 64, 3, 3) and float(agg.conv_offset_mask.weight.abs().sum()) == 0.0
-        assert tuple(agg.weight.shape) == (64, 64, 3, 3) and agg.bias is not None
-        assert m.modulated_deform_conv2d is compat.modulated_deform_conv2d
-        import mrefsr_amd.ops.dcn.deform_conv_ext as ext
-        assert sys.modules['basicsr.ops.dcn.deform_conv_ext'] is ext
-        for name in ('deform_conv_forward', 'deform_conv_backward_input', 'deform_conv_backward_parameters',
-                     'modulated_deform_conv_forward', 'modulated_deform_conv_backward'):   # deform_conv_ext.cpp:150-164
-            assert callable(getattr(ext, name))
-    finally:
-        for k in [k for k in sys.modules if k == 'mmcv' or k.startswith('mmcv.')]:
-            del sys.modules[k]
-        sys.modules.update(saved)
-        for k, v in saved_ops.items():
-            if v is None:
-                sys.modules.pop(k, None)
-            else:
-                sys.modules[k] = v
-        sys.modules.pop('basicsr.archs.ref_mrapa_restoration_arch', None)
-        if ref_arch is not None:
-            sys.modules['basicsr.archs.ref_mrapa_restoration_arch'] = ref_arch
-        compat.install_into_basicsr(ops=False, mmcv=False)
+    assert compat.install_into_basicsr(models=False, ops=True, mmcv=True)
+    from mmcv.ops import ModulatedDeformConv2d, modulated_deform_conv2d
+    assert ModulatedDeformConv2d is compat.ModulatedDeformConv2d and modulated_deform_conv2d is compat.modulated_deform_conv2d
+
+    class DynAgg(ModulatedDeformConv2d):
+        def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, deform_groups=1):
+            super().__init__(in_channels, out_channels, kernel_size, stride, padding, dilation, groups, deform_groups)
+            self.conv_offset_mask = nn.Conv2d(self.in_channels, self.deform_groups * 3 * self.kernel_size[0] * self.kernel_size[1],
+                                              kernel_size=self.kernel_size, stride=self.stride, padding=self.padding,
+                                              dilation=self.dilation, bias=True)
+            self.conv_offset_mask.weight.data.zero_()
+            self.conv_offset_mask.bias.data.zero_()
+
+    agg = DynAgg(64, 64, 3, stride=1, padding=1, dilation=1, deform_groups=8)
+    assert isinstance(agg, compat.ModulatedDeformConv2d) and agg.deform_groups == 8 and agg.groups == 1
+    assert tuple(agg.conv_offset_mask.weight.shape) == (216, 64, 3, 3) and float(agg.conv_offset_mask.weight.detach().abs().sum()) == 0.0
+    assert tuple(agg.weight.shape) == (64, 64, 3, 3) and agg.bias is not None
+    import mrefsr_amd.ops.dcn.deform_conv_ext as ext
+    from mrefsr_amd.ops import dcn, fused_act, upfirdn2d
+    assert sys.modules['basicsr.ops.dcn.deform_conv_ext'] is ext and sys.modules['basicsr.ops.dcn'] is dcn
+    assert sys.modules['basicsr.ops.fused_act'] is fused_act and sys.modules['basicsr.ops.upfirdn2d'] is upfirdn2d
+    for name in ('deform_conv_forward', 'deform_conv_backward_input', 'deform_conv_backward_parameters',
+                 'modulated_deform_conv_forward', 'modulated_deform_conv_backward'):   # deform_conv_ext.cpp:150-164
+        assert callable(getattr(ext, name))
 
 
 def test_sample_patches_is_the_reference_unfold():

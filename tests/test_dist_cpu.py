@@ -165,3 +165,46 @@ def test_bench_line_of_an_n_gpu_run_is_assembled_as_the_contract_says():
     one = bench.assemble_line(args, 1, elapsed, step_ms, None, [31.0] * 5, detail, None, None, None, None, None)
     assert one['n_gpus'] == 1 and abs(one['value'] - 8 * 640 * 640 / 1e6 * 5 / 1.25) < 1e-3 and one['config']['baseline_config'] == 'configs[1]'
     assert 'rank_ms_per_step' not in one and 'rccl' not in one and 'no_gather' not in one
+
+
+def test_bench_dump_outputs_of_the_last_step(tmp_path):
+    """--dump-outputs: the infer step's output and match indices as float32 / float64 .npy files, whole when they fit; the train
+    step adds the loss and net_g's parameters; beyond DUMP_BYTES every array keeps the same fixed sample on every run"""
+    import types
+
+    import numpy as np
+
+    import bench
+    out = torch.rand(2, 3, 16, 16)
+    idx = torch.randint(0, 196, (2, 14, 14))
+    net = torch.nn.Linear(4, 3)
+    model = types.SimpleNamespace(output=out, max_idx=idx, net_g=net, get_bare_model=lambda m: m,
+                                  get_current_log=lambda: {'l_g_pix': 0.25})
+    arrays = bench.last_step_outputs(model, types.SimpleNamespace(mode='infer'))
+    assert sorted(arrays) == ['match_idx', 'output']
+    bench.dump_outputs(arrays, str(tmp_path / 'whole'))
+    got = np.load(tmp_path / 'whole' / 'output.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, out.numpy())
+    got = np.load(tmp_path / 'whole' / 'match_idx.npy')
+    assert got.dtype == np.float64 and np.array_equal(got, idx.numpy())
+    arrays = bench.last_step_outputs(model, types.SimpleNamespace(mode='train'))
+    assert float(arrays['loss']) == 0.25 and arrays['loss'].dtype == np.float64
+    assert np.array_equal(arrays['net_g_params'], torch.cat([net.weight.reshape(-1), net.bias]).detach().numpy())
+    big = dict(output=np.random.default_rng(5).random(3 * 10**6, dtype=np.float32).reshape(3, 1000, 1000),
+               match_idx=np.arange(10**6, dtype=np.float64))          # 20 MB
+    old = bench.DUMP_BYTES
+    try:
+        bench.DUMP_BYTES = 8_000_000
+        for run in ('a', 'b'):
+            bench.dump_outputs(big, str(tmp_path / run))
+    finally:
+        bench.DUMP_BYTES = old
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert files == ['match_idx.npy', 'output.npy']
+    assert sum(os.path.getsize(tmp_path / 'a' / f) for f in files) <= 8_000_000
+    for f in files:
+        a, b = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert a.size > 0 and np.array_equal(a, b)
+    s = np.load(tmp_path / 'a' / 'match_idx.npy')            # positions of the sample, in order, without repeats
+    assert (np.diff(s) > 0).all() and np.isin(s, big['match_idx']).all()
+    assert np.isin(np.load(tmp_path / 'a' / 'output.npy'), big['output']).all()
