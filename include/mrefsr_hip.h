@@ -501,6 +501,58 @@ int mrefsr_mrattn_bwd_nhwc_f32(const float *q, const float *emb, const float *as
 int mrefsr_attn_modulate_bwd_f32(const float *g, const float *refs, const float *mul, float *g_refs, float *g_mul, int64_t n,
                                  mrefsr_stream_t stream);
 
+/* ---- perceptual / style loss of the training step (PerceptualLoss, basicsr/models/losses.py:141-238, under
+ * multi_ref_restoration_model.py:237-279): the VGG19 node of mrefsr_amd/archs/nhwc_train.py.  Channels-last [N][H][W][C]
+ * fp32 tensors, C % 4 == 0.
+ *
+ * mrefsr_maxpool2_nhwc_f32: MaxPool2d(2, 2) (floor sizes: out [N][H/2][W/2][C]); within a window (0,0) (0,1) (1,0) (1,1) the
+ *   first maximum wins (torch's max_pool2d, bit for bit).  relu = 1 pools max(x, 0) (a pre-activation map whose ReLU was not
+ *   stored).  plane (may be NULL): one byte per output element, bits 0-1 the arg-max, bit 2 = (max > 0).
+ * mrefsr_maxpool2_bwd_nhwc_f32: g [N][H/2][W/2][C] -> g_in [N][H][W][C] (every element written; the floored last row / column
+ *   of an odd map gets 0): g goes to the arg-max (from plane, else recomputed from x with the same rule), times the ReLU
+ *   derivative (max > 0) when mask = 1.  amax (may be NULL, zero-initialised): max(amax, max |g_in|), the input scale of the
+ *   fp16-split input-gradient convolution that follows (as mrefsr_act_bwd_nhwc_f32). */
+int mrefsr_maxpool2_nhwc_f32(const float *x, float *out, uint8_t *plane, int N, int H, int W, int C, int relu, mrefsr_stream_t stream);
+int mrefsr_maxpool2_bwd_nhwc_f32(const float *g, const float *x, const uint8_t *plane, float *g_in, float *amax, int N, int H, int W, int C,
+                                 int relu, int mask, mrefsr_stream_t stream);
+/* mrefsr_tap_crit_f32: criterion of up to MREFSR_TAP_MAX_JOBS taps in one launch (+ a one-block second stage).
+ *   crit 0: l1 = mean |x - y| (nn.L1Loss()), 1: fro = ||x - y||_F (torch.norm(p='fro')).  Job j: x, y [n] (n % 4 == 0, 16-byte
+ *   aligned), weight = w_k, group 0 / 1 (perceptual / style total).
+ *   partial (may be NULL when no loss is wanted): mrefsr_tap_crit_workspace_bytes; the sums are formed in a fixed order (double,
+ *   no atomics): two calls give the same bits.  losses[j] (may be NULL) = the criterion of job j; totals[g] (may be NULL) =
+ *   (sum over the jobs of group g, in order, of losses[j] * w_k) * loss_weight_g.
+ *   grad (per job, may be NULL): d total / d x with torch's autograd arithmetic, times gup[group] (device, NULL = 1):
+ *   l1: ((gup * loss_weight) * w_k) * inv_n * sgn(x - y) (inv_n = 1.0f / n), fro: (x - y) * (((gup * loss_weight) * w_k) / norms[j])
+ *   (norms = the losses of the forward; 0 where the norm is 0); accumulate = 1 adds it to grad.  amax (may be NULL): max |grad|. */
+#define MREFSR_TAP_MAX_JOBS 16
+typedef struct {
+    const float *x, *y;
+    float *grad;
+    int64_t n;
+    float inv_n, weight;
+    int group;
+} mrefsr_tap_job;
+int mrefsr_tap_crit_blocks(int64_t n);
+int mrefsr_tap_crit_workspace_bytes(const mrefsr_tap_job *jobs, int n_jobs);
+int mrefsr_tap_crit_f32(const mrefsr_tap_job *jobs, int n_jobs, int crit, float loss_weight0, float loss_weight1, const float *gup,
+                        const float *norms, int accumulate, double *partial, float *losses, float *totals, float *amax,
+                        mrefsr_stream_t stream);
+/* mrefsr_gram_nhwc_f32: gram[n] = F_n^T F_n / (C HW) for f [N][HW][C] (C a multiple of 64) -> gram [N][C][C] (exactly symmetric):
+ *   exact f32 products on v_mfma_f32_16x16x4_f32, upper 64 x 64 tiles only, split over the pixels into mrefsr_gram_splits parts
+ *   whose partial tiles (workspace, mrefsr_gram_workspace_bytes) are added in a fixed order.
+ * mrefsr_gram_bwd_nhwc_f32: df[n] (+)= (2 / (C HW)) F_n S_n with S = d style / d gram(x) of an l1 style term formed inside:
+ *   S = sgn(gx - gg) * ((gup * loss_weight) * weight) / (N C C)  (gx, gg [N][C][C]; gup device, NULL = 1); accumulate = 1 adds to
+ *   df [N][HW][C]; amax (may be NULL): max |df|. */
+int mrefsr_gram_splits(int N, int HW, int C);
+int64_t mrefsr_gram_workspace_bytes(int N, int HW, int C);
+int mrefsr_gram_nhwc_f32(const float *f, int N, int HW, int C, float *gram, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_gram_bwd_nhwc_f32(const float *f, const float *gx, const float *gg, float *df, int N, int HW, int C, const float *gup,
+                             float loss_weight, float weight, int accumulate, float *amax, mrefsr_stream_t stream);
+/* gradient of mrefsr_image_to_nhwc4_f32: g4 [N][HW][ld] (channels 0..2 read) -> g_img [N][3][HW] = g / std3[c] (std3 may be NULL),
+ * then * 0.5 when range_norm -- torch's backward of (x + 1) * 0.5 and (x - mean) / std, bit for bit. */
+int mrefsr_image_to_nhwc4_bwd_f32(const float *g4, int ld, float *g_img, int64_t N, int64_t HW, int range_norm, const float *std3,
+                                  mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -28,6 +28,12 @@ class ConvPackJob(C.Structure):
                 ('Cin', C.c_int32), ('ksize', C.c_int32), ('terms', C.c_int32), ('flip', C.c_int32), ('wscale', C.c_float)]
 
 
+class TapJob(C.Structure):
+    """mirror of mrefsr_tap_job"""
+    _fields_ = [('x', C.c_void_p), ('y', C.c_void_p), ('grad', C.c_void_p), ('n', C.c_int64), ('inv_n', C.c_float), ('weight', C.c_float),
+                ('group', C.c_int32)]
+
+
 # name -> (restype, argtypes): exactly the declarations of include/mrefsr_hip.h
 SIGNATURES = {
     'mrefsr_abi_version': (_i, []),
@@ -88,6 +94,16 @@ SIGNATURES = {
     'mrefsr_bias_relu_pool2_f32': (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp]),
     'mrefsr_image_to_nhwc4_f32': (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
     'mrefsr_weights_checksum': (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    'mrefsr_maxpool2_nhwc_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'mrefsr_maxpool2_bwd_nhwc_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mrefsr_tap_crit_blocks': (_i, [_i64]),
+    'mrefsr_tap_crit_workspace_bytes': (_i, [C.POINTER(TapJob), _i]),
+    'mrefsr_tap_crit_f32': (_i, [C.POINTER(TapJob), _i, _i, _f, _f, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    'mrefsr_gram_splits': (_i, [_i, _i, _i]),
+    'mrefsr_gram_workspace_bytes': (_i64, [_i, _i, _i]),
+    'mrefsr_gram_nhwc_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    'mrefsr_gram_bwd_nhwc_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp]),
+    'mrefsr_image_to_nhwc4_bwd_f32': (_i, [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp]),
     'mrefsr_upfirdn2d_f32': (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     'mrefsr_upfirdn2d': (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
 }

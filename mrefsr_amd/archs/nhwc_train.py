@@ -15,6 +15,8 @@ same graph is recorded over [N,H,W,C] tensors with one autograd node per FUSED l
                  -- backward: HIP im2col / col2im + two library GEMMs (ops/dcn/deform_conv.py)
   _Attention     mrefsr_mrattn_fwd_nhwc_f32 / mrefsr_mrattn_bwd_nhwc_f32 (softmax recomputed, nothing extra saved)
   _Modulate      refs * sigmoid(mul) * 2 + add, one pass each way
+  _VggLoss       the VGG of PerceptualLoss (losses/): output and GT as one batch forward, input gradients of the output image
+                 backward (csrc/percep.hip: pooling, tap criterion, Gram matrices, image packing backward)
 
 Arithmetic: forward and input-gradient convolutions run the bf16 three-term split (terms 6: fp32-equivalent, no range
 limit -- gradients of 1e-8 would be flushed by the fp16 two-term split -- and no host synchronisation when the weights are
@@ -564,6 +566,212 @@ class _Modulate(Function):
         refs, mul = ctx.saved_tensors
         g = g.contiguous()
         return hip.attn_modulate_bwd(g, refs, mul) + (g,)
+
+
+# ---- perceptual / style loss (PerceptualLoss, losses.py:141-238 of the reference model's loss module) ----------------------------
+# Packed copies of the frozen VGG weights: the perceptual VGG is never stepped, so its copies stay out of the per-step multi-tensor
+# refresh (begin_step) and are re-made only when a parameter's version moves (load_state_dict).
+_frozen = {}
+POOL_PLANE = os.environ.get('MREFSR_PERCEP_POOL_PLANE', '0') == '1'   # 1: the forward stores the pool's arg-max plane
+KEEP_TAPS = None   # tests/ set a list: every _VggLoss forward appends its [2B,h,w,c] tap features (sign decisions against fp64)
+
+
+def _frozen_pack(weight, cin_slice, terms, dgrad, wscale):
+    import weakref
+    key = (weight.data_ptr(), weight.numel(), cin_slice, terms, dgrad, wscale)
+    hit = _frozen.get(key)
+    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
+        return hit[2]
+    for k in [k for k, v in _frozen.items() if v[0]() is None]:
+        del _frozen[k]
+    pw = hip.conv_pack_view(weight.detach(), cin_slice, terms, dgrad=dgrad, wscale=wscale)
+    _frozen[key] = (weakref.ref(weight), weight._version, pw)
+    return pw
+
+
+def _vgg_pack(weight, cin_slice, dgrad):
+    """(packed operator, terms) of a frozen VGG convolution: the engine's training arithmetic (forward: FWD_TERMS, input gradient:
+    BWD_TERMS, both with the cached fp16 weight scale; the range-free split inside hip.range_free())"""
+    want16 = (BWD_TERMS == 16 and not hip.is_range_free()) if dgrad else _fwd_terms() == 16
+    if want16:
+        ws = _wscale(weight)
+        if ws is not None:
+            return _frozen_pack(weight, cin_slice, 16, dgrad, ws), 16
+    return _frozen_pack(weight, cin_slice, TERMS, dgrad, 1.0), TERMS
+
+
+class VggLossPlan:
+    """The tapped VGG stack of a PerceptualLoss as a list of convolution layers, each with the names of its ReLU / pool (if the
+    stack reaches them) and which of conv / relu / pool are tapped: what _VggLoss runs"""
+
+    def __init__(self, vgg_net, layer_weights, criterion, perceptual_weight, style_weight, norm_img):
+        from torch import nn
+        items = list(vgg_net._modules.items())
+        self.layers = []
+        for name, mod in items:
+            if isinstance(mod, nn.Conv2d):
+                self.layers.append(dict(conv=mod, names={'conv': name}))
+            elif isinstance(mod, nn.ReLU):
+                self.layers[-1]['names']['relu'] = name
+            elif isinstance(mod, nn.MaxPool2d):
+                self.layers[-1]['names']['pool'] = name
+            else:
+                raise NotImplementedError(f'perceptual loss: VGG layer {name} ({type(mod).__name__}) has no kernel here')
+        self.taps = []   # (layer index, 'conv' | 'relu' | 'pool', weight) in network order
+        for i, l in enumerate(self.layers):
+            for kind in ('conv', 'relu', 'pool'):
+                nm = l['names'].get(kind)
+                if nm is not None and nm in layer_weights:
+                    self.taps.append((i, kind, float(layer_weights[nm])))
+        if len(self.taps) != len(layer_weights) or len(self.taps) > 8:   # (perceptual + style jobs of one criterion launch: <= 16)
+            raise NotImplementedError(f'perceptual loss: layer_weights {sorted(layer_weights)} (at most 8 taps, all inside the VGG stack)')
+        self.crit, self.pw, self.sw, self.norm_img = criterion, float(perceptual_weight), float(style_weight), bool(norm_img)
+
+
+class _VggLoss(Function):
+    """(output x, gt) -> [perceptual total, style total] of PerceptualLoss with one VGG: the output and the GT run as ONE 2B batch
+    through the convolution kernels (the same arithmetic for both feature sets, half the launches); the backward runs the input
+    gradients of the first B images only (the VGG is frozen: no weight gradients) and returns d loss / d x."""
+
+    @staticmethod
+    def forward(ctx, x, gt, plan, mean, std):
+        b = x.shape[0]
+        img = torch.cat([x.detach(), gt.detach()]).contiguous()
+        h = hip.image_to_nhwc4(img, mean, std, plan.norm_img)
+        saved = []          # per layer: (mask source, its ReLU not applied yet, pool plane, pool input shape)
+        tapv = {}           # (layer, kind) -> [2B,h,w,c] tensor
+        last = len(plan.layers) - 1
+        tapped = {(i, k) for i, k, _ in plan.taps}
+        for i, l in enumerate(plan.layers):
+            conv, names = l['conv'], l['names']
+            relu, pool = 'relu' in names, 'pool' in names
+            tc, tr, tp = (i, 'conv') in tapped, (i, 'relu') in tapped, (i, 'pool') in tapped
+            need_t = tc or not relu
+            need_r = relu and (tr or (not pool and i < last) or not need_t)
+            cout = conv.out_channels
+            bias = conv.bias.detach() if conv.bias is not None else None
+            pk, _ = _vgg_pack(conv.weight, (0, conv.in_channels), False)
+            t = hip.conv_nhwc(h, pk, bias, cout, 3) if need_t else None
+            r = hip.conv_nhwc(h, pk, bias, cout, 3, act=True, slope=0.0) if need_r else None
+            src = r if r is not None else t
+            plane = None
+            if pool:
+                h, plane = hip.maxpool2_nhwc(src, relu=r is None, want_plane=POOL_PLANE)
+            else:
+                h = src
+            saved.append((src if (relu or pool) else None, r is None, plane, tuple(src.shape)))
+            if tc:
+                tapv[(i, 'conv')] = t
+            if tr:
+                tapv[(i, 'relu')] = r
+            if tp:
+                tapv[(i, 'pool')] = h
+        feats = [tapv[(i, k)] for i, k, _ in plan.taps]
+        if KEEP_TAPS is not None:
+            KEEP_TAPS.append(feats)
+        ws = [w for _, _, w in plan.taps]
+        xs, ys, wts, grp = [], [], [], []
+        if plan.pw > 0:
+            xs += [f[:b] for f in feats]
+            ys += [f[b:] for f in feats]
+            wts += ws
+            grp += [0] * len(feats)
+        grams = []
+        if plan.sw > 0:
+            grams = [hip.gram_nhwc(f) for f in feats]
+            xs += [g_[:b] for g_ in grams]
+            ys += [g_[b:] for g_ in grams]
+            wts += ws
+            grp += [1] * len(feats)
+        losses, totals = hip.tap_crit_loss(xs, ys, wts, grp, plan.crit if plan.pw > 0 else 'l1', (plan.pw, plan.sw))
+        ctx.plan, ctx.b, ctx.saved = plan, b, saved
+        ctx.save_for_backward(std, losses, *feats, *grams)
+        return totals
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_tot):
+        plan, b, saved = ctx.plan, ctx.b, ctx.saved
+        st = ctx.saved_tensors
+        std, losses = st[0], st[1]
+        nt = len(plan.taps)
+        feats, grams = st[2:2 + nt], st[2 + nt:]
+        g_tot = g_tot.contiguous()
+        tap_of = {(i, k): j for j, (i, k, _) in enumerate(plan.taps)}
+
+        def add_tap(g, i, kind):
+            """g (None = zero) + the tap's loss gradient; -> (g, max |g|)"""
+            j = tap_of.get((i, kind))
+            if j is None:
+                return g, None
+            f, w = feats[j], plan.taps[j][2]
+            acc = g is not None
+            if g is None:
+                g = torch.empty((b,) + tuple(f.shape[1:]), device=f.device, dtype=torch.float32)
+            amax = None
+            if plan.sw > 0:
+                amax = hip.gram_bwd_nhwc(f[:b], grams[j][:b], grams[j][b:], g, plan.sw, w, gup=g_tot[1:2], accumulate=acc,
+                                         want_amax=plan.pw <= 0)
+                acc = True
+            if plan.pw > 0:
+                amax = hip.tap_crit_grad(f[:b], f[b:], g, w, 0, plan.crit, (plan.pw, plan.sw), gup=g_tot,
+                                         norm=losses[j:j + 1] if plan.crit == 'fro' else None, accumulate=acc)
+            return g, amax
+
+        g, amax, masked = None, None, False
+        for i in reversed(range(len(plan.layers))):
+            l = plan.layers[i]
+            conv, names = l['conv'], l['names']
+            src, relu_in, plane, shape = saved[i]
+            if 'pool' in names:
+                g, a = add_tap(g, i, 'pool')
+                amax = a if a is not None else amax
+                if g is not None:
+                    tr = (i, 'relu') in tap_of
+                    g, amax = hip.maxpool2_bwd_nhwc(g, None if plane is not None else src[:b], plane[:b] if plane is not None else None,
+                                                    relu=relu_in, mask=not tr, shape=(b,) + shape[1:])
+                    if tr:
+                        g, _ = add_tap(g, i, 'relu')
+                        g, _, _, amax = hip.act_bwd_nhwc(g, src[:b], 1, 0.0, want_bias=False, want_amax=True)
+            elif 'relu' in names and not masked:
+                g, a = add_tap(g, i, 'relu')
+                amax = a if a is not None else amax
+                if g is not None:
+                    g, _, _, amax = hip.act_bwd_nhwc(g, src[:b], 1, 0.0, want_bias=False, want_amax=True)
+            g, a = add_tap(g, i, 'conv')
+            amax = a if a is not None else amax
+            if g is None:
+                continue
+            cin = conv.in_channels
+            pk, terms = _vgg_pack(conv.weight, (0, cin), True)
+            masked = False
+            if i == 0:
+                g4 = torch.empty(g.shape[:3] + (4,), device=g.device, dtype=torch.float32)
+                hip.conv_nhwc(g, pk, None, cin, 3, out=g4[..., :cin], in_amax=amax if terms == 16 else None)
+                g_x = hip.image_to_nhwc4_bwd(g4, plan.norm_img, std)
+                return g_x, None, None, None, None
+            prev = plan.layers[i - 1]['names']
+            psrc = saved[i - 1][0]
+            if terms == 16 and 'relu' in prev and 'pool' not in prev and (i - 1, 'relu') not in tap_of and cin % 4 == 0:
+                # the ReLU of the layer below rides on this input-gradient launch (its mask from the stored map), with max |g| of the
+                # result for the next input-gradient convolution (mrefsr_conv_nhwc_bwd_f32)
+                g, _, amax = hip.conv_nhwc_bwd(g, pk, cin, 3, residual=psrc[:b], residual_is_mask=True, in_amax=amax)
+                masked = True
+            else:
+                g = hip.conv_nhwc(g, pk, None, cin, 3, in_amax=amax if terms == 16 else None)
+                amax = None
+        return None, None, None, None, None
+
+
+def perceptual(vgg, x, gt, plan):
+    """PerceptualLoss.forward on the training engine: -> [perceptual total, style total] (a device tensor of 2; autograd reaches x)"""
+    if not (x.is_cuda and gt.is_cuda):
+        raise NotImplementedError('PerceptualLoss: mrefsr_amd has no CPU path (HIP kernels only)')
+    if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.shape != gt.shape or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f'PerceptualLoss: two float32 [N,3,H,W] images expected, got {tuple(x.shape)} / {tuple(gt.shape)}')
+    mean = vgg.mean.contiguous() if vgg.use_input_norm else None
+    std = vgg.std.contiguous() if vgg.use_input_norm else None
+    return _VggLoss.apply(x, gt, plan, mean, std)
 
 
 def recording(*tensors):

@@ -1144,3 +1144,126 @@ def upfirdn2d(x, kernel, up_x, up_y, down_x, down_y, pad_x0, pad_x1, pad_y0, pad
     _lib.call('mrefsr_upfirdn2d', _p(x), _p(kernel), _p(out), mj, ih, iw, mn, kh, kw, up_x, up_y, down_x, down_y,
               pad_x0, pad_x1, pad_y0, pad_y1, _DT[x.dtype], _stream())
     return out
+
+
+# ------------------------------------------------------------------ perceptual / style loss (csrc/percep.hip)
+def maxpool2_nhwc(x, relu=False, want_plane=False):
+    """MaxPool2d(2, 2) of [N,H,W,C] (C % 4 == 0; floor sizes, torch's tie rule); relu: pools max(x, 0).  -> (out [N,H//2,W//2,C],
+    plane uint8 [N,H//2,W//2,C] | None: bits 0-1 arg-max, bit 2 max > 0)"""
+    _chk('maxpool2_nhwc', x)
+    n, h, w, c = x.shape
+    out = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.float32)
+    plane = torch.empty((n, h // 2, w // 2, c), device=x.device, dtype=torch.uint8) if want_plane else None
+    with _timed('maxpool2_nhwc', detail=True, nbytes=4.0 * (x.numel() + out.numel())):
+        _lib.call('mrefsr_maxpool2_nhwc_f32', _p(x), _p(out), _p(plane), n, h, w, c, 1 if relu else 0, _stream())
+    return out, plane
+
+
+def maxpool2_bwd_nhwc(g, x=None, plane=None, relu=False, mask=True, shape=None, want_amax=True):
+    """gradient of [ReLU ->] MaxPool2d(2, 2): g [N,H//2,W//2,C] -> (g_in [N,H,W,C], max |g_in| [1] | None).  The arg-max comes from
+    `plane` (maxpool2_nhwc(want_plane=True)) or is recomputed from the pre-pool map x; mask: times the ReLU derivative.
+    shape = (N, H, W, C) when only the plane is given."""
+    _chk('maxpool2_bwd_nhwc', g, x)
+    if plane is not None and (plane.dtype != torch.uint8 or not plane.is_contiguous() or tuple(plane.shape) != tuple(g.shape)):
+        raise ValueError('maxpool2_bwd_nhwc: plane must be a contiguous uint8 tensor of the pooled shape')
+    n, h, w, c = tuple(x.shape) if x is not None else tuple(shape)
+    if tuple(g.shape) != (n, h // 2, w // 2, c):
+        raise ValueError(f'maxpool2_bwd_nhwc: g {tuple(g.shape)} is not the pooled shape of {(n, h, w, c)}')
+    g_in = torch.empty((n, h, w, c), device=g.device, dtype=torch.float32)
+    amax = zeros_f32(g.device, 1) if want_amax else None
+    with _timed('maxpool2_bwd_nhwc', detail=True, nbytes=4.0 * (g.numel() + g_in.numel() + (x.numel() if plane is None else g.numel() / 4))):
+        _lib.call('mrefsr_maxpool2_bwd_nhwc_f32', _p(g), _p(x), _p(plane), _p(g_in), _p(amax), n, h, w, c, 1 if relu else 0,
+                  1 if mask else 0, _stream())
+    return g_in, amax
+
+
+CRIT = {'l1': 0, 'fro': 1}
+
+
+def _tap_jobs(xs, ys, weights, groups, grads=None):
+    import numpy as np
+    jobs = (_lib.TapJob * len(xs))()
+    for j, (x, y) in enumerate(zip(xs, ys)):
+        _chk('tap_crit', x, y)
+        if x.shape != y.shape:
+            raise ValueError('tap_crit: x / y shapes differ')
+        g = grads[j] if grads is not None else None
+        if g is not None:
+            _chk('tap_crit', g)
+            if g.shape != x.shape:
+                raise ValueError('tap_crit: grad must have the shape of x')
+        n = x.numel()
+        jobs[j] = _lib.TapJob(x.data_ptr(), y.data_ptr(), 0 if g is None else g.data_ptr(), n, float(np.float32(1.0) / np.float32(n)),
+                              float(weights[j]), int(groups[j]))
+    return jobs
+
+
+def tap_crit_loss(xs, ys, weights, groups, crit, loss_weights):
+    """criterion of several taps in one launch pair, fixed summation order: -> (losses [J] = l1 mean |x - y| or fro ||x - y||,
+    totals [2] = (sum_j losses[j] * weights[j] over group g) * loss_weights[g])"""
+    jobs = _tap_jobs(xs, ys, weights, groups)
+    lib = _lib.load()
+    nb = lib.mrefsr_tap_crit_workspace_bytes(jobs, len(xs))
+    dev = xs[0].device
+    part = torch.empty(nb // 8, device=dev, dtype=torch.float64)
+    losses = torch.empty(len(xs), device=dev, dtype=torch.float32)
+    totals = torch.empty(2, device=dev, dtype=torch.float32)
+    with _timed('tap_crit', detail=True, nbytes=8.0 * sum(x.numel() for x in xs)):
+        _lib.call('mrefsr_tap_crit_f32', jobs, len(xs), CRIT[crit], C.c_float(loss_weights[0]), C.c_float(loss_weights[1]), None, None, 0,
+                  _p(part), _p(losses), _p(totals), None, _stream())
+    return losses, totals
+
+
+def tap_crit_grad(x, y, grad, weight, group, crit, loss_weights, gup=None, norm=None, accumulate=False, want_amax=True):
+    """grad (+)= d total / d x of one tap (torch's autograd arithmetic, times gup[group] -- a device tensor [2] or None = 1); norm:
+    the tap's Frobenius norm from tap_crit_loss (crit 'fro').  -> max |grad| [1] | None"""
+    jobs = _tap_jobs([x], [y], [weight], [group], [grad])
+    if gup is not None:
+        _chk('tap_crit', gup)
+    if crit == 'fro':
+        _chk('tap_crit', norm)
+    amax = zeros_f32(x.device, 1) if want_amax else None
+    with _timed('tap_crit', detail=True, nbytes=4.0 * x.numel() * (4 if accumulate else 3)):
+        _lib.call('mrefsr_tap_crit_f32', jobs, 1, CRIT[crit], C.c_float(loss_weights[0]), C.c_float(loss_weights[1]), _p(gup),
+                  _p(norm) if crit == 'fro' else None, 1 if accumulate else 0, None, None, None, _p(amax), _stream())
+    return amax
+
+
+def gram_nhwc(f):
+    """f [N,H,W,C] (C a multiple of 64) -> [N,C,C] = F^T F / (C H W) per image (exact f32 MFMA products, fixed summation order)"""
+    _chk('gram_nhwc', f)
+    n, h, w, c = f.shape
+    lib = _lib.load()
+    need = lib.mrefsr_gram_workspace_bytes(n, h * w, c)
+    if need < 0:
+        raise ValueError(f'gram_nhwc: C={c} (a multiple of 64)')
+    ws = _wgrad_workspace(f.device, need)
+    g = torch.empty((n, c, c), device=f.device, dtype=torch.float32)
+    with _timed('gram_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (f.numel() + g.numel())):
+        _lib.call('mrefsr_gram_nhwc_f32', _p(f), n, h * w, c, _p(g), _p(ws), C.c_int64(need), _stream())
+    return g
+
+
+def gram_bwd_nhwc(f, gx, gg, df, loss_weight, weight, gup=None, accumulate=False, want_amax=True):
+    """df [N,H,W,C] (+)= d style / d f of the l1 style term  ((l1(gram(f), gg) * weight) * loss_weight) * gup: (2 / (C H W)) F S,
+    S = sgn(gx - gg) * ((gup * loss_weight) * weight) / (N C C); gx = gram_nhwc(f).  gup: a device scalar or None (= 1).
+    -> max |df| [1] | None"""
+    _chk('gram_bwd_nhwc', f, gx, gg, df, gup)
+    n, h, w, c = f.shape
+    if tuple(gx.shape) != (n, c, c) or tuple(gg.shape) != (n, c, c) or tuple(df.shape) != tuple(f.shape):
+        raise ValueError('gram_bwd_nhwc: inconsistent shapes')
+    amax = zeros_f32(f.device, 1) if want_amax else None
+    with _timed('gram_bwd_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (2 + accumulate) * f.numel()):
+        _lib.call('mrefsr_gram_bwd_nhwc_f32', _p(f), _p(gx), _p(gg), _p(df), n, h * w, c, _p(gup), C.c_float(loss_weight), C.c_float(weight),
+                  1 if accumulate else 0, _p(amax), _stream())
+    return amax
+
+
+def image_to_nhwc4_bwd(g4, range_norm=False, std=None):
+    """gradient of image_to_nhwc4(img, mean, std, range_norm): g4 [N,H,W,ld>=3] (pixel-contiguous) -> [N,3,H,W]"""
+    n, h, w, _ = g4.shape
+    ld = _nhwc_ld('g4', g4)
+    _chk('image_to_nhwc4_bwd', std)
+    out = torch.empty((n, 3, h, w), device=g4.device, dtype=torch.float32)
+    _lib.call('mrefsr_image_to_nhwc4_bwd_f32', _p(g4), ld, _p(out), C.c_int64(n), C.c_int64(h * w), 1 if range_norm else 0, _p(std), _stream())
+    return out

@@ -1,0 +1,14 @@
+"""Mirror of the loss module the reference model builds its criteria from (basicsr/models/losses.py, imported by
+multi_ref_restoration_model.py:17 -- not basicsr/losses/losses.py, which differs).  Classes register in LOSS_REGISTRY under the
+reference's names; ``build_loss`` selects one by ``type`` (the contract of basicsr/losses/__init__.py)."""
+from copy import deepcopy
+
+from ..utils.registry import LOSS_REGISTRY
+from .losses import CharbonnierLoss, L1Loss, MSELoss, PerceptualLoss
+
+__all__ = ['build_loss', 'LOSS_REGISTRY', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'PerceptualLoss']
+
+
+def build_loss(opt):
+    opt = deepcopy(opt)
+    return LOSS_REGISTRY.get(opt.pop('type'))(**opt)

@@ -1,0 +1,111 @@
+"""L1Loss, MSELoss, CharbonnierLoss and PerceptualLoss with the reference's constructor signatures and values
+(basicsr/models/losses.py:17-124, 141-238).
+
+The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
+what the model passes -- reduction='mean', no element weight -- and refuse the rest.  PerceptualLoss runs its VGG19 through ONE
+autograd node of the training engine (archs/nhwc_train.py: _VggLoss): output and GT as one batch through the HIP convolution
+kernels, the input-gradient pass of the output image back through the same kernels, pooling / criterion / Gram matrices on
+csrc/percep.hip.  GPU tensors only, like the ops.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from ..archs.vgg_arch import VGGFeatureExtractor
+from ..utils.registry import LOSS_REGISTRY
+
+
+def _only_mean(name, reduction):
+    if reduction != 'mean':
+        raise NotImplementedError(f"{name}: reduction={reduction!r}; only 'mean' (what the model passes) is implemented")
+
+
+def _no_weight(name, weight):
+    if weight is not None:
+        raise NotImplementedError(f'{name}: element-wise weights are not implemented (the model passes none)')
+
+
+@LOSS_REGISTRY.register()
+class L1Loss(nn.Module):
+    """loss_weight * mean |pred - target|"""
+
+    def __init__(self, loss_weight=1.0, reduction='mean'):
+        super().__init__()
+        _only_mean('L1Loss', reduction)
+        self.loss_weight, self.reduction = loss_weight, reduction
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        _no_weight('L1Loss', weight)
+        return self.loss_weight * F.l1_loss(pred, target)
+
+
+@LOSS_REGISTRY.register()
+class MSELoss(nn.Module):
+    """loss_weight * mean (pred - target)^2"""
+
+    def __init__(self, loss_weight=1.0, reduction='mean'):
+        super().__init__()
+        _only_mean('MSELoss', reduction)
+        self.loss_weight, self.reduction = loss_weight, reduction
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        _no_weight('MSELoss', weight)
+        return self.loss_weight * F.mse_loss(pred, target, reduction='none').mean()   # (the reference's operations: its gradient's bits)
+
+
+@LOSS_REGISTRY.register()
+class CharbonnierLoss(nn.Module):
+    """loss_weight * mean sqrt((pred - target)^2 + eps).  The constructor's eps (default 1e-12) is what the reference's forward
+    passes to charbonnier_loss (whose own default, 1e-6, is therefore never used)."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean', eps=1e-12):
+        super().__init__()
+        _only_mean('CharbonnierLoss', reduction)
+        self.loss_weight, self.reduction, self.eps = loss_weight, reduction, eps
+
+    def forward(self, pred, target, weight=None, **kwargs):
+        _no_weight('CharbonnierLoss', weight)
+        return self.loss_weight * torch.sqrt((pred - target)**2 + self.eps).mean()
+
+
+@LOSS_REGISTRY.register()
+class PerceptualLoss(nn.Module):
+    """Perceptual loss with the style (Gram) loss.  forward(x, gt) -> (perceptual, style), each None when its weight is 0.
+
+    norm_img: (x + 1) * 0.5 on both images before the VGG (the reference applies it although its images are in [0, 1]).
+    Taps are the named layers of the VGG (conv taps before their ReLU).  Perceptual term: sum_k crit(x_k, gt_k) * w_k, times
+    perceptual_weight, crit 'l1' (mean) or 'fro' (Frobenius norm).  Style term: sum_k l1(gram(x_k), gram(gt_k)) * w_k, times
+    style_weight, gram = F F^T / (c h w) per image."""
+
+    def __init__(self, layer_weights, vgg_type='vgg19', use_input_norm=True, perceptual_weight=1.0, style_weight=0, norm_img=True,
+                 criterion='l1'):
+        super().__init__()
+        if criterion == 'l2':
+            raise NotImplementedError("PerceptualLoss: criterion 'l2' -- the reference builds torch.nn.L2loss, which does not exist "
+                                      "(it raises there as well); use 'l1' or 'fro'")
+        if criterion not in ('l1', 'fro'):
+            raise NotImplementedError(f'{criterion} criterion has not been supported in this version.')
+        if style_weight > 0 and criterion == 'fro':
+            raise NotImplementedError("PerceptualLoss: style_weight > 0 with criterion 'fro' -- the reference's style term then calls "
+                                      'its criterion, which is None for fro; use criterion l1 for a style loss')
+        if 'bn' in vgg_type:
+            raise NotImplementedError(f'PerceptualLoss: vgg_type {vgg_type} (batch-normalised VGGs have no kernel here)')
+        self.norm_img = norm_img
+        self.perceptual_weight = perceptual_weight
+        self.style_weight = style_weight
+        self.layer_weights = layer_weights
+        self.criterion_type = criterion
+        self.vgg = VGGFeatureExtractor(layer_name_list=list(layer_weights.keys()), vgg_type=vgg_type, use_input_norm=use_input_norm)
+        self._plan = None
+
+    def forward(self, x, gt):
+        from ..archs import nhwc_train
+        if not (x.is_cuda and gt.is_cuda):
+            raise NotImplementedError('PerceptualLoss: mrefsr_amd has no CPU path (HIP kernels only)')
+        if not (self.perceptual_weight > 0 or self.style_weight > 0):
+            return None, None
+        if self._plan is None:
+            self._plan = nhwc_train.VggLossPlan(self.vgg.vgg_net, self.layer_weights, self.criterion_type, self.perceptual_weight,
+                                                self.style_weight, self.norm_img)
+        totals = nhwc_train.perceptual(self.vgg, x, gt.detach(), self._plan)
+        return (totals[0] if self.perceptual_weight > 0 else None), (totals[1] if self.style_weight > 0 else None)

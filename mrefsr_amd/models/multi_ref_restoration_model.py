@@ -7,8 +7,9 @@ update_learning_rate, save / load of ``{'params': state_dict}`` checkpoints), sa
 layout: Adam with four parameter groups chosen by name (:60-89) --
     'offset' & 'small'  -> lr_relu3_offset     'offset' & 'medium' -> lr_relu2_offset
     other 'offset'      -> lr_offset           everything else     -> lr_g
-Only the pixel (L1) branch of the loss zoo is implemented: it is the only one the shipped config
-enables (yml:77-78); enabling another raises NotImplementedError instead of silently skipping it.
+Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLoss), perceptual_opt and style_opt
+(PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels); gan_type / network_d / texture_opt raise
+NotImplementedError instead of being silently skipped.
 
 What differs underneath (SURVEY 7 "hard parts"):
   * the K references run as one k-major batch through extractor / matching / VGG19 / net_g;
@@ -22,7 +23,6 @@ import os
 from collections import OrderedDict
 
 import torch
-import torch.nn.functional as F
 from torch.nn.parallel import DistributedDataParallel
 
 from ..archs import build_network
@@ -111,18 +111,25 @@ class MultiRefRestorationModel:
 
     # ------------------------------------------------------------------ set-up
     def init_training_settings(self):
+        from .. import losses
         train_opt = self.opt['train']
-        for key in ('perceptual_opt', 'style_opt', 'texture_opt', 'gan_type'):
+        for key in ('texture_opt', 'gan_type'):
             if train_opt.get(key):
-                raise NotImplementedError(f'train.{key}: only the L1 pixel loss of the shipped config is implemented')
+                raise NotImplementedError(f'train.{key}: adversarial and texture losses are not implemented (pixel, perceptual and '
+                                          'style losses are)')
         if self.opt.get('network_d'):
-            raise NotImplementedError('network_d: the shipped config trains without a discriminator')
+            raise NotImplementedError('network_d: training with a discriminator is not implemented')
         if train_opt['pixel_weight'] > 0:
-            if train_opt['pixel_criterion'] != 'L1Loss':
-                raise NotImplementedError(f"pixel_criterion {train_opt['pixel_criterion']}: only L1Loss is implemented")
-            self.pixel_weight = float(train_opt['pixel_weight'])
+            name = train_opt['pixel_criterion']
+            if name not in ('L1Loss', 'MSELoss', 'CharbonnierLoss'):
+                raise NotImplementedError(f'pixel_criterion {name}: L1Loss, MSELoss or CharbonnierLoss')
+            self.cri_pix = losses.LOSS_REGISTRY.get(name)(loss_weight=train_opt['pixel_weight'], reduction='mean').to(self.device)
         else:
-            self.pixel_weight = None
+            logging.getLogger('basicsr').info('Remove pixel loss.')
+            self.cri_pix = None
+        # two PerceptualLoss instances, each with its own VGG, as in the reference (:126-141)
+        self.cri_perceptual = losses.PerceptualLoss(**train_opt['perceptual_opt']).to(self.device) if train_opt.get('perceptual_opt') else None
+        self.cri_style = losses.PerceptualLoss(**train_opt['style_opt']).to(self.device) if train_opt.get('style_opt') else None
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
@@ -177,19 +184,27 @@ class MultiRefRestorationModel:
         return True
 
     def _loss_and_backward(self, step):
-        """L1 branch of ref :197-279: returns True when a gradient was produced (the optimiser may step)"""
+        """net_g's losses of ref :197-279 and their backward: returns True when a gradient was produced (the optimiser may step)"""
         if step <= self.net_g_pretrain_steps:
-            l_pix = self.pixel_weight * F.l1_loss(self.output, self.gt)
+            l_pix = self.cri_pix(self.output, self.gt)
             l_pix.backward()
             self.log_dict['l_pix'] = l_pix.detach()
             return True
         if (step - self.net_g_pretrain_steps) % self.net_d_steps == 0 and \
                 (step - self.net_g_pretrain_steps) > self.net_d_init_steps:
             l_g_total = 0
-            if self.pixel_weight is not None:
-                l_g_pix = self.pixel_weight * F.l1_loss(self.output, self.gt)
+            if self.cri_pix is not None:
+                l_g_pix = self.cri_pix(self.output, self.gt)
                 l_g_total = l_g_total + l_g_pix
                 self.log_dict['l_g_pix'] = l_g_pix.detach()
+            if self.cri_perceptual is not None:
+                l_g_percep, _ = self.cri_perceptual(self.output, self.gt)
+                l_g_total = l_g_total + l_g_percep
+                self.log_dict['l_g_percep'] = l_g_percep.detach()
+            if self.cri_style is not None:
+                _, l_g_style = self.cri_style(self.output, self.gt)
+                l_g_total = l_g_total + l_g_style
+                self.log_dict['l_g_style'] = l_g_style.detach()
             l_g_total.backward()
             return True
         return False
@@ -198,9 +213,11 @@ class MultiRefRestorationModel:
     def _train_graph_wanted(self):
         """opt['train']['hip_graph'] or MREFSR_TRAIN_GRAPH=1 (EXPERIMENTAL, off by default: 1-2 % at the shipped patch size; see the
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
-        a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured)."""
-        return (bool((self.opt.get('train') or {}).get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
-            and not self.opt.get('dist', False)
+        a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
+        not with a perceptual or style loss (their VGG node is not captured)."""
+        train_opt = self.opt.get('train') or {}
+        return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
+            and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
     _GRAPH_WARMUP = 3   # eager steps per input shape before capture (lazy kernel attributes, workspaces, MIOpen find results)

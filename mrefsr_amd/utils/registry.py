@@ -45,3 +45,5 @@ class Registry:
 
 ARCH_REGISTRY = Registry('arch')
 MODEL_REGISTRY = Registry('model')
+
+LOSS_REGISTRY = Registry('loss')
