@@ -553,6 +553,69 @@ int mrefsr_gram_bwd_nhwc_f32(const float *f, const float *gx, const float *gg, f
 int mrefsr_image_to_nhwc4_bwd_f32(const float *g4, int ld, float *g_img, int64_t N, int64_t HW, int range_norm, const float *std3,
                                   mrefsr_stream_t stream);
 
+/* ---- ImageDiscriminator of the adversarial training step (basicsr/archs/discriminator_arch.py:10-45; the D step and the
+ * generator's adversarial term of multi_ref_restoration_model.py:219-278, the gradient penalty of basicsr/models/losses.py:370-404):
+ * the autograd nodes of mrefsr_amd/archs/nhwc_disc.py.  Channels-last [N][H][W][C] fp32 maps; every sum is formed in a fixed
+ * order (no float atomics), so two calls give the same bits.
+ *
+ * mrefsr_disc_pack_image_f32: img [B][3][H][W] -> x4 [B][H][W][4] (channel 3 = 0); mrefsr_disc_unpack_image_f32: its gradient
+ *   g4 [B][H][W][4] -> [B][3][H][W] (channel 3 dropped).
+ * mrefsr_disc_conv_pack_weight_f32: torch's w [Cout][CinR][3][3] -> dgrad 0: [9][Cin][Cout] (the forward's B operand), 1:
+ *   [9][Cout][Cin] (the input gradient's); channels CinR..Cin-1 are 0 (CinR = 3, Cin = 4 for the image).
+ * mrefsr_disc_conv3x3_f32: nn.Conv2d(Cin, Cout, 3, stride, 1) + bias (bias may be NULL): x [N][H][W][Cin] -> y [N][Ho][Wo][Cout],
+ *   Ho = ceil(H / stride) as torch computes it.  Implicit GEMM on v_mfma_f32_16x16x4_f32 (exact f32 products).  Cin = 4 or a
+ *   multiple of 16, Cout a multiple of 16, stride 1 or 2; anything else returns MREFSR_E_UNSUPPORTED.
+ * mrefsr_disc_conv3x3_dgrad_f32: input gradient dy [N][Ho][Wo][Cout] -> dx [N][H][W][Cin] (every element written) with the dgrad = 1
+ *   packing; a stride-2 layer runs as four output-parity phases, each a gather over its 1-2 taps per dimension.
+ * mrefsr_disc_conv3x3_wgrad_f32: dw [Cout][CinR][3][3] = sum over the pixels of x (x) dy (a GEMM over the pixels, split into partial
+ *   tiles added in a fixed order; workspace: mrefsr_disc_conv3x3_wgrad_workspace_bytes). */
+int mrefsr_disc_pack_image_f32(const float *img, float *x4, int B, int H, int W, mrefsr_stream_t stream);
+int mrefsr_disc_unpack_image_f32(const float *g4, float *img, int B, int H, int W, mrefsr_stream_t stream);
+int mrefsr_disc_conv_pack_weight_f32(const float *w, float *wpk, int Cout, int CinR, int Cin, int dgrad, mrefsr_stream_t stream);
+int mrefsr_disc_conv3x3_f32(const float *x, const float *wpk, const float *bias, float *y, int N, int H, int W, int Cin, int Cout, int stride,
+                            mrefsr_stream_t stream);
+int mrefsr_disc_conv3x3_dgrad_f32(const float *dy, const float *wpk_d, float *dx, int N, int H, int W, int Cin, int Cout, int stride,
+                                  mrefsr_stream_t stream);
+int64_t mrefsr_disc_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride);
+int mrefsr_disc_conv3x3_wgrad_f32(const float *x, const float *dy, float *dw, int N, int H, int W, int Cin, int CinR, int Cout, int stride,
+                                  void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+/* Per-channel reductions over P = N H W pixels of C channels (C a multiple of 16 for BatchNorm); workspace:
+ *   mrefsr_disc_chan_workspace_bytes (double partials + merged sums).
+ * mrefsr_disc_bias_grad_f32: db[c] = sum over the pixels of dy (the conv bias gradient).
+ * mrefsr_disc_bn_lrelu_f32: nn.BatchNorm2d (training mode: batch mean, biased variance from per-block (count, mean, M2) partials
+ *   merged in a fixed order) then LeakyReLU(slope): y = lrelu((x - mean) invstd gamma + beta); saves mean and invstd =
+ *   1 / sqrt(var + eps); run_mean / run_var (may be NULL) get torch's update with momentum (variance unbiased by n / (n - 1)),
+ *   *num_batches_tracked (may be NULL) += 1.
+ * mrefsr_disc_bn_lrelu_bwd_f32: g = gy lrelu'(y) (the mask from the output's sign); gx = gamma invstd (g - mean g - xh mean(g xh)),
+ *   ggamma = sum g xh, gbeta = sum g (any output may be NULL).
+ * mrefsr_disc_bn_lrelu_dbl_f32: double backward of the above (torch's batchnorm_double_backward through the mask): from ggx and
+ *   ggamma / gbeta (may be NULL = 0) -> d_gy, d_x, d_gamma (any may be NULL); the beta gradient is 0. */
+int64_t mrefsr_disc_chan_workspace_bytes(int64_t P, int C);
+int mrefsr_disc_bias_grad_f32(const float *dy, float *db, int64_t P, int C, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_bn_lrelu_f32(const float *x, const float *gamma, const float *beta, float *y, float *mean, float *invstd, float *run_mean,
+                             float *run_var, int64_t *num_batches_tracked, int64_t P, int C, float eps, float momentum, float slope,
+                             void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_bn_lrelu_bwd_f32(const float *gy, const float *y, const float *x, const float *mean, const float *invstd, const float *gamma,
+                                 float *gx, float *ggamma, float *gbeta, int64_t P, int C, float slope, void *workspace,
+                                 int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_bn_lrelu_dbl_f32(const float *ggx, const float *ggamma, const float *gbeta, const float *gy, const float *y, const float *x,
+                                 const float *mean, const float *invstd, const float *gamma, float *d_gy, float *d_x, float *d_gamma, int64_t P,
+                                 int C, float slope, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+/* Head: f [N][HW][C] -> AdaptiveAvgPool2d(1) -> 1x1 conv (w1 [J][C], b1 [J]) -> LeakyReLU(slope) -> 1x1 conv (w2 [J], b2 [1]) ->
+ *   Sigmoid = out [N].  Saves pooled [N][C] and hidden (the pre-activation) [N][J].  C a multiple of 16 up to 2048, J up to 4096.
+ * mrefsr_disc_head_bwd_f32: from gs = d / d out: gf [N][HW][C] and the parameter gradients (each may be NULL).
+ * mrefsr_disc_head_dbl_f32: double backward for an upstream gradient ggf of gf alone (the gradient penalty's case): d_gs, d_f and the
+ *   parameter gradients (each may be NULL).  Workspace of both: mrefsr_disc_head_workspace_bytes. */
+int64_t mrefsr_disc_head_workspace_bytes(int N, int C, int J);
+int mrefsr_disc_head_fwd_f32(const float *f, const float *w1, const float *b1, const float *w2, const float *b2, float *out, float *pooled,
+                             float *hidden, int N, int HW, int C, int J, float slope, mrefsr_stream_t stream);
+int mrefsr_disc_head_bwd_f32(const float *gs, const float *s, const float *pooled, const float *hidden, const float *w1, const float *w2,
+                             float *gf, float *gw1, float *gb1, float *gw2, float *gb2, int N, int HW, int C, int J, float slope, void *workspace,
+                             int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_head_dbl_f32(const float *ggf, const float *gs, const float *s, const float *pooled, const float *hidden, const float *w1,
+                             const float *w2, float *d_gs, float *d_f, float *d_w1, float *d_b1, float *d_w2, float *d_b2, int N, int HW, int C,
+                             int J, float slope, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -104,6 +104,22 @@ SIGNATURES = {
     'mrefsr_gram_nhwc_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
     'mrefsr_gram_bwd_nhwc_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp]),
     'mrefsr_image_to_nhwc4_bwd_f32': (_i, [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp]),
+    'mrefsr_disc_pack_image_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'mrefsr_disc_unpack_image_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
+    'mrefsr_disc_conv_pack_weight_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'mrefsr_disc_conv3x3_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mrefsr_disc_conv3x3_dgrad_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mrefsr_disc_conv3x3_wgrad_workspace_bytes': (_i64, [_i, _i, _i, _i, _i, _i]),
+    'mrefsr_disc_conv3x3_wgrad_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i64, _vp]),
+    'mrefsr_disc_chan_workspace_bytes': (_i64, [_i64, _i]),
+    'mrefsr_disc_bias_grad_f32': (_i, [_vp, _vp, _i64, _i, _vp, _i64, _vp]),
+    'mrefsr_disc_bn_lrelu_f32': (_i, [_vp] * 9 + [_i64, _i, _f, _f, _f, _vp, _i64, _vp]),
+    'mrefsr_disc_bn_lrelu_bwd_f32': (_i, [_vp] * 9 + [_i64, _i, _f, _vp, _i64, _vp]),
+    'mrefsr_disc_bn_lrelu_dbl_f32': (_i, [_vp] * 12 + [_i64, _i, _f, _vp, _i64, _vp]),
+    'mrefsr_disc_head_workspace_bytes': (_i64, [_i, _i, _i]),
+    'mrefsr_disc_head_fwd_f32': (_i, [_vp] * 8 + [_i, _i, _i, _i, _f, _vp]),
+    'mrefsr_disc_head_bwd_f32': (_i, [_vp] * 11 + [_i, _i, _i, _i, _f, _vp, _i64, _vp]),
+    'mrefsr_disc_head_dbl_f32': (_i, [_vp] * 13 + [_i, _i, _i, _i, _f, _vp, _i64, _vp]),
     'mrefsr_upfirdn2d_f32': (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     'mrefsr_upfirdn2d': (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
 }

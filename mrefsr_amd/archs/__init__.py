@@ -4,8 +4,8 @@ basicsr/archs/__init__.py:19-25 (``type`` selects the class, the other keys are 
 from copy import deepcopy
 
 from ..utils.registry import ARCH_REGISTRY
-from . import (contras_multi_extractor_arch, corres_generation_arch, ref_mrapa_restoration_arch,  # noqa: F401
-               ref_restoration_arch, vgg_arch)
+from . import (contras_multi_extractor_arch, corres_generation_arch, discriminator_arch,  # noqa: F401
+               ref_mrapa_restoration_arch, ref_restoration_arch, vgg_arch)
 
 __all__ = ['build_network', 'ARCH_REGISTRY']
 

@@ -11,7 +11,7 @@ import sys
 import types
 
 _ARCHS = ('MRAPARestorationNet', 'RestorationNet', 'CorrespondenceGenerationArch', 'ContrasMultiExtractorSep',
-          'ContrasExtractorSep', 'VGGFeatureExtractor')
+          'ContrasExtractorSep', 'VGGFeatureExtractor', 'ImageDiscriminator')
 _MODELS = ('MultiRefRestorationModel', 'RefRestorationModel')
 
 

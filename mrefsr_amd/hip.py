@@ -1267,3 +1267,190 @@ def image_to_nhwc4_bwd(g4, range_norm=False, std=None):
     out = torch.empty((n, 3, h, w), device=g4.device, dtype=torch.float32)
     _lib.call('mrefsr_image_to_nhwc4_bwd_f32', _p(g4), ld, _p(out), C.c_int64(n), C.c_int64(h * w), 1 if range_norm else 0, _p(std), _stream())
     return out
+
+
+# ------------------------------------------------------------------ ImageDiscriminator (csrc/disc.hip)
+def disc_pack_image(img):
+    """img [B,3,H,W] -> [B,H,W,4] (channel 3 = 0)"""
+    _chk('disc_pack_image', img)
+    b, c, h, w = img.shape
+    if c != 3:
+        raise NotImplementedError(f'disc_pack_image: {c} channels (the discriminator takes RGB images)')
+    out = torch.empty((b, h, w, 4), device=img.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_pack_image_f32', _p(img), _p(out), b, h, w, _stream())
+    return out
+
+
+def disc_unpack_image(g4):
+    """gradient of disc_pack_image: [B,H,W,4] -> [B,3,H,W]"""
+    _chk('disc_unpack_image', g4)
+    b, h, w, c = g4.shape
+    if c != 4:
+        raise ValueError('disc_unpack_image: expected 4 channels')
+    out = torch.empty((b, 3, h, w), device=g4.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_unpack_image_f32', _p(g4), _p(out), b, h, w, _stream())
+    return out
+
+
+def disc_conv_pack_weight(w, cin, dgrad):
+    """w [Cout,CinR,3,3] -> [9,cin,Cout] (dgrad False) or [9,Cout,cin] (dgrad True), channels CinR..cin-1 zero"""
+    _chk('disc_conv_pack_weight', w)
+    cout, cinr = w.shape[:2]
+    if tuple(w.shape[2:]) != (3, 3) or cinr > cin:
+        raise ValueError(f'disc_conv_pack_weight: weight {tuple(w.shape)} for {cin} input channels')
+    out = torch.empty((9, cout, cin) if dgrad else (9, cin, cout), device=w.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_conv_pack_weight_f32', _p(w), _p(out), cout, cinr, cin, 1 if dgrad else 0, _stream())
+    return out
+
+
+def _disc_out(n, s):
+    return (n + 1) // 2 if s == 2 else n
+
+
+def disc_conv3x3(x, wpk, bias, stride):
+    """x [N,H,W,Cin] -> [N,ceil(H/s),ceil(W/s),Cout]: 3x3, pad 1, + bias (wpk from disc_conv_pack_weight(dgrad=False))"""
+    _chk('disc_conv3x3', x, wpk, bias)
+    n, h, w, cin = x.shape
+    cout = wpk.shape[2]
+    if tuple(wpk.shape) != (9, cin, cout):
+        raise ValueError('disc_conv3x3: packed weight does not match the input channels')
+    y = torch.empty((n, _disc_out(h, stride), _disc_out(w, stride), cout), device=x.device, dtype=torch.float32)
+    with _timed('disc_conv3x3', 2.0 * y.numel() * 9 * cin, detail=True):
+        _lib.call('mrefsr_disc_conv3x3_f32', _p(x), _p(wpk), _p(bias), _p(y), n, h, w, cin, cout, stride, _stream())
+    return y
+
+
+def disc_conv3x3_dgrad(dy, wpk_d, in_shape, stride):
+    """input gradient: dy [N,Ho,Wo,Cout] -> dx [N,H,W,Cin] (in_shape = x's shape; wpk_d from disc_conv_pack_weight(dgrad=True))"""
+    _chk('disc_conv3x3_dgrad', dy, wpk_d)
+    n, h, w, cin = in_shape
+    cout = dy.shape[3]
+    if tuple(dy.shape) != (n, _disc_out(h, stride), _disc_out(w, stride), cout) or tuple(wpk_d.shape) != (9, cout, cin):
+        raise ValueError('disc_conv3x3_dgrad: inconsistent shapes')
+    dx = torch.empty((n, h, w, cin), device=dy.device, dtype=torch.float32)
+    with _timed('disc_conv3x3_dgrad', 2.0 * dy.numel() * 9 * cin, detail=True):
+        _lib.call('mrefsr_disc_conv3x3_dgrad_f32', _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, stride, _stream())
+    return dx
+
+
+def disc_conv3x3_wgrad(x, dy, cin_real, stride):
+    """weight gradient [Cout,cin_real,3,3] = sum over pixels of x (x) dy"""
+    _chk('disc_conv3x3_wgrad', x, dy)
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    if tuple(dy.shape) != (n, _disc_out(h, stride), _disc_out(w, stride), cout):
+        raise ValueError('disc_conv3x3_wgrad: inconsistent shapes')
+    lib = _lib.load()
+    need = lib.mrefsr_disc_conv3x3_wgrad_workspace_bytes(n, h, w, cin, cout, stride)
+    ws = _wgrad_workspace(x.device, need)
+    dw = torch.empty((cout, cin_real, 3, 3), device=x.device, dtype=torch.float32)
+    with _timed('disc_conv3x3_wgrad', 2.0 * dy.numel() * 9 * cin, detail=True):
+        _lib.call('mrefsr_disc_conv3x3_wgrad_f32', _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, stride, _p(ws), C.c_int64(ws.numel()),
+                  _stream())
+    return dw
+
+
+def _chan_ws(t):
+    p, c = t.numel() // t.shape[-1], t.shape[-1]
+    need = _lib.load().mrefsr_disc_chan_workspace_bytes(p, c)
+    return p, c, _wgrad_workspace(t.device, need)
+
+
+def disc_bias_grad(dy):
+    """[..., C] -> [C] sum over every other dimension"""
+    _chk('disc_bias_grad', dy)
+    p, c, ws = _chan_ws(dy)
+    db = torch.empty(c, device=dy.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_bias_grad_f32', _p(dy), _p(db), C.c_int64(p), c, _p(ws), C.c_int64(ws.numel()), _stream())
+    return db
+
+
+def disc_bn_lrelu(x, gamma, beta, running_mean=None, running_var=None, num_batches_tracked=None, eps=1e-5, momentum=0.1, slope=0.2):
+    """BatchNorm2d (training mode) + LeakyReLU on x [N,H,W,C] -> (y, mean [C], invstd [C]); the running statistics (and
+    num_batches_tracked, int64) are updated in place when given"""
+    _chk('disc_bn_lrelu', x, gamma, beta, running_mean, running_var)
+    if num_batches_tracked is not None:
+        _chk('disc_bn_lrelu', num_batches_tracked, dtype=torch.int64)
+    p, c, ws = _chan_ws(x)
+    y = torch.empty_like(x)
+    mean = torch.empty(c, device=x.device, dtype=torch.float32)
+    invstd = torch.empty(c, device=x.device, dtype=torch.float32)
+    with _timed('disc_bn_lrelu', detail=True):
+        _lib.call('mrefsr_disc_bn_lrelu_f32', _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(invstd), _p(running_mean), _p(running_var),
+                  _p(num_batches_tracked), C.c_int64(p), c, C.c_float(eps), C.c_float(momentum), C.c_float(slope), _p(ws), C.c_int64(ws.numel()),
+                  _stream())
+    return y, mean, invstd
+
+
+def disc_bn_lrelu_bwd(gy, y, x, mean, invstd, gamma, slope=0.2, want_gx=True, want_params=True):
+    """-> (gx | None, ggamma | None, gbeta | None)"""
+    _chk('disc_bn_lrelu_bwd', gy, y, x, mean, invstd, gamma)
+    p, c, ws = _chan_ws(x)
+    gx = torch.empty_like(x) if want_gx else None
+    gg = torch.empty(c, device=x.device, dtype=torch.float32) if want_params else None
+    gb = torch.empty(c, device=x.device, dtype=torch.float32) if want_params else None
+    with _timed('disc_bn_lrelu_bwd', detail=True):
+        _lib.call('mrefsr_disc_bn_lrelu_bwd_f32', _p(gy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(gx), _p(gg), _p(gb), C.c_int64(p), c,
+                  C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+    return gx, gg, gb
+
+
+def disc_bn_lrelu_dbl(ggx, ggamma, gbeta, gy, y, x, mean, invstd, gamma, slope=0.2, want=(True, True, True)):
+    """double backward: (ggx [N,H,W,C], ggamma [C] | None, gbeta [C] | None) -> (d gy, d x, d gamma), each None unless wanted"""
+    _chk('disc_bn_lrelu_dbl', ggx, ggamma, gbeta, gy, y, x, mean, invstd, gamma)
+    p, c, ws = _chan_ws(x)
+    d_gy = torch.empty_like(x) if want[0] else None
+    d_x = torch.empty_like(x) if want[1] else None
+    d_g = torch.empty(c, device=x.device, dtype=torch.float32) if want[2] else None
+    with _timed('disc_bn_lrelu_dbl', detail=True):
+        _lib.call('mrefsr_disc_bn_lrelu_dbl_f32', _p(ggx), _p(ggamma), _p(gbeta), _p(gy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(d_gy),
+                  _p(d_x), _p(d_g), C.c_int64(p), c, C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+    return d_gy, d_x, d_g
+
+
+def _head_ws(f, w1):
+    n, c, j = f.shape[0], f.shape[3], w1.shape[0]
+    need = _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j)
+    return _wgrad_workspace(f.device, need)
+
+
+def disc_head(f, w1, b1, w2, b2, slope=0.2):
+    """f [N,H,W,C] -> (out [N], pooled [N,C], hidden [N,J]); w1 [J,C], w2 [J] (contiguous views of the 1x1 weights)"""
+    _chk('disc_head', f, w1, b1, w2, b2)
+    n, h, w, c = f.shape
+    j = w1.shape[0]
+    out = torch.empty(n, device=f.device, dtype=torch.float32)
+    pooled = torch.empty((n, c), device=f.device, dtype=torch.float32)
+    hidden = torch.empty((n, j), device=f.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_head_fwd_f32', _p(f), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), _p(pooled), _p(hidden), n, h * w, c, j, C.c_float(slope),
+              _stream())
+    return out, pooled, hidden
+
+
+def disc_head_bwd(gs, s, pooled, hidden, w1, w2, f_shape, slope=0.2, want_params=True):
+    """-> (gf [N,H,W,C], gw1 [J,C], gb1 [J], gw2 [J], gb2 [1]) (the parameter gradients None unless wanted)"""
+    _chk('disc_head_bwd', gs, s, pooled, hidden, w1, w2)
+    n, h, w, c = f_shape
+    j = w1.shape[0]
+    dev = gs.device
+    gf = torch.empty((n, h, w, c), device=dev, dtype=torch.float32)
+    pw = [torch.empty(sh, device=dev, dtype=torch.float32) for sh in ((j, c), (j, ), (j, ), (1, ))] if want_params else [None] * 4
+    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j))
+    _lib.call('mrefsr_disc_head_bwd_f32', _p(gs), _p(s), _p(pooled), _p(hidden), _p(w1), _p(w2), _p(gf), *[_p(t) for t in pw], n, h * w, c, j,
+              C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+    return (gf, *pw)
+
+
+def disc_head_dbl(ggf, gs, s, pooled, hidden, w1, w2, slope=0.2, want_gs=True, want_f=True, want_params=True):
+    """double backward for an upstream gradient ggf [N,H,W,C] of gf alone -> (d gs [N], d f [N,H,W,C], d w1, d b1, d w2, d b2)"""
+    _chk('disc_head_dbl', ggf, gs, s, pooled, hidden, w1, w2)
+    n, h, w, c = ggf.shape
+    j = w1.shape[0]
+    dev = ggf.device
+    d_gs = torch.empty(n, device=dev, dtype=torch.float32) if want_gs else None
+    d_f = torch.empty_like(ggf) if want_f else None
+    pw = [torch.empty(sh, device=dev, dtype=torch.float32) for sh in ((j, c), (j, ), (j, ), (1, ))] if want_params else [None] * 4
+    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j))
+    _lib.call('mrefsr_disc_head_dbl_f32', _p(ggf), _p(gs), _p(s), _p(pooled), _p(hidden), _p(w1), _p(w2), _p(d_gs), _p(d_f), *[_p(t) for t in pw], n,
+              h * w, c, j, C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+    return (d_gs, d_f, *pw)

@@ -4,9 +4,11 @@ reference's names; ``build_loss`` selects one by ``type`` (the contract of basic
 from copy import deepcopy
 
 from ..utils.registry import LOSS_REGISTRY
-from .losses import CharbonnierLoss, L1Loss, MSELoss, PerceptualLoss
+from .losses import (CharbonnierLoss, GANLoss, GradientPenaltyLoss, L1Loss, MSELoss, PerceptualLoss,
+                     gradient_penalty_loss)
 
-__all__ = ['build_loss', 'LOSS_REGISTRY', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'PerceptualLoss']
+__all__ = ['build_loss', 'LOSS_REGISTRY', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'PerceptualLoss', 'GANLoss', 'GradientPenaltyLoss',
+           'gradient_penalty_loss']
 
 
 def build_loss(opt):

@@ -1,5 +1,5 @@
-"""L1Loss, MSELoss, CharbonnierLoss and PerceptualLoss with the reference's constructor signatures and values
-(basicsr/models/losses.py:17-124, 141-238).
+"""L1Loss, MSELoss, CharbonnierLoss, PerceptualLoss, GANLoss and GradientPenaltyLoss with the reference's constructor signatures
+and values (basicsr/models/losses.py:17-124, 141-238, 275-427).
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
 what the model passes -- reduction='mean', no element weight -- and refuse the rest.  PerceptualLoss runs its VGG19 through ONE
@@ -109,3 +109,68 @@ class PerceptualLoss(nn.Module):
                                                 self.style_weight, self.norm_img)
         totals = nhwc_train.perceptual(self.vgg, x, gt.detach(), self._plan)
         return (totals[0] if self.perceptual_weight > 0 else None), (totals[1] if self.style_weight > 0 else None)
+
+
+@LOSS_REGISTRY.register()
+class GANLoss(nn.Module):
+    """GAN loss of the adversarial step (basicsr/models/losses.py:275-356): gan_type 'vanilla', 'lsgan', 'wgan' or 'hinge'.
+
+    forward(input, target_is_real, is_disc=False): vanilla = BCEWithLogits(input, label) (applied, as in the reference, to the
+    discriminator's sigmoid output), lsgan = mean (input - label)^2, wgan = -mean(input) for real, mean(input) for fake, hinge =
+    mean relu(1 -/+ input) for the discriminator and -mean(input) for the generator.  Labels are real_label_val / fake_label_val;
+    loss_weight multiplies the generator's loss only.  O(B) scalars: plain torch element-wise operations."""
+
+    def __init__(self, gan_type, real_label_val=1.0, fake_label_val=0.0, loss_weight=1.0):
+        super().__init__()
+        if gan_type not in ('vanilla', 'lsgan', 'wgan', 'hinge'):
+            raise NotImplementedError(f'GAN type {gan_type} is not implemented.')
+        self.gan_type, self.loss_weight = gan_type, loss_weight
+        self.real_label_val, self.fake_label_val = real_label_val, fake_label_val
+        self.loss = {'vanilla': nn.BCEWithLogitsLoss(), 'lsgan': nn.MSELoss(), 'wgan': self._wgan_loss, 'hinge': nn.ReLU()}[gan_type]
+
+    @staticmethod
+    def _wgan_loss(input, target):
+        return -input.mean() if target else input.mean()
+
+    def get_target_label(self, input, target_is_real):
+        if self.gan_type == 'wgan':
+            return target_is_real
+        return input.new_ones(input.size()) * (self.real_label_val if target_is_real else self.fake_label_val)
+
+    def forward(self, input, target_is_real, is_disc=False):
+        if self.gan_type == 'hinge':
+            if is_disc:
+                loss = self.loss(1 + (-input if target_is_real else input)).mean()
+            else:
+                loss = -input.mean()
+        else:
+            loss = self.loss(input, self.get_target_label(input, target_is_real))
+        return loss if is_disc else loss * self.loss_weight
+
+
+def gradient_penalty_loss(discriminator, real_data, fake_data, mask=None):
+    """WGAN-GP penalty mean_b (||d D(x_b) / d x_b||_2 - 1)^2 at x = alpha real + (1 - alpha) fake (basicsr/models/losses.py:
+    359-395).  alpha [B,1,1,1] is drawn by torch.rand on the CPU generator, so under one seed it is the reference's.  The
+    interpolate is a detached leaf: the penalty reaches the discriminator's parameters only.  The discriminator is differentiated
+    twice (create_graph=True); ImageDiscriminator's nodes support that (archs/nhwc_disc.py)."""
+    alpha = torch.rand(real_data.size(0), 1, 1, 1).to(real_data.device)
+    interpolates = (alpha * real_data + (1. - alpha) * fake_data).detach().requires_grad_(True)
+    disc_interpolates = discriminator(interpolates)
+    gradients = torch.autograd.grad(outputs=disc_interpolates, inputs=interpolates, grad_outputs=torch.ones_like(disc_interpolates),
+                                    create_graph=True, retain_graph=True, only_inputs=True)[0]
+    if mask is not None:
+        gradients = gradients * mask
+    gradients = gradients.view(gradients.size(0), -1)
+    return ((gradients.norm(2, dim=1) - 1)**2).mean()
+
+
+@LOSS_REGISTRY.register()
+class GradientPenaltyLoss(nn.Module):
+    """loss_weight * gradient_penalty_loss (basicsr/models/losses.py:398-427)"""
+
+    def __init__(self, loss_weight=1.):
+        super().__init__()
+        self.loss_weight = loss_weight
+
+    def forward(self, discriminator, real_data, fake_data, mask=None):
+        return gradient_penalty_loss(discriminator, real_data, fake_data, mask=mask) * self.loss_weight

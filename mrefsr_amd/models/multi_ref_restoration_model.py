@@ -8,8 +8,10 @@ layout: Adam with four parameter groups chosen by name (:60-89) --
     'offset' & 'small'  -> lr_relu3_offset     'offset' & 'medium' -> lr_relu2_offset
     other 'offset'      -> lr_offset           everything else     -> lr_g
 Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLoss), perceptual_opt and style_opt
-(PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels); gan_type / network_d / texture_opt raise
-NotImplementedError instead of being silently skipped.
+(PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), and the adversarial term: network_d
+(ImageDiscriminator, on the kernels of csrc/disc.hip) with gan_type / gan_weight / grad_penalty_weight, its own Adam
+(optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of :272-276.  texture_opt and
+other discriminators raise NotImplementedError instead of being silently skipped.
 
 What differs underneath (SURVEY 7 "hard parts"):
   * the K references run as one k-major batch through extractor / matching / VGG19 / net_g;
@@ -113,12 +115,34 @@ class MultiRefRestorationModel:
     def init_training_settings(self):
         from .. import losses
         train_opt = self.opt['train']
-        for key in ('texture_opt', 'gan_type'):
-            if train_opt.get(key):
-                raise NotImplementedError(f'train.{key}: adversarial and texture losses are not implemented (pixel, perceptual and '
-                                          'style losses are)')
-        if self.opt.get('network_d'):
-            raise NotImplementedError('network_d: training with a discriminator is not implemented')
+        if train_opt.get('texture_opt'):
+            raise NotImplementedError('train.texture_opt: the texture loss is not implemented (pixel, perceptual, style and adversarial '
+                                      'losses are; the reference model never sets the maps / weights it reads)')
+        net_d_opt = self.opt.get('network_d')
+        if net_d_opt and net_d_opt.get('type') != 'ImageDiscriminator':
+            raise NotImplementedError(f"network_d: {net_d_opt.get('type')} is not implemented (ImageDiscriminator is)")
+        if train_opt.get('gan_type') and not net_d_opt:
+            raise NotImplementedError('train.gan_type without network_d: the reference builds a GAN loss that nothing uses (and fails on '
+                                      'a missing grad_penalty_weight); give a network_d or drop gan_type')
+        if net_d_opt and not train_opt.get('gan_type'):
+            raise NotImplementedError('network_d without train.gan_type: the reference fails at its first D step; set gan_type')
+        # discriminator (ref :98-113), built and loaded before the losses
+        self.net_d = self.cri_gan = self.cri_grad_penalty = None
+        if net_d_opt:
+            self.net_d = build_network(net_d_opt).to(self.device)
+            path = self.opt.get('path') or {}
+            if path.get('pretrain_network_d'):
+                self.load_network(self.net_d, path['pretrain_network_d'], path.get('strict_load', True))
+            if self.opt.get('dist', False):
+                self.net_d = DistributedDataParallel(self.net_d, device_ids=[self.device.index],
+                                                     find_unused_parameters=self.opt.get('find_unused_parameters', False),
+                                                     broadcast_buffers=self.opt.get('broadcast_buffers', True))
+            self.net_d.train()
+            # GANLoss(gan_type, 1.0, 0.0, gan_weight) and the gradient penalty (ref :149-169: both keys are required)
+            self.cri_gan = losses.GANLoss(train_opt['gan_type'], real_label_val=1.0, fake_label_val=0.0,
+                                          loss_weight=train_opt['gan_weight']).to(self.device)
+            if train_opt['grad_penalty_weight'] > 0:
+                self.cri_grad_penalty = losses.GradientPenaltyLoss(loss_weight=train_opt['grad_penalty_weight']).to(self.device)
         if train_opt['pixel_weight'] > 0:
             name = train_opt['pixel_criterion']
             if name not in ('L1Loss', 'MSELoss', 'CharbonnierLoss'):
@@ -133,6 +157,11 @@ class MultiRefRestorationModel:
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
+        if self.net_d is not None:   # ref :178-185: appended before the schedulers are made, so it gets one of its own
+            self.optimizer_d = torch.optim.Adam(self.net_d.parameters(), lr=train_opt['lr_d'], weight_decay=train_opt.get('weight_decay_d', 0),
+                                                betas=train_opt['beta_d'],
+                                                fused=bool(train_opt.get('fused_adam', True)) and self.device.type == 'cuda')
+            self.optimizers.append(self.optimizer_d)
         sched = dict(train_opt['scheduler'])
         stype = sched.pop('type')
         if stype not in ('MultiStepLR', 'MultiStepRestartLR'):
@@ -205,6 +234,11 @@ class MultiRefRestorationModel:
                 _, l_g_style = self.cri_style(self.output, self.gt)
                 l_g_total = l_g_total + l_g_style
                 self.log_dict['l_g_style'] = l_g_style.detach()
+            if self.net_d is not None:   # ref :272-276 (D's parameters are frozen: no weight gradient of D is computed)
+                fake_g_pred = self.net_d(self.output)
+                l_g_gan = self.cri_gan(fake_g_pred, True, is_disc=False)
+                l_g_total = l_g_total + l_g_gan
+                self.log_dict['l_g_gan'] = l_g_gan.detach()
             l_g_total.backward()
             return True
         return False
@@ -214,10 +248,11 @@ class MultiRefRestorationModel:
         """opt['train']['hip_graph'] or MREFSR_TRAIN_GRAPH=1 (EXPERIMENTAL, off by default: 1-2 % at the shipped patch size; see the
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
         a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
-        not with a perceptual or style loss (their VGG node is not captured)."""
+        not with a perceptual or style loss (their VGG node is not captured), nor with a discriminator."""
         train_opt = self.opt.get('train') or {}
         return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
-            and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt')
+            and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt') \
+            and not self.opt.get('network_d')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
     _GRAPH_WARMUP = 3   # eager steps per input shape before capture (lazy kernel attributes, workspaces, MIOpen find results)
@@ -346,6 +381,53 @@ class MultiRefRestorationModel:
             torch.cuda.synchronize()
         return True
 
+    def _discriminator_step(self):
+        """ref :219-245: D on the GT and on the detached output, the gradient penalty, backward, optimizer_d.step()"""
+        self.optimizer_d.zero_grad()
+        for p in self.net_d.parameters():
+            p.requires_grad = True
+        real_d_pred = self.net_d(self.gt)
+        l_d_real = self.cri_gan(real_d_pred, True, is_disc=True)
+        self.log_dict['l_d_real'] = l_d_real.detach()
+        self.log_dict['out_d_real'] = torch.mean(real_d_pred.detach())
+        fake_d_pred = self.net_d(self.output.detach())
+        l_d_fake = self.cri_gan(fake_d_pred, False, is_disc=True)
+        self.log_dict['l_d_fake'] = l_d_fake.detach()
+        self.log_dict['out_d_fake'] = torch.mean(fake_d_pred.detach())
+        l_d_total = l_d_real + l_d_fake
+        if self.cri_grad_penalty is not None:
+            l_grad_penalty = self.cri_grad_penalty(self.net_d, self.gt, self.output)
+            self.log_dict['l_grad_penalty'] = l_grad_penalty.detach()
+            l_d_total = l_d_total + l_grad_penalty
+        l_d_total.backward()
+        self.optimizer_d.step()
+        for p in self.net_d.parameters():   # ref :249-251, before the G step
+            p.requires_grad = False
+
+    def _optimize_adversarial(self, step):
+        """a step with a discriminator past net_g_pretrain_steps.  The fp16-range flag is read right after net_g's forward (one 4-byte
+        readback), so that a forward re-run on the range-free kernels happens before the D step: D's Adam step and each BatchNorm's
+        running statistics are updated once per D forward of the reference.  Should net_g's backward trip the flag, the G step is
+        re-run on the range-free kernels with D's running statistics left as they are (the D step is not repeated)."""
+        from .. import hip
+        from ..archs import nhwc_disc, nhwc_train
+        if self._range_tripped('optimize_parameters'):
+            nhwc_train.reset_scales()
+            with hip.range_free():
+                self.output = self._forward()
+            hip.conv_range_tripped()
+        self._discriminator_step()
+        stepped = self._loss_and_backward(step)
+        if self._range_tripped('optimize_parameters'):
+            nhwc_train.reset_scales()
+            self.optimizer_g.zero_grad()
+            with hip.range_free(), nhwc_disc.frozen_statistics():
+                self.output = self._forward()
+                stepped = self._loss_and_backward(step)
+            hip.conv_range_tripped()
+        if stepped:
+            self.optimizer_g.step()
+
     def optimize_parameters(self, step):
         from .. import hip
         from ..archs import nhwc_train
@@ -355,6 +437,8 @@ class MultiRefRestorationModel:
         self.optimizer_g.zero_grad()
         nhwc_train.begin_step()     # every packed copy of net_g's weights refreshed in one launch (they changed in optimizer_g.step())
         self.output = self._forward()
+        if getattr(self, 'net_d', None) is not None and step > self.net_g_pretrain_steps:
+            return self._optimize_adversarial(step)
         stepped = self._loss_and_backward(step)
         if self._range_tripped('optimize_parameters'):   # the frozen feature networks and the DCN forward run on the split kernels
             nhwc_train.reset_scales()
@@ -496,11 +580,13 @@ class MultiRefRestorationModel:
         return dict(psnr=avg_psnr, psnr_y=avg_psnr_y, ssim_y=avg_ssim_y)
 
     def save(self, epoch, current_iter):
-        """net_g checkpoint as {'params': state_dict} under path.models (ref :304-308, base_model.py:198-226)"""
+        """net_g (and net_d) checkpoints as {'params': state_dict} under path.models (ref :304-308, base_model.py:198-226)"""
         models_dir = self.opt.get('path', {}).get('models')
         if models_dir and self.opt.get('rank', 0) == 0:
             name = 'latest' if current_iter == -1 else current_iter
             self.save_network(self.net_g, os.path.join(models_dir, f'net_g_{name}.pth'))
+            if getattr(self, 'net_d', None) is not None:
+                self.save_network(self.net_d, os.path.join(models_dir, f'net_d_{name}.pth'))
 
     def save_training_state(self, epoch, current_iter):
         """optimizer / scheduler states as {epoch, iter, optimizers, schedulers} in

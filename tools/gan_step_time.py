@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""What the adversarial term adds to a training step.
+
+  python tools/gan_step_time.py [--steps 10] [--warmup 3] [--out FILE.json] [--trace]
+
+(1) MultiRefRestorationModel.optimize_parameters at B = 4, K = 5, LR 40 x 40 (GT 160 x 160) in three configurations -- L1 only,
+L1 + ImageDiscriminator(3, 32) with WGAN-GP (gan_weight 1e-3, grad_penalty_weight 10), L1 + vanilla GAN -- ms per step (median of
+--steps, after --warmup);
+(2) the discriminator part alone on [4,3,160,160] images: the WGAN-GP D step (D on real and fake, the penalty, backward) and the G
+step's D forward + backward, on the HIP kernels;
+(3) for comparison, the same D step through torch's NCHW autograd of the same module (MIOpen convolutions) on the same GPU.
+--trace: one WGAN-GP step only (for rocprofv3 --kernel-trace --stats)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+GAN = {'wgan_gp': dict(gan_type='wgan', gan_weight=1e-3, grad_penalty_weight=10.0),
+       'vanilla': dict(gan_type='vanilla', gan_weight=1e-3, grad_penalty_weight=0.0)}
+
+
+def _opt(gan):
+    train = dict(lr_g=1e-4, lr_offset=1e-4, lr_relu2_offset=1e-5, lr_relu3_offset=1e-6, weight_decay_g=0, beta_g=[0.9, 0.999],
+                 scheduler=dict(type='MultiStepLR', milestones=[300000], gamma=0.5), net_g_pretrain_steps=0, pixel_criterion='L1Loss',
+                 pixel_weight=1.0)
+    opt = dict(name='gan_time', model_type='MultiRefRestorationModel', scale=4, crop_border=4, num_gpu=1, is_train=True, dist=False,
+               network_g=dict(type='MRAPARestorationNet', ngf=64, n_blocks=16, groups=8),
+               network_map=dict(type='CorrespondenceGenerationArch', patch_size=3, stride=1, vgg_layer_list=['relu1_1', 'relu2_1', 'relu3_1'],
+                                vgg_type='vgg19'),
+               network_extractor=dict(type='ContrasMultiExtractorSep'), path={}, train=train)
+    if gan:
+        train.update(GAN[gan], lr_d=1e-4, beta_d=[0.9, 0.999])
+        opt['network_d'] = dict(type='ImageDiscriminator', in_nc=3, ndf=32)
+    return opt
+
+
+def _model(gan):
+    import synth
+    import synth_disc
+    from mrefsr_amd.models import build_model
+    model = build_model(_opt(gan))
+    nets = [model.get_bare_model(model.net_g), model.net_extractor, model.net_map]
+    for net in nets:
+        spec = [(k, tuple(v.shape)) for k, v in net.state_dict().items()]
+        net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.state_dict(spec).items()})
+    if gan:
+        spec = [(k, tuple(v.shape)) for k, v in model.net_d.state_dict().items()]
+        model.net_d.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth_disc.state_dict(spec).items()})
+    samples = [synth.sr_sample(f'gan_time/s{i}', 5, 40, 40) for i in range(4)]
+    model.feed_data({n: torch.from_numpy(np.stack([s[n] for s in samples])) for n in samples[0]})
+    return model
+
+
+def _median_ms(fn, steps, warmup):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts)
+
+
+def _d_step(net, real, fake, gan, gp):
+    for p in net.parameters():
+        p.grad = None
+    loss = gan(net(real), True, is_disc=True) + gan(net(fake), False, is_disc=True) + gp(net, real, fake)
+    loss.backward()
+
+
+def _torch_d(net):
+    """the same module run through torch's own NCHW autograd (MIOpen convolutions, native BatchNorm)"""
+    def fwd(x):
+        h = x
+        for blk in net.blocks():
+            for i in (0, 3):
+                h = F.leaky_relu(blk[i + 1](blk[i](h)), 0.2)
+        return net.out_block(h)
+    return fwd
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--out')
+    ap.add_argument('--trace', action='store_true')
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    if a.trace:
+        model = _model('wgan_gp')
+        model.optimize_parameters(1)
+        torch.cuda.synchronize()
+        print('traced one WGAN-GP step')
+        return
+    res = {}
+    for cfg in (None, 'wgan_gp', 'vanilla'):
+        model = _model(cfg)
+        it = [0]
+
+        def step():
+            it[0] += 1
+            model.optimize_parameters(it[0])
+        res[f'step_ms_{cfg or "l1"}'] = _median_ms(step, a.steps, a.warmup)
+        del model
+        torch.cuda.empty_cache()
+    from mrefsr_amd.archs import build_network
+    from mrefsr_amd.losses import GANLoss, GradientPenaltyLoss
+    g = torch.Generator().manual_seed(0)
+    real = (torch.rand(4, 3, 160, 160, generator=g) * 2 - 1).cuda()
+    fake = (torch.rand(4, 3, 160, 160, generator=g) * 2 - 1).cuda()
+    net = build_network(dict(type='ImageDiscriminator')).cuda().train()
+    gan, gp = GANLoss('wgan'), GradientPenaltyLoss(10.0)
+    res['d_step_wgan_gp_ms_hip'] = _median_ms(lambda: _d_step(net, real, fake, gan, gp), a.steps, a.warmup)
+    fk = fake.clone().requires_grad_(True)
+
+    def g_part():
+        for p in net.parameters():
+            p.requires_grad_(False)
+        gan(net(fk), True).backward()
+        for p in net.parameters():
+            p.requires_grad_(True)
+    res['g_step_d_part_ms_hip'] = _median_ms(g_part, a.steps, a.warmup)
+
+    class TorchD(torch.nn.Module):
+        def __init__(self, net):
+            super().__init__()
+            self.net, self.fwd = net, _torch_d(net)
+
+        def forward(self, x):
+            return self.fwd(x)
+    tnet = TorchD(net)
+    res['d_step_wgan_gp_ms_torch_miopen'] = _median_ms(lambda: _d_step(tnet, real, fake, gan, gp), a.steps, a.warmup)
+    res['adversarial_adds_ms_wgan_gp'] = res['step_ms_wgan_gp'] - res['step_ms_l1']
+    res['adversarial_adds_ms_vanilla'] = res['step_ms_vanilla'] - res['step_ms_l1']
+    print(json.dumps(res, indent=1))
+    if a.out:
+        with open(a.out, 'w') as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == '__main__':
+    main()
