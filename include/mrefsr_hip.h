@@ -616,6 +616,51 @@ int mrefsr_disc_head_dbl_f32(const float *ggf, const float *gs, const float *s, 
                              const float *w2, float *d_gs, float *d_f, float *d_w1, float *d_b1, float *d_w2, float *d_b2, int N, int HW, int C,
                              int J, float slope, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
 
+/* ---- VGGStyleDiscriminator of the adversarial training step (basicsr/archs/discriminator_arch.py:47-125 with input_size 160; the
+ * same D step and penalty as above): the kernels of mrefsr_amd/archs/nhwc_vggdisc.py that the ImageDiscriminator entry points above
+ * do not cover.  Its BatchNorm + LeakyReLU layers and the image packing use mrefsr_disc_bn_lrelu*_f32 and mrefsr_disc_pack_image_f32.
+ * Channels-last fp32 maps, fixed summation orders (no float atomics).
+ *
+ * mrefsr_disc_vconv_pack_weight_f32: torch's w [Cout][CinR][ks][ks] -> dgrad 0: [Cout][ks ks][Cin] (the forward's operand), 1:
+ *   [Cin][ks ks][Cout] (the input gradient's); channels CinR..Cin-1 are 0.
+ * mrefsr_disc_vconv_f32: nn.Conv2d(Cin, Cout, ks, stride, 1) with ks 3 (stride 1: conv{i}_0, discriminator_arch.py:62, 66, 71, 76,
+ *   81) or ks 4 (stride 2: conv{i}_1, :63, 68, 73, 78, 83) + bias (may be NULL), then LeakyReLU(slope) when act (conv0_0, :103):
+ *   x [N][H][W][Cin] -> y [N][Ho][Wo][Cout], Ho = H for ks 3 and floor(H / 2) for ks 4, as torch computes them.  Implicit GEMM on
+ *   v_mfma_f32_16x16x4_f32 (exact f32 products) with LDS-staged operand tiles; Cin a multiple of 4, Cout of 16.  Small layers split
+ *   the reduction into partial tiles added in a fixed order (workspace: mrefsr_disc_vconv_workspace_bytes(.., dgrad 0), may be 0).
+ * mrefsr_disc_vconv_dgrad_f32: input gradient dy [N][Ho][Wo][Cout] -> dx [N][H][W][Cin] (every element written) with the dgrad = 1
+ *   packing; ks 4 runs as four output-parity phases, each a gather over exactly 2 x 2 taps (workspace: .._workspace_bytes(.., 1)).
+ * mrefsr_disc_vconv_wgrad_f32: dw [Cout][CinR][ks][ks] = sum over the output pixels of x (x) dy, split over the pixels into partial
+ *   tiles added in a fixed order (workspace: mrefsr_disc_vconv_wgrad_workspace_bytes).
+ * mrefsr_disc_lrelu_mask_f32: out = g lrelu'(y), the mask from the sign of the LeakyReLU's output y: the backward of conv0_0's
+ *   LeakyReLU, and (applied to the upstream gradient of its result) its double backward w.r.t. g; the one w.r.t. y is 0. */
+int mrefsr_disc_vconv_pack_weight_f32(const float *w, float *wpk, int Cout, int CinR, int Cin, int ks, int dgrad, mrefsr_stream_t stream);
+int64_t mrefsr_disc_vconv_workspace_bytes(int N, int H, int W, int Cin, int Cout, int ks, int dgrad);
+int mrefsr_disc_vconv_f32(const float *x, const float *wpk, const float *bias, float *y, int N, int H, int W, int Cin, int Cout, int ks, int act,
+                          float slope, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_vconv_dgrad_f32(const float *dy, const float *wpk_d, float *dx, int N, int H, int W, int Cin, int Cout, int ks, void *workspace,
+                                int64_t workspace_bytes, mrefsr_stream_t stream);
+int64_t mrefsr_disc_vconv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int ks);
+int mrefsr_disc_vconv_wgrad_f32(const float *x, const float *dy, float *dw, int N, int H, int W, int Cin, int CinR, int Cout, int ks, void *workspace,
+                                int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_lrelu_mask_f32(const float *g, const float *y, float *out, int64_t n, float slope, mrefsr_stream_t stream);
+/* Linear head (discriminator_arch.py:115-118): f [N][HW][C] channels-last, flattened in the reference's NCHW order (feature c HW + p,
+ *   view(B, -1)) -> linear1 (w1 [J][C HW] in torch's layout, b1 [J]) -> LeakyReLU(slope) -> linear2 (w2 [J], b2 [1]) = out [N]; saves
+ *   hidden (linear1's output before the activation) [N][J].
+ * mrefsr_disc_linear_head_bwd_f32: from gs = d / d out: gf [N][HW][C] and the parameter gradients (each output may be NULL; f is read
+ *   for gw1 only).
+ * mrefsr_disc_linear_head_dbl_f32: double backward for an upstream gradient ggf of gf alone (the gradient penalty's case): d_gs, d_w1,
+ *   d_w2 (each may be NULL); the gradients w.r.t. f, b1 and b2 are 0 (the LeakyReLU mask is piecewise constant).  Workspace:
+ *   mrefsr_disc_linear_head_workspace_bytes. */
+int mrefsr_disc_linear_head_fwd_f32(const float *f, const float *w1, const float *b1, const float *w2, const float *b2, float *out, float *hidden,
+                                    int N, int HW, int C, int J, float slope, mrefsr_stream_t stream);
+int mrefsr_disc_linear_head_bwd_f32(const float *gs, const float *hidden, const float *f, const float *w1, const float *w2, float *gf, float *gw1,
+                                    float *gb1, float *gw2, float *gb2, int N, int HW, int C, int J, float slope, mrefsr_stream_t stream);
+int64_t mrefsr_disc_linear_head_workspace_bytes(int N, int J);
+int mrefsr_disc_linear_head_dbl_f32(const float *ggf, const float *gs, const float *hidden, const float *w1, const float *w2, float *d_gs,
+                                    float *d_w1, float *d_w2, int N, int HW, int C, int J, float slope, void *workspace, int64_t workspace_bytes,
+                                    mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -120,6 +120,17 @@ SIGNATURES = {
     'mrefsr_disc_head_fwd_f32': (_i, [_vp] * 8 + [_i, _i, _i, _i, _f, _vp]),
     'mrefsr_disc_head_bwd_f32': (_i, [_vp] * 11 + [_i, _i, _i, _i, _f, _vp, _i64, _vp]),
     'mrefsr_disc_head_dbl_f32': (_i, [_vp] * 13 + [_i, _i, _i, _i, _f, _vp, _i64, _vp]),
+    'mrefsr_disc_vconv_pack_weight_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'mrefsr_disc_vconv_workspace_bytes': (_i64, [_i] * 7),
+    'mrefsr_disc_vconv_f32': (_i, [_vp] * 4 + [_i] * 7 + [_f, _vp, _i64, _vp]),
+    'mrefsr_disc_vconv_dgrad_f32': (_i, [_vp] * 3 + [_i] * 6 + [_vp, _i64, _vp]),
+    'mrefsr_disc_vconv_wgrad_workspace_bytes': (_i64, [_i] * 6),
+    'mrefsr_disc_vconv_wgrad_f32': (_i, [_vp] * 3 + [_i] * 7 + [_vp, _i64, _vp]),
+    'mrefsr_disc_lrelu_mask_f32': (_i, [_vp, _vp, _vp, _i64, _f, _vp]),
+    'mrefsr_disc_linear_head_fwd_f32': (_i, [_vp] * 7 + [_i, _i, _i, _i, _f, _vp]),
+    'mrefsr_disc_linear_head_bwd_f32': (_i, [_vp] * 10 + [_i, _i, _i, _i, _f, _vp]),
+    'mrefsr_disc_linear_head_workspace_bytes': (_i64, [_i, _i]),
+    'mrefsr_disc_linear_head_dbl_f32': (_i, [_vp] * 8 + [_i, _i, _i, _i, _f, _vp, _i64, _vp]),
     'mrefsr_upfirdn2d_f32': (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     'mrefsr_upfirdn2d': (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
 }

@@ -1,8 +1,11 @@
-"""ImageDiscriminator (basicsr/archs/discriminator_arch.py:10-45): the discriminator of the adversarial training step.
+"""ImageDiscriminator (basicsr/archs/discriminator_arch.py:10-45) and VGGStyleDiscriminator (:47-125): the discriminators of the
+adversarial training step.
 
 Same module tree, parameter and buffer names (74 state_dict entries at ndf 32) and initialisation (srntt_init_weights, normal
 0.02, BatchNorm weights N(1, 0.02)) as the reference, so its checkpoints load unchanged.  The forward runs on the kernels of
 csrc/disc.hip through the autograd nodes of archs/nhwc_disc.py, which are differentiable twice (the WGAN-GP gradient penalty).
+VGGStyleDiscriminator keeps the reference's attribute order and PyTorch's default initialisation, so under one torch.manual_seed it
+builds the reference's exact parameters; its forward runs on csrc/disc_vgg.hip through archs/nhwc_vggdisc.py.
 Construction and state_dict work on the CPU; forward on a CPU tensor raises NotImplementedError, as every op of the package does.
 """
 import torch
@@ -47,3 +50,55 @@ class ImageDiscriminator(nn.Module):
             raise NotImplementedError(f'ImageDiscriminator: input {tuple(x.shape)} {x.dtype}; fp32 [B,3,H,W] only')
         from . import nhwc_disc
         return nhwc_disc.discriminator(self, x)
+
+
+@ARCH_REGISTRY.register()
+class VGGStyleDiscriminator(nn.Module):
+    """the reference's VGG-style discriminator with its default input_size of 160 (the GT crop of the training config).
+    input_size 256 is refused: the reference builds conv5_* / bn5_* for it but keeps linear1 sized for a 5 x 5 map, so its forward
+    cannot run."""
+
+    def __init__(self, num_in_ch, num_feat, input_size=160):
+        super().__init__()
+        self.input_size = input_size
+        assert self.input_size == 160 or self.input_size == 256, (f'input size must be 160 or 256, but received {input_size}')
+        if input_size == 256:
+            raise NotImplementedError('VGGStyleDiscriminator: input_size 256 -- the reference adds conv5_* / bn5_* but sizes linear1 for a '
+                                      '5 x 5 map, which a 256 input cannot give after six halvings (its forward fails in linear1)')
+        if num_in_ch != 3:
+            raise NotImplementedError(f'VGGStyleDiscriminator: num_in_ch={num_in_ch}; the kernels take RGB images (num_in_ch 3)')
+        if num_feat <= 0 or num_feat % 16:
+            raise NotImplementedError(f'VGGStyleDiscriminator: num_feat={num_feat}; the convolution kernels need a multiple of 16')
+        f = num_feat
+        # the reference's attribute (and so default-initialisation) order
+        self.conv0_0 = nn.Conv2d(num_in_ch, f, 3, 1, 1, bias=True)
+        self.conv0_1 = nn.Conv2d(f, f, 4, 2, 1, bias=False)
+        self.bn0_1 = nn.BatchNorm2d(f, affine=True)
+        for i, (cin, cout) in enumerate(((f, 2 * f), (2 * f, 4 * f), (4 * f, 8 * f), (8 * f, 8 * f)), 1):
+            setattr(self, f'conv{i}_0', nn.Conv2d(cin, cout, 3, 1, 1, bias=False))
+            setattr(self, f'bn{i}_0', nn.BatchNorm2d(cout, affine=True))
+            setattr(self, f'conv{i}_1', nn.Conv2d(cout, cout, 4, 2, 1, bias=False))
+            setattr(self, f'bn{i}_1', nn.BatchNorm2d(cout, affine=True))
+        self.linear1 = nn.Linear(f * 8 * 5 * 5, 100)
+        self.linear2 = nn.Linear(100, 1)
+        self.lrelu = nn.LeakyReLU(negative_slope=0.2, inplace=True)
+
+    def conv_bn_layers(self):
+        """the nine (conv, BatchNorm) pairs after conv0_0, in forward order"""
+        out = [(self.conv0_1, self.bn0_1)]
+        for i in range(1, 5):
+            out += [(getattr(self, f'conv{i}_0'), getattr(self, f'bn{i}_0')), (getattr(self, f'conv{i}_1'), getattr(self, f'bn{i}_1'))]
+        return out
+
+    def forward(self, x):
+        assert x.size(2) == self.input_size, (f'Input size must be identical to input_size, but received {x.size()}.')
+        if not x.is_cuda:
+            raise NotImplementedError('VGGStyleDiscriminator: mrefsr_amd has no CPU path (HIP kernels only)')
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+            raise NotImplementedError(f'VGGStyleDiscriminator: input {tuple(x.shape)} {x.dtype}; fp32 [B,3,H,W] only')
+        for _, bn in self.conv_bn_layers():
+            if not (bn.training and bn.track_running_stats and bn.momentum is not None):
+                raise NotImplementedError('VGGStyleDiscriminator: BatchNorm2d runs in training mode with running statistics and a momentum '
+                                          'only (the model trains net_d; eval-mode statistics have no kernel here)')
+        from . import nhwc_vggdisc
+        return nhwc_vggdisc.discriminator(self, x)

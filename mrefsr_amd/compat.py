@@ -11,7 +11,7 @@ import sys
 import types
 
 _ARCHS = ('MRAPARestorationNet', 'RestorationNet', 'CorrespondenceGenerationArch', 'ContrasMultiExtractorSep',
-          'ContrasExtractorSep', 'VGGFeatureExtractor', 'ImageDiscriminator')
+          'ContrasExtractorSep', 'VGGFeatureExtractor', 'ImageDiscriminator', 'VGGStyleDiscriminator')
 _MODELS = ('MultiRefRestorationModel', 'RefRestorationModel')
 
 

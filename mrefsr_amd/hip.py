@@ -1454,3 +1454,124 @@ def disc_head_dbl(ggf, gs, s, pooled, hidden, w1, w2, slope=0.2, want_gs=True, w
     _lib.call('mrefsr_disc_head_dbl_f32', _p(ggf), _p(gs), _p(s), _p(pooled), _p(hidden), _p(w1), _p(w2), _p(d_gs), _p(d_f), *[_p(t) for t in pw], n,
               h * w, c, j, C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
     return (d_gs, d_f, *pw)
+
+
+# ------------------------------------------------------------------ VGGStyleDiscriminator (csrc/disc_vgg.hip)
+def _vout(n, ks):
+    return n // 2 if ks == 4 else n
+
+
+def disc_vconv_pack_weight(w, cin, dgrad):
+    """w [Cout,CinR,ks,ks] (ks 3 or 4) -> [Cout,ks*ks,cin] (dgrad False) or [cin,ks*ks,Cout] (dgrad True), channels CinR..cin-1 zero"""
+    _chk('disc_vconv_pack_weight', w)
+    cout, cinr, ks = w.shape[0], w.shape[1], w.shape[2]
+    if ks not in (3, 4) or w.shape[3] != ks or cinr > cin:
+        raise ValueError(f'disc_vconv_pack_weight: weight {tuple(w.shape)} for {cin} input channels')
+    out = torch.empty((cin, ks * ks, cout) if dgrad else (cout, ks * ks, cin), device=w.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_vconv_pack_weight_f32', _p(w), _p(out), cout, cinr, cin, ks, 1 if dgrad else 0, _stream())
+    return out
+
+
+def _vconv_ws(device, nbytes):
+    return _wgrad_workspace(device, nbytes) if nbytes > 0 else None
+
+
+def disc_vconv(x, wpk, bias, ks, act_slope=None):
+    """x [N,H,W,Cin] -> [N,Ho,Wo,Cout]: ks 3 (stride 1) or 4 (stride 2), pad 1, + bias, then LeakyReLU(act_slope) unless it is None
+    (wpk from disc_vconv_pack_weight(dgrad=False))"""
+    _chk('disc_vconv', x, wpk, bias)
+    n, h, w, cin = x.shape
+    cout = wpk.shape[0]
+    if tuple(wpk.shape) != (cout, ks * ks, cin):
+        raise ValueError('disc_vconv: packed weight does not match the input channels')
+    y = torch.empty((n, _vout(h, ks), _vout(w, ks), cout), device=x.device, dtype=torch.float32)
+    need = _lib.load().mrefsr_disc_vconv_workspace_bytes(n, h, w, cin, cout, ks, 0)
+    ws = _vconv_ws(x.device, need)
+    with _timed(f'disc_vconv{ks}', 2.0 * y.numel() * ks * ks * cin, detail=True):
+        _lib.call('mrefsr_disc_vconv_f32', _p(x), _p(wpk), _p(bias), _p(y), n, h, w, cin, cout, ks, 0 if act_slope is None else 1,
+                  C.c_float(0.0 if act_slope is None else act_slope), _p(ws), C.c_int64(0 if ws is None else ws.numel()), _stream())
+    return y
+
+
+def disc_vconv_dgrad(dy, wpk_d, in_shape, ks):
+    """input gradient: dy [N,Ho,Wo,Cout] -> dx [N,H,W,Cin] (in_shape = x's shape; wpk_d from disc_vconv_pack_weight(dgrad=True))"""
+    _chk('disc_vconv_dgrad', dy, wpk_d)
+    n, h, w, cin = in_shape
+    cout = dy.shape[3]
+    if tuple(dy.shape) != (n, _vout(h, ks), _vout(w, ks), cout) or tuple(wpk_d.shape) != (cin, ks * ks, cout):
+        raise ValueError('disc_vconv_dgrad: inconsistent shapes')
+    dx = torch.empty((n, h, w, cin), device=dy.device, dtype=torch.float32)
+    need = _lib.load().mrefsr_disc_vconv_workspace_bytes(n, h, w, cin, cout, ks, 1)
+    ws = _vconv_ws(dy.device, need)
+    with _timed(f'disc_vconv{ks}_dgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
+        _lib.call('mrefsr_disc_vconv_dgrad_f32', _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, ks, _p(ws), C.c_int64(0 if ws is None else ws.numel()),
+                  _stream())
+    return dx
+
+
+def disc_vconv_wgrad(x, dy, cin_real, ks):
+    """weight gradient [Cout,cin_real,ks,ks] = sum over the output pixels of x (x) dy"""
+    _chk('disc_vconv_wgrad', x, dy)
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    if tuple(dy.shape) != (n, _vout(h, ks), _vout(w, ks), cout):
+        raise ValueError('disc_vconv_wgrad: inconsistent shapes')
+    need = _lib.load().mrefsr_disc_vconv_wgrad_workspace_bytes(n, h, w, cin, cout, ks)
+    ws = _wgrad_workspace(x.device, need)
+    dw = torch.empty((cout, cin_real, ks, ks), device=x.device, dtype=torch.float32)
+    with _timed(f'disc_vconv{ks}_wgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
+        _lib.call('mrefsr_disc_vconv_wgrad_f32', _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, ks, _p(ws), C.c_int64(ws.numel()), _stream())
+    return dw
+
+
+def disc_lrelu_mask(g, y, slope=0.2):
+    """g * lrelu'(y), the mask from the sign of the LeakyReLU output y"""
+    _chk('disc_lrelu_mask', g, y)
+    if g.shape != y.shape:
+        raise ValueError('disc_lrelu_mask: g and y differ in shape')
+    out = torch.empty_like(g)
+    _lib.call('mrefsr_disc_lrelu_mask_f32', _p(g), _p(y), _p(out), C.c_int64(g.numel()), C.c_float(slope), _stream())
+    return out
+
+
+def disc_linear_head(f, w1, b1, w2, b2, slope=0.2):
+    """f [N,H,W,C] -> (out [N], hidden [N,J]): linear2(lrelu(linear1(f flattened in NCHW order))); w1 [J,C*H*W] (torch's layout),
+    w2 [J] (a contiguous view of linear2.weight)"""
+    _chk('disc_linear_head', f, w1, b1, w2, b2)
+    n, h, w, c = f.shape
+    j = w1.shape[0]
+    if tuple(w1.shape) != (j, c * h * w) or tuple(w2.shape) != (j, ):
+        raise RuntimeError(f'disc_linear_head: linear1 expects {w1.shape[1]} input features, the map [{n},{c},{h},{w}] gives {c * h * w}')
+    out = torch.empty(n, device=f.device, dtype=torch.float32)
+    hidden = torch.empty((n, j), device=f.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_linear_head_fwd_f32', _p(f), _p(w1), _p(b1), _p(w2), _p(b2), _p(out), _p(hidden), n, h * w, c, j, C.c_float(slope),
+              _stream())
+    return out, hidden
+
+
+def disc_linear_head_bwd(gs, hidden, f, w1, w2, slope=0.2, want_f=True, want_params=True):
+    """-> (gf [N,H,W,C] | None, gw1 [J,K], gb1 [J], gw2 [J], gb2 [1]) (the parameter gradients None unless wanted)"""
+    _chk('disc_linear_head_bwd', gs, hidden, f, w1, w2)
+    n, h, w, c = f.shape
+    j = w1.shape[0]
+    dev = gs.device
+    gf = torch.empty_like(f) if want_f else None
+    pw = [torch.empty(sh, device=dev, dtype=torch.float32) for sh in ((j, c * h * w), (j, ), (j, ), (1, ))] if want_params else [None] * 4
+    _lib.call('mrefsr_disc_linear_head_bwd_f32', _p(gs), _p(hidden), _p(f), _p(w1), _p(w2), _p(gf), *[_p(t) for t in pw], n, h * w, c, j,
+              C.c_float(slope), _stream())
+    return (gf, *pw)
+
+
+def disc_linear_head_dbl(ggf, gs, hidden, w1, w2, slope=0.2, want_gs=True, want_params=True):
+    """double backward for an upstream gradient ggf [N,H,W,C] of gf alone -> (d gs [N], d w1 [J,K], d w2 [J]), each None unless wanted"""
+    _chk('disc_linear_head_dbl', ggf, gs, hidden, w1, w2)
+    n, h, w, c = ggf.shape
+    j = w1.shape[0]
+    dev = ggf.device
+    d_gs = torch.empty(n, device=dev, dtype=torch.float32) if want_gs else None
+    d_w1 = torch.empty((j, c * h * w), device=dev, dtype=torch.float32) if want_params else None
+    d_w2 = torch.empty(j, device=dev, dtype=torch.float32) if want_params else None
+    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_linear_head_workspace_bytes(n, j))
+    _lib.call('mrefsr_disc_linear_head_dbl_f32', _p(ggf), _p(gs), _p(hidden), _p(w1), _p(w2), _p(d_gs), _p(d_w1), _p(d_w2), n, h * w, c, j,
+              C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+    return d_gs, d_w1, d_w2

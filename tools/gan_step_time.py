@@ -2,6 +2,7 @@
 """What the adversarial term adds to a training step.
 
   python tools/gan_step_time.py [--steps 10] [--warmup 3] [--out FILE.json] [--trace]
+                                [--network-d {ImageDiscriminator,VGGStyleDiscriminator}]
 
 (1) MultiRefRestorationModel.optimize_parameters at B = 4, K = 5, LR 40 x 40 (GT 160 x 160) in three configurations -- L1 only,
 L1 + ImageDiscriminator(3, 32) with WGAN-GP (gan_weight 1e-3, grad_penalty_weight 10), L1 + vanilla GAN -- ms per step (median of
@@ -9,6 +10,8 @@ L1 + ImageDiscriminator(3, 32) with WGAN-GP (gan_weight 1e-3, grad_penalty_weigh
 (2) the discriminator part alone on [4,3,160,160] images: the WGAN-GP D step (D on real and fake, the penalty, backward) and the G
 step's D forward + backward, on the HIP kernels;
 (3) for comparison, the same D step through torch's NCHW autograd of the same module (MIOpen convolutions) on the same GPU.
+--network-d: the discriminator of (1)-(3): ImageDiscriminator(3, 32) (the default) or VGGStyleDiscriminator(3, 64), for which (4) also
+times every convolution launch of the discriminator (forward, input gradient, weight gradient) at B = 4, 160 x 160, as ms and TF/s.
 --trace: one WGAN-GP step only (for rocprofv3 --kernel-trace --stats)."""
 import argparse
 import json
@@ -28,7 +31,11 @@ GAN = {'wgan_gp': dict(gan_type='wgan', gan_weight=1e-3, grad_penalty_weight=10.
        'vanilla': dict(gan_type='vanilla', gan_weight=1e-3, grad_penalty_weight=0.0)}
 
 
-def _opt(gan):
+NETWORK_D = {'ImageDiscriminator': dict(type='ImageDiscriminator', in_nc=3, ndf=32),
+             'VGGStyleDiscriminator': dict(type='VGGStyleDiscriminator', num_in_ch=3, num_feat=64)}
+
+
+def _opt(gan, network_d='ImageDiscriminator'):
     train = dict(lr_g=1e-4, lr_offset=1e-4, lr_relu2_offset=1e-5, lr_relu3_offset=1e-6, weight_decay_g=0, beta_g=[0.9, 0.999],
                  scheduler=dict(type='MultiStepLR', milestones=[300000], gamma=0.5), net_g_pretrain_steps=0, pixel_criterion='L1Loss',
                  pixel_weight=1.0)
@@ -39,22 +46,24 @@ def _opt(gan):
                network_extractor=dict(type='ContrasMultiExtractorSep'), path={}, train=train)
     if gan:
         train.update(GAN[gan], lr_d=1e-4, beta_d=[0.9, 0.999])
-        opt['network_d'] = dict(type='ImageDiscriminator', in_nc=3, ndf=32)
+        opt['network_d'] = dict(NETWORK_D[network_d])
     return opt
 
 
-def _model(gan):
+def _model(gan, network_d='ImageDiscriminator'):
     import synth
     import synth_disc
+    import synth_vggdisc
     from mrefsr_amd.models import build_model
-    model = build_model(_opt(gan))
+    model = build_model(_opt(gan, network_d))
     nets = [model.get_bare_model(model.net_g), model.net_extractor, model.net_map]
     for net in nets:
         spec = [(k, tuple(v.shape)) for k, v in net.state_dict().items()]
         net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.state_dict(spec).items()})
     if gan:
         spec = [(k, tuple(v.shape)) for k, v in model.net_d.state_dict().items()]
-        model.net_d.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth_disc.state_dict(spec).items()})
+        sd = (synth_vggdisc if network_d == 'VGGStyleDiscriminator' else synth_disc).state_dict(spec)
+        model.net_d.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
     samples = [synth.sr_sample(f'gan_time/s{i}', 5, 40, 40) for i in range(4)]
     model.feed_data({n: torch.from_numpy(np.stack([s[n] for s in samples])) for n in samples[0]})
     return model
@@ -84,6 +93,14 @@ def _d_step(net, real, fake, gan, gp):
 
 def _torch_d(net):
     """the same module run through torch's own NCHW autograd (MIOpen convolutions, native BatchNorm)"""
+    if hasattr(net, 'conv_bn_layers'):   # VGGStyleDiscriminator: its own forward is the reference's, written out
+        def vgg(x):
+            h = F.leaky_relu(net.conv0_0(x), 0.2)
+            for conv, bn in net.conv_bn_layers():
+                h = F.leaky_relu(bn(conv(h)), 0.2)
+            return net.linear2(F.leaky_relu(net.linear1(h.reshape(h.shape[0], -1)), 0.2))
+        return vgg
+
     def fwd(x):
         h = x
         for blk in net.blocks():
@@ -93,23 +110,47 @@ def _torch_d(net):
     return fwd
 
 
+def _vgg_layers(steps, warmup, b=4, nf=64):
+    """ms and TF/s of every convolution launch of VGGStyleDiscriminator(3, nf) at [b,3,160,160] (forward, input and weight gradient)"""
+    from mrefsr_amd import hip
+    out, cin, h = [], 4, 160
+    chans = [nf, nf, 2 * nf, 2 * nf, 4 * nf, 4 * nf, 8 * nf, 8 * nf, 8 * nf, 8 * nf]
+    for i, c in enumerate(chans):
+        ks = 3 if i % 2 == 0 else 4
+        x = torch.randn(b, h, h, cin, device='cuda')
+        w = torch.randn(c, cin, ks, ks, device='cuda') * 0.05
+        ho = h // 2 if ks == 4 else h
+        dy = torch.randn(b, ho, ho, c, device='cuda')
+        wpk, wpd = hip.disc_vconv_pack_weight(w, cin, False), hip.disc_vconv_pack_weight(w, cin, True)
+        flop = 2.0 * b * ho * ho * c * cin * ks * ks
+        row = dict(layer=f'conv{i // 2}_{i % 2}', ks=ks, cin=cin, cout=c, out=ho, gflop=flop / 1e9)
+        for name, fn in (('fwd', lambda: hip.disc_vconv(x, wpk, None, ks)), ('dgrad', lambda: hip.disc_vconv_dgrad(dy, wpd, tuple(x.shape), ks)),
+                         ('wgrad', lambda: hip.disc_vconv_wgrad(x, dy, cin, ks))):
+            ms = _median_ms(fn, steps, warmup)
+            row[f'{name}_ms'], row[f'{name}_tflops'] = ms, flop / ms / 1e9
+        out.append(row)
+        cin, h = c, ho
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--out')
     ap.add_argument('--trace', action='store_true')
+    ap.add_argument('--network-d', choices=sorted(NETWORK_D), default='ImageDiscriminator')
     a = ap.parse_args()
     torch.cuda.set_device(0)
     if a.trace:
-        model = _model('wgan_gp')
+        model = _model('wgan_gp', a.network_d)
         model.optimize_parameters(1)
         torch.cuda.synchronize()
         print('traced one WGAN-GP step')
         return
     res = {}
     for cfg in (None, 'wgan_gp', 'vanilla'):
-        model = _model(cfg)
+        model = _model(cfg, a.network_d)
         it = [0]
 
         def step():
@@ -123,7 +164,7 @@ def main():
     g = torch.Generator().manual_seed(0)
     real = (torch.rand(4, 3, 160, 160, generator=g) * 2 - 1).cuda()
     fake = (torch.rand(4, 3, 160, 160, generator=g) * 2 - 1).cuda()
-    net = build_network(dict(type='ImageDiscriminator')).cuda().train()
+    net = build_network(dict(NETWORK_D[a.network_d])).cuda().train()
     gan, gp = GANLoss('wgan'), GradientPenaltyLoss(10.0)
     res['d_step_wgan_gp_ms_hip'] = _median_ms(lambda: _d_step(net, real, fake, gan, gp), a.steps, a.warmup)
     fk = fake.clone().requires_grad_(True)
@@ -147,6 +188,8 @@ def main():
     res['d_step_wgan_gp_ms_torch_miopen'] = _median_ms(lambda: _d_step(tnet, real, fake, gan, gp), a.steps, a.warmup)
     res['adversarial_adds_ms_wgan_gp'] = res['step_ms_wgan_gp'] - res['step_ms_l1']
     res['adversarial_adds_ms_vanilla'] = res['step_ms_vanilla'] - res['step_ms_l1']
+    if a.network_d == 'VGGStyleDiscriminator':
+        res['layers'] = _vgg_layers(a.steps, a.warmup)
     print(json.dumps(res, indent=1))
     if a.out:
         with open(a.out, 'w') as f:
