@@ -661,6 +661,36 @@ int mrefsr_disc_linear_head_dbl_f32(const float *ggf, const float *gs, const flo
                                     float *d_w1, float *d_w2, int N, int HW, int C, int J, float slope, void *workspace, int64_t workspace_bytes,
                                     mrefsr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Validation metrics: basicsr/utils/img_util.py:38-94 (tensor2img) and basicsr/metrics/psnr_ssim.py (calculate_psnr,
+ * calculate_ssim) as restated by mrefsr_amd/metrics.py, on the device (the reference runs them in numpy on the host).
+ * --------------------------------------------------------------------------------------------- */
+
+/* mrefsr_tensor2img_u8: tensor2img's quantisation, x [N][C][H][W] fp32 -> img [N][H][W][C] uint8: clamp to [0, 1], times 255.0f in
+ *   fp32, round half to even, to uint8 (NaN gives 0). */
+int mrefsr_tensor2img_u8(const float *x, uint8_t *img, int N, int C, int H, int W, mrefsr_stream_t stream);
+
+/* mrefsr_val_metrics_f32: per image of out [N][3][H][W] against gt [N][3][Hg][Wg] (fp32 in [0, 1]), both quantised as above:
+ *   the valid region is rows [0, oh) and columns [0, ow) (sizes [N][2] = (oh, ow) in HOST memory, the dataset's zero-padding crop;
+ *   NULL: oh = H, ow = W, and the shapes must be equal); the metrics see that region less crop_border on every side, h x w.
+ *   res [N][8] int64 (device), one row per image, fp64 values stored by their bits:
+ *     [0] sum of squared uint8 differences over the h x w x 3 values (exact)
+ *     [1] count of non-finite values of out and gt in the valid region
+ *     [2] fp64 sum of squared differences of the Y planes (metrics.rgb_to_y, BT.601) over h x w
+ *     [3] fp64 sum of the Y SSIM map over (h - 10) x (w - 10)        (flags & MREFSR_VALM_SSIM_Y, else 0)
+ *     [4..6] the same for the R, G and B planes                       (flags & MREFSR_VALM_SSIM_RGB, else 0)
+ *     [7] 0
+ *   The caller forms mse = [0] / (3 h w) and 10 log10(255^2 / mse) exactly as calculate_psnr does; SSIM is the map sum over its
+ *   count.  SSIM: 11 x 11 Gaussian window (sigma 1.5) as a separable "valid" filter in fp64, c1 = (0.01 * 255)^2,
+ *   c2 = (0.03 * 255)^2.  Needs h, w >= 1, and >= 11 with an SSIM flag.  img: NULL, or the [N][H][W][3] uint8 image of out
+ *   (mrefsr_tensor2img_u8's).  Fixed summation orders, no atomics: bitwise reproducible.  Up to 32 images per set of three
+ *   launches.  Workspace: mrefsr_val_metrics_workspace_bytes. */
+#define MREFSR_VALM_SSIM_Y 1
+#define MREFSR_VALM_SSIM_RGB 2
+int64_t mrefsr_val_metrics_workspace_bytes(int N, int H, int W);
+int mrefsr_val_metrics_f32(const float *out, const float *gt, int N, int H, int W, int Hg, int Wg, const int *sizes, int crop_border,
+                           int flags, uint8_t *img, int64_t *res, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -133,6 +133,9 @@ SIGNATURES = {
     'mrefsr_disc_linear_head_dbl_f32': (_i, [_vp] * 8 + [_i, _i, _i, _i, _f, _vp, _i64, _vp]),
     'mrefsr_upfirdn2d_f32': (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     'mrefsr_upfirdn2d': (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
+    'mrefsr_tensor2img_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'mrefsr_val_metrics_workspace_bytes': (_i64, [_i, _i, _i]),
+    'mrefsr_val_metrics_f32': (_i, [_vp, _vp] + [_i] * 5 + [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

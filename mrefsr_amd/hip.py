@@ -1575,3 +1575,47 @@ def disc_linear_head_dbl(ggf, gs, hidden, w1, w2, slope=0.2, want_gs=True, want_
     _lib.call('mrefsr_disc_linear_head_dbl_f32', _p(ggf), _p(gs), _p(hidden), _p(w1), _p(w2), _p(d_gs), _p(d_w1), _p(d_w2), n, h * w, c, j,
               C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
     return d_gs, d_w1, d_w2
+
+
+# ------------------------------------------------------------------ validation metrics (csrc/metrics.hip)
+VALM_SSIM_Y, VALM_SSIM_RGB = 1, 2
+_metrics_ws = {}
+
+
+def tensor2img_u8(x):
+    """x [N,C,H,W] fp32 -> [N,H,W,C] uint8 with the quantisation of metrics.tensor2img"""
+    _chk('tensor2img', x)
+    if x.dim() != 4:
+        raise ValueError(f'tensor2img: expected [N,C,H,W], got {tuple(x.shape)}')
+    n, c, h, w = x.shape
+    img = torch.empty((n, h, w, c), device=x.device, dtype=torch.uint8)
+    _lib.call('mrefsr_tensor2img_u8', _p(x), _p(img), n, c, h, w, _stream())
+    return img
+
+
+def val_metrics(out, gt, crop_border, sizes=None, flags=VALM_SSIM_Y, want_img=False):
+    """out [N,3,H,W], gt [N,3,Hg,Wg] fp32; sizes: None or N pairs (oh, ow), the valid region of each image ->
+    (res int64 [N,8] on the device: the rows of mrefsr_val_metrics_f32, the output's uint8 image [N,H,W,3] or None)"""
+    _chk('val_metrics', out, gt)
+    if out.dim() != 4 or gt.dim() != 4 or out.shape[1] != 3 or gt.shape[1] != 3 or out.shape[0] != gt.shape[0]:
+        raise ValueError(f'val_metrics: expected [N,3,H,W] output and GT, got {tuple(out.shape)} and {tuple(gt.shape)}')
+    n, _, h, w = out.shape
+    hg, wg = gt.shape[2:]
+    sz = C.c_void_p(0)
+    if sizes is not None:
+        flat = [int(v) for s in sizes for v in tuple(s)[:2]]
+        if len(flat) != 2 * n:
+            raise ValueError(f'val_metrics: {len(flat) // 2} valid sizes for {n} images')
+        sz_host = (C.c_int * len(flat))(*flat)     # host memory, read before the call returns
+        sz = C.cast(sz_host, C.c_void_p)
+    lib = _lib.load()
+    need = lib.mrefsr_val_metrics_workspace_bytes(n, h, w)
+    key = (out.device.index, torch.cuda.current_stream().cuda_stream)
+    ws = _metrics_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _metrics_ws[key] = torch.empty(need, device=out.device, dtype=torch.uint8)
+    res = torch.empty((n, 8), device=out.device, dtype=torch.int64)
+    img = torch.empty((n, h, w, 3), device=out.device, dtype=torch.uint8) if want_img else None
+    _lib.call('mrefsr_val_metrics_f32', _p(out), _p(gt), n, h, w, hg, wg, sz, int(crop_border), int(flags), _p(img), _p(res), _p(ws),
+              C.c_int64(ws.numel()), _stream())
+    return res, img

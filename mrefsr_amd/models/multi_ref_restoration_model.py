@@ -538,24 +538,50 @@ class MultiRefRestorationModel:
         if self.opt.get('rank', 0) == 0:  # rank 0 only, like the reference (:312-314)
             return self.nondist_validation(dataloader, current_iter, tb_logger, save_img)
 
+    def _metrics_on_device(self):
+        """opt['val']['metrics_on_device'] (off by default): validation's PSNR, PSNR-Y and SSIM-Y on the HIP kernels of
+        csrc/metrics.hip (metrics.validation_metrics) instead of numpy on the host; the same numbers, logs and return value"""
+        return bool((self.opt.get('val') or {}).get('metrics_on_device'))
+
     def nondist_validation(self, dataloader, current_iter, tb_logger, save_img):
         """per image: feed_data -> test -> uint8 image -> crop the dataset's zero padding -> [PNG] -> PSNR (RGB), PSNR (Y),
         SSIM (Y) with crop_border from the options (ref :324-386).  save_img writes
-        path.visualization/<img>/<img>_<iter>.png while training, path.visualization/<dataset>/<img>_<name>[_suffix].png when testing."""
-        from ..metrics import calculate_psnr, calculate_ssim, imwrite, tensor2img
+        path.visualization/<img>/<img>_<iter>.png while training, path.visualization/<dataset>/<img>_<name>[_suffix].png when testing.
+        With val.metrics_on_device the metrics run on the GPU and only their scalars (and, for save_img, the image) come back; an
+        image with non-finite values in its output or GT takes the numpy path."""
+        from ..metrics import calculate_psnr, calculate_ssim, imwrite, tensor2img, validation_metrics
         logger = logging.getLogger('basicsr')
         dataset_name = getattr(getattr(dataloader, 'dataset', None), 'opt', {}).get('name', 'val')
+        on_device = self._metrics_on_device()
         psnrs, psnrs_y, ssims_y = [], [], []
         for idx, val_data in enumerate(dataloader):
             lq_path = val_data.get('lq_path', [f'{idx:04d}'])
             img_name = os.path.splitext(os.path.basename(lq_path[0] if isinstance(lq_path, (list, tuple)) else lq_path))[0]
             self.feed_data(val_data)
             self.test()
-            sr_img = tensor2img(self.output[:1])
-            gt_img = tensor2img(self.gt[:1])
+            cb = self.opt['crop_border']
+            size = None
             if 'padding' in val_data and val_data['padding']:
-                oh, ow = [int(v) for v in val_data['original_size']][:2]
-                sr_img, gt_img = sr_img[:oh, :ow], gt_img[:oh, :ow]
+                size = [int(v) for v in val_data['original_size']][:2]
+            dev = None
+            if on_device:
+                dev = validation_metrics(self.output[:1], self.gt[:1], cb, sizes=None if size is None else [size], return_img=save_img)
+                dev = dev if dev['finite'][0] else None
+            if dev is not None:
+                sr_img = None
+                if save_img:
+                    img = dev['img'][0]
+                    sr_img = (img if size is None else img[:size[0], :size[1]]).cpu().numpy()
+                psnr, psnr_y, ssim_y = dev['psnr'][0], dev['psnr_y'][0], dev['ssim_y'][0]
+            else:
+                sr_img = tensor2img(self.output[:1])
+                gt_img = tensor2img(self.gt[:1])
+                if size is not None:
+                    oh, ow = size
+                    sr_img, gt_img = sr_img[:oh, :ow], gt_img[:oh, :ow]
+                psnr = calculate_psnr(sr_img, gt_img, crop_border=cb)
+                psnr_y = calculate_psnr(sr_img, gt_img, crop_border=cb, test_y_channel=True)
+                ssim_y = calculate_ssim(sr_img, gt_img, crop_border=cb, test_y_channel=True)
             if save_img:
                 vis = self.opt['path']['visualization']
                 if self.opt['is_train']:
@@ -564,10 +590,9 @@ class MultiRefRestorationModel:
                     suffix = f"_{self.opt['suffix']}" if self.opt.get('suffix') else ''
                     save_path = os.path.join(vis, dataset_name, f"{img_name}_{self.opt['name']}{suffix}.png")
                 imwrite(sr_img, save_path)
-            cb = self.opt['crop_border']
-            psnrs.append(calculate_psnr(sr_img, gt_img, crop_border=cb))
-            psnrs_y.append(calculate_psnr(sr_img, gt_img, crop_border=cb, test_y_channel=True))
-            ssims_y.append(calculate_ssim(sr_img, gt_img, crop_border=cb, test_y_channel=True))
+            psnrs.append(psnr)
+            psnrs_y.append(psnr_y)
+            ssims_y.append(ssim_y)
             if not self.is_train:
                 logger.info(f'# img {img_name} # PSNR: {psnrs[-1]:.4e} # PSNR_Y: {psnrs_y[-1]:.4e} # SSIM_Y: {ssims_y[-1]:.4e}.')
         n = max(len(psnrs), 1)
