@@ -691,6 +691,45 @@ int64_t mrefsr_val_metrics_workspace_bytes(int N, int H, int W);
 int mrefsr_val_metrics_f32(const float *out, const float *gt, int N, int H, int W, int Hg, int Wg, const int *sizes, int crop_border,
                            int flags, uint8_t *img, int64_t *res, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
 
+/* ---- UNetDiscriminatorSN of the adversarial training step (basicsr/archs/discriminator_arch.py:127-200; the same D step and
+ * penalty as above): the kernels of mrefsr_amd/archs/nhwc_unetdisc.py that the entry points above do not cover.  conv0 .. conv8 run
+ * on mrefsr_disc_vconv*_f32 (conv1 .. conv8 with W = W_orig / sigma), the image packing on mrefsr_disc_pack_image_f32.
+ * Channels-last fp32 maps, fixed summation orders (no float atomics).
+ *
+ * mrefsr_disc_sn_power_f32: torch.nn.utils.spectral_norm (n_power_iterations 1, dim 0) of L <= 8 layers in four launches (two when
+ *   update is 0).  Host arrays of L device pointers: w[l] = W_orig as a rows[l] x cols[l] matrix, u[l] [rows], v[l] [cols].  update 1
+ *   (training): v = W^T u / max(|W^T u|, eps), u = W v / max(|W v|, eps), written to u[l], v[l] in place and to the snapshots snap_u
+ *   [sum rows], snap_v [sum cols] (layers concatenated); update 0 (eval): the snapshots are copies of u, v.  sigma[l] = snap_u . (W
+ *   snap_v).  Workspace: mrefsr_disc_sn_workspace_bytes.
+ * mrefsr_disc_sn_scale_f32: w[l] = w_orig[l] / sigma[l] (sigma in device memory) for every layer in one launch.
+ * mrefsr_disc_sn_bwd_f32: dw[l] = g[l] / sigma - (<g[l], w_orig[l]> / sigma^2) u v^T with the snapshot's u, v, sigma (the gradient of
+ *   W = W_orig / sigma(W_orig) at fixed u, v); the dot product split into chunks added in a fixed order.  Workspace:
+ *   mrefsr_disc_sn_bwd_workspace_bytes. */
+int64_t mrefsr_disc_sn_workspace_bytes(const int *rows, const int *cols, int L);
+int mrefsr_disc_sn_power_f32(const float *const *w, float *const *u, float *const *v, const int *rows, const int *cols, int L, int update, float eps,
+                             float *snap_u, float *snap_v, float *sigma, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_sn_scale_f32(const float *const *w_orig, float *const *w, const int *rows, const int *cols, int L, const float *sigma,
+                             mrefsr_stream_t stream);
+int64_t mrefsr_disc_sn_bwd_workspace_bytes(const int *rows, const int *cols, int L);
+int mrefsr_disc_sn_bwd_f32(const float *const *g, const float *const *w_orig, float *const *dw, const int *rows, const int *cols, int L,
+                           const float *snap_u, const float *snap_v, const float *sigma, void *workspace, int64_t workspace_bytes,
+                           mrefsr_stream_t stream);
+/* mrefsr_disc_up2_f32: F.interpolate(y (+ skip), scale_factor=2, mode='bilinear', align_corners=False) on y [N][h][w][C] (skip may be
+ *   NULL) -> out [N][2h][2w][C], C a multiple of 4 (16-byte aligned tensors).  mrefsr_disc_up2_adj_f32: its adjoint, g [N][2h][2w][C]
+ *   -> out [N][h][w][C], a gather over at most 4 x 4 taps.  mrefsr_disc_add_f32: out = a + b. */
+int mrefsr_disc_up2_f32(const float *y, const float *skip, float *out, int N, int h, int w, int C, mrefsr_stream_t stream);
+int mrefsr_disc_up2_adj_f32(const float *g, float *out, int N, int h, int w, int C, mrefsr_stream_t stream);
+int mrefsr_disc_add_f32(const float *a, const float *b, float *out, int64_t n, mrefsr_stream_t stream);
+/* conv9 (nn.Conv2d(C, 1, 3, 1, 1), discriminator_arch.py:150): x [N][H][W][C] -> y [N][H][W] (+ bias[0] when bias is not NULL);
+ *   w in torch's [1][C][3][3] layout; C a multiple of 4, at most 512.  _dgrad: gy [N][H][W] -> dx [N][H][W][C].  _wgrad: dw [1][C][3][3]
+ *   = sum over the pixels of x (x) gy, split over pixel chunks added in a fixed order (workspace: mrefsr_disc_conv9_wgrad_workspace_bytes);
+ *   the bias gradient is mrefsr_disc_bias_grad_f32 of gy. */
+int mrefsr_disc_conv9_f32(const float *x, const float *w, const float *bias, float *y, int N, int H, int W, int C, mrefsr_stream_t stream);
+int mrefsr_disc_conv9_dgrad_f32(const float *gy, const float *w, float *dx, int N, int H, int W, int C, mrefsr_stream_t stream);
+int64_t mrefsr_disc_conv9_wgrad_workspace_bytes(int N, int H, int W, int C);
+int mrefsr_disc_conv9_wgrad_f32(const float *x, const float *gy, float *dw, int N, int H, int W, int C, void *workspace, int64_t workspace_bytes,
+                                mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

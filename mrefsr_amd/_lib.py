@@ -131,6 +131,18 @@ SIGNATURES = {
     'mrefsr_disc_linear_head_bwd_f32': (_i, [_vp] * 10 + [_i, _i, _i, _i, _f, _vp]),
     'mrefsr_disc_linear_head_workspace_bytes': (_i64, [_i, _i]),
     'mrefsr_disc_linear_head_dbl_f32': (_i, [_vp] * 8 + [_i, _i, _i, _i, _f, _vp, _i64, _vp]),
+    'mrefsr_disc_sn_workspace_bytes': (_i64, [_vp, _vp, _i]),
+    'mrefsr_disc_sn_power_f32': (_i, [_vp] * 5 + [_i, _i, _f] + [_vp] * 4 + [_i64, _vp]),
+    'mrefsr_disc_sn_scale_f32': (_i, [_vp] * 4 + [_i, _vp, _vp]),
+    'mrefsr_disc_sn_bwd_workspace_bytes': (_i64, [_vp, _vp, _i]),
+    'mrefsr_disc_sn_bwd_f32': (_i, [_vp] * 5 + [_i] + [_vp] * 4 + [_i64, _vp]),
+    'mrefsr_disc_up2_f32': (_i, [_vp] * 3 + [_i] * 4 + [_vp]),
+    'mrefsr_disc_up2_adj_f32': (_i, [_vp] * 2 + [_i] * 4 + [_vp]),
+    'mrefsr_disc_add_f32': (_i, [_vp] * 3 + [_i64, _vp]),
+    'mrefsr_disc_conv9_f32': (_i, [_vp] * 4 + [_i] * 4 + [_vp]),
+    'mrefsr_disc_conv9_dgrad_f32': (_i, [_vp] * 3 + [_i] * 4 + [_vp]),
+    'mrefsr_disc_conv9_wgrad_workspace_bytes': (_i64, [_i] * 4),
+    'mrefsr_disc_conv9_wgrad_f32': (_i, [_vp] * 3 + [_i] * 4 + [_vp, _i64, _vp]),
     'mrefsr_upfirdn2d_f32': (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     'mrefsr_upfirdn2d': (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
     'mrefsr_tensor2img_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1,15 +1,19 @@
-"""ImageDiscriminator (basicsr/archs/discriminator_arch.py:10-45) and VGGStyleDiscriminator (:47-125): the discriminators of the
-adversarial training step.
+"""ImageDiscriminator (basicsr/archs/discriminator_arch.py:10-45), VGGStyleDiscriminator (:47-125) and UNetDiscriminatorSN
+(:127-200): the discriminators of the adversarial training step.
 
 Same module tree, parameter and buffer names (74 state_dict entries at ndf 32) and initialisation (srntt_init_weights, normal
 0.02, BatchNorm weights N(1, 0.02)) as the reference, so its checkpoints load unchanged.  The forward runs on the kernels of
 csrc/disc.hip through the autograd nodes of archs/nhwc_disc.py, which are differentiable twice (the WGAN-GP gradient penalty).
 VGGStyleDiscriminator keeps the reference's attribute order and PyTorch's default initialisation, so under one torch.manual_seed it
-builds the reference's exact parameters; its forward runs on csrc/disc_vgg.hip through archs/nhwc_vggdisc.py.
+builds the reference's exact parameters; its forward runs on csrc/disc_vgg.hip through archs/nhwc_vggdisc.py.  UNetDiscriminatorSN
+does the same with torch.nn.utils.spectral_norm (weight_orig / weight_u / weight_v, torch's own state_dict hooks); its forward runs
+on csrc/disc_unet.hip and disc_vgg.hip through archs/nhwc_unetdisc.py.
 Construction and state_dict work on the CPU; forward on a CPU tensor raises NotImplementedError, as every op of the package does.
 """
 import torch
 from torch import nn
+from torch.nn.utils import spectral_norm
+from torch.nn.utils.spectral_norm import SpectralNorm
 
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import srntt_init_weights
@@ -102,3 +106,67 @@ class VGGStyleDiscriminator(nn.Module):
                                           'only (the model trains net_d; eval-mode statistics have no kernel here)')
         from . import nhwc_vggdisc
         return nhwc_vggdisc.discriminator(self, x)
+
+
+@ARCH_REGISTRY.register(suffix='basicsr')
+class UNetDiscriminatorSN(nn.Module):
+    """Real-ESRGAN's U-Net discriminator with spectral normalisation (conv1 .. conv8), registered as the reference registers it
+    (UNetDiscriminatorSN_basicsr; `type: UNetDiscriminatorSN` resolves through the registry's suffix fallback).
+
+    forward does not call the conv modules: their spectral-norm pre-hooks would run the power iteration on rocBLAS.  It runs the
+    iteration on the kernels instead (once per forward in training mode, updating weight_u / weight_v in place; none in eval mode),
+    so convN.weight, the attribute the hook refreshes, keeps whatever the last hook call left in it: read W_orig / sigma from
+    nhwc_unetdisc.spectral_norm_weights, not from there.  Input H and W must be multiples of 8."""
+
+    def __init__(self, num_in_ch, num_feat=64, skip_connection=True):
+        super().__init__()
+        if num_in_ch != 3:
+            raise NotImplementedError(f'UNetDiscriminatorSN: num_in_ch={num_in_ch}; the kernels take RGB images (num_in_ch 3)')
+        if num_feat <= 0 or num_feat % 16:
+            raise NotImplementedError(f'UNetDiscriminatorSN: num_feat={num_feat}; the convolution kernels need a multiple of 16')
+        self.skip_connection = skip_connection
+        norm = spectral_norm
+        f = num_feat
+        # the reference's attribute (and so default-initialisation and power-iteration RNG) order
+        self.conv0 = nn.Conv2d(num_in_ch, f, kernel_size=3, stride=1, padding=1)
+        self.conv1 = norm(nn.Conv2d(f, f * 2, 4, 2, 1, bias=False))
+        self.conv2 = norm(nn.Conv2d(f * 2, f * 4, 4, 2, 1, bias=False))
+        self.conv3 = norm(nn.Conv2d(f * 4, f * 8, 4, 2, 1, bias=False))
+        self.conv4 = norm(nn.Conv2d(f * 8, f * 4, 3, 1, 1, bias=False))
+        self.conv5 = norm(nn.Conv2d(f * 4, f * 2, 3, 1, 1, bias=False))
+        self.conv6 = norm(nn.Conv2d(f * 2, f, 3, 1, 1, bias=False))
+        self.conv7 = norm(nn.Conv2d(f, f, 3, 1, 1, bias=False))
+        self.conv8 = norm(nn.Conv2d(f, f, 3, 1, 1, bias=False))
+        self.conv9 = nn.Conv2d(f, 1, 3, 1, 1)
+
+    def sn_convs(self):
+        return [getattr(self, f'conv{i}') for i in range(1, 9)]
+
+    def sn_hooks(self):
+        """the SpectralNorm pre-hook of each of conv1 .. conv8; refuses what the kernels do not compute"""
+        hooks = []
+        for i, conv in enumerate(self.sn_convs(), 1):
+            found = [h for h in conv._forward_pre_hooks.values() if isinstance(h, SpectralNorm) and h.name == 'weight']
+            if len(found) != 1:
+                raise NotImplementedError(f'UNetDiscriminatorSN: conv{i} has no spectral norm of its weight (torch.nn.utils.spectral_norm)')
+            h = found[0]
+            if h.n_power_iterations != 1 or h.dim != 0:
+                raise NotImplementedError(f'UNetDiscriminatorSN: conv{i} spectral norm with n_power_iterations={h.n_power_iterations}, '
+                                          f'dim={h.dim}; the kernels run the reference\'s (1 iteration, dim 0)')
+            hooks.append(h)
+        return hooks
+
+    def sn_eps(self):
+        eps = {h.eps for h in self.sn_hooks()}
+        if len(eps) != 1:
+            raise NotImplementedError(f'UNetDiscriminatorSN: spectral norms with different eps {sorted(eps)}')
+        return eps.pop()
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise NotImplementedError('UNetDiscriminatorSN: mrefsr_amd has no CPU path (HIP kernels only)')
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+            raise NotImplementedError(f'UNetDiscriminatorSN: input {tuple(x.shape)} {x.dtype}; fp32 [B,3,H,W] only')
+        self.sn_hooks()
+        from . import nhwc_unetdisc
+        return nhwc_unetdisc.discriminator(self, x)

@@ -11,7 +11,8 @@ import sys
 import types
 
 _ARCHS = ('MRAPARestorationNet', 'RestorationNet', 'CorrespondenceGenerationArch', 'ContrasMultiExtractorSep',
-          'ContrasExtractorSep', 'VGGFeatureExtractor', 'ImageDiscriminator', 'VGGStyleDiscriminator')
+          'ContrasExtractorSep', 'VGGFeatureExtractor', 'ImageDiscriminator', 'VGGStyleDiscriminator',
+          'UNetDiscriminatorSN_basicsr')
 _MODELS = ('MultiRefRestorationModel', 'RefRestorationModel')
 
 

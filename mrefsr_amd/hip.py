@@ -1619,3 +1619,139 @@ def val_metrics(out, gt, crop_border, sizes=None, flags=VALM_SSIM_Y, want_img=Fa
     _lib.call('mrefsr_val_metrics_f32', _p(out), _p(gt), n, h, w, hg, wg, sz, int(crop_border), int(flags), _p(img), _p(res), _p(ws),
               C.c_int64(ws.numel()), _stream())
     return res, img
+
+
+# ------------------------------------------------------------------ UNetDiscriminatorSN (csrc/disc_unet.hip)
+def _c(t):
+    return t if t is None or t.is_contiguous() else t.contiguous()
+
+
+def _ptrs(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _sn_geometry(ws):
+    return (C.c_int * len(ws))(*[w.shape[0] for w in ws]), (C.c_int * len(ws))(*[w[0].numel() for w in ws])
+
+
+def disc_sn_power(w_origs, us, vs, update, eps=1e-12):
+    """spectral norm of the layers w_origs ([Cout,...] each, at most 8) -> (snap_u [sum Cout], snap_v [sum fan-in], sigma [L]): one
+    power iteration from the buffers us, vs, written back in place, when update; else the stored u, v as they are"""
+    _chk('disc_sn_power', *w_origs, *us, *vs)
+    if not 1 <= len(w_origs) <= 8 or not len(w_origs) == len(us) == len(vs):
+        raise ValueError('disc_sn_power: 1 to 8 layers, one u and one v each')
+    for w, u, v in zip(w_origs, us, vs):
+        if not (w.is_contiguous() and u.is_contiguous() and v.is_contiguous()) or u.numel() != w.shape[0] or v.numel() != w[0].numel():
+            raise ValueError(f'disc_sn_power: weight {tuple(w.shape)} with u {tuple(u.shape)}, v {tuple(v.shape)}')
+    rows, cols = _sn_geometry(w_origs)
+    dev = w_origs[0].device
+    snap_u = torch.empty(sum(rows), device=dev, dtype=torch.float32)
+    snap_v = torch.empty(sum(cols), device=dev, dtype=torch.float32)
+    sigma = torch.empty(len(w_origs), device=dev, dtype=torch.float32)
+    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_sn_workspace_bytes(rows, cols, len(w_origs)))
+    with _timed('disc_sn_power', 4.0 * sum(r * c for r, c in zip(rows, cols)), detail=True):
+        _lib.call('mrefsr_disc_sn_power_f32', _ptrs(w_origs), _ptrs(us), _ptrs(vs), rows, cols, len(w_origs), 1 if update else 0, C.c_float(eps),
+                  _p(snap_u), _p(snap_v), _p(sigma), _p(ws), C.c_int64(ws.numel()), _stream())
+    return snap_u, snap_v, sigma
+
+
+def disc_sn_scale(w_origs, sigma):
+    """[w_orig / sigma[l]] for every layer, one launch"""
+    _chk('disc_sn_scale', *w_origs, sigma)
+    outs = [torch.empty_like(w, memory_format=torch.contiguous_format) for w in w_origs]
+    rows, cols = _sn_geometry(w_origs)
+    _lib.call('mrefsr_disc_sn_scale_f32', _ptrs([_c(w) for w in w_origs]), _ptrs(outs), rows, cols, len(w_origs), _p(sigma), _stream())
+    return outs
+
+
+def disc_sn_bwd(gs, w_origs, snap_u, snap_v, sigma):
+    """[g / sigma - (<g, w_orig> / sigma^2) u v^T] per layer (u, v, sigma from disc_sn_power)"""
+    _chk('disc_sn_bwd', *gs, *w_origs, snap_u, snap_v, sigma)
+    if any(g.shape != w.shape or not g.is_contiguous() or not w.is_contiguous() for g, w in zip(gs, w_origs)):
+        raise ValueError('disc_sn_bwd: gradients must be contiguous and shaped like the weights')
+    rows, cols = _sn_geometry(w_origs)
+    dws = [torch.empty_like(w) for w in w_origs]
+    ws = _wgrad_workspace(gs[0].device, _lib.load().mrefsr_disc_sn_bwd_workspace_bytes(rows, cols, len(w_origs)))
+    with _timed('disc_sn_bwd', 4.0 * sum(r * c for r, c in zip(rows, cols)), detail=True):
+        _lib.call('mrefsr_disc_sn_bwd_f32', _ptrs(gs), _ptrs(w_origs), _ptrs(dws), rows, cols, len(w_origs), _p(snap_u), _p(snap_v), _p(sigma), _p(ws),
+                  C.c_int64(ws.numel()), _stream())
+    return dws
+
+
+def _aligned(name, *ts):
+    for t in ts:
+        if t is not None and (not t.is_contiguous() or t.data_ptr() % 16):
+            raise ValueError(f'{name}: tensors must be contiguous and 16-byte aligned')
+
+
+def disc_up2(y, skip=None):
+    """bilinear x2 (align_corners False) of y (+ skip) [N,h,w,C] -> [N,2h,2w,C]"""
+    _chk('disc_up2', y, skip)
+    _aligned('disc_up2', y, skip)
+    n, h, w, c = y.shape
+    if skip is not None and skip.shape != y.shape:
+        raise RuntimeError(f'disc_up2: the skip addend {tuple(skip.shape)} does not match {tuple(y.shape)}')
+    out = torch.empty((n, 2 * h, 2 * w, c), device=y.device, dtype=torch.float32)
+    with _timed('disc_up2', detail=True, nbytes=4.0 * (y.numel() * (1 if skip is None else 2) + out.numel())):
+        _lib.call('mrefsr_disc_up2_f32', _p(y), _p(skip), _p(out), n, h, w, c, _stream())
+    return out
+
+
+def disc_up2_adj(g):
+    """adjoint of disc_up2: g [N,2h,2w,C] -> [N,h,w,C]"""
+    _chk('disc_up2_adj', g)
+    _aligned('disc_up2_adj', g)
+    n, h2, w2, c = g.shape
+    if h2 % 2 or w2 % 2:
+        raise ValueError(f'disc_up2_adj: {h2} x {w2} is not an upsampled size')
+    out = torch.empty((n, h2 // 2, w2 // 2, c), device=g.device, dtype=torch.float32)
+    with _timed('disc_up2_adj', detail=True, nbytes=4.0 * (g.numel() + out.numel())):
+        _lib.call('mrefsr_disc_up2_adj_f32', _p(g), _p(out), n, h2 // 2, w2 // 2, c, _stream())
+    return out
+
+
+def disc_add(a, b):
+    _chk('disc_add', a, b)
+    if a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous():
+        raise RuntimeError(f'disc_add: {tuple(a.shape)} + {tuple(b.shape)}')
+    out = torch.empty_like(a)
+    _lib.call('mrefsr_disc_add_f32', _p(a), _p(b), _p(out), C.c_int64(a.numel()), _stream())
+    return out
+
+
+def disc_conv9(x, w, bias=None):
+    """nn.Conv2d(C, 1, 3, 1, 1) on x [N,H,W,C] -> [N,H,W,1]; w [1,C,3,3]"""
+    _chk('disc_conv9', x, w, bias)
+    _aligned('disc_conv9', x)
+    n, h, wd, c = x.shape
+    if tuple(w.shape) != (1, c, 3, 3):
+        raise ValueError(f'disc_conv9: weight {tuple(w.shape)} for {c} channels')
+    y = torch.empty((n, h, wd, 1), device=x.device, dtype=torch.float32)
+    with _timed('disc_conv9', 2.0 * x.numel() * 9, detail=True):
+        _lib.call('mrefsr_disc_conv9_f32', _p(x), _p(_c(w)), _p(bias), _p(y), n, h, wd, c, _stream())
+    return y
+
+
+def disc_conv9_dgrad(gy, w):
+    """input gradient: gy [N,H,W,1] -> [N,H,W,C]"""
+    _chk('disc_conv9_dgrad', gy, w)
+    n, h, wd, _ = gy.shape
+    c = w.shape[1]
+    dx = torch.empty((n, h, wd, c), device=gy.device, dtype=torch.float32)
+    with _timed('disc_conv9_dgrad', 2.0 * dx.numel() * 9, detail=True):
+        _lib.call('mrefsr_disc_conv9_dgrad_f32', _p(_c(gy)), _p(_c(w)), _p(dx), n, h, wd, c, _stream())
+    return dx
+
+
+def disc_conv9_wgrad(x, gy):
+    """weight gradient [1,C,3,3] = sum over the pixels of x (x) gy"""
+    _chk('disc_conv9_wgrad', x, gy)
+    _aligned('disc_conv9_wgrad', x)
+    n, h, wd, c = x.shape
+    if tuple(gy.shape) != (n, h, wd, 1):
+        raise ValueError('disc_conv9_wgrad: inconsistent shapes')
+    ws = _wgrad_workspace(x.device, _lib.load().mrefsr_disc_conv9_wgrad_workspace_bytes(n, h, wd, c))
+    dw = torch.empty((1, c, 3, 3), device=x.device, dtype=torch.float32)
+    with _timed('disc_conv9_wgrad', 2.0 * x.numel() * 9, detail=True):
+        _lib.call('mrefsr_disc_conv9_wgrad_f32', _p(x), _p(_c(gy)), _p(dw), n, h, wd, c, _p(ws), C.c_int64(ws.numel()), _stream())
+    return dw

@@ -9,8 +9,8 @@ layout: Adam with four parameter groups chosen by name (:60-89) --
     other 'offset'      -> lr_offset           everything else     -> lr_g
 Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLoss), perceptual_opt and style_opt
 (PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), and the adversarial term: network_d
-(ImageDiscriminator or VGGStyleDiscriminator, on the kernels of csrc/disc.hip and csrc/disc_vgg.hip) with gan_type / gan_weight /
-grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
+(ImageDiscriminator, VGGStyleDiscriminator or UNetDiscriminatorSN, on the kernels of csrc/disc.hip, disc_vgg.hip and disc_unet.hip)
+with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
 :272-276.  texture_opt and other discriminators raise NotImplementedError instead of being silently skipped.
 
 What differs underneath (SURVEY 7 "hard parts"):
@@ -119,8 +119,12 @@ class MultiRefRestorationModel:
             raise NotImplementedError('train.texture_opt: the texture loss is not implemented (pixel, perceptual, style and adversarial '
                                       'losses are; the reference model never sets the maps / weights it reads)')
         net_d_opt = self.opt.get('network_d')
-        if net_d_opt and net_d_opt.get('type') not in ('ImageDiscriminator', 'VGGStyleDiscriminator'):
-            raise NotImplementedError(f"network_d: {net_d_opt.get('type')} is not implemented (ImageDiscriminator and VGGStyleDiscriminator are)")
+        if net_d_opt and net_d_opt.get('type') not in ('ImageDiscriminator', 'VGGStyleDiscriminator', 'UNetDiscriminatorSN',
+                                                       'UNetDiscriminatorSN_basicsr'):
+            raise NotImplementedError(f"network_d: {net_d_opt.get('type')} is not implemented (ImageDiscriminator, VGGStyleDiscriminator and "
+                                      "UNetDiscriminatorSN are)")
+        if net_d_opt and net_d_opt['type'].startswith('UNetDiscriminatorSN') and 'num_in_ch' not in net_d_opt:
+            raise NotImplementedError(f"network_d: {net_d_opt['type']} without num_in_ch (the reference's constructor has no default for it)")
         if train_opt.get('gan_type') and not net_d_opt:
             raise NotImplementedError('train.gan_type without network_d: the reference builds a GAN loss that nothing uses (and fails on '
                                       'a missing grad_penalty_weight); give a network_d or drop gan_type')

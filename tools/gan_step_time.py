@@ -2,7 +2,7 @@
 """What the adversarial term adds to a training step.
 
   python tools/gan_step_time.py [--steps 10] [--warmup 3] [--out FILE.json] [--trace]
-                                [--network-d {ImageDiscriminator,VGGStyleDiscriminator}]
+                                [--network-d {ImageDiscriminator,VGGStyleDiscriminator,UNetDiscriminatorSN}]
 
 (1) MultiRefRestorationModel.optimize_parameters at B = 4, K = 5, LR 40 x 40 (GT 160 x 160) in three configurations -- L1 only,
 L1 + ImageDiscriminator(3, 32) with WGAN-GP (gan_weight 1e-3, grad_penalty_weight 10), L1 + vanilla GAN -- ms per step (median of
@@ -10,8 +10,10 @@ L1 + ImageDiscriminator(3, 32) with WGAN-GP (gan_weight 1e-3, grad_penalty_weigh
 (2) the discriminator part alone on [4,3,160,160] images: the WGAN-GP D step (D on real and fake, the penalty, backward) and the G
 step's D forward + backward, on the HIP kernels;
 (3) for comparison, the same D step through torch's NCHW autograd of the same module (MIOpen convolutions) on the same GPU.
---network-d: the discriminator of (1)-(3): ImageDiscriminator(3, 32) (the default) or VGGStyleDiscriminator(3, 64), for which (4) also
-times every convolution launch of the discriminator (forward, input gradient, weight gradient) at B = 4, 160 x 160, as ms and TF/s.
+--network-d: the discriminator of (1)-(3): ImageDiscriminator(3, 32) (the default), VGGStyleDiscriminator(3, 64) or
+UNetDiscriminatorSN(3, 64) (whose torch counterpart in (3) calls the conv modules, so torch's spectral_norm hooks run the power
+iteration), for the last two of which (4) also times every convolution launch of the discriminator (forward, input gradient, weight
+gradient) at B = 4, 160 x 160, as ms and TF/s.
 --trace: one WGAN-GP step only (for rocprofv3 --kernel-trace --stats)."""
 import argparse
 import json
@@ -32,7 +34,8 @@ GAN = {'wgan_gp': dict(gan_type='wgan', gan_weight=1e-3, grad_penalty_weight=10.
 
 
 NETWORK_D = {'ImageDiscriminator': dict(type='ImageDiscriminator', in_nc=3, ndf=32),
-             'VGGStyleDiscriminator': dict(type='VGGStyleDiscriminator', num_in_ch=3, num_feat=64)}
+             'VGGStyleDiscriminator': dict(type='VGGStyleDiscriminator', num_in_ch=3, num_feat=64),
+             'UNetDiscriminatorSN': dict(type='UNetDiscriminatorSN', num_in_ch=3, num_feat=64)}
 
 
 def _opt(gan, network_d='ImageDiscriminator'):
@@ -53,6 +56,7 @@ def _opt(gan, network_d='ImageDiscriminator'):
 def _model(gan, network_d='ImageDiscriminator'):
     import synth
     import synth_disc
+    import synth_unetdisc
     import synth_vggdisc
     from mrefsr_amd.models import build_model
     model = build_model(_opt(gan, network_d))
@@ -62,7 +66,7 @@ def _model(gan, network_d='ImageDiscriminator'):
         net.load_state_dict({k: torch.from_numpy(v) for k, v in synth.state_dict(spec).items()})
     if gan:
         spec = [(k, tuple(v.shape)) for k, v in model.net_d.state_dict().items()]
-        sd = (synth_vggdisc if network_d == 'VGGStyleDiscriminator' else synth_disc).state_dict(spec)
+        sd = {'VGGStyleDiscriminator': synth_vggdisc, 'UNetDiscriminatorSN': synth_unetdisc}.get(network_d, synth_disc).state_dict(spec)
         model.net_d.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
     samples = [synth.sr_sample(f'gan_time/s{i}', 5, 40, 40) for i in range(4)]
     model.feed_data({n: torch.from_numpy(np.stack([s[n] for s in samples])) for n in samples[0]})
@@ -93,6 +97,19 @@ def _d_step(net, real, fake, gan, gp):
 
 def _torch_d(net):
     """the same module run through torch's own NCHW autograd (MIOpen convolutions, native BatchNorm)"""
+    if hasattr(net, 'sn_convs'):   # UNetDiscriminatorSN: the reference's forward, the conv modules' spectral-norm hooks included
+        def unet(x):
+            def up(t):
+                return F.interpolate(t, scale_factor=2, mode='bilinear', align_corners=False)
+            x0 = F.leaky_relu(net.conv0(x), 0.2)
+            x1 = F.leaky_relu(net.conv1(x0), 0.2)
+            x2 = F.leaky_relu(net.conv2(x1), 0.2)
+            x3 = F.leaky_relu(net.conv3(x2), 0.2)
+            x4 = F.leaky_relu(net.conv4(up(x3)), 0.2) + x2
+            x5 = F.leaky_relu(net.conv5(up(x4)), 0.2) + x1
+            x6 = F.leaky_relu(net.conv6(up(x5)), 0.2) + x0
+            return net.conv9(F.leaky_relu(net.conv8(F.leaky_relu(net.conv7(x6), 0.2)), 0.2))
+        return unet
     if hasattr(net, 'conv_bn_layers'):   # VGGStyleDiscriminator: its own forward is the reference's, written out
         def vgg(x):
             h = F.leaky_relu(net.conv0_0(x), 0.2)
@@ -110,26 +127,45 @@ def _torch_d(net):
     return fwd
 
 
-def _vgg_layers(steps, warmup, b=4, nf=64):
-    """ms and TF/s of every convolution launch of VGGStyleDiscriminator(3, nf) at [b,3,160,160] (forward, input and weight gradient)"""
-    from mrefsr_amd import hip
+def _vgg_shapes(nf=64):
     out, cin, h = [], 4, 160
     chans = [nf, nf, 2 * nf, 2 * nf, 4 * nf, 4 * nf, 8 * nf, 8 * nf, 8 * nf, 8 * nf]
     for i, c in enumerate(chans):
         ks = 3 if i % 2 == 0 else 4
+        out.append((f'conv{i // 2}_{i % 2}', ks, cin, c, h))
+        cin, h = c, (h // 2 if ks == 4 else h)
+    return out
+
+
+def _unet_shapes(nf=64):
+    return [('conv0', 3, 4, nf, 160), ('conv1', 4, nf, 2 * nf, 160), ('conv2', 4, 2 * nf, 4 * nf, 80), ('conv3', 4, 4 * nf, 8 * nf, 40),
+            ('conv4', 3, 8 * nf, 4 * nf, 40), ('conv5', 3, 4 * nf, 2 * nf, 80), ('conv6', 3, 2 * nf, nf, 160), ('conv7', 3, nf, nf, 160),
+            ('conv8', 3, nf, nf, 160), ('conv9', 3, nf, 1, 160)]
+
+
+def _conv_layers(shapes, steps, warmup, b=4):
+    """ms and TF/s of every convolution launch of a discriminator at [b,3,160,160] (forward, input and weight gradient); shapes:
+    (name, ks, Cin, Cout, input size); Cout 1 is conv9's kernels"""
+    from mrefsr_amd import hip
+    out = []
+    for name, ks, cin, c, h in shapes:
         x = torch.randn(b, h, h, cin, device='cuda')
         w = torch.randn(c, cin, ks, ks, device='cuda') * 0.05
         ho = h // 2 if ks == 4 else h
         dy = torch.randn(b, ho, ho, c, device='cuda')
-        wpk, wpd = hip.disc_vconv_pack_weight(w, cin, False), hip.disc_vconv_pack_weight(w, cin, True)
         flop = 2.0 * b * ho * ho * c * cin * ks * ks
-        row = dict(layer=f'conv{i // 2}_{i % 2}', ks=ks, cin=cin, cout=c, out=ho, gflop=flop / 1e9)
-        for name, fn in (('fwd', lambda: hip.disc_vconv(x, wpk, None, ks)), ('dgrad', lambda: hip.disc_vconv_dgrad(dy, wpd, tuple(x.shape), ks)),
-                         ('wgrad', lambda: hip.disc_vconv_wgrad(x, dy, cin, ks))):
+        row = dict(layer=name, ks=ks, cin=cin, cout=c, out=ho, gflop=flop / 1e9)
+        if c == 1:
+            fns = (('fwd', lambda: hip.disc_conv9(x, w, None)), ('dgrad', lambda: hip.disc_conv9_dgrad(dy, w)),
+                   ('wgrad', lambda: hip.disc_conv9_wgrad(x, dy)))
+        else:
+            wpk, wpd = hip.disc_vconv_pack_weight(w, cin, False), hip.disc_vconv_pack_weight(w, cin, True)
+            fns = (('fwd', lambda: hip.disc_vconv(x, wpk, None, ks)), ('dgrad', lambda: hip.disc_vconv_dgrad(dy, wpd, tuple(x.shape), ks)),
+                   ('wgrad', lambda: hip.disc_vconv_wgrad(x, dy, cin, ks)))
+        for kind, fn in fns:
             ms = _median_ms(fn, steps, warmup)
-            row[f'{name}_ms'], row[f'{name}_tflops'] = ms, flop / ms / 1e9
+            row[f'{kind}_ms'], row[f'{kind}_tflops'] = ms, flop / ms / 1e9
         out.append(row)
-        cin, h = c, ho
     return out
 
 
@@ -189,7 +225,9 @@ def main():
     res['adversarial_adds_ms_wgan_gp'] = res['step_ms_wgan_gp'] - res['step_ms_l1']
     res['adversarial_adds_ms_vanilla'] = res['step_ms_vanilla'] - res['step_ms_l1']
     if a.network_d == 'VGGStyleDiscriminator':
-        res['layers'] = _vgg_layers(a.steps, a.warmup)
+        res['layers'] = _conv_layers(_vgg_shapes(), a.steps, a.warmup)
+    if a.network_d == 'UNetDiscriminatorSN':
+        res['layers'] = _conv_layers(_unet_shapes(), a.steps, a.warmup)
     print(json.dumps(res, indent=1))
     if a.out:
         with open(a.out, 'w') as f:
