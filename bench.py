@@ -15,12 +15,19 @@ Workload at N=1 = BASELINE.json configs[1]: 5-ref 4x SR inference, LR 160x160 ->
 fp32.  N > 1 keeps 8 samples per GPU (weak scaling; configs[3] = 64 samples over 8 GPUs).
 Metric: output Mpix/s = N * B * 640 * 640 / 1e6 / t_step.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields plus what the timed region itself yields:
   roofline     for the correlation kernel, measured live with HIP events on its launch stream
-  cpu_baseline the CPU port (oracle/pipeline.py) timed on this host's cores on a bounded sample (rank 0, any N)
   step_ms      median / min / max of the K timed steps (HIP events between steps) and value_median = the metric on the median
   clock_mhz    shader clock sampled from sysfs during the timed region (the convolution phase runs power-limited)
-  at N > 1: rank_ms_per_step (min / max over ranks) and no_gather (the same loop without the RCCL all_gather of the outputs)
+  at N > 1: rank_ms_per_step (min / max over ranks)
+
+--full also runs what takes passes of its own after the timed region and adds it to the line:
+  roofline_conv, roofline_attn  every convolution / DCN / attention launch of one extra, untimed inference pass (rank 0)
+  train_step   the configs[2]-shaped training step (infer mode, fp32; --no-train-step leaves it out)
+  cpu_baseline the CPU port (oracle/pipeline.py) timed on this host's cores on a bounded sample (rank 0, any N; --no-cpu-baseline
+               leaves it out)
+  at N > 1: no_gather (the same loop without the RCCL all_gather of the outputs)
+Without --full a run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.
 
 --dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, for output-for-output comparisons of two
 builds: inputs and weights come from fixed seeds, so the same arguments give the same inputs on every run.
@@ -531,13 +538,15 @@ def main():
     ap.add_argument('--refs', type=int, default=5)
     ap.add_argument('--lr', type=int, default=160, help='LR side (output is 4x)')
     ap.add_argument('--mode', choices=('infer', 'train'), default='infer')
+    ap.add_argument('--full', action='store_true', help='after the timed region also run the per-kernel pass, the training-step '
+                                                        'figure, the CPU baseline and (N > 1) the loop without the gather')
     ap.add_argument('--cpu-lr', type=int, default=160)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
     ap.add_argument('--dtype', choices=('fp32', 'bf16'), default='fp32',
                     help='bf16: BASELINE configs[4] arithmetic (weights / activations rounded to bf16, fp32 accumulate)')
     ap.add_argument('--graph', action='store_true', help='replay the inference pass (MREFSR_GRAPH=1) / the training step (MREFSR_TRAIN_GRAPH=1) as hipGraphs: small shapes')
     ap.add_argument('--miopen-find', action='store_true', help='torch.backends.cudnn.benchmark = True')
-    ap.add_argument('--no-train-step', action='store_true', help='skip the training-step figure (train_step on the JSON line) after the inference loop')
+    ap.add_argument('--no-train-step', action='store_true', help='--full: skip the training-step figure (train_step on the JSON line) after the inference loop')
     ap.add_argument('--train-steps', type=int, default=10, help='timed training steps of the train_step figure')
     ap.add_argument('--no-gather', action='store_true', help='N > 1: leave the RCCL all_gather of the outputs out of the step (the line then carries only that figure)')
     ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed (rank 0) as DIR/<name>.npy, '
@@ -634,7 +643,7 @@ def main():
     corr_ms = hip.kernel_timings().get('corr_top1', [])
     hip.set_kernel_timing(False)
     detail, detail_bytes = None, {}
-    if rank == 0 and args.mode == 'infer':
+    if args.full and rank == 0 and args.mode == 'infer':
         # one extra, untimed pass with an event pair around every convolution / DCN launch (rank 0 only, so
         # WITHOUT the collective of step(): the other ranks are already past the timed region)
         hip.set_kernel_timing(True, detail=True)
@@ -645,7 +654,7 @@ def main():
         hip.set_kernel_timing(False)
 
     no_gather_fig = None
-    if dist_on and args.mode == 'infer' and with_gather[0]:
+    if args.full and dist_on and args.mode == 'infer' and with_gather[0]:
         # the same loop without the exchange (half the steps, at least 2: a reported companion figure, every rank takes part)
         with_gather[0] = False
         k2 = max(2, args.steps // 2)
@@ -654,14 +663,14 @@ def main():
         no_gather_fig = dict(steps=k2, ms_per_step=round(e2 / k2 * 1e3, 2), value=round(world * args.batch * (4 * args.lr) ** 2 / 1e6 * k2 / e2, 4),
                              note='the timed loop again without the RCCL all_gather of the outputs (per-rank inference only)')
     train_fig = None
-    if args.mode == 'infer' and not args.no_train_step and args.dtype == 'fp32':
+    if args.full and args.mode == 'infer' and not args.no_train_step and args.dtype == 'fp32':
         try:
             train_fig = train_step_figure(args, dist_on, rank)
         except Exception as e:   # a reported extra, never a reason to lose the headline line (a rank-local failure under DDP would
             train_fig = dict(ms_per_step=None, error=f'{type(e).__name__}: {e}')   # still stall its peers: RCCL's watchdog ends them)
     if rank == 0:
         res = assemble_line(args, world, elapsed, step_ms, rank_elapsed, corr_ms, detail, detail_bytes, clock.summary(), no_gather_fig, rccl_world, train_fig)
-        if not args.no_cpu_baseline:   # (rank 0 at any N: the other ranks wait at the closing barrier)
+        if args.full and not args.no_cpu_baseline:   # (rank 0 at any N: the other ranks wait at the closing barrier)
             try:
                 res['cpu_baseline'] = cpu_baseline(sds, args, model)
             except Exception as e:  # the baseline is a reported number, never a reason to lose the GPU line

@@ -19,7 +19,7 @@ def test_bench_rccl_path_with_one_rank():
     env = dict(os.environ, MREFSR_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
                           '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '1', '--batch', '1', '--lr', '40', '--steps', '1',
-                          '--warmup', '1', '--cpu-lr', '16', '--no-train-step'], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+                          '--warmup', '1', '--cpu-lr', '16', '--no-train-step', '--full'], cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith('{')][-1])
     assert line['n_gpus'] == 1 and line['value'] > 0 and line['scaling'] == 'weak'
@@ -47,7 +47,7 @@ def test_bench_starts_its_own_ranks_and_reports_a_ddp_training_step():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(MREFSR_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--batch', '1', '--lr', '40', '--steps', '1', '--warmup', '1',
-                          '--no-cpu-baseline', '--train-steps', '3'], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+                          '--no-cpu-baseline', '--train-steps', '3', '--full'], cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -56,6 +56,33 @@ def test_bench_starts_its_own_ranks_and_reports_a_ddp_training_step():
     ts = line['train_step']
     assert ts.get('error') is None, ts
     assert ts['parallelism'] == 'ddp1' and ts['ms_per_step'] > 0 and ts['loss'] > 0
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_carries_the_headline_and_leaves_the_full_figures_out(tmp_path):
+    """`python bench.py --gpus 1` without --full (N = 1, in-process): the contract fields and what the timed region itself yields,
+    the outputs of the last timed step under --dump-outputs, and none of the figures that take passes of their own."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MREFSR_BENCH_FORCE_DIST')}
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--batch', '1', '--lr', '40', '--steps', '2', '--warmup', '1',
+                          '--dump-outputs', str(tmp_path)], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line['n_gpus'] == 1 and line['steps'] == 2 and line['warmup'] == 1 and line['value'] > 0 and line['ms_per_step'] > 0
+    assert line['unit'] == 'Mpix/s' and line['higher_is_better'] is True and line['dtype'] == 'f32'
+    assert line['roofline']['launches'] == 2 and 'step_ms' in line and 'clock_mhz' in line
+    for key in ('roofline_conv', 'roofline_attn', 'train_step', 'cpu_baseline', 'no_gather'):
+        assert key not in line, key
+    assert sorted(os.listdir(tmp_path)) == ['match_idx.npy', 'output.npy']
+    assert np.load(tmp_path / 'output.npy').shape == (1, 3, 160, 160)
 
 
 @pytest.mark.gpu
