@@ -501,6 +501,24 @@ int mrefsr_mrattn_bwd_nhwc_f32(const float *q, const float *emb, const float *as
 int mrefsr_attn_modulate_bwd_f32(const float *g, const float *refs, const float *mul, float *g_refs, float *g_mul, int64_t n,
                                  mrefsr_stream_t stream);
 
+/* ---- reflect padding and cropping of channels-last maps (MRAPAFusion, ref_mrapa_restoration_arch.py:306-311, 348), with their
+ * adjoints: the pad / crop nodes of the training engine.  [N][H][W][C] fp32, C a multiple of 4, 16-byte aligned; nothing is
+ * allocated, nothing is synchronised.
+ *
+ * mrefsr_reflect_pad_nhwc_f32: x [N][H][W][C] -> out [N][H+ph][W+pw][C], the bottom and right padded by ph, pw in 0..3 with
+ *   F.pad(mode='reflect') semantics (padded row H + i is source row H - 2 - i, likewise for columns); ph < H and pw < W, as F.pad
+ *   requires.  Bit-identical to F.pad.
+ * mrefsr_reflect_pad_bwd_nhwc_f32: its adjoint, g [N][H+ph][W+pw][C] -> gx [N][H][W][C]: each source pixel adds to its own
+ *   gradient the row image, the column image and the corner image that mirror it, in this order (deterministic, no atomics).
+ * mrefsr_crop_nhwc_f32: the top-left H0 x W0 window of x [N][H][W][C] -> out [N][H0][W0][C]; amax (may be NULL, zero-initialised
+ *   by the caller) = max(amax[0], max |out|), the Winograd input scale of the convolution that reads the crop
+ *   (as mrefsr_conv_nhwc_amax_f32's out_amax).
+ * mrefsr_crop_bwd_nhwc_f32: its adjoint, g [N][H0][W0][C] -> gx [N][H][W][C]: g inside the window, zero in the band. */
+int mrefsr_reflect_pad_nhwc_f32(const float *x, float *out, int N, int H, int W, int C, int ph, int pw, mrefsr_stream_t stream);
+int mrefsr_reflect_pad_bwd_nhwc_f32(const float *g, float *gx, int N, int H, int W, int C, int ph, int pw, mrefsr_stream_t stream);
+int mrefsr_crop_nhwc_f32(const float *x, float *out, float *amax, int N, int H, int W, int C, int H0, int W0, mrefsr_stream_t stream);
+int mrefsr_crop_bwd_nhwc_f32(const float *g, float *gx, int N, int H, int W, int C, int H0, int W0, mrefsr_stream_t stream);
+
 /* ---- perceptual / style loss of the training step (PerceptualLoss, basicsr/models/losses.py:141-238, under
  * multi_ref_restoration_model.py:237-279): the VGG19 node of mrefsr_amd/archs/nhwc_train.py.  Channels-last [N][H][W][C]
  * fp32 tensors, C % 4 == 0.

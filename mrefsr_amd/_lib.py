@@ -83,6 +83,10 @@ SIGNATURES = {
     'mrefsr_conv_wgrad3x3_batch_f32': (_i, [_i, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     'mrefsr_mrattn_bwd_nhwc_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'mrefsr_attn_modulate_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    'mrefsr_reflect_pad_nhwc_f32': (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
+    'mrefsr_reflect_pad_bwd_nhwc_f32': (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
+    'mrefsr_crop_nhwc_f32': (_i, [_vp, _vp, _vp] + [_i] * 6 + [_vp]),
+    'mrefsr_crop_bwd_nhwc_f32': (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
     'mrefsr_conv_nhwc_f32': (_i, [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'mrefsr_dcn_fwd': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(DcnShape), _f, _i, _vp]),
     'mrefsr_dcn_im2col': (_i, [_vp, _vp, _vp, _vp, C.POINTER(DcnShape), _i, _vp]),

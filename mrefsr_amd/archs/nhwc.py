@@ -11,8 +11,9 @@ callers written against the reference see the same shapes and values.
 
 With autograd enabled (training of net_g) the same launches are recorded as autograd nodes
 (archs/nhwc_train.py).  There is no switch that routes the path to a library: what the engine cannot
-take (non-fp32 tensors, training maps whose sides are not multiples of 4, module kinds it does not
-know) falls to the generic torch forms of arch_util.py -- listed in INTEGRATION.md.  ``ENABLED`` is a
+take (non-fp32 tensors, module kinds it does not know, training maps too small for MRAPAFusion's reflect
+pad) falls to the generic torch forms of arch_util.py -- listed in INTEGRATION.md.  Maps whose sides are
+not multiples of 4 are padded and cropped by HIP kernels in both modes (csrc/pad.hip).  ``ENABLED`` is a
 module attribute for the tests that compare the two (tests/ flip it; no environment variable).
 """
 import os
@@ -121,6 +122,28 @@ def to_nhwc(x):
 def as_nchw(x):
     """[N,H,W,C] storage -> logical NCHW view (no copy)"""
     return _keep_amax(x, x.permute(0, 3, 1, 2))
+
+
+def reflect_pad(x, ph, pw):
+    """[N,H,W,C] fp32 -> bottom / right reflect-padded by ph, pw (F.pad(mode='reflect')); an autograd node when x is part of a graph.
+    The result keeps x's max |x| word: a reflection adds no new value."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        from . import nhwc_train
+        return nhwc_train.reflect_pad(x, ph, pw)
+    return _keep_amax(x, hip.reflect_pad_nhwc(x, ph, pw))
+
+
+def crop(x, h0, w0):
+    """top-left h0 x w0 window of [N,H,W,C] fp32; an autograd node when x is part of a graph, else the crop kernel also measures
+    the result's max |x| word (a window can have a smaller maximum than its source: the source's word is never copied)"""
+    if torch.is_grad_enabled() and x.requires_grad:
+        from . import nhwc_train
+        return nhwc_train.crop(x, h0, w0)
+    slot = hip.amax_slot(x.device) if WINO_INSCALE else None
+    y = hip.crop_nhwc(x, h0, w0, out_amax=slot)
+    if slot is not None:
+        setattr(y, AMAX_ATTR, slot)
+    return y
 
 
 def image_to_nhwc4(img, mean=None, std=None, range_norm=False):

@@ -15,6 +15,7 @@ same graph is recorded over [N,H,W,C] tensors with one autograd node per FUSED l
                  -- backward: HIP im2col / col2im + two library GEMMs (ops/dcn/deform_conv.py)
   _Attention     mrefsr_mrattn_fwd_nhwc_f32 / mrefsr_mrattn_bwd_nhwc_f32 (softmax recomputed, nothing extra saved)
   _Modulate      refs * sigmoid(mul) * 2 + add, one pass each way
+  _Pad, _Crop    MRAPAFusion's reflect pad to a multiple of 4 and the crop back (csrc/pad.hip), one pass each way
   _VggLoss       the VGG of PerceptualLoss (losses/): output and GT as one batch forward, input gradients of the output image
                  backward (csrc/percep.hip: pooling, tap criterion, Gram matrices, image packing backward)
 
@@ -568,6 +569,34 @@ class _Modulate(Function):
         return hip.attn_modulate_bwd(g, refs, mul) + (g,)
 
 
+class _Pad(Function):
+    """bottom / right reflect pad of [N,H,W,C] by ph, pw in 0..3   ref :306-311"""
+
+    @staticmethod
+    def forward(ctx, x, ph, pw):
+        ctx.pads = (ph, pw)
+        return hip.reflect_pad_nhwc(x, ph, pw)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return hip.reflect_pad_bwd_nhwc(g.contiguous(), *ctx.pads), None, None
+
+
+class _Crop(Function):
+    """top-left h0 x w0 window of [N,H,W,C]   ref :348"""
+
+    @staticmethod
+    def forward(ctx, x, h0, w0):
+        ctx.hw = tuple(x.shape[1:3])
+        return hip.crop_nhwc(x, h0, w0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return hip.crop_bwd_nhwc(g.contiguous(), *ctx.hw), None, None
+
+
 # ---- perceptual / style loss (PerceptualLoss, losses.py:141-238 of the reference model's loss module) ----------------------------
 # Packed copies of the frozen VGG weights: the perceptual VGG is never stepped, so its copies stay out of the per-step multi-tensor
 # refresh (begin_step) and are re-made only when a parameter's version moves (load_state_dict).
@@ -830,3 +859,5 @@ conv_dynagg = _ConvDynAgg.apply
 dcn = _Dcn.apply
 attention = _Attention.apply
 modulate = _Modulate.apply
+reflect_pad = _Pad.apply
+crop = _Crop.apply

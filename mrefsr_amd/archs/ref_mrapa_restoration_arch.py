@@ -229,7 +229,7 @@ class MRAPARestorationNet(nn.Module):
         """same with the K references already stacked k-major on the batch axis ([K*B,...])."""
         if nhwc.BF16 and nhwc.active(x):
             x = x.bfloat16().float()
-        if (nhwc.active(x) or (nhwc.train_active(x) and x.shape[2] % 4 == 0 and x.shape[3] % 4 == 0)) and self.dyn_agg_restore.nhwc_ok(x):
+        if (nhwc.active(x) or (nhwc.train_active(x) and MRAPAFusion.pads_ok(x.shape[2], x.shape[3]))) and self.dyn_agg_restore.nhwc_ok(x):
             ce = self.content_extractor
             feat = nhwc.res_chain(ce.body, nhwc.conv(ce.conv_first, nhwc.image_to_nhwc4(x), slope=0.1))
             refs = {key: nhwc.to_nhwc(v if v.dtype == feat.dtype else v.to(feat.dtype)) for key, v in img_ref_feat.items()}
@@ -369,9 +369,20 @@ class MRAPAFusion(nn.Module):
         self.spatial_attn_add2 = nn.Conv2d(channels * 2, channels * 2, 3, padding=1)
         self.lrelu = nn.LeakyReLU(negative_slope=0.1, inplace=True)
 
+    @staticmethod
+    def pads(h, w):
+        """bottom / right padding that brings an h x w map to a multiple of 4 (:306-311)"""
+        return (4 - h % 4) % 4, (4 - w % 4) % 4
+
+    @staticmethod
+    def pads_ok(h, w):
+        """the reflect pad of every fusion head of an LR input of h x w exists (F.pad needs pad < side): the heads see h x w and
+        2h x 2w (4h x 4w needs none)"""
+        return all((4 - s % 4) % 4 < s for side in (h, w) for s in (side, 2 * side))
+
     def spatial_padding(self, feats):
         _, _, h, w = feats.size()
-        pad_h, pad_w = (4 - h % 4) % 4, (4 - w % 4) % 4
+        pad_h, pad_w = self.pads(h, w)
         if pad_h == 0 and pad_w == 0:
             return feats
         return F.pad(feats, [0, pad_w, 0, pad_h], mode='reflect')
@@ -386,14 +397,19 @@ class MRAPAFusion(nn.Module):
         return self._fuse(target, refs, t, t_major=True)
 
     def forward_nhwc(self, target, refs, t):
-        """channels-last inference form: target [n,H,W,nf], refs [t*n,H,W,ref_nf] t-major -> [n,H,W,nf].
-        torch.cat of :339/:346 = two-source convolutions; H, W that are not multiples of 4 are reflect-padded
-        and cropped back as in :306-311, :348 (CUFED5's 125 x 125 LR inputs need it at two scales)."""
+        """channels-last form (inference and, under autograd, training): target [n,H,W,nf], refs [t*n,H,W,ref_nf] t-major ->
+        [n,H,W,nf].  torch.cat of :339/:346 = two-source convolutions; H, W that are not multiples of 4 are reflect-padded
+        and cropped back as in :306-311, :348 (CUFED5's 125 x 125 LR inputs need it at two scales) by the HIP kernels of
+        csrc/pad.hip -- autograd nodes when a graph is recorded."""
         h_in, w_in = target.shape[1:3]
-        if h_in % 4 or w_in % 4:
-            target = nhwc.to_nhwc(self.spatial_padding(nhwc.as_nchw(target)))
-            refs = nhwc.to_nhwc(self.spatial_padding(nhwc.as_nchw(refs)))
-            return self.forward_nhwc(target, refs, t)[:, :h_in, :w_in, :].contiguous()
+        ph, pw = self.pads(h_in, w_in)
+        if ph or pw:
+            if target.dtype != torch.float32:   # (bf16 storage: the kernels are fp32)
+                target = nhwc.to_nhwc(self.spatial_padding(nhwc.as_nchw(target)))
+                refs = nhwc.to_nhwc(self.spatial_padding(nhwc.as_nchw(refs)))
+                return self.forward_nhwc(target, refs, t)[:, :h_in, :w_in, :].contiguous()
+            out = self.forward_nhwc(nhwc.reflect_pad(target, ph, pw), nhwc.reflect_pad(refs, ph, pw), t)
+            return nhwc.crop(out, h_in, w_in)
         q = nhwc.conv(self.conv_emb1[0], target, prelu=self.conv_emb1[1], amax=False)   # (q, emb, ass: attention operands)
         train = q.requires_grad   # a graph is being recorded (archs/nhwc_train.py): no in-place edits of saved tensors
         fold = not train and q.dtype == torch.float32 and not nhwc.BF16   # q * scale formed inside the attention kernel (same bits, no pass over q)

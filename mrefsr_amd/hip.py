@@ -945,6 +945,47 @@ def attn_modulate_bwd(g, refs, mul):
     return g_refs, g_mul
 
 
+# ---- reflect pad / crop of channels-last maps (csrc/pad.hip): MRAPAFusion's pad to a multiple of 4 and crop back
+def reflect_pad_nhwc(x, ph, pw):
+    """x [N,H,W,C] -> [N,H+ph,W+pw,C], bottom / right reflect-padded (F.pad(mode='reflect') bit for bit); ph, pw in 0..3, < H, W"""
+    _chk('reflect_pad_nhwc', x)
+    n, h, w, c = x.shape
+    out = torch.empty((n, h + ph, w + pw, c), device=x.device, dtype=torch.float32)
+    with _timed('reflect_pad_nhwc', detail=True, nbytes=4.0 * (x.numel() + out.numel())):
+        _lib.call('mrefsr_reflect_pad_nhwc_f32', _p(x), _p(out), n, h, w, c, ph, pw, _stream())
+    return out
+
+
+def reflect_pad_bwd_nhwc(g, ph, pw):
+    """adjoint of reflect_pad_nhwc: g [N,H+ph,W+pw,C] -> [N,H,W,C] (mirrored contributions added in a fixed order)"""
+    _chk('reflect_pad_bwd_nhwc', g)
+    n, hp, wp, c = g.shape
+    gx = torch.empty((n, hp - ph, wp - pw, c), device=g.device, dtype=torch.float32)
+    with _timed('reflect_pad_bwd_nhwc', detail=True, nbytes=4.0 * (g.numel() + gx.numel())):
+        _lib.call('mrefsr_reflect_pad_bwd_nhwc_f32', _p(g), _p(gx), n, hp - ph, wp - pw, c, ph, pw, _stream())
+    return gx
+
+
+def crop_nhwc(x, h0, w0, out_amax=None):
+    """top-left h0 x w0 window of x [N,H,W,C] -> [N,h0,w0,C]; out_amax (a zeroed 1-element device word: amax_slot) receives max |out|"""
+    _chk('crop_nhwc', x, out_amax)
+    n, h, w, c = x.shape
+    out = torch.empty((n, h0, w0, c), device=x.device, dtype=torch.float32)
+    with _timed('crop_nhwc', detail=True, nbytes=8.0 * out.numel()):
+        _lib.call('mrefsr_crop_nhwc_f32', _p(x), _p(out), _p(out_amax), n, h, w, c, h0, w0, _stream())
+    return out
+
+
+def crop_bwd_nhwc(g, h, w):
+    """adjoint of crop_nhwc: g [N,h0,w0,C] -> [N,h,w,C], zero outside the window"""
+    _chk('crop_bwd_nhwc', g)
+    n, h0, w0, c = g.shape
+    gx = torch.empty((n, h, w, c), device=g.device, dtype=torch.float32)
+    with _timed('crop_bwd_nhwc', detail=True, nbytes=4.0 * (g.numel() + gx.numel())):
+        _lib.call('mrefsr_crop_bwd_nhwc_f32', _p(g), _p(gx), n, h, w, c, h0, w0, _stream())
+    return gx
+
+
 # ---- max |out| words of the forward launches (mrefsr_conv_nhwc_amax_f32 / mrefsr_dcn_fwd_amax_f32): one zeroed float per producing
 # launch, handed to the consumer as its in_amax.  A pool per device, two halves: a half is zeroed (one memset) when the slot counter
 # enters it -- its words were handed out >= AMAX_POOL / 2 launches ago, their tensors have long been consumed.  amax_pool_reset()
