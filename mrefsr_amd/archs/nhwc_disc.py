@@ -38,6 +38,10 @@ def frozen_statistics():
         _frozen[0] = prev
 
 
+def statistics_frozen():
+    return _frozen[0]
+
+
 def _c(t):
     return t if t is None or t.is_contiguous() else t.contiguous()
 
@@ -212,7 +216,7 @@ def discriminator(net, x):
         conv1, bn1, _, conv2, bn2, _ = blk
         for conv, bn, stride in ((conv1, bn1, 1), (conv2, bn2, 2)):
             h = _Conv.apply(h, conv.weight, conv.bias, stride)
-            stats = (None, None, None) if _frozen[0] else (bn.running_mean, bn.running_var, bn.num_batches_tracked)
+            stats = (None, None, None) if statistics_frozen() else (bn.running_mean, bn.running_var, bn.num_batches_tracked)
             h = _Bn.apply(h, bn.weight, bn.bias, *stats, bn.eps, bn.momentum)
     head = net.out_block
     c1, c2 = head[1], head[3]

@@ -7,22 +7,37 @@ same graph is recorded over [N,H,W,C] tensors with one autograd node per FUSED l
 
   _Conv          conv_nhwc (bias, broadcast pre-activation term, LeakyReLU / ReLU / PReLU, residual, PixelShuffle, two-source
                  concatenation fused) -- backward: ONE pass for the activation derivative + bias gradient (+ PReLU weight
-                 gradient) (mrefsr_act_bwd_nhwc_f32), the input gradients as conv_nhwc launches on the point-mirrored,
-                 transposed weights (mrefsr_conv_pack_weight_view_f32: dgrad of a stride-1 'same' convolution IS such a
-                 convolution), the weight gradient by MIOpen's channels-last wgrad kernels on the same storage (no transposes)
+                 gradient) + max |g| (mrefsr_act_bwd_nhwc_f32), the input gradients as conv_nhwc launches on the point-mirrored,
+                 transposed weights (dgrad of a stride-1 'same' convolution IS such a convolution), the weight gradient on
+                 csrc/wgrad.hip (conv_wgrad3x3 / conv_wgrad1x1, on the same storage: no transposes)
+  _ResBlock      x + conv2(relu(conv1(x))) as one node: the skip's gradient rides on conv1's input-gradient launch
+  _ResChain      a trunk of such blocks as one node (RESCHAIN; RESBLOCK alone records them one by one): per block two input-gradient
+                 launches that carry the ReLU mask, the skip add, the bias gradients and max |g| (mrefsr_conv_nhwc_bwd_f32), all
+                 weight gradients of the trunk as batched launches at the end (mrefsr_conv_wgrad3x3_batch_f32)
   _ConvDynAgg    conv_offset_mask + DynAgg glue (mrefsr_conv_dynagg_f32) -- backward through mrefsr_dynagg_prep_bwd_f32
   _Dcn           fused gather + MFMA deformable convolution on channels-last features (mrefsr_dcn_fwd_f32) with its LeakyReLU
-                 -- backward: HIP im2col / col2im + two library GEMMs (ops/dcn/deform_conv.py)
+                 -- backward: two fused launches (dcn_bwd_data: columns gradient with the offset / mask / input gradients as its
+                 epilogue; dcn_bwd_weight: columns re-gathered inside the GEMM), no C*9*H*W buffer
   _Attention     mrefsr_mrattn_fwd_nhwc_f32 / mrefsr_mrattn_bwd_nhwc_f32 (softmax recomputed, nothing extra saved)
   _Modulate      refs * sigmoid(mul) * 2 + add, one pass each way
   _Pad, _Crop    MRAPAFusion's reflect pad to a multiple of 4 and the crop back (csrc/pad.hip), one pass each way
   _VggLoss       the VGG of PerceptualLoss (losses/): output and GT as one batch forward, input gradients of the output image
                  backward (csrc/percep.hip: pooling, tap criterion, Gram matrices, image packing backward)
 
-Arithmetic: forward and input-gradient convolutions run the bf16 three-term split (terms 6: fp32-equivalent, no range
-limit -- gradients of 1e-8 would be flushed by the fp16 two-term split -- and no host synchronisation when the weights are
-re-packed after every optimiser step).  Gradients match the reference's own optimisation step to the fingerprints of
-tests/golden/e2e_c2.npz (tests/test_configs_gpu.py).  ``ENABLED`` is flipped by tests/ only (generic NCHW autograd forms as the comparison).
+Arithmetic: forward and input-gradient convolutions run the fp16 two-term split (terms 16, three products; FWD_TERMS /
+BWD_TERMS) on weights packed with a cached power-of-two scale (_wscale, watched by check_scales()); an input-gradient launch
+scales its incoming gradient by the power of two that the launch before it derived from max |g| (gradients of 1e-8 are far below
+the fp16 normal range).  All packed copies are refreshed by ONE multi-tensor launch per step (begin_step()).
+
+The range-free re-run (hip.range_free(): an activation or weight left the fp16 range, the model repeats the batch) uses instead:
+the bf16 three-term split (terms 6: fp32-equivalent, no range limit) for every convolution, _fwd_pack / _bwd_pack / _vgg_pack
+choosing it -- also for a weight without a scale (all zero); the generic forms of _wgrad (a split-K bmm for 1x1, MIOpen's
+channels-last weight gradient for 3x3) per convolution, also inside _ResChain; the four-launch block backward in _ResChain; the
+unfused PReLU in conv(); and for the DCN, as for shapes its fused kernels refuse, im2col / col2im with two library GEMMs
+(ops/dcn/deform_conv.py, fused=False).
+
+Gradients match the reference's own optimisation step to the fingerprints of tests/golden/e2e_c2.npz
+(tests/test_configs_gpu.py).  ``ENABLED`` is flipped by tests/ only (generic NCHW autograd forms as the comparison).
 """
 import os
 
@@ -32,7 +47,7 @@ from torch.autograd.function import once_differentiable
 
 from .. import hip
 
-# MIOpen's channels-last kernels for the weight gradients (read once by torch, at its first MIOpen convolution)
+# MIOpen's channels-last kernels for the generic weight gradients of _wgrad (read once by torch, at its first MIOpen convolution)
 os.environ.setdefault('PYTORCH_MIOPEN_SUGGEST_NHWC', '1')
 
 ENABLED = True
@@ -129,7 +144,6 @@ BWD_TERMS = int(os.environ.get('MREFSR_TRAIN_BWD_TERMS', '16'))
 # older than its parameter (``_version``; callers that drive net_g without the model).  A new (weight, slice, arithmetic)
 # is packed by itself once and joins the table of the following refresh.
 _packs = {}        # device index -> {'entries': {key: [weakref, PackedWeight, stamp, job, last refresh it was used in]}, 'table', 'rows', 'dirty', 'refresh'}
-PACK_MULTI = os.environ.get('MREFSR_TRAIN_PACK_MULTI', '1') != '0'
 _PACK_KEEP = 4     # refreshes an unused entry survives (validation passes, a second network)
 
 
@@ -167,8 +181,6 @@ def _refresh_packs(device):
 
 def begin_step(device=None):
     """top of an optimisation step: refresh every packed weight copy (one launch per device that has any)"""
-    if not PACK_MULTI:
-        return
     for idx in list(_packs) if device is None else [torch.device(device).index]:
         if idx in _packs and _packs[idx]['entries']:
             _refresh_packs(torch.device('cuda', idx))
@@ -176,8 +188,6 @@ def begin_step(device=None):
 
 def _packed(weight, cin_slice, terms, dgrad=False, wscale=1.0):
     """hip.conv_pack_view(weight, cin_slice, terms, dgrad, wscale) from the step's refreshed copies"""
-    if not PACK_MULTI:
-        return hip.conv_pack_view(weight, cin_slice, terms, dgrad=dgrad, wscale=wscale)
     st = _pack_state(weight.device)
     cap, epoch = hip.capture_epoch()
     key = (weight.data_ptr(), weight.numel(), tuple(weight.shape), cin_slice, terms, dgrad, wscale)
@@ -222,6 +232,15 @@ def capture_state():
     return objs, tuple(ptrs)
 
 
+def _fwd_pack(weight, cin_slice):
+    """(packed forward operator, terms): fp16 two-term with the weight's cached scale, else the range-free split"""
+    if _fwd_terms() == 16:
+        ws = _wscale(weight)
+        if ws is not None:
+            return _packed(weight, cin_slice, 16, wscale=ws), 16
+    return _packed(weight, cin_slice, TERMS), TERMS
+
+
 def _bwd_pack(weight, cin_slice):
     """(packed dgrad operator, terms): fp16 two-term with the weight's cached scale, else the range-free split"""
     if BWD_TERMS == 16 and not hip.is_range_free():
@@ -237,18 +256,13 @@ def _unshuffle(t):
     return t.view(n, h2 // 2, 2, w2 // 2, 2, c).permute(0, 1, 3, 5, 2, 4).reshape(n, h2 // 2, w2 // 2, 4 * c)
 
 
-DCN_FUSED_BWD = os.environ.get('MREFSR_TRAIN_DCN_FUSED', '1') != '0'   # 0: im2col / library GEMMs / col2im (the round-3 structure)
-
-# weight gradients on the library's own kernels (csrc/wgrad.hip).  The generic forms below serve what those refuse: a batch that is
-# being re-run on the range-free path (an activation left the fp16 range) -- see INTEGRATION.md
-WGRAD_HIP = True
-
-
 def _wgrad(g_pre, cout, x, cin, k, amax=None):
-    """d loss / d weight [cout,cin,k,k] from channels-last storage (g_pre [N,H,W,>=cout], x [N,H,W,>=cin])"""
-    if k == 3 and WGRAD_HIP and amax is not None and not hip.is_range_free():
+    """d loss / d weight [cout,cin,k,k] from channels-last storage (g_pre [N,H,W,>=cout], x [N,H,W,>=cin]): the library's own
+    kernels (csrc/wgrad.hip); the generic forms below serve what those refuse, a batch that is being re-run on the range-free path
+    (an activation left the fp16 range) -- see INTEGRATION.md"""
+    if k == 3 and amax is not None and not hip.is_range_free():
         return hip.conv_wgrad3x3(x, g_pre, cin, cout, amax)
-    if k == 1 and WGRAD_HIP and amax is not None and not hip.is_range_free():
+    if k == 1 and amax is not None and not hip.is_range_free():
         return hip.conv_wgrad1x1(x, g_pre, cin, cout, amax)
     if k == 1:
         # (range-free re-runs) a plain GEMM over the pixels, g^T [cout, P] . x [P, cin], on the tensors as they lie; K = P is ~10^5 against M, N of a
@@ -284,12 +298,7 @@ class _Conv(Function):
             raise NotImplementedError('nhwc_train: cin_slice with a second source')
         weight = weight.contiguous()
         a, b = cin_slice if cin_slice is not None else (0, ci)
-        terms, wscale = _fwd_terms(), 1.0
-        if terms == 16:
-            wscale = _wscale(weight)
-            if wscale is None:
-                terms, wscale = TERMS, 1.0
-        packed = _packed(weight, (a, b), terms, wscale=wscale)
+        packed, _ = _fwd_pack(weight, (a, b))
         out = hip.conv_nhwc(x1, packed, bias, co, k, x2=x2, pre=pre, residual=residual, act=act != 0, slope=slope if act == 1 else 0.0,
                             slope_ptr=prelu_w, epilogue=epilogue)
         ctx.meta = (act, slope, epilogue, (a, b), k, bias is not None, 0 if pre is None else pre.shape[0])
@@ -341,6 +350,14 @@ class _Conv(Function):
         return g_x1, g_x2, g_w, g_bias, g_slope, g_p, g_res, None, None, None
 
 
+def _resblock_fwd(x, w1, b1, w2, b2):
+    """(t, out) = (relu(conv1(x)), x + conv2(t)): the two launches of a residual block"""
+    pk1, _ = _fwd_pack(w1, (0, w1.shape[1]))
+    pk2, _ = _fwd_pack(w2, (0, w2.shape[1]))
+    t = hip.conv_nhwc(x, pk1, b1, w1.shape[0], 3, act=True, slope=0.0)
+    return t, hip.conv_nhwc(t, pk2, b2, w2.shape[0], 3, residual=x)
+
+
 class _ResBlock(Function):
     """x + conv2(relu(conv1(x))) -- ResidualBlockNoBN with res_scale 1 (arch_util.py:45-70) -- as ONE autograd node: recorded as
     two _Conv nodes, autograd adds the two gradients of x (identity path and conv1's input gradient) in a launch of its own, 48
@@ -348,18 +365,8 @@ class _ResBlock(Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2):
-        c = w1.shape[0]
         w1, w2 = w1.contiguous(), w2.contiguous()
-        pks = []
-        for w in (w1, w2):
-            terms, wscale = _fwd_terms(), 1.0
-            if terms == 16:
-                wscale = _wscale(w)
-                if wscale is None:
-                    terms, wscale = TERMS, 1.0
-            pks.append(_packed(w, (0, w.shape[1]), terms, wscale=wscale))
-        t = hip.conv_nhwc(x, pks[0], b1, c, 3, act=True, slope=0.0)
-        out = hip.conv_nhwc(t, pks[1], b2, w2.shape[0], 3, residual=x)
+        t, out = _resblock_fwd(x, w1, b1, w2, b2)
         ctx.save_for_backward(x, t, w1, w2)
         ctx.has_bias = (b1 is not None, b2 is not None)
         return out
@@ -393,20 +400,9 @@ class _ResChain(Function):
     @staticmethod
     def forward(ctx, x, *params):
         nb = len(params) // 4
-        c = params[0].shape[0]
         saved = [x]
         for i in range(nb):
-            w1, b1, w2, b2 = params[4 * i:4 * i + 4]
-            pks = []
-            for w in (w1, w2):
-                terms, wscale = _fwd_terms(), 1.0
-                if terms == 16:
-                    wscale = _wscale(w)
-                    if wscale is None:
-                        terms, wscale = TERMS, 1.0
-                pks.append(_packed(w, (0, c), terms, wscale=wscale))
-            t = hip.conv_nhwc(x, pks[0], b1, c, 3, act=True, slope=0.0)
-            x = hip.conv_nhwc(t, pks[1], b2, c, 3, residual=x)
+            t, x = _resblock_fwd(x, *params[4 * i:4 * i + 4])   # (reschain() admits square blocks of one width only)
             saved += [t, x]
         ctx.nb = nb
         ctx.save_for_backward(*saved[:-1], *params)     # x_0, (t_i, x_i+1) ... without the output
@@ -431,7 +427,7 @@ class _ResChain(Function):
                 g_b2, amax2 = stats
             pk2, terms2 = _bwd_pack(w2, (0, c))
             pk1, terms1 = _bwd_pack(w1, (0, c))
-            if FUSED_BWD and terms1 == 16 and terms2 == 16:
+            if terms1 == 16 and terms2 == 16:
                 # both element-wise passes of the block ride on the input-gradient launches: conv2's takes the ReLU mask from t and
                 # leaves conv1's bias gradient and the scale of its own output; conv1's adds the skip and leaves the same for the
                 # block above (mrefsr_conv_nhwc_bwd_f32) -- two launches per block instead of four, no extra pass over g
@@ -466,12 +462,8 @@ class _ConvDynAgg(Function):
     @staticmethod
     def forward(ctx, feat, weight, bias, pre_offset, dg, abs_sum):
         weight = weight.contiguous()
-        terms, wscale = _fwd_terms(), 1.0
-        if terms == 16:
-            wscale = _wscale(weight)
-            if wscale is None:
-                terms, wscale = TERMS, 1.0
-        offset, mask = hip.conv_dynagg(feat, _packed(weight, None, terms, wscale=wscale), bias, pre_offset, dg, abs_sum)
+        packed, _ = _fwd_pack(weight, None)
+        offset, mask = hip.conv_dynagg(feat, packed, bias, pre_offset, dg, abs_sum)
         ctx.dg = dg
         ctx.save_for_backward(feat, weight, mask)
         return offset, mask
@@ -513,7 +505,7 @@ class _Dcn(Function):
         x, offset, mask, weight, out = ctx.saved_tensors
         g = g.contiguous()
         c, co = x.shape[3], weight.shape[0]
-        ws = _wscale(weight) if (DCN_FUSED_BWD and not hip.is_range_free()) else None
+        ws = None if hip.is_range_free() else _wscale(weight)
         if ws is not None and c % 32 == 0 and c // ctx.dg in (8, 16, 32) and co % 16 == 0:
             # fused: d columns = W^T . g on the matrix pipe with the offset / mask / input gradients as its epilogue, d W with the
             # columns re-gathered inside the GEMM -- no C*9*H*W buffer, no library GEMM (deform_conv_cuda.cpp:571-685 as two launches)
@@ -833,7 +825,6 @@ def resblock(blk, x):
 
 
 RESCHAIN = os.environ.get('MREFSR_TRAIN_RESCHAIN', '1') != '0'
-FUSED_BWD = os.environ.get('MREFSR_TRAIN_FUSED_BWD', '1') != '0'
 
 
 def reschain(blocks, x):

@@ -158,7 +158,7 @@ def discriminator(net, x):
     """UNetDiscriminatorSN.forward on the kernels: x [B,3,H,W] (cuda, fp32) -> [B,1,H,W]"""
     n, _, h, w = x.shape
     check_size(net, h, w)
-    ws, _ = spectral_norm_weights(net, net.training and not nhwc_disc._frozen[0])
+    ws, _ = spectral_norm_weights(net, net.training and not nhwc_disc.statistics_frozen())
     skip = net.skip_connection
     x0 = _VConv.apply(_Pack.apply(x), net.conv0.weight, net.conv0.bias, 3, True)
     x1 = _VConv.apply(x0, ws[0], None, 4, True)

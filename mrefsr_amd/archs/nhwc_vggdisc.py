@@ -154,7 +154,7 @@ def discriminator(net, x):
     h = _VConv.apply(h, net.conv0_0.weight, net.conv0_0.bias, 3, True)
     for conv, bn in net.conv_bn_layers():
         h = _VConv.apply(h, conv.weight, None, conv.kernel_size[0], False)
-        stats = (None, None, None) if nhwc_disc._frozen[0] else (bn.running_mean, bn.running_var, bn.num_batches_tracked)
+        stats = (None, None, None) if nhwc_disc.statistics_frozen() else (bn.running_mean, bn.running_var, bn.num_batches_tracked)
         h = _Bn.apply(h, bn.weight, bn.bias, *stats, bn.eps, bn.momentum)
     out = _LinearHead.apply(h, net.linear1.weight, net.linear1.bias, net.linear2.weight.view(-1), net.linear2.bias)
     return out.view(-1, 1)

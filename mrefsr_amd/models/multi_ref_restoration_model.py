@@ -20,6 +20,7 @@ What differs underneath (SURVEY 7 "hard parts"):
     failure mode); net_g is wrapped in DistributedDataParallel (RCCL all-reduce of its 94.8 MB);
   * `l.item()` logging is deferred: log_dict holds device scalars until get_current_log().
 """
+import contextlib
 import logging
 import os
 from collections import OrderedDict
@@ -216,6 +217,24 @@ class MultiRefRestorationModel:
             f'(no range limit, ~1.5x slower); {self.range_fallbacks} such batch(es) so far')
         return True
 
+    def _rerun_range_free(self, what, body, default=None, zero_grad=False, frozen_d=False, reset_scales=True, tripped=None):
+        """the fallback of every pass that reads the fp16-range flag: if it is set (``tripped`` None: read here, one 4-byte readback;
+        test() has read it already), the cached weight scales are dropped (not in test(): it trains nothing), net_g's gradients are
+        zeroed on request, body() runs again under hip.range_free() -- with D's running statistics frozen when the D step has already
+        been taken -- and the flag is read once more to clear it.  Returns body()'s value, or ``default`` when nothing tripped."""
+        from .. import hip
+        from ..archs import nhwc_disc, nhwc_train
+        if not (self._range_tripped(what) if tripped is None else tripped):
+            return default
+        if reset_scales:
+            nhwc_train.reset_scales()
+        if zero_grad:
+            self.optimizer_g.zero_grad()
+        with hip.range_free(), (nhwc_disc.frozen_statistics() if frozen_d else contextlib.nullcontext()):
+            out = body()
+        hip.conv_range_tripped()
+        return out
+
     def _loss_and_backward(self, step):
         """net_g's losses of ref :197-279 and their backward: returns True when a gradient was produced (the optimiser may step)"""
         if step <= self.net_g_pretrain_steps:
@@ -247,6 +266,10 @@ class MultiRefRestorationModel:
             return True
         return False
 
+    def _forward_backward(self, step):
+        self.output = self._forward()
+        return self._loss_and_backward(step)
+
     # ------------------------------------------------------------------ hipGraph replay of the training step
     def _train_graph_wanted(self):
         """opt['train']['hip_graph'] or MREFSR_TRAIN_GRAPH=1 (EXPERIMENTAL, off by default: 1-2 % at the shipped patch size; see the
@@ -260,13 +283,6 @@ class MultiRefRestorationModel:
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
     _GRAPH_WARMUP = 3   # eager steps per input shape before capture (lazy kernel attributes, workspaces, MIOpen find results)
-    # Experiment knobs of tools/train_graph_replay_fault.py (set on the class by the reproducer's child process, never by the product):
-    #   _REPLAY_FENCE    False: no host fence behind the update graph (the fault shows) | 'sleep' | 'event' | 'device': other waits in its place
-    #   _GRAPH_VARIANT   'shared_pool' (shipped: the update graph allocates from the forward / backward graph's pool) | 'own_pool' |
-    #                    'one_graph' (forward, backward and update captured as ONE executable) | 'pack_outside' (the weight-pack launch
-    #                    of begin_step() runs eagerly in front of each replay instead of inside the graph)
-    _REPLAY_FENCE = True
-    _GRAPH_VARIANT = 'shared_pool'
 
     def _optimize_graphed(self, step):
         """True when the step was taken by graph replay"""
@@ -303,27 +319,17 @@ class MultiRefRestorationModel:
             logging.getLogger('basicsr').warning(
                 'hip_graph (training) is EXPERIMENTAL: hipStreamSynchronize is called behind every replayed update (without it the runtime of '
                 'ROCm 7.2 faults after 25-50 graph launches: profiles/r5_train_graph_replay_fault.txt)')
-            variant = self._GRAPH_VARIANT
-            fb, upd = torch.cuda.CUDAGraph(), (None if variant == 'one_graph' else torch.cuda.CUDAGraph())
+            fb, upd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             lr_val = [float(pg['lr']) for pg in self.optimizer_g.param_groups]
             lr_dev = [torch.tensor(v, device=self.device, dtype=torch.float32) for v in lr_val]
-            if variant == 'pack_outside':
-                nhwc_train.begin_step()
             try:
                 with torch.cuda.graph(fb):
-                    if variant != 'pack_outside':
-                        nhwc_train.begin_step()   # the packed weight copies are refreshed by the graph itself (one launch)
-                    self.output = self._forward()
-                    self._loss_and_backward(step)
-                    if upd is None:
-                        for pg, t in zip(self.optimizer_g.param_groups, lr_dev):
-                            pg['lr'] = t
-                        self.optimizer_g.step()
-                if upd is not None:
-                    for pg, t in zip(self.optimizer_g.param_groups, lr_dev):
-                        pg['lr'] = t           # the captured update reads its learning rates from device memory ...
-                    with (torch.cuda.graph(upd) if variant == 'own_pool' else torch.cuda.graph(upd, pool=fb.pool())):
-                        self.optimizer_g.step()
+                    nhwc_train.begin_step()   # the packed weight copies are refreshed by the graph itself (one launch)
+                    self._forward_backward(step)
+                for pg, t in zip(self.optimizer_g.param_groups, lr_dev):
+                    pg['lr'] = t           # the captured update reads its learning rates from device memory ...
+                with torch.cuda.graph(upd, pool=fb.pool()):
+                    self.optimizer_g.step()
             finally:
                 for pg, v in zip(self.optimizer_g.param_groups, lr_val):
                     pg['lr'] = v       # ... while the schedulers keep working on plain numbers
@@ -348,41 +354,25 @@ class MultiRefRestorationModel:
             if v != st['lr_val'][i]:
                 st['lr_dev'][i].fill_(v)
                 st['lr_val'][i] = v
-        if self._GRAPH_VARIANT == 'pack_outside':
-            nhwc_train.begin_step()
         st['fb'].replay()
         self.output, self.max_idx = st['out'], st['idx']
         self.log_dict.update(st['log'])
-        if self._range_tripped('optimize_parameters'):   # rare: redo this step eagerly on the range-free kernels
-            nhwc_train.reset_scales()
-            self.optimizer_g.zero_grad()
-            with hip.range_free():
-                self.output = self._forward()
-                stepped = self._loss_and_backward(step)
-            hip.conv_range_tripped()
+        # rare: redo this step eagerly on the range-free kernels (None: nothing tripped)
+        stepped = self._rerun_range_free('optimize_parameters', lambda: self._forward_backward(step), zero_grad=True)
+        if stepped is not None:
             if stepped:
                 self.optimizer_g.step()
             return True
-        if st['upd'] is not None:
-            st['upd'].replay()
+        st['upd'].replay()
         # hipStreamSynchronize behind the update graph.  Without it a run of replayed steps ends in a GPU memory access fault after
         # 25-50 replays (ROCm 7.2; never in eager mode).  It is not an ordering fence: an event recorded here and waited for on the
         # host (the GPU provably idle at the next launch), or a 20-ms sleep, do NOT remove the fault, hipStreamSynchronize /
         # hipDeviceSynchronize do; the update graph in a pool of its own, or forward + backward + update as ONE executable, fault
         # alike; every fault address is page 0x37 / 0x38 of a 2-MB block (220 KB = the kernel-argument segments of one launch of this
         # ~700-node graph).  What the call does is make the runtime retire its per-launch bookkeeping of completed graph launches
-        # (profiles/r5_train_graph_replay_fault.txt).  Cost: ~0.2 ms of host work not overlapped.
-        if self._REPLAY_FENCE is True:
-            torch.cuda.current_stream().synchronize()
-        elif self._REPLAY_FENCE == 'sleep':      # (experiments: a host wait without any HIP call)
-            import time
-            time.sleep(0.02)
-        elif self._REPLAY_FENCE == 'event':      # (experiments: an event recorded behind the update graph, waited for on the host)
-            ev = torch.cuda.Event()
-            ev.record()
-            ev.synchronize()
-        elif self._REPLAY_FENCE == 'device':     # (experiments: hipDeviceSynchronize instead of the stream's)
-            torch.cuda.synchronize()
+        # (profiles/r5_train_graph_replay_fault.txt, profiles/r4_train_graph_replay_fault.txt).  Cost: ~0.2 ms of host work not
+        # overlapped.
+        torch.cuda.current_stream().synchronize()
         return True
 
     def _discriminator_step(self):
@@ -408,32 +398,7 @@ class MultiRefRestorationModel:
         for p in self.net_d.parameters():   # ref :249-251, before the G step
             p.requires_grad = False
 
-    def _optimize_adversarial(self, step):
-        """a step with a discriminator past net_g_pretrain_steps.  The fp16-range flag is read right after net_g's forward (one 4-byte
-        readback), so that a forward re-run on the range-free kernels happens before the D step: D's Adam step and each BatchNorm's
-        running statistics are updated once per D forward of the reference.  Should net_g's backward trip the flag, the G step is
-        re-run on the range-free kernels with D's running statistics left as they are (the D step is not repeated)."""
-        from .. import hip
-        from ..archs import nhwc_disc, nhwc_train
-        if self._range_tripped('optimize_parameters'):
-            nhwc_train.reset_scales()
-            with hip.range_free():
-                self.output = self._forward()
-            hip.conv_range_tripped()
-        self._discriminator_step()
-        stepped = self._loss_and_backward(step)
-        if self._range_tripped('optimize_parameters'):
-            nhwc_train.reset_scales()
-            self.optimizer_g.zero_grad()
-            with hip.range_free(), nhwc_disc.frozen_statistics():
-                self.output = self._forward()
-                stepped = self._loss_and_backward(step)
-            hip.conv_range_tripped()
-        if stepped:
-            self.optimizer_g.step()
-
     def optimize_parameters(self, step):
-        from .. import hip
         from ..archs import nhwc_train
         nhwc_train.check_scales()   # cached fp16 weight scales of the training convolutions still valid? (device side)
         if self._train_graph_wanted() and self._optimize_graphed(step):
@@ -441,16 +406,18 @@ class MultiRefRestorationModel:
         self.optimizer_g.zero_grad()
         nhwc_train.begin_step()     # every packed copy of net_g's weights refreshed in one launch (they changed in optimizer_g.step())
         self.output = self._forward()
-        if getattr(self, 'net_d', None) is not None and step > self.net_g_pretrain_steps:
-            return self._optimize_adversarial(step)
+        adversarial = getattr(self, 'net_d', None) is not None and step > self.net_g_pretrain_steps
+        if adversarial:
+            # The fp16-range flag is read right after net_g's forward (one 4-byte readback), so that a forward re-run on the range-free
+            # kernels happens before the D step: D's Adam step and each BatchNorm's running statistics are updated once per D forward
+            # of the reference.  Should net_g's backward trip the flag below, the G step is re-run with D's running statistics left as
+            # they are (the D step is not repeated).
+            self.output = self._rerun_range_free('optimize_parameters', self._forward, self.output)
+            self._discriminator_step()
         stepped = self._loss_and_backward(step)
-        if self._range_tripped('optimize_parameters'):   # the frozen feature networks and the DCN forward run on the split kernels
-            nhwc_train.reset_scales()
-            self.optimizer_g.zero_grad()
-            with hip.range_free():
-                self.output = self._forward()
-                stepped = self._loss_and_backward(step)
-            hip.conv_range_tripped()
+        # (the frozen feature networks and the DCN forward run on the split kernels too)
+        stepped = self._rerun_range_free('optimize_parameters', lambda: self._forward_backward(step), stepped, zero_grad=True,
+                                         frozen_d=adversarial)
         if stepped:
             self.optimizer_g.step()
 
@@ -467,9 +434,7 @@ class MultiRefRestorationModel:
                 self.output = self._forward()
                 tripped = self._range_tripped('test')
             if tripped:
-                with hip.range_free():
-                    self.output = self._forward()
-                hip.conv_range_tripped()
+                self.output = self._rerun_range_free('test', self._forward, reset_scales=False, tripped=True)
         self.net_g.train()
 
     # ------------------------------------------------------------------ hipGraph replay of the inference pass
