@@ -14,10 +14,8 @@ _EXACT_ONLY = os.environ.get('MREFSR_CORR_EXACT', '0') == '1'
 # The pre-filter operand: one fp16 plane (one MFMA per term) with a window derived from the MEASURED rounding error
 # of the feature maps (hip.prefilter_window: ~2x tighter than the worst case, which made this variant overflow its
 # candidate lists on maps full of near-ties) -- the default for 256-channel features; MREFSR_CORR_FP16=0 selects
-# the bf16 two-term split (three MFMAs per term, fixed window), MREFSR_CORR_WINDOW=worst the fp16 operand with the
-# worst-case window (A/B measurements).
+# the bf16 two-term split (three MFMAs per term, fixed window).
 _BF16_PREFILTER = os.environ.get('MREFSR_CORR_FP16', '1') == '0'
-_WORST_CASE_WINDOW = os.environ.get('MREFSR_CORR_WINDOW', '') == 'worst'
 
 
 def sample_patches(inputs, patch_size=3, stride=1):
@@ -81,7 +79,7 @@ def match_normalised_batch(feat_in, feat_ref):
         y_ref, n2_ref, bf_ref = prep(feat_ref, True)
     nrm_in, _ = hip.patch_norm(n2_in)
     _, inv_ref = hip.patch_norm(n2_ref)
-    if fmt == 'fp16' and not _EXACT_ONLY and not _WORST_CASE_WINDOW:
+    if fmt == 'fp16' and not _EXACT_ONLY:
         tau = hip.prefilter_window(nrm_in, inv_ref, d2_in, d2_ref)   # data-dependent, proven window
     idx, _ = hip.corr_top1(y_in, y_ref, inv_ref, nrm_in, h, w, want_val=False, ybf_in=bf_in, ybf_ref=bf_ref, tau=tau)
     return idx

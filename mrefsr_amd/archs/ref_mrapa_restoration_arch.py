@@ -22,7 +22,6 @@ What is different underneath:
     gradients in csrc/wgrad.hip, the DCN backward in csrc/dcn_bwd.hip; generic torch forms only for what the engine refuses.
 """
 import logging
-import os
 
 import torch
 import torch.nn as nn
@@ -35,8 +34,6 @@ from ..ops.dcn import modulated_deform_conv
 from ..utils.registry import ARCH_REGISTRY
 from . import nhwc, nhwc_train
 from .arch_util import ResidualBlockNoBN, conv_act, default_init_weights, make_layer, srntt_init_weights
-
-TAIL_FUSED = os.environ.get('MREFSR_TAIL_FUSED', '1') != '0'   # (0: the ATen tail, for A/B)
 
 
 class _DynAggPrep(Function):
@@ -234,7 +231,7 @@ class MRAPARestorationNet(nn.Module):
             feat = nhwc.res_chain(ce.body, nhwc.conv(ce.conv_first, nhwc.image_to_nhwc4(x), slope=0.1))
             refs = {key: nhwc.to_nhwc(v if v.dtype == feat.dtype else v.to(feat.dtype)) for key, v in img_ref_feat.items()}
             out = self.dyn_agg_restore.forward_nhwc(feat, pre_offset, refs, k)
-            if TAIL_FUSED and not nhwc.BF16 and out.dtype == torch.float32 and x.dtype == torch.float32 and not (out.requires_grad or x.requires_grad):
+            if not nhwc.BF16 and out.dtype == torch.float32 and x.dtype == torch.float32 and not (out.requires_grad or x.requires_grad):
                 return hip.tail_bilinear_add(out, x, 4)   # F.interpolate + add + NCHW copy of :132-137 in one pass (torch's interpolation bits)
             base = F.interpolate(x, None, 4, 'bilinear', False)
             return nhwc.rnd_((nhwc.as_nchw(out).float() + nhwc.rnd_(base)).contiguous())

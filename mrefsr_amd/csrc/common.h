@@ -4,6 +4,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include "../../include/mrefsr_hip.h"
 
@@ -43,6 +44,16 @@ inline bool first_use_on_device(unsigned long long &done)
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Switches of A/B measurements (tools/; MREFSR_HIP_LIB = a -DMREFSR_AB_KERNELS build): such a build reads them from the environment
+// per call.  In the product they are their defaults at compile time: no getenv, and the branch a switch guards folds away.
+#ifdef MREFSR_AB_KERNELS
+inline long ab_int(const char *name, long dflt) { const char *e = getenv(name); return e ? atol(e) : dflt; }
+inline bool ab_flag(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] != '0' : dflt; }
+#else
+constexpr long ab_int(const char *, long dflt) { return dflt; }
+constexpr bool ab_flag(const char *, bool dflt) { return dflt; }
+#endif
+
 // corr.hip: exact correlation kernel on the query tiles flagged by the pre-filter (corr_prefilter.hip)
 int launch_corr_top1_flagged(const float *y_in, const float *y_ref, const float *inv_ref, const float *nrm_in, int64_t *max_idx,
                              float *max_val, int n_in, int n_pair, int Cp, int h, int w, const int *tile_flag, const int *flag_count,
@@ -56,7 +67,7 @@ namespace mrefsr {
 int launch_corr_prefilter_rs16(const void *yh_in, const void *yh_ref, const float *inv_ref, const float *nrm_in, const float *tau,
                                const mrefsr_corr::PrefilterOut &out, int n_in, int n_pair, int h, int w, float tau_scale, float *dbg,
                                void *scratch, hipStream_t stream);
-// bytes of `scratch` (per-lane candidate lists of the exchanged-products kernel; NULL scratch = the previous kernel, lists in LDS)
+// bytes of `scratch` (per-lane candidate lists of the exchanged-products kernel)
 int64_t corr_prefilter_rs16_scratch_bytes(int n_pair, int h, int w);
 int64_t corr_prefilter_rs16_mfma_flop(int h, int w, const char **name);
 }  // namespace mrefsr

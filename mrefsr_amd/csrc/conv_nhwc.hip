@@ -1140,10 +1140,16 @@ __global__ __launch_bounds__(512, 2) void conv_nhwc8_kernel(const ConvArgs A)
 #ifndef MREFSR_CONV_NT
 #define MREFSR_CONV_NT 1
 #endif
-static long xcd_min_blocks()
+// The launch policy the three kernels of this file share: streaming stores for an output the caches cannot hold, and XCD band order
+// once the grid has 128 blocks (2048 at first: the 40^2 ... 160^2 launches of the training step gain too, 38.5 -> 37.9 ms).
+// MREFSR_CONV_XCD=0 / MREFSR_CONV_XCD_MIN: dispatch order / another threshold (A/B builds).
+static ConvArgs with_launch_policy(const ConvArgs &a, int N, const dim3 &grid)
 {
-    static const long v = getenv("MREFSR_CONV_XCD_MIN") ? atol(getenv("MREFSR_CONV_XCD_MIN")) : 128;   // (2048 at first: the 40^2 ... 160^2 launches of the training step gain too, 38.5 -> 37.9 ms)
-    return v;
+    ConvArgs b = a;
+    b.stream_out = MREFSR_CONV_NT && (size_t)N * a.H * a.W * a.ld_out * sizeof(float) > ((size_t)256 << 20);
+    b.xcd_bands = mrefsr::ab_flag("MREFSR_CONV_XCD", MREFSR_CONV_XCD_DEFAULT) &&
+                  (long)grid.x * grid.y * grid.z >= mrefsr::ab_int("MREFSR_CONV_XCD_MIN", 128);
+    return b;
 }
 
 // ---- 1 x 1 convolutions of fp32 tensors (MODE 2): the channel-reduction layers in front of the trunks (the DynAgg fusion layers and
@@ -1303,10 +1309,7 @@ int launch1x1(const ConvArgs &a, int N, hipStream_t stream)
     if (mrefsr::first_use_on_device(attr1))
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv1x1_kernel<RES>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
     dim3 grid(((a.W + TW - 1) / TW) * a.n_cb, (a.H + THB - 1) / THB, N);
-    ConvArgs b = a;
-    b.stream_out = MREFSR_CONV_NT && (size_t)N * a.H * a.W * a.ld_out * sizeof(float) > ((size_t)256 << 20);
-    const char *ex = getenv("MREFSR_CONV_XCD");
-    b.xcd_bands = (ex ? ex[0] != '0' : MREFSR_CONV_XCD_DEFAULT) && (long)grid.x * grid.y * grid.z >= xcd_min_blocks();
+    ConvArgs b = with_launch_policy(a, N, grid);
     b.warm_w = 0;
     hipLaunchKernelGGL((conv1x1_kernel<RES>), grid, dim3(256), lds1, stream, b);
     return mrefsr::check_launch("conv1x1");
@@ -1338,9 +1341,8 @@ int launch(const ConvArgs &a, int N, hipStream_t stream)
     }
     if constexpr (MODE == 2 && !IO16 && KS == 3 && RPW == 4) {
         // Cout > 64 on a launch that fills the chip with 512-thread blocks: two cout blocks share one split halo tile
-        // (conv_nhwc8_kernel).  MREFSR_CONV8=0 keeps the 4-wave kernel (A/B runs; same bits either way).
-        const char *e8 = getenv("MREFSR_CONV8");   // (read per call: tests flip it inside one process)
-        const bool conv8 = !(e8 && e8[0] == '0');
+        // (conv_nhwc8_kernel).  MREFSR_CONV8=0 keeps the 4-wave kernel (A/B builds; same bits either way).
+        const bool conv8 = mrefsr::ab_flag("MREFSR_CONV8", true);
         const long groups = (long)((a.W + TW - 1) / TW) * (a.n_cb / 2) * ((a.H + TH - 1) / TH) * N;
         const bool fits = (a.C1 % KC) == 0 && (a.C2 % KC) == 0 && (size_t)a.H * a.W * (size_t)(a.ld1 > a.ld2 ? a.ld1 : a.ld2) * 4 < ((size_t)1 << 32) &&
                           (size_t)a.H * a.W < ((size_t)1 << 24);
@@ -1354,13 +1356,8 @@ int launch(const ConvArgs &a, int N, hipStream_t stream)
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_nhwc8_kernel<KS, RES, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_nhwc8_kernel<KS, RES, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds8);
             }
-            ConvArgs b = a;
-            b.stream_out = MREFSR_CONV_NT && (size_t)N * a.H * a.W * a.ld_out * sizeof(float) > ((size_t)256 << 20);
             dim3 grid(((a.W + TW - 1) / TW) * (a.n_cb / 2), (a.H + TH - 1) / TH, N);
-            {
-                const char *ex = getenv("MREFSR_CONV_XCD");
-                b.xcd_bands = (ex ? ex[0] != '0' : MREFSR_CONV_XCD_DEFAULT) && (long)grid.x * grid.y * grid.z >= xcd_min_blocks();
-            }
+            const ConvArgs b = with_launch_policy(a, N, grid);
             const int tail = a.Cout % NB;   // couts of the last block: 1..32 -> that block runs one MFMA column
             if (tail == 0 || tail > 32) hipLaunchKernelGGL((conv_nhwc8_kernel<KS, RES, true>), grid, dim3(512), lds8, stream, b);
             else hipLaunchKernelGGL((conv_nhwc8_kernel<KS, RES, false>), grid, dim3(512), lds8, stream, b);
@@ -1390,13 +1387,8 @@ int launch(const ConvArgs &a, int N, hipStream_t stream)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(conv_nhwc_kernel<MODE, KS, IO16, RES, RPW>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
     dim3 grid(((a.W + TW - 1) / TW) * a.n_cb, (a.H + THB - 1) / THB, N);
-    ConvArgs b = a;
-    b.stream_out = MREFSR_CONV_NT && (size_t)N * a.H * a.W * a.ld_out * sizeof(float) > ((size_t)256 << 20);
-    {
-        const char *ex = getenv("MREFSR_CONV_XCD");   // (read per call: A/B runs flip it inside one process)
-        b.xcd_bands = (ex ? ex[0] != '0' : MREFSR_CONV_XCD_DEFAULT) && (long)grid.x * grid.y * grid.z >= xcd_min_blocks();
-    }
-    static const long warm_max = getenv("MREFSR_CONV_WARM") ? atol(getenv("MREFSR_CONV_WARM")) : 1024;
+    ConvArgs b = with_launch_policy(a, N, grid);
+    const long warm_max = mrefsr::ab_int("MREFSR_CONV_WARM", 1024);   // (A/B builds)
     {   // blocks per XCD and cout block share the slab's lines between them (1 = every block requests all of it, 0 = off)
         const long nblk = (long)grid.x * grid.y * grid.z, share = nblk / (8 * a.n_cb);
         b.warm_w = nblk <= warm_max ? (int)(share < 1 ? 1 : (share > 8 ? 8 : share)) : 0;

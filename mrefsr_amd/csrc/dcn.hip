@@ -1316,7 +1316,7 @@ static int dcn_fwd_entry(const float *x, const float *offset, const float *mask,
                        (long)workspace_bytes);
         float *wp = (float *)workspace;
         const long tot = (long)g.Co * g.C * 9;
-        static const int xcd_order = [] { const char *e = getenv("MREFSR_DCN_XCD"); return (e && e[0] == '0') ? 0 : 1; }();
+        const int xcd_order = mrefsr::ab_flag("MREFSR_DCN_XCD", true);
         const long nblk = (long)mrefsr::cdiv(HWo, 64) * g.B;
         dim3 grid((unsigned)(xcd_order ? ((nblk + 7) / 8) * 8 : nblk));
         // Channels-last input runs on the 16-bit matrix pipe from exact operand splits (fp32-equivalent results):
@@ -1375,9 +1375,8 @@ static int dcn_fwd_entry(const float *x, const float *offset, const float *mask,
                 // (four tiles = 64 accumulator registers per 32 x 32 wave tile: only the Co = 64 shapes have room for them)
                 // (the paired four-channel mapping also where a deformable group is 16 channels: the lanes of a quad then form their two
                 //  setups twice, which costs no instruction, and every corner is one 64-byte request: 6.4 -> 6.0 ms at C = 128;
-                //  MREFSR_DCN_MAP8=1: the eight-channel mapping, A/B runs)
-                const char *e_m8 = getenv("MREFSR_DCN_MAP8");
-                const bool map8 = e_m8 && e_m8[0] == '1';
+                //  MREFSR_DCN_MAP8=1: the eight-channel mapping, A/B builds)
+                const bool map8 = mrefsr::ab_flag("MREFSR_DCN_MAP8", false);
                 if (g.Co == 256) MREFSR_DCNPT(2, 2, true, MREFSR_DCNPT_T2);
                 else if (g.Co == 128 && map8) MREFSR_DCNPT(1, 2, true, MREFSR_DCNPT_T2);
                 else if (g.Co == 128) MREFSR_DCNPT(1, 2, false, MREFSR_DCNPT_T2);

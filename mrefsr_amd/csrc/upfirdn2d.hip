@@ -520,8 +520,8 @@ int launch_upfirdn2d(const void *in, const void *kernel, void *out, UpParams p, 
             const int tiles_x = mrefsr::cdiv(p.out_w, tw), tiles_y = mrefsr::cdiv(p.out_h, th);
             const long tiles = (long)tiles_x * tiles_y * p.major;
             // tiles per block: 2 once the launch has more than four rounds of resident blocks (measured at 16384 tiles: 1 / 2 / 4 / 8 tiles per
-            // block = 140 / 134 / 135 / 141 us for the blur, 98 / 98 / 105 / 114 for down x2); MREFSR_UP_TPB overrides (A/B)
-            static const int tpb_env = getenv("MREFSR_UP_TPB") ? atoi(getenv("MREFSR_UP_TPB")) : 0;
+            // block = 140 / 134 / 135 / 141 us for the blur, 98 / 98 / 105 / 114 for down x2); MREFSR_UP_TPB overrides (A/B builds)
+            const int tpb_env = (int)mrefsr::ab_int("MREFSR_UP_TPB", 0);
             int tpb = tpb_env > 0 ? tpb_env : (tiles >= 256L * 4 * 4 ? 2 : 1);
             tpb = tpb < 1 ? 1 : (tpb > 8 ? 8 : tpb);
             const long blocks = (tiles + tpb - 1) / tpb;

@@ -6,7 +6,6 @@ tensor raises (the reference's native ops raise NotImplementedError on CPU tenso
 basicsr/ops/dcn/deform_conv.py:61-62).
 """
 import ctypes as C
-import os
 
 import torch
 
@@ -322,7 +321,6 @@ def capture_epoch():
 
 _zero_chunks = {}
 _ZCHUNK = 1 << 18
-ZERO_POOL = os.environ.get('MREFSR_ZERO_POOL', '1') != '0'
 _ZALIGN = 128         # floats: slices start on 512-byte boundaries like allocations of their own (float atomics into a slice at
                       # 16-byte granularity ran 17 % slower: act_bwd_nhwc 5.66 -> 4.87 ms per training step)
 
@@ -333,8 +331,6 @@ def zeros_f32(device, n):
     slice is handed out once and never re-zeroed, so it may be kept (autograd adopts the bias gradient as ``.grad``); the chunk
     lives as long as any of its slices.  Chunks are per stream and per side of a capture boundary (the fill that zeroes a chunk
     has to be part of the graph whose kernels accumulate into it)."""
-    if not ZERO_POOL:
-        return torch.zeros(n, device=device, dtype=torch.float32)
     cap, epoch = capture_epoch()
     key = (device.index, torch.cuda.current_stream().cuda_stream, cap)
     n4 = (n + _ZALIGN - 1) // _ZALIGN * _ZALIGN

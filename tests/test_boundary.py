@@ -29,6 +29,29 @@ def test_library_builds_and_exports_every_header_symbol():
     assert _lib.load().mrefsr_abi_version() == 1
 
 
+def test_product_library_reads_eight_switches_and_carries_no_retired_kernel():
+    """the environment variables libmrefsr_hip.so reads are the six the tests flip in one process and the two user-facing arithmetic
+    fallbacks; every other kernel-variant switch, and the retired row-stationary pre-filter that MREFSR_CORR_RS_DUP
+    selects, exist only in the -DMREFSR_AB_KERNELS build (mrefsr_amd/lib_ab)"""
+    csrc = os.path.join(ROOT, 'mrefsr_amd', 'csrc')
+    subprocess.check_call(['make', '-C', csrc, '-s'])
+    subprocess.check_call(['make', '-C', csrc, '-s', '-j4', 'OBJDIR=_obj_ab', 'OUTDIR=../lib_ab', 'EXTRA=-DMREFSR_AB_KERNELS'])
+    kept = {'MREFSR_CORR_W', 'MREFSR_CORR_RESCORE', 'MREFSR_DCN_PT', 'MREFSR_DCN_T', 'MREFSR_CONV1X1', 'MREFSR_WINO_WAVES',
+            'MREFSR_DCN_BF16', 'MREFSR_DCN_TERMS'}
+    ab_only = {'MREFSR_CONV_XCD', 'MREFSR_CONV_XCD_MIN', 'MREFSR_CONV8', 'MREFSR_CONV_WARM', 'MREFSR_CORR_XCD', 'MREFSR_CORR_RS_DUP',
+               'MREFSR_DCN_XCD', 'MREFSR_DCN_MAP8', 'MREFSR_UP_TPB'}
+
+    def env_names(blob):   # a name given to getenv is a whole C string (names inside messages are not)
+        return {m.decode() for m in re.findall(rb'(?<=\0)MREFSR_[A-Z0-9_]+(?=\0)', blob)}
+
+    product = open(os.path.join(ROOT, 'mrefsr_amd', 'lib', 'libmrefsr_hip.so'), 'rb').read()
+    assert env_names(product) == kept
+    assert b'corr_prefilter_rs16_kernel' not in product          # no host stub, no device symbol, no name string
+    ab = open(os.path.join(ROOT, 'mrefsr_amd', 'lib_ab', 'libmrefsr_hip.so'), 'rb').read()
+    assert env_names(ab) >= kept | ab_only
+    assert b'corr_prefilter_rs16_kernel' in ab
+
+
 def test_no_crossed_packed_fp32_multiply_in_the_device_code(tmp_path):
     """`v_pk_mul_f32 ... op_sel:[0,1] op_sel_hi:[1,0]` (crossed halves, formed by the SLP vectoriser) returned wrong
     values in lanes 48..63 on gfx950 while other workgroups' MFMAs shared the SIMD: the kernels are

@@ -127,7 +127,7 @@ def test_attention_and_modulation_nodes_match_fp64_autograd(c):
 
 
 def test_training_step_on_both_engines(golden, monkeypatch):
-    """the channels-last engine (default) and the MIOpen / NCHW autograd path (MREFSR_NHWC_TRAIN=0) produce the same loss
+    """the channels-last engine (default) and the MIOpen / NCHW autograd path (nhwc_train.ENABLED = False) produce the same loss
     and the same gradients, parameter by parameter, at the small golden shape"""
     from test_configs_gpu import _golden_model
     from mrefsr_amd.archs import nhwc_train

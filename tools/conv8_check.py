@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """conv_nhwc8_kernel (8 waves, two cout blocks per halo tile) against conv_nhwc_kernel on the benchmark's Cout >= 128 shapes:
-bit-identical outputs (same accumulation order) and the time of each.   python tools/conv8_check.py"""
+bit-identical outputs (same accumulation order) and the time of each.  MREFSR_CONV8 is a switch of the A/B build only:
+    MREFSR_HIP_LIB=mrefsr_amd/lib_ab/libmrefsr_hip.so python tools/conv8_check.py"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

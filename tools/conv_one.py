@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """a few launches of ONE convolution shape through both kernels (for rocprofv3 --pmc / --kernel-trace passes):
-    python tools/conv_one.py N H W CIN COUT [iters]"""
+    MREFSR_HIP_LIB=mrefsr_amd/lib_ab/libmrefsr_hip.so python tools/conv_one.py N H W CIN COUT [iters]
+(MREFSR_CONV8 is a switch of the A/B build only: the product library stays on conv_nhwc8_kernel)"""
 import os
 import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

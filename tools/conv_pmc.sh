@@ -1,5 +1,6 @@
 #!/bin/bash
 # PMC passes over tools/conv_one.py (one shape, both convolution kernels):  bash tools/conv_pmc.sh N H W CIN COUT -> gpurun_out/conv_pmc_<shape>.json
+# (needs MREFSR_HIP_LIB=mrefsr_amd/lib_ab/libmrefsr_hip.so: the product library ignores MREFSR_CONV8)
 set -u
 R=${GRAFT_REPO_ROOT:-$PWD}
 O=$R/gpurun_out/conv_pmc

@@ -8,7 +8,7 @@ import sys
 from collections import defaultdict
 
 db = sys.argv[1]
-marker = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith('--') else 'corr_prefilter_rs16'
+marker = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith('--') else 'corr_prefilter_rx16'
 top = int(sys.argv[sys.argv.index('--top') + 1]) if '--top' in sys.argv else 40
 c = sqlite3.connect(db)
 tabs = [r[0] for r in c.execute("select name from sqlite_master where type='table'")]
