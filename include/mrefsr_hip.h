@@ -748,6 +748,39 @@ int64_t mrefsr_disc_conv9_wgrad_workspace_bytes(int N, int H, int W, int C);
 int mrefsr_disc_conv9_wgrad_f32(const float *x, const float *gy, float *dw, int N, int H, int W, int C, void *workspace, int64_t workspace_bytes,
                                 mrefsr_stream_t stream);
 
+/* ---- StyleGAN2Discriminator of the adversarial training step (basicsr/archs/stylegan2_arch.py:733-799; the same D step and penalty
+ * as above): the kernels of mrefsr_amd/archs/nhwc_sg2disc.py that the entry points above do not cover.  conv1 of every ResBlock and
+ * final_conv run on mrefsr_disc_vconv*_f32 (ks 3), final_linear on mrefsr_disc_linear_head*_f32, the image packing on
+ * mrefsr_disc_pack_image_f32.  Channels-last fp32 maps, fixed summation orders (no float atomics).
+ *
+ * mrefsr_disc_sg2_fir_f32: upfirdn2d(x, outer(taps, taps), up 1, down, pad (pad0, pad1)) with a separable FIR of L = 2 .. 4 taps (HOST
+ *   memory, already normalised to sum 1), down 1 or 2, on x [N][H][W][C] -> y [N][Ho][Wo][C], Ho = (H + pad0 + pad1 - L) / down + 1; C a
+ *   multiple of 4.  adjoint 1: its input gradient, x = the gradient [N][Ho][Wo][C] -> y [N][H][W][C] (H, W still name the forward's
+ *   input; every element written).  Both are gathers; each is the other's backward.
+ * mrefsr_disc_sg2_pack_weight_f32: torch's w [Cout][CinR][ks][ks] (ks 1 or 3) -> dgrad 0: [Cout][ks ks][Cin], 1: [Cin][ks ks][Cout];
+ *   channels CinR..Cin-1 are 0.
+ * mrefsr_disc_sg2_conv_f32: conv2d(x, w, stride, padding 0) with ks 3 (stride 2: conv2 of a ResBlock, on the FIR's output) or ks 1
+ *   (stride 1: the ResBlock's skip, on the FIR's stride-2 output, and the input stage on the packed image): x [N][H][W][Cin] ->
+ *   y [N][Ho][Wo][Cout], Ho = (H - 3) / 2 + 1 or H; y = lrelu(conv + bias, slope) (bias may be NULL; LeakyReLU when act) + res (may be
+ *   NULL; [N][Ho][Wo][Cout]: the ResBlock's merge).  Implicit GEMM on v_mfma_f32_16x16x4_f32 with LDS-staged operand tiles; Cin a
+ *   multiple of 4, Cout of 16; small layers split the reduction into partial tiles added in a fixed order (workspace:
+ *   mrefsr_disc_sg2_conv_workspace_bytes(.., dgrad 0), may be 0).
+ * mrefsr_disc_sg2_conv_dgrad_f32: input gradient dy [N][Ho][Wo][Cout] -> dx [N][H][W][Cin] (every element written); ks 3 runs as four
+ *   input-parity phases of 4, 2, 2 and 1 taps (workspace: .._workspace_bytes(.., 1)).
+ * mrefsr_disc_sg2_conv_wgrad_f32: dw [Cout][CinR][ks][ks] = sum over the output pixels of x (x) dy, split over the pixels into partial
+ *   tiles added in a fixed order (workspace: mrefsr_disc_sg2_conv_wgrad_workspace_bytes). */
+int mrefsr_disc_sg2_fir_f32(const float *x, float *y, int N, int H, int W, int C, const float *taps, int L, int pad0, int pad1, int down,
+                            int adjoint, mrefsr_stream_t stream);
+int mrefsr_disc_sg2_pack_weight_f32(const float *w, float *wpk, int Cout, int CinR, int Cin, int ks, int dgrad, mrefsr_stream_t stream);
+int64_t mrefsr_disc_sg2_conv_workspace_bytes(int N, int H, int W, int Cin, int Cout, int ks, int dgrad);
+int mrefsr_disc_sg2_conv_f32(const float *x, const float *wpk, const float *bias, const float *res, float *y, int N, int H, int W, int Cin,
+                             int Cout, int ks, int act, float slope, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_disc_sg2_conv_dgrad_f32(const float *dy, const float *wpk_d, float *dx, int N, int H, int W, int Cin, int Cout, int ks,
+                                   void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int64_t mrefsr_disc_sg2_conv_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int ks);
+int mrefsr_disc_sg2_conv_wgrad_f32(const float *x, const float *dy, float *dw, int N, int H, int W, int Cin, int CinR, int Cout, int ks,
+                                   void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

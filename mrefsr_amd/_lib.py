@@ -147,6 +147,13 @@ SIGNATURES = {
     'mrefsr_disc_conv9_dgrad_f32': (_i, [_vp] * 3 + [_i] * 4 + [_vp]),
     'mrefsr_disc_conv9_wgrad_workspace_bytes': (_i64, [_i] * 4),
     'mrefsr_disc_conv9_wgrad_f32': (_i, [_vp] * 3 + [_i] * 4 + [_vp, _i64, _vp]),
+    'mrefsr_disc_sg2_fir_f32': (_i, [_vp, _vp] + [_i] * 4 + [_vp] + [_i] * 5 + [_vp]),
+    'mrefsr_disc_sg2_pack_weight_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'mrefsr_disc_sg2_conv_workspace_bytes': (_i64, [_i] * 7),
+    'mrefsr_disc_sg2_conv_f32': (_i, [_vp] * 5 + [_i] * 7 + [_f, _vp, _i64, _vp]),
+    'mrefsr_disc_sg2_conv_dgrad_f32': (_i, [_vp] * 3 + [_i] * 6 + [_vp, _i64, _vp]),
+    'mrefsr_disc_sg2_conv_wgrad_workspace_bytes': (_i64, [_i] * 6),
+    'mrefsr_disc_sg2_conv_wgrad_f32': (_i, [_vp] * 3 + [_i] * 7 + [_vp, _i64, _vp]),
     'mrefsr_upfirdn2d_f32': (_i, [_vp, _vp, _vp] + [_i] * 14 + [_vp]),
     'mrefsr_upfirdn2d': (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
     'mrefsr_tensor2img_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

@@ -1,5 +1,5 @@
-"""ImageDiscriminator (basicsr/archs/discriminator_arch.py:10-45), VGGStyleDiscriminator (:47-125) and UNetDiscriminatorSN
-(:127-200): the discriminators of the adversarial training step.
+"""ImageDiscriminator (basicsr/archs/discriminator_arch.py:10-45), VGGStyleDiscriminator (:47-125), UNetDiscriminatorSN
+(:127-200) and StyleGAN2Discriminator (basicsr/archs/stylegan2_arch.py:733-799): the discriminators of the adversarial training step.
 
 Same module tree, parameter and buffer names (74 state_dict entries at ndf 32) and initialisation (srntt_init_weights, normal
 0.02, BatchNorm weights N(1, 0.02)) as the reference, so its checkpoints load unchanged.  The forward runs on the kernels of
@@ -7,9 +7,13 @@ csrc/disc.hip through the autograd nodes of archs/nhwc_disc.py, which are differ
 VGGStyleDiscriminator keeps the reference's attribute order and PyTorch's default initialisation, so under one torch.manual_seed it
 builds the reference's exact parameters; its forward runs on csrc/disc_vgg.hip through archs/nhwc_vggdisc.py.  UNetDiscriminatorSN
 does the same with torch.nn.utils.spectral_norm (weight_orig / weight_u / weight_v, torch's own state_dict hooks); its forward runs
-on csrc/disc_unet.hip and disc_vgg.hip through archs/nhwc_unetdisc.py.
+on csrc/disc_unet.hip and disc_vgg.hip through archs/nhwc_unetdisc.py.  StyleGAN2Discriminator is built from the blocks of
+archs/stylegan2_ops.py in the reference's order (torch.randn weights, zero biases, no FIR buffer); its forward runs on csrc/disc_sg2.hip
+and disc_vgg.hip through archs/nhwc_sg2disc.py.
 Construction and state_dict work on the CPU; forward on a CPU tensor raises NotImplementedError, as every op of the package does.
 """
+import math
+
 import torch
 from torch import nn
 from torch.nn.utils import spectral_norm
@@ -17,6 +21,7 @@ from torch.nn.utils.spectral_norm import SpectralNorm
 
 from ..utils.registry import ARCH_REGISTRY
 from .arch_util import srntt_init_weights
+from .stylegan2_ops import ConvLayer, EqualLinear, ResBlock
 
 
 @ARCH_REGISTRY.register()
@@ -170,3 +175,59 @@ class UNetDiscriminatorSN(nn.Module):
         self.sn_hooks()
         from . import nhwc_unetdisc
         return nhwc_unetdisc.discriminator(self, x)
+
+
+@ARCH_REGISTRY.register()
+class StyleGAN2Discriminator(nn.Module):
+    """the residual StyleGAN2 critic: a 1x1 input stage, one ResBlock per halving from out_size down to 4 x 4, the minibatch-stddev
+    channel, final_conv and a two-layer final_linear.  The modules hold the reference's parameters under its names; forward does not
+    call them (they would run on the generic ops) but archs/nhwc_sg2disc.py.  Input [B, 3, out_size, out_size]: another H x W raises
+    RuntimeError naming final_linear, where the reference fails; an input that is not a 4-D RGB fp32 batch raises the siblings'
+    NotImplementedError (the reference fails in its first convolution there, not in final_linear)."""
+
+    def __init__(self, out_size, channel_multiplier=2, resample_kernel=(1, 3, 3, 1), stddev_group=4, narrow=1):
+        super().__init__()
+        if not isinstance(out_size, int) or out_size < 8 or out_size > 1024 or out_size & (out_size - 1):
+            raise NotImplementedError(f'StyleGAN2Discriminator: out_size={out_size}; a power of two in 8 .. 1024 (the reference has channel '
+                                      'counts for these sizes only, and one ResBlock per halving down to 4 x 4)')
+        kernel = torch.as_tensor(resample_kernel, dtype=torch.float32)
+        if kernel.ndim != 1 or not 2 <= kernel.numel() <= 4:
+            raise NotImplementedError(f'StyleGAN2Discriminator: resample_kernel={resample_kernel}; the FIR kernels take a 1-D list of 2 to 4 '
+                                      'magnitudes (applied as their outer product)')
+        if not isinstance(stddev_group, int) or stddev_group < 1:
+            raise NotImplementedError(f'StyleGAN2Discriminator: stddev_group={stddev_group}; a positive integer')
+        channels = {
+            '4': int(512 * narrow), '8': int(512 * narrow), '16': int(512 * narrow), '32': int(512 * narrow),
+            '64': int(256 * channel_multiplier * narrow), '128': int(128 * channel_multiplier * narrow),
+            '256': int(64 * channel_multiplier * narrow), '512': int(32 * channel_multiplier * narrow),
+            '1024': int(16 * channel_multiplier * narrow)}
+        log_size = int(math.log(out_size, 2))
+        for i in range(log_size, 1, -1):
+            c = channels[f'{2 ** i}']
+            if c <= 0 or c % 16:
+                raise NotImplementedError(f'StyleGAN2Discriminator: {c} channels at {2 ** i} x {2 ** i} (narrow={narrow}, channel_multiplier='
+                                          f'{channel_multiplier}); the convolution kernels need a multiple of 16')
+        # the reference's construction (and so torch.randn) order
+        conv_body = [ConvLayer(3, channels[f'{out_size}'], 1, bias=True, activate=True)]
+        in_channels = channels[f'{out_size}']
+        for i in range(log_size, 2, -1):
+            out_channels = channels[f'{2 ** (i - 1)}']
+            conv_body.append(ResBlock(in_channels, out_channels, resample_kernel))
+            in_channels = out_channels
+        self.conv_body = nn.Sequential(*conv_body)
+        self.final_conv = ConvLayer(in_channels + 1, channels['4'], 3, bias=True, activate=True)
+        self.final_linear = nn.Sequential(
+            EqualLinear(channels['4'] * 4 * 4, channels['4'], bias=True, bias_init_val=0, lr_mul=1, activation='fused_lrelu'),
+            EqualLinear(channels['4'], 1, bias=True, bias_init_val=0, lr_mul=1, activation=None))
+        self.out_size = out_size
+        self.resample_taps = tuple((kernel / kernel.sum()).tolist())   # make_resample_kernel's outer product, per axis
+        self.stddev_group = stddev_group
+        self.stddev_feat = 1
+
+    def forward(self, x):
+        if not x.is_cuda:
+            raise NotImplementedError('StyleGAN2Discriminator: mrefsr_amd has no CPU path (HIP kernels only)')
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
+            raise NotImplementedError(f'StyleGAN2Discriminator: input {tuple(x.shape)} {x.dtype}; fp32 [B,3,H,W] only')
+        from . import nhwc_sg2disc
+        return nhwc_sg2disc.discriminator(self, x)

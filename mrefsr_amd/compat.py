@@ -12,7 +12,7 @@ import types
 
 _ARCHS = ('MRAPARestorationNet', 'RestorationNet', 'CorrespondenceGenerationArch', 'ContrasMultiExtractorSep',
           'ContrasExtractorSep', 'VGGFeatureExtractor', 'ImageDiscriminator', 'VGGStyleDiscriminator',
-          'UNetDiscriminatorSN_basicsr')
+          'UNetDiscriminatorSN_basicsr', 'StyleGAN2Discriminator')
 _MODELS = ('MultiRefRestorationModel', 'RefRestorationModel')
 
 

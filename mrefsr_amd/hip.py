@@ -1792,3 +1792,91 @@ def disc_conv9_wgrad(x, gy):
     with _timed('disc_conv9_wgrad', 2.0 * x.numel() * 9, detail=True):
         _lib.call('mrefsr_disc_conv9_wgrad_f32', _p(x), _p(_c(gy)), _p(dw), n, h, wd, c, _p(ws), C.c_int64(ws.numel()), _stream())
     return dw
+
+
+# ------------------------------------------------------------------ StyleGAN2Discriminator (csrc/disc_sg2.hip)
+def _sg2_out(n, ks):
+    return (n - 3) // 2 + 1 if ks == 3 else n
+
+
+def disc_sg2_fir_out(n, taps, pad, down):
+    return (n + pad[0] + pad[1] - len(taps)) // down + 1
+
+
+def disc_sg2_fir(x, taps, pad, down=1, adjoint_shape=None):
+    """upfirdn2d(x, outer(taps, taps), down=down, pad=pad) on channels-last x [N,H,W,C] with 2 .. 4 normalised taps (a sequence of
+    floats).  adjoint_shape (N, H, W, C): x is a gradient of that operation's output instead and the result its input gradient"""
+    _chk('disc_sg2_fir', x)
+    taps = [float(t) for t in taps]
+    n, h, w, c = x.shape if adjoint_shape is None else adjoint_shape
+    ho, wo = disc_sg2_fir_out(h, taps, pad, down), disc_sg2_fir_out(w, taps, pad, down)
+    if adjoint_shape is not None and tuple(x.shape) != (n, ho, wo, c):
+        raise ValueError('disc_sg2_fir: the gradient does not have the output shape of the FIR')
+    y = torch.empty((n, ho, wo, c) if adjoint_shape is None else (n, h, w, c), device=x.device, dtype=torch.float32)
+    k = (C.c_float * len(taps))(*taps)
+    with _timed('disc_sg2_fir', 2.0 * y.numel() * len(taps) ** 2, detail=True):
+        _lib.call('mrefsr_disc_sg2_fir_f32', _p(x), _p(y), n, h, w, c, C.cast(k, C.c_void_p), len(taps), pad[0], pad[1], down,
+                  0 if adjoint_shape is None else 1, _stream())
+    return y
+
+
+def disc_sg2_pack_weight(w, cin, dgrad):
+    """w [Cout,CinR,ks,ks] (ks 1 or 3) -> [Cout,ks*ks,cin] (dgrad False) or [cin,ks*ks,Cout] (dgrad True), channels CinR..cin-1 zero"""
+    _chk('disc_sg2_pack_weight', w)
+    cout, cinr, ks = w.shape[0], w.shape[1], w.shape[2]
+    if ks not in (1, 3) or w.shape[3] != ks or cinr > cin:
+        raise ValueError(f'disc_sg2_pack_weight: weight {tuple(w.shape)} for {cin} input channels')
+    out = torch.empty((cin, ks * ks, cout) if dgrad else (cout, ks * ks, cin), device=w.device, dtype=torch.float32)
+    _lib.call('mrefsr_disc_sg2_pack_weight_f32', _p(w), _p(out), cout, cinr, cin, ks, 1 if dgrad else 0, _stream())
+    return out
+
+
+def disc_sg2_conv(x, wpk, bias, ks, act_slope=None, res=None):
+    """x [N,H,W,Cin] -> [N,Ho,Wo,Cout]: pad 0, ks 3 (stride 2) or 1 (stride 1); lrelu(conv + bias, act_slope) (no activation when
+    act_slope is None) + res (wpk from disc_sg2_pack_weight(dgrad=False))"""
+    _chk('disc_sg2_conv', x, wpk, bias, res)
+    n, h, w, cin = x.shape
+    cout = wpk.shape[0]
+    if tuple(wpk.shape) != (cout, ks * ks, cin):
+        raise ValueError('disc_sg2_conv: packed weight does not match the input channels')
+    y = torch.empty((n, _sg2_out(h, ks), _sg2_out(w, ks), cout), device=x.device, dtype=torch.float32)
+    if res is not None and res.shape != y.shape:
+        raise ValueError(f'disc_sg2_conv: residual {tuple(res.shape)} for an output {tuple(y.shape)}')
+    need = _lib.load().mrefsr_disc_sg2_conv_workspace_bytes(n, h, w, cin, cout, ks, 0)
+    ws = _vconv_ws(x.device, need)
+    with _timed(f'disc_sg2_conv{ks}', 2.0 * y.numel() * ks * ks * cin, detail=True):
+        _lib.call('mrefsr_disc_sg2_conv_f32', _p(x), _p(wpk), _p(bias), _p(res), _p(y), n, h, w, cin, cout, ks, 0 if act_slope is None else 1,
+                  C.c_float(0.0 if act_slope is None else act_slope), _p(ws), C.c_int64(0 if ws is None else ws.numel()), _stream())
+    return y
+
+
+def disc_sg2_conv_dgrad(dy, wpk_d, in_shape, ks):
+    """input gradient: dy [N,Ho,Wo,Cout] -> dx [N,H,W,Cin] (in_shape = x's shape; wpk_d from disc_sg2_pack_weight(dgrad=True))"""
+    _chk('disc_sg2_conv_dgrad', dy, wpk_d)
+    n, h, w, cin = in_shape
+    cout = dy.shape[3]
+    if tuple(dy.shape) != (n, _sg2_out(h, ks), _sg2_out(w, ks), cout) or tuple(wpk_d.shape) != (cin, ks * ks, cout):
+        raise ValueError('disc_sg2_conv_dgrad: inconsistent shapes')
+    dx = torch.empty((n, h, w, cin), device=dy.device, dtype=torch.float32)
+    need = _lib.load().mrefsr_disc_sg2_conv_workspace_bytes(n, h, w, cin, cout, ks, 1)
+    ws = _vconv_ws(dy.device, need)
+    with _timed(f'disc_sg2_conv{ks}_dgrad', 2.0 * dy.numel() * ks * ks * cin / (4 if ks == 3 else 1), detail=True):
+        _lib.call('mrefsr_disc_sg2_conv_dgrad_f32', _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, ks, _p(ws),
+                  C.c_int64(0 if ws is None else ws.numel()), _stream())
+    return dx
+
+
+def disc_sg2_conv_wgrad(x, dy, cin_real, ks):
+    """weight gradient [Cout,cin_real,ks,ks] = sum over the output pixels of x (x) dy"""
+    _chk('disc_sg2_conv_wgrad', x, dy)
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    if tuple(dy.shape) != (n, _sg2_out(h, ks), _sg2_out(w, ks), cout):
+        raise ValueError('disc_sg2_conv_wgrad: inconsistent shapes')
+    need = _lib.load().mrefsr_disc_sg2_conv_wgrad_workspace_bytes(n, h, w, cin, cout, ks)
+    ws = _wgrad_workspace(x.device, need)
+    dw = torch.empty((cout, cin_real, ks, ks), device=x.device, dtype=torch.float32)
+    with _timed(f'disc_sg2_conv{ks}_wgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
+        _lib.call('mrefsr_disc_sg2_conv_wgrad_f32', _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, ks, _p(ws), C.c_int64(ws.numel()),
+                  _stream())
+    return dw

@@ -9,7 +9,8 @@ layout: Adam with four parameter groups chosen by name (:60-89) --
     other 'offset'      -> lr_offset           everything else     -> lr_g
 Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLoss), perceptual_opt and style_opt
 (PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), and the adversarial term: network_d
-(ImageDiscriminator, VGGStyleDiscriminator or UNetDiscriminatorSN, on the kernels of csrc/disc.hip, disc_vgg.hip and disc_unet.hip)
+(ImageDiscriminator, VGGStyleDiscriminator, UNetDiscriminatorSN or StyleGAN2Discriminator, on the kernels of csrc/disc.hip, disc_vgg.hip,
+disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
 :272-276.  texture_opt and other discriminators raise NotImplementedError instead of being silently skipped.
 
@@ -121,9 +122,9 @@ class MultiRefRestorationModel:
                                       'losses are; the reference model never sets the maps / weights it reads)')
         net_d_opt = self.opt.get('network_d')
         if net_d_opt and net_d_opt.get('type') not in ('ImageDiscriminator', 'VGGStyleDiscriminator', 'UNetDiscriminatorSN',
-                                                       'UNetDiscriminatorSN_basicsr'):
-            raise NotImplementedError(f"network_d: {net_d_opt.get('type')} is not implemented (ImageDiscriminator, VGGStyleDiscriminator and "
-                                      "UNetDiscriminatorSN are)")
+                                                       'UNetDiscriminatorSN_basicsr', 'StyleGAN2Discriminator'):
+            raise NotImplementedError(f"network_d: {net_d_opt.get('type')} is not implemented (ImageDiscriminator, VGGStyleDiscriminator, "
+                                      "UNetDiscriminatorSN and StyleGAN2Discriminator are)")
         if net_d_opt and net_d_opt['type'].startswith('UNetDiscriminatorSN') and 'num_in_ch' not in net_d_opt:
             raise NotImplementedError(f"network_d: {net_d_opt['type']} without num_in_ch (the reference's constructor has no default for it)")
         if train_opt.get('gan_type') and not net_d_opt:
