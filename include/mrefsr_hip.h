@@ -151,6 +151,17 @@ int mrefsr_dynagg_prep_bwd_f32(const float *g_offset, const float *g_mask, const
  * (both zero-initialised by the caller; either may be NULL).  27*dg <= 256. */
 int mrefsr_dynagg_prep_bwd_nhwc_f32(const float *g_offset, const float *g_mask, const float *mask, float *g_om, float *bias_grad,
                                     float *amax, int B, int dg, int H, int W, mrefsr_stream_t stream);
+/* The same, bitwise reproducible: every block writes its per-channel sums to its own row of `workspace`
+ * ([mrefsr_dynagg_prep_bwd_blocks][27*dg] floats, workspace_bytes >= mrefsr_dynagg_prep_bwd_det_workspace_bytes), and the block
+ * that finishes last adds the rows in ascending block order (image-major, then pixel tiles) into bias_grad -- a fixed order
+ * instead of the float atomics above, in the same launch.  ticket[0] (device memory) is 0 before the first launch; the launch
+ * leaves it 0 again, so it needs no memset between launches or graph replays.  One launch at a time per workspace / ticket.
+ * g_om and amax as above, bit for bit. */
+int mrefsr_dynagg_prep_bwd_blocks(int B, int dg, int H, int W);
+int64_t mrefsr_dynagg_prep_bwd_det_workspace_bytes(int B, int dg, int H, int W);
+int mrefsr_dynagg_prep_bwd_nhwc_det_f32(const float *g_offset, const float *g_mask, const float *mask, float *g_om, float *bias_grad,
+                                        float *amax, int B, int dg, int H, int W, void *workspace, int64_t workspace_bytes,
+                                        uint32_t *ticket, mrefsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * DCNv2 / DCNv1: basicsr/ops/dcn (deform_conv_ext: deform_conv_ext.cpp:52-147) and
@@ -405,6 +416,15 @@ int mrefsr_conv_nhwc_amax_f32(const mrefsr_conv_desc *d, const float *x1, const 
 int mrefsr_conv_nhwc_bwd_f32(const mrefsr_conv_desc *d, const float *x1, const void *packed, const float *residual,
                              int residual_is_mask, float *out, int *range_flag, const float *in_amax, float *stat_sum,
                              float *stat_amax, mrefsr_stream_t stream);
+/* The same, bitwise reproducible: every block writes its 64 per-cout sums to its own row of `workspace` (workspace_bytes >=
+ * mrefsr_conv_nhwc_bwd_det_workspace_bytes(d)), the rows of a cout block in (image, tile row, tile column) order whatever order
+ * the blocks ran in, and the block that finishes last adds them in that order into stat_sum -- a fixed order instead of float
+ * atomics, in the same launch.  ticket[0] (device memory) is 0 before the first launch and 0 again after every launch (no
+ * memset between launches or graph replays).  One launch at a time per workspace / ticket.  out and stat_amax as above, bit for bit. */
+int64_t mrefsr_conv_nhwc_bwd_det_workspace_bytes(const mrefsr_conv_desc *d);
+int mrefsr_conv_nhwc_bwd_det_f32(const mrefsr_conv_desc *d, const float *x1, const void *packed, const float *residual,
+                                 int residual_is_mask, float *out, int *range_flag, const float *in_amax, float *stat_sum,
+                                 float *stat_amax, void *workspace, int64_t workspace_bytes, uint32_t *ticket, mrefsr_stream_t stream);
 /* conv_offset_mask of a DynAgg + its glue in one launch (ref_mrapa_restoration_arch.py:56-73: chunk / cat / repeat /
  * re-order / add / sigmoid / mean-abs): the 3x3 convolution `x` [N][H][W][C1] -> 27*dg channels runs as in
  * mrefsr_conv_nhwc_f32 (same packed weights, terms, wscale, range flag; fields N, H, W, C1, ld1, Cout = 27*dg, ksize = 3,
@@ -471,6 +491,16 @@ int mrefsr_upfirdn2d(const void *in, const void *kernel, void *out, int major, i
 int mrefsr_act_bwd_blocks(int64_t npix, int C);
 int mrefsr_act_bwd_nhwc_f32(const float *g_out, const float *out, float *g_pre, int ld_pre, float *bias_grad, float *slope_grad, float *amax,
                             int64_t npix, int C, int act, float slope, const float *slope_ptr, int *flag, mrefsr_stream_t stream);
+/* mrefsr_act_bwd_nhwc_det_f32: the same, bitwise reproducible.  Every block writes its C channel sums and its slope sum to its
+ *   own row of `workspace` ([mrefsr_act_bwd_blocks][C + 1] floats, workspace_bytes >= mrefsr_act_bwd_det_workspace_bytes), and
+ *   the block that finishes last adds the rows in ascending block order into bias_grad / slope_grad -- a fixed order instead of
+ *   float atomics, in the same launch.  ticket[0] (device memory) is 0 before the first launch and 0 again after every launch
+ *   (no memset between launches or graph replays).  One launch at a time per workspace / ticket.  g_pre, amax and *flag as
+ *   above, bit for bit. */
+int64_t mrefsr_act_bwd_det_workspace_bytes(int64_t npix, int C);
+int mrefsr_act_bwd_nhwc_det_f32(const float *g_out, const float *out, float *g_pre, int ld_pre, float *bias_grad, float *slope_grad, float *amax,
+                                int64_t npix, int C, int act, float slope, const float *slope_ptr, int *flag, void *workspace,
+                                int64_t workspace_bytes, uint32_t *ticket, mrefsr_stream_t stream);
 /* Weight gradient of a 3x3 stride-1 'same' convolution over channels-last tensors (torch's miopenConvolutionBackwardWeights in
  * the reference's training step):  dw[co][ci][ty][tx] (+)= sum_{n,y,x} g[n][y][x][co] * x[n][y+ty-1][x+tx-1][ci].
  *   x [N][H][W][ld_x] (channels [0, Cin) used), g [N][H][W][ld_g] (channels [0, Cout)); dw element (co, ci, tap) at

@@ -70,6 +70,10 @@ struct ConvArgs {
     int res_mask;
     float *stat_sum;
     unsigned int *stat_amax;
+    // deterministic form of stat_sum (mrefsr_conv_nhwc_bwd_det_f32), NULL otherwise: one 64-float row per block, the rows of a cout
+    // block in (image, tile row, tile column) order; the block that draws the last ticket adds them in that order
+    float *stat_part;
+    unsigned int *stat_ticket;
     int xcd_bands;    // 4-wave kernel: re-label the blocks so that an XCD works on a contiguous band of tiles
     int warm_w;       // 4-wave kernel, launches of few blocks: request 1 / warm_w of the block's weight slab before the chunk loop (0 = off)
     int wino_N;       // conv_wino.hip (persistent blocks): images of the launch

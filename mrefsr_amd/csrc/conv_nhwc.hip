@@ -552,17 +552,32 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &A, f32x16 (&acc)[R
         if (lane < 16) *reinterpret_cast<float4 *>(red + wv * 64 + c4) = ssum;
         if (lane == 0) red[NWV * 64 + wv] = samx;
         __syncthreads();
+        // (A.stat_part: the deterministic form -- the block's sums go to its own workspace row, in the order of the tiles in the
+        //  tensor whatever order the blocks were dispatched in, and the last block to finish adds the rows in that order)
+        const bool det = A.stat_part != nullptr;
+        const int n_sp = gridDim.z * ((H + 4 * RPW - 1) / (4 * RPW)) * ((W + TW - 1) / TW);   // blocks per cout block
         if (tid < 64 && cb * NB + tid < Cout) {
             float t = 0.f;
 #pragma unroll
             for (int w = 0; w < NWV; ++w) t += red[w * 64 + tid];
-            atomicAdd(A.stat_sum + cb * NB + tid, t);
+            if (det) {
+                const int sp = (n * ((H + 4 * RPW - 1) / (4 * RPW)) + y0 / (4 * RPW)) * ((W + TW - 1) / TW) + x0 / TW;
+                mrefsr::store_partial(A.stat_part + ((long)cb * n_sp + sp) * NB + tid, t);
+            } else {
+                atomicAdd(A.stat_sum + cb * NB + tid, t);
+            }
         }
         if (tid == 0 && A.stat_amax) {
             float t = 0.f;
 #pragma unroll
             for (int w = 0; w < NWV; ++w) t = fmaxf(t, red[NWV * 64 + w]);
             if (t > 0.f && t < 3.0e38f) atomicMax(A.stat_amax, __float_as_uint(t));
+        }
+        if (det) {
+            int *last = reinterpret_cast<int *>(red + NWV * 64 + NWV);
+            if (mrefsr::last_block_by_ticket(A.stat_ticket, gridDim.x * gridDim.y * gridDim.z, last))
+                for (int c = tid; c < Cout; c += NTHR)
+                    A.stat_sum[c] += mrefsr::sum_rows_in_order(A.stat_part + (long)(c / NB) * n_sp * NB, n_sp, NB, c % NB);
         }
     } else if (MODE == 2 && !IO16) {
         publish_amax(A.stat_amax, samx);
@@ -1466,7 +1481,7 @@ MREFSR_EXPORT int mrefsr_conv_nhwc_f32(const mrefsr_conv_desc *d, const float *x
 namespace {
 int conv_entry(const mrefsr_conv_desc *d, const float *x1, const float *x2, const void *packed, const float *bias, const float *slope_ptr,
                const float *pre, const float *residual, float *out, int *range_flag, const float *in_amax, int res_mask, float *stat_sum,
-               float *stat_amax, mrefsr_stream_t stream);
+               float *stat_amax, float *stat_part, unsigned int *stat_ticket, mrefsr_stream_t stream);
 }
 
 // mrefsr_conv_nhwc_scaled_f32 + out_amax[0] = max(out_amax[0], max |out|) (device memory, zero-initialised by the caller, may be NULL):
@@ -1476,14 +1491,14 @@ MREFSR_EXPORT int mrefsr_conv_nhwc_amax_f32(const mrefsr_conv_desc *d, const flo
                                             const float *in_amax, float *out_amax, mrefsr_stream_t stream)
 {
     MREFSR_REQUIRE(!out_amax || (d && (d->terms == 16 || d->terms == 17)), "conv_nhwc_amax: out_amax belongs to the fp32-equivalent modes (terms = 16, 17)");
-    return conv_entry(d, x1, x2, packed, bias, slope_ptr, pre, residual, out, range_flag, in_amax, 0, nullptr, out_amax, stream);
+    return conv_entry(d, x1, x2, packed, bias, slope_ptr, pre, residual, out, range_flag, in_amax, 0, nullptr, out_amax, nullptr, nullptr, stream);
 }
 
 MREFSR_EXPORT int mrefsr_conv_nhwc_scaled_f32(const mrefsr_conv_desc *d, const float *x1, const float *x2, const void *packed,
                                               const float *bias, const float *slope_ptr, const float *pre, const float *residual, float *out,
                                               int *range_flag, const float *in_amax, mrefsr_stream_t stream)
 {
-    return conv_entry(d, x1, x2, packed, bias, slope_ptr, pre, residual, out, range_flag, in_amax, 0, nullptr, nullptr, stream);
+    return conv_entry(d, x1, x2, packed, bias, slope_ptr, pre, residual, out, range_flag, in_amax, 0, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // The input-gradient convolution of a training step with the element-wise pass that would follow it folded into its epilogue:
@@ -1499,13 +1514,37 @@ MREFSR_EXPORT int mrefsr_conv_nhwc_bwd_f32(const mrefsr_conv_desc *d, const floa
     MREFSR_REQUIRE(d->Cout % 4 == 0 && d->ld_out % 4 == 0, "conv_nhwc_bwd: Cout=%d ld_out=%d (multiples of 4)", d->Cout, d->ld_out);
     MREFSR_REQUIRE(!residual_is_mask || (residual && d->ld_res % 4 == 0), "conv_nhwc_bwd: the mask source is the residual operand (ld_res a multiple of 4)");
     return conv_entry(d, x1, nullptr, packed, nullptr, nullptr, nullptr, residual, out, range_flag, in_amax, residual_is_mask ? 1 : 0, stat_sum, stat_amax,
-                      stream);
+                      nullptr, nullptr, stream);
+}
+
+// Bytes of the partial-sum workspace of mrefsr_conv_nhwc_bwd_det_f32: one 64-float row per block of the smallest tile (4 x 32
+// pixels x 64 couts) the launcher may choose for the shape.
+MREFSR_EXPORT int64_t mrefsr_conv_nhwc_bwd_det_workspace_bytes(const mrefsr_conv_desc *d)
+{
+    if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0) return -1;
+    return (int64_t)d->N * ((d->H + 3) / 4) * ((d->W + TW - 1) / TW) * ((d->Cout + NB - 1) / NB) * NB * (int64_t)sizeof(float);
+}
+
+// mrefsr_conv_nhwc_bwd_f32 with stat_sum added in a fixed order: bitwise reproducible.
+MREFSR_EXPORT int mrefsr_conv_nhwc_bwd_det_f32(const mrefsr_conv_desc *d, const float *x1, const void *packed, const float *residual,
+                                               int residual_is_mask, float *out, int *range_flag, const float *in_amax, float *stat_sum,
+                                               float *stat_amax, void *workspace, int64_t workspace_bytes, uint32_t *ticket,
+                                               mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(d && d->terms == 16 && d->epilogue == 0 && d->act == 0 && d->C2 == 0, "conv_nhwc_bwd_det: terms 16, plain epilogue, one source, no activation");
+    MREFSR_REQUIRE(d->Cout % 4 == 0 && d->ld_out % 4 == 0, "conv_nhwc_bwd_det: Cout=%d ld_out=%d (multiples of 4)", d->Cout, d->ld_out);
+    MREFSR_REQUIRE(!residual_is_mask || (residual && d->ld_res % 4 == 0), "conv_nhwc_bwd_det: the mask source is the residual operand (ld_res a multiple of 4)");
+    MREFSR_REQUIRE(!stat_sum || (workspace && ticket && workspace_bytes >= mrefsr_conv_nhwc_bwd_det_workspace_bytes(d)),
+                   "conv_nhwc_bwd_det: workspace of %ld bytes (%ld needed) and a ticket word", (long)workspace_bytes,
+                   (long)mrefsr_conv_nhwc_bwd_det_workspace_bytes(d));
+    return conv_entry(d, x1, nullptr, packed, nullptr, nullptr, nullptr, residual, out, range_flag, in_amax, residual_is_mask ? 1 : 0, stat_sum, stat_amax,
+                      reinterpret_cast<float *>(workspace), ticket, stream);
 }
 
 namespace {
 int conv_entry(const mrefsr_conv_desc *d, const float *x1, const float *x2, const void *packed, const float *bias, const float *slope_ptr,
                const float *pre, const float *residual, float *out, int *range_flag, const float *in_amax, int res_mask, float *stat_sum,
-               float *stat_amax, mrefsr_stream_t stream)
+               float *stat_amax, float *stat_part, unsigned int *stat_ticket, mrefsr_stream_t stream)
 {
     MREFSR_REQUIRE(d && x1 && packed && out, "conv_nhwc: null pointer");
     MREFSR_REQUIRE(!in_amax || d->terms == 16 || d->terms == 17, "conv_nhwc_scaled: the input scale belongs to the fp16 two-term modes (terms = 16, 17)");
@@ -1538,6 +1577,7 @@ int conv_entry(const mrefsr_conv_desc *d, const float *x1, const float *x2, cons
     a.bias = bias, a.slope_ptr = slope_ptr, a.pre = pre, a.residual = residual, a.out = out, a.range_flag = range_flag;
     a.in_amax = in_amax;
     a.res_mask = res_mask, a.stat_sum = stat_sum, a.stat_amax = reinterpret_cast<unsigned int *>(stat_amax);
+    a.stat_part = stat_sum ? stat_part : nullptr, a.stat_ticket = stat_ticket;
     a.H = d->H, a.W = d->W, a.C1 = d->C1, a.ld1 = d->ld1, a.N1 = d->N1;
     a.C2 = d->C2, a.ld2 = d->C2 > 0 ? d->ld2 : 4, a.N2 = d->C2 > 0 ? d->N2 : 1;
     a.Cout = d->Cout, a.ld_out = d->ld_out, a.ld_res = d->ld_res, a.pre_N = pre ? d->pre_N : 1;

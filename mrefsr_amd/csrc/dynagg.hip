@@ -124,13 +124,16 @@ __global__ __launch_bounds__(256) void dynagg_prep_bwd_kernel(const float *__res
 // conv_offset_mask read -- plus the two reductions its consumers need: per-channel sums (the bias gradient) and max |g_om| (the
 // scale of the fp16-split kernels).  32 pixels x 27 dg channels pass through an LDS tile (planar reads along the pixels,
 // channels-last writes along the channels); a block walks `groups` such tiles and adds its sums with one atomic per channel.
+// DET (mrefsr_dynagg_prep_bwd_nhwc_det_f32): the block's sums go to row blockIdx.y * gridDim.x + blockIdx.x of `part`
+// ([blocks][27 dg] floats) instead; the block that draws the last `ticket` adds the rows in ascending order -- bitwise reproducible.
 // (Planar result + ATen's transposing copy + a reduction pass: 587 + 100 us at 20 x 160^2 x 216.)
 constexpr int PXT = 32;   // pixels per tile (64: 55 KB of LDS and 64 values per thread in flight -- slower, 0.95 against 0.73 ms per step)
 
+template <bool DET>
 __global__ __launch_bounds__(256) void dynagg_prep_bwd_nhwc_kernel(const float *__restrict__ g_offset, const float *__restrict__ g_mask,
                                                                    const float *__restrict__ mask, float *__restrict__ g_om,
                                                                    float *__restrict__ bias_grad, unsigned int *__restrict__ amax_bits, int dg, int HW,
-                                                                   int groups)
+                                                                   int groups, float *part, unsigned int *ticket)
 {
     extern __shared__ float tile[];   // [PXT][nc + 1]
     const int n_i = dg * 9, nc = 3 * n_i, ld = nc + 1, b = blockIdx.y, t = threadIdx.x, px = t & (PXT - 1), c0 = t / PXT;
@@ -184,7 +187,16 @@ __global__ __launch_bounds__(256) void dynagg_prep_bwd_nhwc_kernel(const float *
         }
         __syncthreads();
     }
-    if (bias_grad && t < nc) atomicAdd(bias_grad + t, sum);
+    if constexpr (DET) {
+        if (bias_grad) {
+            __shared__ int last;
+            const unsigned int nblk = gridDim.x * gridDim.y;
+            if (t < nc) mrefsr::store_partial(part + (long)(blockIdx.y * gridDim.x + blockIdx.x) * nc + t, sum);
+            if (mrefsr::last_block_by_ticket(ticket, nblk, &last) && t < nc) bias_grad[t] += mrefsr::sum_rows_in_order(part, (int)nblk, nc, t);
+        }
+    } else {
+        if (bias_grad && t < nc) atomicAdd(bias_grad + t, sum);
+    }
     if (amax_bits) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
@@ -226,17 +238,63 @@ MREFSR_EXPORT int mrefsr_dynagg_prep_bwd_f32(const float *g_offset, const float 
     return mrefsr::check_launch("dynagg_prep_bwd");
 }
 
+namespace {
+inline long dynagg_bwd_groups(long HW, int B)   // tiles per block: a pure function of the shape
+{
+    const long groups = HW * B / (PXT * 512);
+    return groups < 1 ? 1 : (groups > 32 ? 32 : groups);
+}
+
+int dynagg_prep_bwd_nhwc_launch(const char *what, const float *g_offset, const float *g_mask, const float *mask, float *g_om, float *bias_grad, float *amax,
+                                int B, int dg, int H, int W, bool det, void *workspace, int64_t workspace_bytes, unsigned int *ticket,
+                                mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(g_offset && g_mask && mask && g_om, "%s: null pointer", what);
+    MREFSR_REQUIRE(B > 0 && B <= 65535 && dg > 0 && 27 * dg <= 256 && H > 0 && W > 0, "%s: B=%d dg=%d H=%d W=%d (27 dg <= 256)", what, B, dg, H, W);
+    const long HW = (long)H * W;
+    const long groups = dynagg_bwd_groups(HW, B);
+    const size_t lds = (size_t)PXT * (27 * dg + 1) * sizeof(float);
+    const dim3 grid(mrefsr::cdiv(HW, PXT * groups), B);
+    unsigned int *am = reinterpret_cast<unsigned int *>(amax);
+    if (det) {
+        if (bias_grad)
+            MREFSR_REQUIRE(workspace && ticket && workspace_bytes >= mrefsr_dynagg_prep_bwd_det_workspace_bytes(B, dg, H, W),
+                           "%s: workspace of %ld bytes (%ld needed) and a ticket word", what, (long)workspace_bytes,
+                           (long)mrefsr_dynagg_prep_bwd_det_workspace_bytes(B, dg, H, W));
+        hipLaunchKernelGGL(dynagg_prep_bwd_nhwc_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, g_offset, g_mask, mask, g_om, bias_grad, am, dg,
+                           (int)HW, (int)groups, reinterpret_cast<float *>(workspace), ticket);
+    } else {
+        hipLaunchKernelGGL(dynagg_prep_bwd_nhwc_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, g_offset, g_mask, mask, g_om, bias_grad, am, dg,
+                           (int)HW, (int)groups, static_cast<float *>(nullptr), static_cast<unsigned int *>(nullptr));
+    }
+    return mrefsr::check_launch(what);
+}
+}  // namespace
+
 MREFSR_EXPORT int mrefsr_dynagg_prep_bwd_nhwc_f32(const float *g_offset, const float *g_mask, const float *mask, float *g_om, float *bias_grad,
                                                   float *amax, int B, int dg, int H, int W, mrefsr_stream_t stream)
 {
-    MREFSR_REQUIRE(g_offset && g_mask && mask && g_om, "dynagg_prep_bwd_nhwc: null pointer");
-    MREFSR_REQUIRE(B > 0 && B <= 65535 && dg > 0 && 27 * dg <= 256 && H > 0 && W > 0, "dynagg_prep_bwd_nhwc: B=%d dg=%d H=%d W=%d (27 dg <= 256)", B, dg,
-                   H, W);
+    return dynagg_prep_bwd_nhwc_launch("dynagg_prep_bwd_nhwc", g_offset, g_mask, mask, g_om, bias_grad, amax, B, dg, H, W, false, nullptr, 0, nullptr,
+                                       stream);
+}
+
+MREFSR_EXPORT int mrefsr_dynagg_prep_bwd_blocks(int B, int dg, int H, int W)
+{
+    if (B <= 0 || B > 65535 || dg <= 0 || 27 * dg > 256 || H <= 0 || W <= 0) return -1;
     const long HW = (long)H * W;
-    long groups = HW * B / (PXT * 512);
-    groups = groups < 1 ? 1 : (groups > 32 ? 32 : groups);
-    const size_t lds = (size_t)PXT * (27 * dg + 1) * sizeof(float);
-    hipLaunchKernelGGL(dynagg_prep_bwd_nhwc_kernel, dim3(mrefsr::cdiv(HW, PXT * groups), B), dim3(256), lds, (hipStream_t)stream, g_offset, g_mask, mask,
-                       g_om, bias_grad, reinterpret_cast<unsigned int *>(amax), dg, (int)HW, (int)groups);
-    return mrefsr::check_launch("dynagg_prep_bwd_nhwc");
+    return mrefsr::cdiv(HW, PXT * dynagg_bwd_groups(HW, B)) * B;
+}
+
+MREFSR_EXPORT int64_t mrefsr_dynagg_prep_bwd_det_workspace_bytes(int B, int dg, int H, int W)
+{
+    const int blocks = mrefsr_dynagg_prep_bwd_blocks(B, dg, H, W);
+    return blocks > 0 ? (int64_t)blocks * 27 * dg * (int64_t)sizeof(float) : -1;
+}
+
+MREFSR_EXPORT int mrefsr_dynagg_prep_bwd_nhwc_det_f32(const float *g_offset, const float *g_mask, const float *mask, float *g_om, float *bias_grad,
+                                                      float *amax, int B, int dg, int H, int W, void *workspace, int64_t workspace_bytes,
+                                                      uint32_t *ticket, mrefsr_stream_t stream)
+{
+    return dynagg_prep_bwd_nhwc_launch("dynagg_prep_bwd_nhwc_det", g_offset, g_mask, mask, g_om, bias_grad, amax, B, dg, H, W, true, workspace,
+                                       workspace_bytes, ticket, stream);
 }

@@ -4,7 +4,8 @@
 //   act_bwd_nhwc      g_pre = g_out * act'(out), per-channel sums of g_pre (= bias gradient), PReLU slope gradient
 //   mrattn_bwd_nhwc   gradient of the multi-reference attention core (:321-335) on [N,H,W,C] tensors, probabilities recomputed
 //   attn_modulate_bwd gradient of refs * sigmoid(mul) * 2 + add (:343-345)
-// All HBM-bound.  Channel sums: fixed order inside a block, one float atomic per channel and block.
+// All HBM-bound.  Channel sums: fixed order inside a block, one float atomic per channel and block -- or, in the deterministic
+// form (mrefsr_act_bwd_nhwc_det_f32), one workspace row per block, the rows added in block order by the block that finishes last.
 #include "common.h"
 
 namespace {
@@ -16,12 +17,14 @@ namespace {
 // act: 0 none (g_pre may be NULL: sums only), 1 LeakyReLU(slope) (slope 0 = ReLU), 2 PReLU(*slope_ptr) (+ slope gradient:
 // x = out / slope for out < 0, which needs slope > 0 -- `flag` is raised otherwise and the caller re-runs unfused)
 // ---------------------------------------------------------------------------------------------------------------
-template <int V>
+// DET: the blocks' sums go to row blockIdx.x of `part` ([gridDim.x][C + 1] floats: C channel sums, the slope sum) instead of
+// into atomics; the block that draws the last `ticket` adds the rows in ascending block order (common.h) -- bitwise reproducible.
+template <int V, bool DET>
 __global__ __launch_bounds__(256) void act_bwd_nhwc_kernel(const float *__restrict__ g_out, const float *__restrict__ out,
                                                            float *__restrict__ g_pre, int ld_pre, float *__restrict__ bias_grad,
                                                            float *__restrict__ slope_grad, unsigned int *__restrict__ amax_bits, long npix,
                                                            int C, int act, float slope, const float *__restrict__ slope_ptr,
-                                                           int *__restrict__ flag)
+                                                           int *__restrict__ flag, float *part, unsigned int *ticket)
 {
     __shared__ float red[1024 + 256];
     float amx = 0.f;
@@ -89,17 +92,31 @@ __global__ __launch_bounds__(256) void act_bwd_nhwc_kernel(const float *__restri
     __syncthreads();
     // block totals (fixed order inside the block), then one float atomic per channel and block into the zero-initialised
     // gradient: the order of the blocks' contributions is not fixed -- as in the reference's own backward kernels, which
-    // accumulate with atomics (deform_conv_cuda_kernel.cu:330,688) -- and costs neither a second launch nor a device-wide fence
+    // accumulate with atomics (deform_conv_cuda_kernel.cu:330,688) -- and costs neither a second launch nor a device-wide fence.
+    // Where two runs have to agree bit for bit, the DET sibling of this kernel (mrefsr_act_bwd_nhwc_det_f32) orders the blocks (one ticket per block).
+    float *row = DET ? part + (long)blockIdx.x * (C + 1) : nullptr;
     if (bias_grad)
         for (int c = t; c < C; c += 256) {
             float s = 0.f;
             for (int q = 0; q < ppp; ++q) s += red[q * C + c];
-            atomicAdd(bias_grad + c, s);
+            if constexpr (DET) mrefsr::store_partial(row + c, s);
+            else atomicAdd(bias_grad + c, s);
         }
     if (slope_grad && t == 0) {
         float s = 0.f;
         for (int q = 0; q < 256; ++q) s += red[1024 + q];
-        atomicAdd(slope_grad, s);
+        if constexpr (DET) mrefsr::store_partial(row + C, s);
+        else atomicAdd(slope_grad, s);
+    }
+    if constexpr (DET) {
+        if (bias_grad || slope_grad) {
+            __shared__ int last;
+            if (mrefsr::last_block_by_ticket(ticket, gridDim.x, &last)) {
+                if (bias_grad)
+                    for (int c = t; c < C; c += 256) bias_grad[c] += mrefsr::sum_rows_in_order(part, (int)gridDim.x, C + 1, c);
+                if (slope_grad && t == 0) *slope_grad += mrefsr::sum_rows_in_order(part, (int)gridDim.x, C + 1, C);
+            }
+        }
     }
     if (amax_bits) {   // max |g_pre| (non-negative floats order like their bit patterns): the scale of the fp16-split dgrad
 #pragma unroll
@@ -221,25 +238,60 @@ MREFSR_EXPORT int mrefsr_act_bwd_blocks(int64_t npix, int C)
     return (int)(want < 1 ? 1 : (want > ACT_BWD_MAXB ? ACT_BWD_MAXB : want));
 }
 
+namespace {
+int act_bwd_launch(const char *what, const float *g_out, const float *out, float *g_pre, int ld_pre, float *bias_grad, float *slope_grad, float *amax,
+                   int64_t npix, int C, int act, float slope, const float *slope_ptr, int *flag, bool det, void *workspace, int64_t workspace_bytes,
+                   unsigned int *ticket, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(g_out, "%s: null pointer", what);
+    MREFSR_REQUIRE(act >= 0 && act <= 2 && (act == 0 || out) && (act != 2 || slope_ptr), "%s: act=%d needs out%s", what, act,
+                   act == 2 ? " and slope_ptr" : "");
+    const int blocks = mrefsr_act_bwd_blocks(npix, C);
+    MREFSR_REQUIRE(blocks > 0, "%s: npix=%ld C=%d (C <= 1024; C <= 256 unless a multiple of 4)", what, (long)npix, C);
+    MREFSR_REQUIRE(!g_pre || ld_pre >= C, "%s: ld_pre=%d < C=%d", what, ld_pre, C);
+    MREFSR_REQUIRE(C % 4 != 0 || !g_pre || ld_pre % 4 == 0, "%s: ld_pre=%d must be a multiple of 4", what, ld_pre);
+    if (det && (bias_grad || slope_grad))
+        MREFSR_REQUIRE(workspace && ticket && workspace_bytes >= mrefsr_act_bwd_det_workspace_bytes(npix, C),
+                       "%s: workspace of %ld bytes (%ld needed) and a ticket word", what, (long)workspace_bytes,
+                       (long)mrefsr_act_bwd_det_workspace_bytes(npix, C));
+    float *part = reinterpret_cast<float *>(workspace);
+    unsigned int *am = reinterpret_cast<unsigned int *>(amax);
+    hipStream_t st = (hipStream_t)stream;
+#define MREFSR_ACT_BWD(V, DET)                                                                                                                 \
+    hipLaunchKernelGGL((act_bwd_nhwc_kernel<V, DET>), dim3(blocks), dim3(256), 0, st, g_out, out, g_pre, ld_pre, bias_grad, slope_grad, am, \
+                       (long)npix, C, act, slope, slope_ptr, flag, part, ticket)
+    if (C % 4 == 0) {
+        if (det) MREFSR_ACT_BWD(4, true);
+        else MREFSR_ACT_BWD(4, false);
+    } else {
+        if (det) MREFSR_ACT_BWD(1, true);
+        else MREFSR_ACT_BWD(1, false);
+    }
+#undef MREFSR_ACT_BWD
+    return mrefsr::check_launch(what);
+}
+}  // namespace
+
 MREFSR_EXPORT int mrefsr_act_bwd_nhwc_f32(const float *g_out, const float *out, float *g_pre, int ld_pre, float *bias_grad, float *slope_grad,
                                           float *amax, int64_t npix, int C, int act, float slope, const float *slope_ptr, int *flag,
                                           mrefsr_stream_t stream)
 {
-    MREFSR_REQUIRE(g_out, "act_bwd_nhwc: null pointer");
-    MREFSR_REQUIRE(act >= 0 && act <= 2 && (act == 0 || out) && (act != 2 || slope_ptr), "act_bwd_nhwc: act=%d needs out%s", act,
-                   act == 2 ? " and slope_ptr" : "");
+    return act_bwd_launch("act_bwd_nhwc", g_out, out, g_pre, ld_pre, bias_grad, slope_grad, amax, npix, C, act, slope, slope_ptr, flag, false, nullptr, 0,
+                          nullptr, stream);
+}
+
+MREFSR_EXPORT int64_t mrefsr_act_bwd_det_workspace_bytes(int64_t npix, int C)
+{
     const int blocks = mrefsr_act_bwd_blocks(npix, C);
-    MREFSR_REQUIRE(blocks > 0, "act_bwd_nhwc: npix=%ld C=%d (C <= 1024; C <= 256 unless a multiple of 4)", (long)npix, C);
-    MREFSR_REQUIRE(!g_pre || ld_pre >= C, "act_bwd_nhwc: ld_pre=%d < C=%d", ld_pre, C);
-    if (C % 4 == 0) {
-        MREFSR_REQUIRE(!g_pre || ld_pre % 4 == 0, "act_bwd_nhwc: ld_pre=%d must be a multiple of 4", ld_pre);
-        hipLaunchKernelGGL(act_bwd_nhwc_kernel<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g_out, out, g_pre, ld_pre, bias_grad, slope_grad,
-                           reinterpret_cast<unsigned int *>(amax), (long)npix, C, act, slope, slope_ptr, flag);
-    } else {
-        hipLaunchKernelGGL(act_bwd_nhwc_kernel<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, g_out, out, g_pre, ld_pre, bias_grad, slope_grad,
-                           reinterpret_cast<unsigned int *>(amax), (long)npix, C, act, slope, slope_ptr, flag);
-    }
-    return mrefsr::check_launch("act_bwd_nhwc");
+    return blocks > 0 ? (int64_t)blocks * (C + 1) * (int64_t)sizeof(float) : -1;
+}
+
+MREFSR_EXPORT int mrefsr_act_bwd_nhwc_det_f32(const float *g_out, const float *out, float *g_pre, int ld_pre, float *bias_grad, float *slope_grad,
+                                              float *amax, int64_t npix, int C, int act, float slope, const float *slope_ptr, int *flag,
+                                              void *workspace, int64_t workspace_bytes, uint32_t *ticket, mrefsr_stream_t stream)
+{
+    return act_bwd_launch("act_bwd_nhwc_det", g_out, out, g_pre, ld_pre, bias_grad, slope_grad, amax, npix, C, act, slope, slope_ptr, flag, true, workspace,
+                          workspace_bytes, ticket, stream);
 }
 
 MREFSR_EXPORT int mrefsr_mrattn_bwd_nhwc_f32(const float *q, const float *emb, const float *ass, const float *g_out, float *g_q,

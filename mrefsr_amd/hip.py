@@ -71,6 +71,76 @@ def _p(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+# ------------------------------------------------------------------ deterministic mode
+# net_g's backward adds three kinds of per-channel sums over blocks with float atomics (bias gradients and the PReLU slope gradient
+# in act_bwd_nhwc, conv_offset_mask's bias gradient in dynagg_prep_bwd_nhwc, the per-cout sums in the epilogue of conv_nhwc_bwd):
+# the order of the blocks is the hardware's.  With the switch on, those three calls take the library's *_det_f32 entry points:
+# one workspace row per block, added in block order by the block that finishes last -- the same launches, the same element-wise
+# bits, sums that two runs agree on bit for bit.  Off (the default), nothing changes.
+_deterministic = [None]   # None: follow torch.are_deterministic_algorithms_enabled()
+
+
+def set_deterministic(mode):
+    """True / False: fixed-order gradient reductions on / off; None (the default): as torch.use_deterministic_algorithms says"""
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError(f'set_deterministic: True, False or None expected, got {mode!r}')
+    _deterministic[0] = mode
+
+
+def is_deterministic():
+    mode = _deterministic[0]
+    return torch.are_deterministic_algorithms_enabled() if mode is None else mode
+
+
+class deterministic:
+    """``with hip.deterministic():`` -- the switch on (or ``deterministic(False)``: off) inside the block, what it was behind it.
+    The switch is one per process, not per thread: autograd runs the backward on a thread of its own."""
+
+    def __init__(self, mode=True):
+        if mode is not None and not isinstance(mode, bool):
+            raise TypeError(f'deterministic: True, False or None expected, got {mode!r}')
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev = _deterministic[0]
+        _deterministic[0] = self.mode
+        return self
+
+    def __exit__(self, *exc):
+        _deterministic[0] = self.prev
+
+
+def nondeterministic_alert(what):
+    """for an operation that has no fixed-order form (the float-atomic scatter of the DCN input gradient): with the switch on raise
+    like torch does -- or only warn when torch.use_deterministic_algorithms(True, warn_only=True) says so"""
+    if not is_deterministic():
+        return
+    msg = (f'{what} does not have a deterministic implementation, but you set mrefsr_amd.hip.set_deterministic(True) / '
+           "'torch.use_deterministic_algorithms(True)' (or train.deterministic: true). You can turn the mode off for this operation "
+           'with `with mrefsr_amd.hip.deterministic(False):`, or ask for warnings only with '
+           "'torch.use_deterministic_algorithms(True, warn_only=True)'.")
+    if torch.is_deterministic_algorithms_warn_only_enabled():
+        import warnings
+        warnings.warn(msg)
+    else:
+        raise RuntimeError(msg)
+
+
+_det_tickets = {}
+
+
+def _det_scratch(device, nbytes):
+    """(partials workspace, ticket word) of one deterministic reduction launch: the workspace is the stream's cached one (launches
+    on a stream are ordered, a launch has consumed its partials when it ends), the ticket a zeroed word per stream and side of a
+    capture boundary that every launch leaves zero again"""
+    ws = _workspace(device, max(int(nbytes), 4))
+    key = (device.index, torch.cuda.current_stream().cuda_stream, torch.cuda.is_current_stream_capturing())
+    t = _det_tickets.get(key)
+    if t is None:
+        t = _det_tickets[key] = torch.zeros(1, device=device, dtype=torch.int32)
+    return ws, t
+
+
 def _chk(name, *tensors, dtype=torch.float32):
     for t in tensors:
         if t is None:
@@ -248,6 +318,11 @@ def dynagg_prep_bwd_nhwc(g_offset, g_mask, mask, dg, want_bias=True):
     nc = 27 * dg
     g_om = torch.empty((b, h, w, nc), device=mask.device, dtype=torch.float32)
     z = zeros_f32(mask.device, nc + 1)
+    if want_bias and is_deterministic():   # the bias gradient added in block order (bitwise reproducible)
+        ws, ticket = _det_scratch(mask.device, _lib.load().mrefsr_dynagg_prep_bwd_det_workspace_bytes(b, dg, h, w))
+        _lib.call('mrefsr_dynagg_prep_bwd_nhwc_det_f32', _p(g_offset), _p(g_mask), _p(mask), _p(g_om), _p(z[:nc]), _p(z[nc:]), b, dg, h, w,
+                  _p(ws), C.c_int64(ws.numel()), _p(ticket), _stream())
+        return g_om, z[:nc], z[nc:]
     _lib.call('mrefsr_dynagg_prep_bwd_nhwc_f32', _p(g_offset), _p(g_mask), _p(mask), _p(g_om), _p(z[:nc]) if want_bias else None, _p(z[nc:]), b, dg, h, w,
               _stream())
     return g_om, (z[:nc] if want_bias else None), z[nc:]
@@ -290,6 +365,8 @@ def release_capture_workspaces():
         del _ws_cache[k]
     for k in [k for k in _zero_chunks if k[2]]:
         del _zero_chunks[k]
+    for k in [k for k in _det_tickets if k[2]]:
+        del _det_tickets[k]
 
 
 def capture_refs():
@@ -297,7 +374,8 @@ def capture_refs():
     in: whoever owns the graph keeps this list as long as the graph lives"""
     # (only the buffers that were handed out UNDER a capture: an eager regrowth of some other stream's workspace -- validation at
     #  another size, the correlation call's scratch -- does not move anything a graph baked in, and must not force a recapture)
-    return [[t for k, t in _ws_cache.items() if k[2]], [c[0] for k, c in _zero_chunks.items() if k[2]], list(_wgrad_ws.values())]
+    return [[t for k, t in _ws_cache.items() if k[2]] + [t for k, t in _det_tickets.items() if k[2]],
+            [c[0] for k, c in _zero_chunks.items() if k[2]], list(_wgrad_ws.values())]
 
 
 def capture_ptrs():
@@ -414,6 +492,8 @@ def dcn_im2col(x, offset, mask, weight_shape, stride, padding, dilation, groups,
 
 
 def dcn_col2im(grad_col, x, offset, mask, weight_shape, stride, padding, dilation, groups, dg, need_grad_x=True):
+    if need_grad_x:
+        nondeterministic_alert('dcn_col2im (the float-atomic scatter of the deformable convolution\'s input gradient)')
     if x.dtype == torch.float16:   # gradients of an f16 call are accumulated in f32 (atomics), then rounded
         gx, goff, gmask = dcn_col2im(grad_col.float(), x.float(), offset.float(), None if mask is None else mask.float(), weight_shape, stride,
                                      padding, dilation, groups, dg, need_grad_x)
@@ -447,6 +527,8 @@ def dcn_bwd_data(g_out, x, offset, mask, packed_wT, dg, g_amax=None, need_grad_x
     """Fused backward of DCNv2 (3x3, stride 1, pad 1) w.r.t. offset, mask and input (mrefsr_dcn_bwd_data_f32): g_out [B,H,W,Co] and
     x [B,H,W,C] channels-last, offset / mask planar; packed_wT = conv_pack_view(weight, terms=16, dgrad='T', wscale=...);
     g_amax: device float max |g_out| (None: no scaling).  -> (grad_x planar [B,C,H,W] | None, grad_offset, grad_mask | None)"""
+    if need_grad_x:
+        nondeterministic_alert('dcn_bwd_data (the float-atomic scatter of the deformable convolution\'s input gradient)')
     _chk('dcn_bwd_data', g_out, x, offset, mask, g_amax)
     b, h, w, c = x.shape
     co = g_out.shape[3]
@@ -864,8 +946,14 @@ def act_bwd_nhwc(g_out, out, act, slope=0.0, slope_ptr=None, want_bias=True, wan
     g_bias = z[:c] if want_bias else None
     g_slope = z[c:c + 1] if act == 2 else None
     amax = z[c + 1:c + 2] if want_amax else None
-    _lib.call('mrefsr_act_bwd_nhwc_f32', _p(g_out), _p(out if act else None), _p(g_pre), ld, _p(g_bias), _p(g_slope), _p(amax), C.c_int64(npix), c,
-              act, C.c_float(slope), _p(slope_ptr), _p(_range_flag(g_out.device)) if act == 2 else None, _stream())
+    flag = _p(_range_flag(g_out.device)) if act == 2 else None
+    if (g_bias is not None or g_slope is not None) and is_deterministic():   # the sums added in block order (bitwise reproducible)
+        ws, ticket = _det_scratch(g_out.device, blocks * (c + 1) * 4)
+        _lib.call('mrefsr_act_bwd_nhwc_det_f32', _p(g_out), _p(out if act else None), _p(g_pre), ld, _p(g_bias), _p(g_slope), _p(amax),
+                  C.c_int64(npix), c, act, C.c_float(slope), _p(slope_ptr), flag, _p(ws), C.c_int64(ws.numel()), _p(ticket), _stream())
+    else:
+        _lib.call('mrefsr_act_bwd_nhwc_f32', _p(g_out), _p(out if act else None), _p(g_pre), ld, _p(g_bias), _p(g_slope), _p(amax), C.c_int64(npix), c,
+                  act, C.c_float(slope), _p(slope_ptr), flag, _stream())
     if want_amax:
         return (g_out if g_pre is None else g_pre), g_bias, g_slope, amax
     return (g_out if g_pre is None else g_pre), g_bias, g_slope
@@ -1108,6 +1196,11 @@ def conv_nhwc_bwd(x, packed, cout, ksize, residual=None, residual_is_mask=False,
     d.ld_out = cout
     _chk('conv_nhwc_bwd', x, residual, in_amax)
     z = zeros_f32(x.device, cout + 1) if want_stats else None
+    if want_stats and is_deterministic():   # the per-cout sums added in tile order (bitwise reproducible)
+        ws, ticket = _det_scratch(x.device, _lib.load().mrefsr_conv_nhwc_bwd_det_workspace_bytes(C.byref(d)))
+        _lib.call('mrefsr_conv_nhwc_bwd_det_f32', C.byref(d), _p(x), _p(packed.data), _p(residual), 1 if residual_is_mask else 0, _p(out),
+                  _p(_range_flag(x.device)), _p(in_amax), _p(z[:cout]), _p(z[cout:]), _p(ws), C.c_int64(ws.numel()), _p(ticket), _stream())
+        return out, z[:cout], z[cout:]
     _lib.call('mrefsr_conv_nhwc_bwd_f32', C.byref(d), _p(x), _p(packed.data), _p(residual), 1 if residual_is_mask else 0, _p(out),
               _p(_range_flag(x.device)), _p(in_amax), _p(z[:cout]) if want_stats else None, _p(z[cout:]) if want_stats else None, _stream())
     return out, (z[:cout] if want_stats else None), (z[cout:] if want_stats else None)

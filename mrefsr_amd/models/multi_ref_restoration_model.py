@@ -82,6 +82,7 @@ class MultiRefRestorationModel:
                                                  broadcast_buffers=opt.get('broadcast_buffers', True))
         self.log_dict = OrderedDict()
         if self.is_train:
+            self._check_deterministic_options()
             self.net_g.train()
             train_opt = opt['train']
             groups = {'g': [], 'offset': [], 'relu3': [], 'relu2': []}
@@ -399,7 +400,36 @@ class MultiRefRestorationModel:
         for p in self.net_d.parameters():   # ref :249-251, before the G step
             p.requires_grad = False
 
+    # ------------------------------------------------------------------ bit-reproducible steps
+    def _deterministic_wanted(self):
+        """opt['train']['deterministic'], or the process-wide switch (hip.set_deterministic / torch.use_deterministic_algorithms):
+        net_g's gradient reductions are added in a fixed order, two runs from one seed produce the same bits"""
+        from .. import hip
+        return bool((self.opt.get('train') or {}).get('deterministic')) or hip.is_deterministic()
+
+    def _check_deterministic_options(self):
+        """the deterministic mode and the (experimental) hipGraph replay of the training step are not offered together: refused, not
+        one of them dropped"""
+        if self._deterministic_wanted() and self._train_graph_wanted():
+            raise ValueError('train.deterministic (or torch.use_deterministic_algorithms(True)) cannot be combined with train.hip_graph / '
+                             'MREFSR_TRAIN_GRAPH=1: the graph replay of the training step is experimental and is not covered by the '
+                             'bit-reproducibility tests; turn one of the two off')
+
+    _deterministic_logged = False
+
     def optimize_parameters(self, step):
+        from .. import hip
+        if not self._deterministic_wanted():
+            return self._optimize_parameters(step)
+        self._check_deterministic_options()   # (torch's flag may have been set after construction)
+        if not self._deterministic_logged:
+            self._deterministic_logged = True
+            logging.getLogger('basicsr').info('deterministic training step: the bias / PReLU / per-channel gradient sums of net_g are added '
+                                              'in a fixed order (bitwise reproducible from run to run)')
+        with hip.deterministic(True):   # (the range-fallback re-run of the step happens inside)
+            return self._optimize_parameters(step)
+
+    def _optimize_parameters(self, step):
         from ..archs import nhwc_train
         nhwc_train.check_scales()   # cached fp16 weight scales of the training convolutions still valid? (device side)
         if self._train_graph_wanted() and self._optimize_graphed(step):
