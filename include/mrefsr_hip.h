@@ -811,6 +811,45 @@ int64_t mrefsr_disc_sg2_conv_wgrad_workspace_bytes(int N, int H, int W, int Cin,
 int mrefsr_disc_sg2_conv_wgrad_f32(const float *x, const float *dy, float *dw, int N, int H, int W, int Cin, int CinR, int Cout, int ks,
                                    void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
 
+/* ---- the parameter update: Adam and the exponential moving average (EMA) of net_g, multi-tensor ---------------------------------
+ * The reference's optimiser is a plain torch.optim.Adam over four parameter groups (multi_ref_restoration_model.py:60-104, stepped
+ * at :277); basicsr's EMA of net_g is one mul_ and one add_ per parameter (base_model.py:75-82, model_ema; sr_model.py:118-119).
+ * Here both are ONE launch over a table of jobs in DEVICE memory (as mrefsr_conv_pack_weights_multi_f32), one job per tensor:
+ *   p     the parameter, n floats, 4-byte aligned (any 4-byte alignment works; streams that share their offset inside 16 bytes,
+ *         as separately allocated tensors do, are moved 16 bytes at a time)
+ *   g     its gradient, or NULL: the job takes no Adam step (torch skips parameters whose .grad is None); m, v the moments
+ *         exp_avg / exp_avg_sq (not NULL where g is not)
+ *   ema   the EMA copy of p, or NULL
+ *   first_chunk   the jobs are laid end to end in chunks: first_chunk of job 0 is 0, of job j + 1 it is first_chunk[j] +
+ *         mrefsr_optim_job_chunks(n[j]) (no job may get fewer chunks than that; the elements beyond them would be left out)
+ *   group index into `groups` (Adam only)
+ * No atomics, no workspace; a table is read-only and can be reused for as long as its addresses hold.
+ *
+ * mrefsr_ema_multi_f32: ema = ema * decay + p * one_minus_decay for every job with an ema (g, m, v, group are not looked at); two
+ *   roundings (the product p * one_minus_decay, then one fused multiply-add).  decay == 0 copies p's bits and does not read ema
+ *   (model_ema(0), the reference's initialisation).
+ * mrefsr_adam_multi_f32: torch.optim.Adam's step (weight_decay added to the gradient, no amsgrad, no maximize) in fp32, the bias
+ *   corrections 1 - beta^step in double from the group's values:
+ *     g += weight_decay p;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;
+ *     p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ *   `step` is the count INCLUDING this update (>= 1).  Jobs with an ema get the EMA update of the new p in the same pass, jobs
+ *   without a gradient included; ema_decay as for mrefsr_ema_multi_f32. */
+typedef struct mrefsr_optim_job {
+    float *p;
+    const float *g;
+    float *m, *v, *ema;
+    int64_t n;
+    int32_t first_chunk, group;
+} mrefsr_optim_job;
+typedef struct mrefsr_adam_group {
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t step;
+} mrefsr_adam_group;
+int mrefsr_optim_job_chunks(int64_t n); /* -1: n < 0 or n > 2^40 */
+int mrefsr_ema_multi_f32(const mrefsr_optim_job *jobs, int n_jobs, float decay, float one_minus_decay, mrefsr_stream_t stream);
+int mrefsr_adam_multi_f32(const mrefsr_optim_job *jobs, int n_jobs, const mrefsr_adam_group *groups, int n_groups, float ema_decay,
+                          float one_minus_ema_decay, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

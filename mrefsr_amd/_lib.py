@@ -34,6 +34,17 @@ class TapJob(C.Structure):
                 ('group', C.c_int32)]
 
 
+class OptimJob(C.Structure):
+    """mirror of mrefsr_optim_job"""
+    _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('ema', C.c_void_p), ('n', C.c_int64),
+                ('first_chunk', C.c_int32), ('group', C.c_int32)]
+
+
+class AdamGroup(C.Structure):
+    """mirror of mrefsr_adam_group"""
+    _fields_ = [(n, C.c_double) for n in ('lr', 'beta1', 'beta2', 'eps', 'weight_decay')] + [('step', C.c_int64)]
+
+
 # name -> (restype, argtypes): exactly the declarations of include/mrefsr_hip.h
 SIGNATURES = {
     'mrefsr_abi_version': (_i, []),
@@ -165,6 +176,9 @@ SIGNATURES = {
     'mrefsr_upfirdn2d': (_i, [_vp, _vp, _vp] + [_i] * 15 + [_vp]),
     'mrefsr_tensor2img_u8': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'mrefsr_val_metrics_workspace_bytes': (_i64, [_i, _i, _i]),
+    'mrefsr_optim_job_chunks': (_i, [_i64]),
+    'mrefsr_ema_multi_f32': (_i, [_vp, _i, _f, _f, _vp]),
+    'mrefsr_adam_multi_f32': (_i, [_vp, _i, _vp, _i, _f, _f, _vp]),
     'mrefsr_val_metrics_f32': (_i, [_vp, _vp] + [_i] * 5 + [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
 }
 

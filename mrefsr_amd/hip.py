@@ -922,6 +922,88 @@ def conv_pack_multi(table, n_jobs):
     _lib.call('mrefsr_conv_pack_weights_multi_f32', _p(table), n_jobs, _p(_range_flag(table.device)), _stream())
 
 
+# ------------------------------------------------------------------ the parameter update (csrc/optim.hip): Adam and the EMA of net_g
+_OPTIM_CHUNK = 1024   # elements per chunk of csrc/optim.hip (mrefsr_optim_job_chunks(n) = ceil((n + 3) / 1024), 0 for n = 0)
+
+
+class OptimTable:
+    """a table of mrefsr_optim_job in device memory and the addresses it was built from (``key``); it holds no tensor alive: a
+    table is only ever used with the tensors whose addresses have just been compared with its key"""
+    __slots__ = ('key', 'table', 'n_jobs')
+
+
+def optim_table(ps, gs=None, ms=None, vs=None, emas=None, groups=None, cached=None):
+    """The job table of ema_multi / adam_multi over the parameters ``ps``: per parameter its gradient, moments and EMA copy (each
+    list may be None, each entry may be None) and its index into the Adam groups.  ``cached``: the table of the call before; it
+    is returned as it is when no address, size or group has moved, otherwise a new one is built and uploaded (a synchronous
+    copy of 56 bytes per tensor: not under hipGraph capture)."""
+    n = len(ps)
+    none = [None] * n
+    gs, ms, vs, emas = gs or none, ms or none, vs or none, emas or none
+    groups = groups or [0] * n
+    key = tuple((p.data_ptr(), 0 if g is None else g.data_ptr(), 0 if m is None else m.data_ptr(), 0 if v is None else v.data_ptr(),
+                 0 if e is None else e.data_ptr(), p.numel(), gi) for p, g, m, v, e, gi in zip(ps, gs, ms, vs, emas, groups))
+    if cached is not None and cached.key == key:
+        return cached
+    if n == 0:
+        raise ValueError('optim_table: no tensors')
+    import numpy as np
+    device = ps[0].device
+    old = cached.key if cached is not None and len(cached.key) == n else none
+    for row, was, p, g, m, v, e in zip(key, old, ps, gs, ms, vs, emas):
+        if row == was:   # (checked when the table before this one was built)
+            continue
+        for k, t in enumerate((p, g, m, v, e)):
+            if t is not None and (was is None or row[k] != was[k] or row[5] != was[5]):
+                _chk('optim_table', t)
+                if t.numel() != row[5] or t.device != device:
+                    raise ValueError('optim_table: a gradient, moment or EMA tensor does not match its parameter (size / device)')
+        if g is not None and (m is None or v is None):
+            raise ValueError('optim_table: a gradient without both moments')
+    rows = np.array(key, dtype=np.int64)                    # mrefsr_optim_job: five addresses, n, then first_chunk | group << 32
+    chunks = np.where(rows[:, 5] > 0, (rows[:, 5] + 3 + _OPTIM_CHUNK - 1) // _OPTIM_CHUNK, 0)   # mrefsr_optim_job_chunks
+    first = np.cumsum(chunks) - chunks
+    if int(first[-1] + chunks[-1]) >= 2 ** 31:
+        raise ValueError('optim_table: too many elements')
+    rows[:, 6] = first | ((rows[:, 6] & 0xFFFFFFFF) << 32)
+    tab = OptimTable()
+    tab.key, tab.n_jobs = key, n
+    tab.table = torch.from_numpy(rows).to(device)
+    return tab
+
+
+def _written(tensors):
+    # the kernels write through raw pointers: autograd's version counters are moved by hand, so that everything keyed by them
+    # (the packed weight copies of packed_weight / nhwc_train, verify_packed, the inference graph's key) sees the change
+    torch.autograd.graph.increment_version(tensors)
+
+
+def ema_multi(tab, decay, emas):
+    """ema = decay * ema + (1 - decay) * p for every job of ``tab`` that has an EMA tensor (``emas``: those tensors), one launch;
+    decay 0 copies p bit for bit"""
+    decay = float(decay)
+    if not 0.0 <= decay <= 1.0:
+        raise ValueError(f'ema_multi: decay {decay} outside [0, 1]')
+    _lib.call('mrefsr_ema_multi_f32', _p(tab.table), tab.n_jobs, C.c_float(decay), C.c_float(1.0 - decay), _stream())
+    _written(emas)
+
+
+def adam_multi(tab, groups, written, ema_decay=0.0):
+    """torch.optim.Adam's step for every job of ``tab`` that has a gradient, one launch: ``groups`` = [(lr, beta1, beta2, eps,
+    weight_decay, step), ...] with ``step`` counting this update; jobs with an EMA tensor get its update with ``ema_decay`` in
+    the same pass.  ``written``: the parameters and EMA tensors the launch writes (the moments carry no version anyone reads)."""
+    ema_decay = float(ema_decay)
+    if not 0.0 <= ema_decay <= 1.0:
+        raise ValueError(f'adam_multi: ema_decay {ema_decay} outside [0, 1]')
+    if not groups or any(int(g[5]) < 1 for g in groups):
+        raise ValueError('adam_multi: no groups / a step count below 1')
+    arr = (_lib.AdamGroup * len(groups))(*[_lib.AdamGroup(*(float(x) for x in g[:5]), int(g[5])) for g in groups])
+    dev = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(tab.table.device)
+    _lib.call('mrefsr_adam_multi_f32', _p(tab.table), tab.n_jobs, _p(dev), len(groups), C.c_float(ema_decay), C.c_float(1.0 - ema_decay),
+              _stream())
+    _written(written)
+
+
 def act_bwd_nhwc(g_out, out, act, slope=0.0, slope_ptr=None, want_bias=True, want_amax=False):
     """Backward of a fused convolution epilogue on [..., C] contiguous tensors: g_pre = g_out * act'(out) with act 0 none,
     1 LeakyReLU(slope) (0 = ReLU), 2 PReLU(slope_ptr).  Returns (g_pre [..., ld] with ld = C rounded up to 4 (extra channels

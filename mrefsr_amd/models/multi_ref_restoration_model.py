@@ -3,7 +3,7 @@ basicsr/models/multi_ref_restoration_model.py:20-386 for what the shipped yml ex
 
 Same option keys (network_g / network_map / network_extractor / path.* / train.*), same methods
 (feed_data :190-195, optimize_parameters :197-279, test :281-294, get_current_log,
-update_learning_rate, save / load of ``{'params': state_dict}`` checkpoints), same optimiser
+update_learning_rate, save / load of ``{'params': state_dict}`` checkpoints -- with train.ema_decay ``{'params', 'params_ema'}``), same optimiser
 layout: Adam with four parameter groups chosen by name (:60-89) --
     'offset' & 'small'  -> lr_relu3_offset     'offset' & 'medium' -> lr_relu2_offset
     other 'offset'      -> lr_offset           everything else     -> lr_g
@@ -23,6 +23,7 @@ What differs underneath (SURVEY 7 "hard parts"):
 """
 import contextlib
 import logging
+import math
 import os
 from collections import OrderedDict
 
@@ -52,6 +53,24 @@ class _MultiStepRestartLR(torch.optim.lr_scheduler._LRScheduler):
         return [group['lr'] * self.gamma**self.milestones[self.last_epoch] for group in self.optimizer.param_groups]
 
 
+class _CosineAnnealingRestartLR(torch.optim.lr_scheduler._LRScheduler):
+    """basicsr/models/lr_scheduler.py:36-96 (cosine annealing inside each period, restarted with a weight at the period's end)"""
+
+    def __init__(self, optimizer, periods, restart_weights=(1, ), eta_min=0, last_epoch=-1):
+        self.periods, self.restart_weights, self.eta_min = list(periods), list(restart_weights), eta_min
+        assert len(self.periods) == len(self.restart_weights), 'periods and restart_weights should have the same length.'
+        self.cumulative_period = [sum(self.periods[0:i + 1]) for i in range(len(self.periods))]
+        super().__init__(optimizer, last_epoch)
+
+    def get_lr(self):
+        # the first period whose (cumulative) end has not been passed (ref :36-54; past the last one the reference fails too)
+        idx = next(i for i, period in enumerate(self.cumulative_period) if self.last_epoch <= period)
+        weight, period = self.restart_weights[idx], self.periods[idx]
+        nearest_restart = 0 if idx == 0 else self.cumulative_period[idx - 1]
+        return [self.eta_min + weight * 0.5 * (base_lr - self.eta_min) * (1 + math.cos(math.pi * ((self.last_epoch - nearest_restart) / period)))
+                for base_lr in self.base_lrs]
+
+
 @MODEL_REGISTRY.register()
 class MultiRefRestorationModel:
 
@@ -75,7 +94,7 @@ class MultiRefRestorationModel:
 
         self.net_g = build_network(opt['network_g']).to(self.device)
         if path.get('pretrain_network_g'):
-            self.load_network(self.net_g, path['pretrain_network_g'], path.get('strict_load', True))
+            self.load_network(self.net_g, path['pretrain_network_g'], path.get('strict_load', True), path.get('param_key_g', 'params'))
         if opt.get('dist', False):
             self.net_g = DistributedDataParallel(self.net_g, device_ids=[self.device.index],
                                                  find_unused_parameters=opt.get('find_unused_parameters', False),
@@ -83,8 +102,10 @@ class MultiRefRestorationModel:
         self.log_dict = OrderedDict()
         if self.is_train:
             self._check_deterministic_options()
+            self._check_update_options()
             self.net_g.train()
             train_opt = opt['train']
+            self._setup_ema()
             groups = {'g': [], 'offset': [], 'relu3': [], 'relu2': []}
             for name, v in self.get_bare_model(self.net_g).named_parameters():
                 if not v.requires_grad:
@@ -100,7 +121,7 @@ class MultiRefRestorationModel:
                         groups['offset'].append(v)
                 else:
                     groups['g'].append(v)
-            self.optimizer_g = torch.optim.Adam(
+            self.optimizer_g = self._adam(
                 [{'params': groups['g']},
                  {'params': groups['offset'], 'lr': train_opt['lr_offset']},
                  {'params': groups['relu3'], 'lr': train_opt['lr_relu3_offset']},
@@ -111,8 +132,70 @@ class MultiRefRestorationModel:
                 # instead of ~60; train.fused_adam: false keeps the per-operation foreach form (under hipGraph replay the foreach
                 # form with device-side step counters costs 14 ms per step: 52.6 against 37.2 ms)
                 fused=bool(train_opt.get('fused_adam', True)) and self.device.type == 'cuda')
+            if self.net_g_ema is not None and self._hip_adam_wanted():   # the EMA is written by the pass that updates net_g
+                bare, ema = dict(self.get_bare_model(self.net_g).named_parameters()), dict(self.net_g_ema.named_parameters())
+                self.optimizer_g.ema_params = {bare[k]: v for k, v in ema.items()}
+                self.optimizer_g.ema_decay = self.ema_decay
             self.optimizers.append(self.optimizer_g)
             self.init_training_settings()
+
+    # ------------------------------------------------------------------ the parameter update: train.hip_adam, train.ema_decay
+    def _hip_adam_wanted(self):
+        """opt['train']['hip_adam']: optimizer_g and optimizer_d are optim.HipAdam -- torch.optim.Adam's state and arithmetic, the
+        update of all parameter groups as one launch of this project's kernel (csrc/optim.hip) instead of torch's fused
+        multi-tensor Adam.  Off by default."""
+        return bool((self.opt.get('train') or {}).get('hip_adam'))
+
+    def _adam(self, params, **kw):
+        if not self._hip_adam_wanted():
+            return torch.optim.Adam(params, **kw)
+        from ..optim import HipAdam
+        kw.pop('fused', None)
+        kw.pop('capturable', None)
+        return HipAdam(params, **kw)
+
+    def _check_update_options(self):
+        """train.ema_decay and train.hip_adam are not offered together with the (experimental) hipGraph replay of the training
+        step: refused, not one of them dropped"""
+        train_opt = self.opt.get('train') or {}
+        on = [f'train.{k}' for k in ('ema_decay', 'hip_adam') if train_opt.get(k)]
+        if on and self._train_graph_wanted():
+            raise ValueError(f"{' and '.join(on)} cannot be combined with train.hip_graph / MREFSR_TRAIN_GRAPH=1: the graph replay of the "
+                             "training step is experimental and captures torch's own Adam update only; turn one of the two off")
+
+    net_g_ema = None
+
+    def _setup_ema(self):
+        """train.ema_decay > 0 (sr_model.py:39-53): net_g_ema, a second network_g in eval mode without gradients, never wrapped in
+        DDP (it is used for testing on one GPU and for saving), loaded from path.pretrain_network_g under the key params_ema
+        (falling back to params) or else set to net_g's weights by an update with decay 0"""
+        self.ema_decay = (self.opt.get('train') or {}).get('ema_decay', 0) or 0
+        if not self.ema_decay > 0:
+            return
+        logging.getLogger('basicsr').info(f'Use Exponential Moving Average with decay: {self.ema_decay}')
+        self.net_g_ema = build_network(self.opt['network_g']).to(self.device).eval()
+        for p in self.net_g_ema.parameters():
+            p.requires_grad_(False)
+        path = self.opt.get('path') or {}
+        if path.get('pretrain_network_g'):
+            self.load_network(self.net_g_ema, path['pretrain_network_g'], path.get('strict_load', True), 'params_ema')
+        else:
+            self.model_ema(0)
+
+    def model_ema(self, decay=0.999):
+        """base_model.py:75-82: net_g_ema = decay * net_g_ema + (1 - decay) * net_g over the parameters, as ONE launch (hip.ema_multi)
+        instead of a mul_ and an add_ per parameter; the job table is rebuilt only when a tensor has moved"""
+        from .. import hip
+        bare, ema = dict(self.get_bare_model(self.net_g).named_parameters()), dict(self.net_g_ema.named_parameters())
+        emas = list(ema.values())
+        self._ema_table = hip.optim_table([bare[k] for k in ema], emas=emas, cached=getattr(self, '_ema_table', None))
+        hip.ema_multi(self._ema_table, decay, emas)
+
+    def _step_g(self):
+        """optimizer_g.step() and the EMA update behind it (sr_model.py:114-119); with train.hip_adam the step has written the EMA"""
+        self.optimizer_g.step()
+        if self.net_g_ema is not None and not self._hip_adam_wanted():
+            self.model_ema(self.ema_decay)
 
     # ------------------------------------------------------------------ set-up
     def init_training_settings(self):
@@ -165,16 +248,16 @@ class MultiRefRestorationModel:
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
         if self.net_d is not None:   # ref :178-185: appended before the schedulers are made, so it gets one of its own
-            self.optimizer_d = torch.optim.Adam(self.net_d.parameters(), lr=train_opt['lr_d'], weight_decay=train_opt.get('weight_decay_d', 0),
+            self.optimizer_d = self._adam(self.net_d.parameters(), lr=train_opt['lr_d'], weight_decay=train_opt.get('weight_decay_d', 0),
                                                 betas=train_opt['beta_d'],
                                                 fused=bool(train_opt.get('fused_adam', True)) and self.device.type == 'cuda')
             self.optimizers.append(self.optimizer_d)
         sched = dict(train_opt['scheduler'])
         stype = sched.pop('type')
-        if stype not in ('MultiStepLR', 'MultiStepRestartLR'):
+        if stype not in ('MultiStepLR', 'MultiStepRestartLR', 'CosineAnnealingRestartLR'):   # base_model.py:113-124
             raise NotImplementedError(f'Scheduler {stype} is not implemented yet.')
         for optimizer in self.optimizers:
-            self.schedulers.append(_MultiStepRestartLR(optimizer, **sched))
+            self.schedulers.append((_CosineAnnealingRestartLR if stype == 'CosineAnnealingRestartLR' else _MultiStepRestartLR)(optimizer, **sched))
 
     @staticmethod
     def get_bare_model(net):
@@ -363,7 +446,7 @@ class MultiRefRestorationModel:
         stepped = self._rerun_range_free('optimize_parameters', lambda: self._forward_backward(step), zero_grad=True)
         if stepped is not None:
             if stepped:
-                self.optimizer_g.step()
+                self._step_g()
             return True
         st['upd'].replay()
         # hipStreamSynchronize behind the update graph.  Without it a run of replayed steps ends in a GPU memory access fault after
@@ -450,9 +533,18 @@ class MultiRefRestorationModel:
         stepped = self._rerun_range_free('optimize_parameters', lambda: self._forward_backward(step), stepped, zero_grad=True,
                                          frozen_d=adversarial)
         if stepped:
-            self.optimizer_g.step()
+            self._step_g()
 
     def test(self):
+        if self.net_g_ema is None:
+            return self._test()
+        net_g, self.net_g = self.net_g, self.net_g_ema   # sr_model.py:121-125: the EMA weights are the ones tested (and shipped)
+        try:
+            self._test()
+        finally:
+            self.net_g = net_g
+
+    def _test(self):
         from .. import hip
         self.net_g.eval()
         with torch.no_grad():
@@ -466,7 +558,8 @@ class MultiRefRestorationModel:
                 tripped = self._range_tripped('test')
             if tripped:
                 self.output = self._rerun_range_free('test', self._forward, reset_scales=False, tripped=True)
-        self.net_g.train()
+        if self.net_g is not self.net_g_ema:   # (net_g_ema stays in eval mode)
+            self.net_g.train()
 
     # ------------------------------------------------------------------ hipGraph replay of the inference pass
     _INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack')
@@ -609,7 +702,10 @@ class MultiRefRestorationModel:
         models_dir = self.opt.get('path', {}).get('models')
         if models_dir and self.opt.get('rank', 0) == 0:
             name = 'latest' if current_iter == -1 else current_iter
-            self.save_network(self.net_g, os.path.join(models_dir, f'net_g_{name}.pth'))
+            if self.net_g_ema is not None:   # sr_model.py:227-228: both sets in one file
+                self.save_network([self.net_g, self.net_g_ema], os.path.join(models_dir, f'net_g_{name}.pth'), param_key=['params', 'params_ema'])
+            else:
+                self.save_network(self.net_g, os.path.join(models_dir, f'net_g_{name}.pth'))
             if getattr(self, 'net_d', None) is not None:
                 self.save_network(self.net_d, os.path.join(models_dir, f'net_d_{name}.pth'))
 
@@ -662,15 +758,26 @@ class MultiRefRestorationModel:
         return [param_group['lr'] for param_group in self.optimizers[0].param_groups]
 
     def save_network(self, net, path, param_key='params'):
-        state = OrderedDict((k[7:] if k.startswith('module.') else k, v.cpu())
-                            for k, v in self.get_bare_model(net).state_dict().items())
+        """one network under one key, or lists of both (base_model.py:198-226)"""
+        nets, keys = (net, param_key) if isinstance(net, list) else ([net], [param_key])
+        assert len(nets) == len(keys), 'The lengths of net and param_key should be the same.'
+        save = {key: OrderedDict((k[7:] if k.startswith('module.') else k, v.cpu()) for k, v in self.get_bare_model(n).state_dict().items())
+                for n, key in zip(nets, keys)}
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        torch.save({param_key: state}, path)
+        torch.save(save, path)
 
     def load_network(self, net, load_path, strict=True, param_key='params'):
+        """base_model.py:280-306: the state dict under ``param_key`` of the file; a file without that key but with 'params' gives
+        those (a checkpoint written without an EMA, asked for 'params_ema').  A file with neither is taken as a flat state dict."""
+        logger = logging.getLogger('basicsr')
         load_net = torch.load(load_path, map_location='cpu')
-        if param_key is not None and param_key in load_net:
-            load_net = load_net[param_key]
+        if param_key is not None:
+            if param_key not in load_net and 'params' in load_net:
+                param_key = 'params'
+                logger.info('Loading: params_ema does not exist, use params.')
+            if param_key in load_net:
+                load_net = load_net[param_key]
+                logger.info(f'Loading {self.get_bare_model(net).__class__.__name__} model from {load_path}, with param key: [{param_key}].')
         load_net = OrderedDict((k[7:] if k.startswith('module.') else k, v) for k, v in load_net.items())
         self.get_bare_model(net).load_state_dict(load_net, strict=strict)
 
