@@ -850,6 +850,38 @@ int mrefsr_ema_multi_f32(const mrefsr_optim_job *jobs, int n_jobs, float decay, 
 int mrefsr_adam_multi_f32(const mrefsr_optim_job *jobs, int n_jobs, const mrefsr_adam_group *groups, int n_groups, float ema_decay,
                           float one_minus_ema_decay, mrefsr_stream_t stream);
 
+/* ---- gradient-norm clipping and non-finite step skipping over the same job table ------------------------------------------------
+ * torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False) between backward and the update, without a host
+ * synchronisation: total_norm = sqrt(sum g^2) over every job with a gradient, coef = min(max_norm / (total_norm + 1e-6), 1) in
+ * fp32, the update consumes fl32(g * coef) (multiplied also when coef == 1: no bit changes).  Squares are taken and added per
+ * lane in fp32, so a square -- or a lane's sum -- that overflows fp32 is inf and the norm counts as NON-FINITE although every
+ * gradient element is finite (|g| above 1.8e19); lanes and blocks are added in double, in a fixed order, without atomics: the
+ * same bits from run to run.  The relative error of total_norm is at most ((L + 1) / 2 + 2) 2^-24, L = 4 ceil(T / 2048) the
+ * squares one lane adds, T the chunks of the table.
+ *
+ * mrefsr_grad_sqnorm_multi_f32: reads job.g only (jobs without one are skipped; p, m, v, ema, group are not looked at) and writes
+ *   one double per block into `workspace` (mrefsr_grad_norm_workspace_bytes() bytes, 8-byte aligned, owned by the caller).
+ * mrefsr_grad_norm_finalize_f32: one block; adds the workspace in index order and writes *state: total_norm (unclipped), coef
+ *   (max_norm <= 0: no clipping, coef = 1; a NaN norm gives a NaN coef, an infinite one 0, as in torch), found_inf = 1 when
+ *   total_norm is inf or NaN, else 0 (a float, so that it can be handed to torch's fused Adam as optimizer.found_inf), and
+ *   skipped += 1 when found_inf and skip_nonfinite.  The caller zeroes *state once; `skipped` is written by this launch only.
+ * mrefsr_grad_scale_multi_f32: g = fl32(g * state->coef) in place for every job with a gradient (torch's clip; for torch's Adam).
+ * mrefsr_adam_multi_clip_f32: mrefsr_adam_multi_f32 on fl32(g * state->coef) formed in registers -- the gradient tensors are not
+ *   written.  With skip_nonfinite and state->found_inf, no job takes its Adam step (p, m, v keep their bits) while the EMA
+ *   update is done as always.  The bias corrections are taken at group.step - state->skipped (at least 1): the host may go on
+ *   counting skipped steps and need not read the state back.  All entries must be launched on one stream, in this order. */
+typedef struct mrefsr_grad_clip_state {
+    float total_norm, coef, found_inf, reserved;
+    int64_t skipped;
+} mrefsr_grad_clip_state;
+int64_t mrefsr_grad_norm_workspace_bytes(void);
+int mrefsr_grad_sqnorm_multi_f32(const mrefsr_optim_job *jobs, int n_jobs, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_grad_norm_finalize_f32(const void *workspace, int64_t workspace_bytes, float max_norm, int skip_nonfinite,
+                                  mrefsr_grad_clip_state *state, mrefsr_stream_t stream);
+int mrefsr_grad_scale_multi_f32(const mrefsr_optim_job *jobs, int n_jobs, const mrefsr_grad_clip_state *state, mrefsr_stream_t stream);
+int mrefsr_adam_multi_clip_f32(const mrefsr_optim_job *jobs, int n_jobs, const mrefsr_adam_group *groups, int n_groups, float ema_decay,
+                               float one_minus_ema_decay, const mrefsr_grad_clip_state *state, int skip_nonfinite, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -45,6 +45,11 @@ class AdamGroup(C.Structure):
     _fields_ = [(n, C.c_double) for n in ('lr', 'beta1', 'beta2', 'eps', 'weight_decay')] + [('step', C.c_int64)]
 
 
+class GradClipState(C.Structure):
+    """mirror of mrefsr_grad_clip_state"""
+    _fields_ = [(n, C.c_float) for n in ('total_norm', 'coef', 'found_inf', 'reserved')] + [('skipped', C.c_int64)]
+
+
 # name -> (restype, argtypes): exactly the declarations of include/mrefsr_hip.h
 SIGNATURES = {
     'mrefsr_abi_version': (_i, []),
@@ -179,6 +184,11 @@ SIGNATURES = {
     'mrefsr_optim_job_chunks': (_i, [_i64]),
     'mrefsr_ema_multi_f32': (_i, [_vp, _i, _f, _f, _vp]),
     'mrefsr_adam_multi_f32': (_i, [_vp, _i, _vp, _i, _f, _f, _vp]),
+    'mrefsr_grad_norm_workspace_bytes': (_i64, []),
+    'mrefsr_grad_sqnorm_multi_f32': (_i, [_vp, _i, _vp, _i64, _vp]),
+    'mrefsr_grad_norm_finalize_f32': (_i, [_vp, _i64, _f, _i, _vp, _vp]),
+    'mrefsr_grad_scale_multi_f32': (_i, [_vp, _i, _vp, _vp]),
+    'mrefsr_adam_multi_clip_f32': (_i, [_vp, _i, _vp, _i, _f, _f, _vp, _i, _vp]),
     'mrefsr_val_metrics_f32': (_i, [_vp, _vp] + [_i] * 5 + [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
 }
 

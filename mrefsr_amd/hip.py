@@ -6,6 +6,7 @@ tensor raises (the reference's native ops raise NotImplementedError on CPU tenso
 basicsr/ops/dcn/deform_conv.py:61-62).
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -932,11 +933,12 @@ class OptimTable:
     __slots__ = ('key', 'table', 'n_jobs')
 
 
-def optim_table(ps, gs=None, ms=None, vs=None, emas=None, groups=None, cached=None):
+def optim_table(ps, gs=None, ms=None, vs=None, emas=None, groups=None, cached=None, need_moments=True):
     """The job table of ema_multi / adam_multi over the parameters ``ps``: per parameter its gradient, moments and EMA copy (each
     list may be None, each entry may be None) and its index into the Adam groups.  ``cached``: the table of the call before; it
     is returned as it is when no address, size or group has moved, otherwise a new one is built and uploaded (a synchronous
-    copy of 56 bytes per tensor: not under hipGraph capture)."""
+    copy of 56 bytes per tensor: not under hipGraph capture).  ``need_moments`` False: a table of gradients alone, for
+    grad_norm_multi / grad_scale_multi in front of an optimiser that is not adam_multi (which takes no step without moments)."""
     n = len(ps)
     none = [None] * n
     gs, ms, vs, emas = gs or none, ms or none, vs or none, emas or none
@@ -958,7 +960,7 @@ def optim_table(ps, gs=None, ms=None, vs=None, emas=None, groups=None, cached=No
                 _chk('optim_table', t)
                 if t.numel() != row[5] or t.device != device:
                     raise ValueError('optim_table: a gradient, moment or EMA tensor does not match its parameter (size / device)')
-        if g is not None and (m is None or v is None):
+        if need_moments and g is not None and (m is None or v is None):
             raise ValueError('optim_table: a gradient without both moments')
     rows = np.array(key, dtype=np.int64)                    # mrefsr_optim_job: five addresses, n, then first_chunk | group << 32
     chunks = np.where(rows[:, 5] > 0, (rows[:, 5] + 3 + _OPTIM_CHUNK - 1) // _OPTIM_CHUNK, 0)   # mrefsr_optim_job_chunks
@@ -988,10 +990,45 @@ def ema_multi(tab, decay, emas):
     _written(emas)
 
 
-def adam_multi(tab, groups, written, ema_decay=0.0):
+class GradClipState:
+    """mrefsr_grad_clip_state in device memory (``buf``: 24 bytes as six fp32 words) with 0-dim views of its fields -- the
+    unclipped ``total_norm``, ``coef``, ``found_inf`` (fp32 0 / 1: torch's fused Adam takes it as optimizer.found_inf) and
+    ``skipped`` (int64) -- and the workspace of the norm's per-block partial sums.  Nothing is read back here."""
+    __slots__ = ('buf', 'total_norm', 'coef', 'found_inf', 'skipped', 'workspace')
+
+    def __init__(self, device):
+        self.buf = torch.zeros(C.sizeof(_lib.GradClipState) // 4, device=device, dtype=torch.float32)
+        self.total_norm, self.coef, self.found_inf = self.buf[0], self.buf[1], self.buf[2]
+        self.skipped = self.buf[4:6].view(torch.int64)[0]
+        self.workspace = torch.empty(_lib.load().mrefsr_grad_norm_workspace_bytes() // 8, device=device, dtype=torch.float64)
+
+
+def grad_norm_multi(tab, state, max_norm=0.0, skip=False):
+    """The global L2 norm of every gradient of ``tab`` into ``state`` (a GradClipState), two launches: the per-block sums of
+    squares and the one-block finalize that also writes coef = min(max_norm / (total_norm + 1e-6), 1) (``max_norm`` <= 0: no
+    clipping, 1), found_inf, and counts a skipped step when ``skip`` and the norm is not finite.  Fixed summation order."""
+    max_norm = float(max_norm)
+    if not math.isfinite(max_norm):
+        raise ValueError(f'grad_norm_multi: max_norm {max_norm} is not finite')
+    ws = state.workspace
+    _lib.call('mrefsr_grad_sqnorm_multi_f32', _p(tab.table), tab.n_jobs, _p(ws), ws.numel() * 8, _stream())
+    _lib.call('mrefsr_grad_norm_finalize_f32', _p(ws), ws.numel() * 8, C.c_float(max_norm), int(bool(skip)), _p(state.buf), _stream())
+
+
+def grad_scale_multi(tab, state, grads):
+    """g = fl32(g * state.coef) in place for every gradient of ``tab`` (``grads``: those tensors), one launch: the second half
+    of torch's clip_grad_norm_, for an optimiser that reads the gradient tensors (adam_multi's ``clip=`` needs no such pass)"""
+    _lib.call('mrefsr_grad_scale_multi_f32', _p(tab.table), tab.n_jobs, _p(state.buf), _stream())
+    _written(grads)
+
+
+def adam_multi(tab, groups, written, ema_decay=0.0, clip=None, skip=False):
     """torch.optim.Adam's step for every job of ``tab`` that has a gradient, one launch: ``groups`` = [(lr, beta1, beta2, eps,
     weight_decay, step), ...] with ``step`` counting this update; jobs with an EMA tensor get its update with ``ema_decay`` in
-    the same pass.  ``written``: the parameters and EMA tensors the launch writes (the moments carry no version anyone reads)."""
+    the same pass.  ``written``: the parameters and EMA tensors the launch writes (the moments carry no version anyone reads).
+    ``clip``: the GradClipState that grad_norm_multi has just filled for this table -- the gradients enter as fl32(g * coef)
+    without being written, the step counts are taken less ``clip.skipped``, and with ``skip`` a non-finite norm leaves
+    parameters and moments as they are (the EMA update is still made)."""
     ema_decay = float(ema_decay)
     if not 0.0 <= ema_decay <= 1.0:
         raise ValueError(f'adam_multi: ema_decay {ema_decay} outside [0, 1]')
@@ -999,8 +1036,14 @@ def adam_multi(tab, groups, written, ema_decay=0.0):
         raise ValueError('adam_multi: no groups / a step count below 1')
     arr = (_lib.AdamGroup * len(groups))(*[_lib.AdamGroup(*(float(x) for x in g[:5]), int(g[5])) for g in groups])
     dev = torch.frombuffer(bytearray(arr), dtype=torch.uint8).to(tab.table.device)
-    _lib.call('mrefsr_adam_multi_f32', _p(tab.table), tab.n_jobs, _p(dev), len(groups), C.c_float(ema_decay), C.c_float(1.0 - ema_decay),
-              _stream())
+    if clip is None:
+        if skip:
+            raise ValueError('adam_multi: skip needs the clip state of grad_norm_multi')
+        _lib.call('mrefsr_adam_multi_f32', _p(tab.table), tab.n_jobs, _p(dev), len(groups), C.c_float(ema_decay), C.c_float(1.0 - ema_decay),
+                  _stream())
+    else:
+        _lib.call('mrefsr_adam_multi_clip_f32', _p(tab.table), tab.n_jobs, _p(dev), len(groups), C.c_float(ema_decay),
+                  C.c_float(1.0 - ema_decay), _p(clip.buf), int(bool(skip)), _stream())
     _written(written)
 
 

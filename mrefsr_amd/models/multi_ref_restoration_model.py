@@ -132,6 +132,7 @@ class MultiRefRestorationModel:
                 # instead of ~60; train.fused_adam: false keeps the per-operation foreach form (under hipGraph replay the foreach
                 # form with device-side step counters costs 14 ms per step: 52.6 against 37.2 ms)
                 fused=bool(train_opt.get('fused_adam', True)) and self.device.type == 'cuda')
+            self._setup_grad_clip(self.optimizer_g, 'g')
             if self.net_g_ema is not None and self._hip_adam_wanted():   # the EMA is written by the pass that updates net_g
                 bare, ema = dict(self.get_bare_model(self.net_g).named_parameters()), dict(self.net_g_ema.named_parameters())
                 self.optimizer_g.ema_params = {bare[k]: v for k, v in ema.items()}
@@ -158,10 +159,58 @@ class MultiRefRestorationModel:
         """train.ema_decay and train.hip_adam are not offered together with the (experimental) hipGraph replay of the training
         step: refused, not one of them dropped"""
         train_opt = self.opt.get('train') or {}
-        on = [f'train.{k}' for k in ('ema_decay', 'hip_adam') if train_opt.get(k)]
+        on = [f'train.{k}' for k in ('ema_decay', 'hip_adam') + self._CLIP_OPTIONS if train_opt.get(k)]
         if on and self._train_graph_wanted():
             raise ValueError(f"{' and '.join(on)} cannot be combined with train.hip_graph / MREFSR_TRAIN_GRAPH=1: the graph replay of the "
                              "training step is experimental and captures torch's own Adam update only; turn one of the two off")
+        for k in self._CLIP_OPTIONS[:2]:
+            v = train_opt.get(k)
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0)):
+                raise ValueError(f'train.{k}: {v!r} is not a finite number above 0 (leave the option out for no clipping)')
+        if train_opt.get('skip_nonfinite_steps') and not train_opt.get('fused_adam', True) and not train_opt.get('hip_adam'):
+            raise ValueError("train.skip_nonfinite_steps cannot be combined with train.fused_adam: false unless train.hip_adam is on: "
+                             "torch's non-fused Adam has no found_inf to skip an update by")
+
+    # ------------------------------------------------------------------ train.grad_clip_norm_g / _d, train.skip_nonfinite_steps
+    _CLIP_OPTIONS = ('grad_clip_norm_g', 'grad_clip_norm_d', 'skip_nonfinite_steps')
+
+    def _setup_grad_clip(self, optimizer, which):
+        """train.grad_clip_norm_<which>: torch.nn.utils.clip_grad_norm_ (global L2 norm over all parameter groups) in front of that
+        optimiser's update; train.skip_nonfinite_steps: an update whose gradient norm is inf or NaN is left out, on the device
+        (parameters, moments and step counts keep their bits; the EMA update is made all the same).  Both absent: nothing is set
+        up and no launch is added.  HipAdam does it inside its step; for torch's Adam, _clip_gradients runs in front of it."""
+        train_opt = self.opt.get('train') or {}
+        max_norm, skip = train_opt.get(f'grad_clip_norm_{which}'), bool(train_opt.get('skip_nonfinite_steps'))
+        optimizer._mrefsr_clip = (max_norm, skip) if max_norm is not None or skip else None
+        if optimizer._mrefsr_clip and self._hip_adam_wanted():
+            optimizer.max_grad_norm, optimizer.skip_nonfinite = max_norm, skip
+
+    def _clip_gradients(self, optimizer, which):
+        """the norm (and, for torch's Adam, the scaling in place and found_inf) in front of optimizer.step(), and the log entries
+        grad_norm_<which> (unclipped) / skipped_steps_<which>: views of the device state, read at get_current_log()"""
+        cfg = getattr(optimizer, '_mrefsr_clip', None)
+        if not cfg:
+            return
+        from .. import hip
+        if self._hip_adam_wanted():
+            state = optimizer.clip_state   # (filled by the step that has just run)
+        else:
+            params = [p for group in optimizer.param_groups for p in group['params'] if p.grad is not None]
+            if not params:
+                return
+            grads = [p.grad for p in params]
+            state = getattr(optimizer, 'clip_state', None)
+            if state is None:
+                state = optimizer.clip_state = hip.GradClipState(params[0].device)
+            optimizer._clip_table = hip.optim_table(params, grads, cached=getattr(optimizer, '_clip_table', None), need_moments=False)
+            hip.grad_norm_multi(optimizer._clip_table, state, cfg[0] or 0.0, cfg[1])
+            if cfg[0]:
+                hip.grad_scale_multi(optimizer._clip_table, state, grads)
+            if cfg[1]:
+                optimizer.found_inf = state.found_inf   # torch's fused Adam leaves the update out and takes its step counts back
+        if state is not None:
+            self.log_dict[f'grad_norm_{which}'] = state.total_norm
+            self.log_dict[f'skipped_steps_{which}'] = state.skipped
 
     net_g_ema = None
 
@@ -193,9 +242,21 @@ class MultiRefRestorationModel:
 
     def _step_g(self):
         """optimizer_g.step() and the EMA update behind it (sr_model.py:114-119); with train.hip_adam the step has written the EMA"""
+        if not self._hip_adam_wanted():
+            self._clip_gradients(self.optimizer_g, 'g')
         self.optimizer_g.step()
+        if self._hip_adam_wanted():
+            self._clip_gradients(self.optimizer_g, 'g')
         if self.net_g_ema is not None and not self._hip_adam_wanted():
             self.model_ema(self.ema_decay)
+
+    def _step_d(self):
+        """optimizer_d.step() behind train.grad_clip_norm_d / train.skip_nonfinite_steps"""
+        if not self._hip_adam_wanted():
+            self._clip_gradients(self.optimizer_d, 'd')
+        self.optimizer_d.step()
+        if self._hip_adam_wanted():
+            self._clip_gradients(self.optimizer_d, 'd')
 
     # ------------------------------------------------------------------ set-up
     def init_training_settings(self):
@@ -251,6 +312,7 @@ class MultiRefRestorationModel:
             self.optimizer_d = self._adam(self.net_d.parameters(), lr=train_opt['lr_d'], weight_decay=train_opt.get('weight_decay_d', 0),
                                                 betas=train_opt['beta_d'],
                                                 fused=bool(train_opt.get('fused_adam', True)) and self.device.type == 'cuda')
+            self._setup_grad_clip(self.optimizer_d, 'd')
             self.optimizers.append(self.optimizer_d)
         sched = dict(train_opt['scheduler'])
         stype = sched.pop('type')
@@ -479,7 +541,7 @@ class MultiRefRestorationModel:
             self.log_dict['l_grad_penalty'] = l_grad_penalty.detach()
             l_d_total = l_d_total + l_grad_penalty
         l_d_total.backward()
-        self.optimizer_d.step()
+        self._step_d()
         for p in self.net_d.parameters():   # ref :249-251, before the G step
             p.requires_grad = False
 
@@ -732,7 +794,11 @@ class MultiRefRestorationModel:
 
     # ------------------------------------------------------------------ bookkeeping
     def get_current_log(self):
-        return OrderedDict((k, v.item() if torch.is_tensor(v) else v) for k, v in self.log_dict.items())
+        log = OrderedDict((k, v.item() if torch.is_tensor(v) else v) for k, v in self.log_dict.items())
+        for which in ('g', 'd'):   # (HipAdam.state_dict() moves the device's count of skipped steps into its host counters)
+            if f'skipped_steps_{which}' in log:
+                log[f'skipped_steps_{which}'] += getattr(getattr(self, f'optimizer_{which}'), 'skipped_folded', 0)
+        return log
 
     def get_current_visuals(self):
         out = OrderedDict(img_in_lq=self.img_in_lq.detach().cpu(), rlt=self.output.detach().cpu())
