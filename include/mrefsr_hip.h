@@ -882,6 +882,27 @@ int mrefsr_grad_scale_multi_f32(const mrefsr_optim_job *jobs, int n_jobs, const 
 int mrefsr_adam_multi_clip_f32(const mrefsr_optim_job *jobs, int n_jobs, const mrefsr_adam_group *groups, int n_groups, float ema_decay,
                                float one_minus_ema_decay, const mrefsr_grad_clip_state *state, int skip_nonfinite, mrefsr_stream_t stream);
 
+/* ---- R1 regularisation of the discriminator (csrc/gan_reg.hip) --------------------------------------------------------------------
+ * basicsr/losses/losses.py:391-405 (r1_penalty): grad_real.pow(2).view(B, -1).sum(1) of the discriminator's input gradient on the
+ * real images, applied every net_d_reg_every steps in basicsr/models/stylegan2_model.py:208-219.  The discriminator's double
+ * backward runs on its own nodes; these entries are the per-sample sum of squares and its backward.
+ *
+ * mrefsr_r1_sqnorm_f32 (losses.py:404): g is `batch` contiguous rows of n floats, the first row at any 4-byte boundary;
+ *   out[b] = sum_i g[b][i]^2.  Squares are taken and added per lane in fp32 -- a lane's four elements as (q0 + q1) + (q2 + q3),
+ *   then onto its accumulator -- so a square that overflows fp32 is inf, and inf / NaN elements reach out[b] as they are (no
+ *   clamp); lanes, waves and the mrefsr_r1_sqnorm_row_blocks(n) blocks of a row are added in double in a fixed order, out[b] is
+ *   that sum rounded to fp32.  No atomics: the same bits from run to run.  Relative error against the float64 sum of the same
+ *   fp32 elements: at most (L / 4 + 3) 2^-24, below ((L + 1) / 2 + 2) 2^-24, L = 4 ceil(T / row_blocks) the squares one lane
+ *   adds, T = ceil((n + 3) / 1024).  Two launches (per-block partials into `workspace`, mrefsr_r1_sqnorm_workspace_bytes(batch, n)
+ *   bytes, 8-byte aligned, owned by the caller; then one block per row).
+ * mrefsr_r1_sqnorm_bwd_f32 (the backward of losses.py:404 towards grad_real): gg[b][i] = fl32(fl32(2 gs[b]) g[b][i]), the bits of
+ *   torch's g * (2 * gs).view(B, 1); gg has g's layout and may sit at any 4-byte boundary too.  One launch.
+ * batch in 1..65535, n in 1..2^40 (the -1 of the two size queries otherwise). */
+int mrefsr_r1_sqnorm_row_blocks(int64_t n);
+int64_t mrefsr_r1_sqnorm_workspace_bytes(int batch, int64_t n);
+int mrefsr_r1_sqnorm_f32(const float *g, int batch, int64_t n, float *out, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_r1_sqnorm_bwd_f32(const float *g, const float *gs, int batch, int64_t n, float *gg, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

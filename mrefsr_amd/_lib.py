@@ -190,6 +190,10 @@ SIGNATURES = {
     'mrefsr_grad_scale_multi_f32': (_i, [_vp, _i, _vp, _vp]),
     'mrefsr_adam_multi_clip_f32': (_i, [_vp, _i, _vp, _i, _f, _f, _vp, _i, _vp]),
     'mrefsr_val_metrics_f32': (_i, [_vp, _vp] + [_i] * 5 + [_vp, _i, _i, _vp, _vp, _vp, _i64, _vp]),
+    'mrefsr_r1_sqnorm_row_blocks': (_i, [_i64]),
+    'mrefsr_r1_sqnorm_workspace_bytes': (_i64, [_i, _i64]),
+    'mrefsr_r1_sqnorm_f32': (_i, [_vp, _i, _i64, _vp, _vp, _i64, _vp]),
+    'mrefsr_r1_sqnorm_bwd_f32': (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
 }
 
 _lib = None

@@ -1047,6 +1047,51 @@ def adam_multi(tab, groups, written, ema_decay=0.0, clip=None, skip=False):
     _written(written)
 
 
+# ------------------------------------------------------------------ R1 regularisation of the discriminator (csrc/gan_reg.hip)
+def r1_lane_squares(n):
+    """L of r1_sqnorm's error bound ((L + 1) / 2 + 2) 2^-24: the squares one lane adds for rows of ``n`` elements"""
+    blocks = _lib.load().mrefsr_r1_sqnorm_row_blocks(n)
+    if blocks <= 0:
+        raise ValueError(f'r1_lane_squares: n = {n}')
+    chunks = (n + 3 + _OPTIM_CHUNK - 1) // _OPTIM_CHUNK
+    return 4 * ((chunks + blocks - 1) // blocks)
+
+
+def _r1_rows(name, g):
+    if g.dim() < 1 or g.numel() == 0:
+        raise ValueError(f'{name}: a non-empty [B, ...] tensor expected, got {tuple(g.shape)}')
+    return g.shape[0], g.numel() // g.shape[0]
+
+
+def r1_sqnorm(g):
+    """g [B, ...] (contiguous fp32, any 4-byte alignment) -> [B] fp32: g.pow(2).view(B, -1).sum(1) of r1_penalty
+    (basicsr/losses/losses.py:404), added in a fixed order -- fp32 per lane, double across lanes, waves and blocks; two launches,
+    no atomics, the same bits from run to run"""
+    _chk('r1_sqnorm', g)
+    b, n = _r1_rows('r1_sqnorm', g)
+    nbytes = _lib.load().mrefsr_r1_sqnorm_workspace_bytes(b, n)
+    if nbytes <= 0:
+        raise ValueError(f'r1_sqnorm: unsupported shape {tuple(g.shape)}')
+    ws = torch.empty(nbytes // 8, device=g.device, dtype=torch.float64)
+    out = torch.empty(b, device=g.device, dtype=torch.float32)
+    _lib.call('mrefsr_r1_sqnorm_f32', _p(g), b, n, _p(out), _p(ws), nbytes, _stream())
+    return out
+
+
+def r1_sqnorm_bwd(g, gs, out=None):
+    """the backward of r1_sqnorm towards g: fl32(fl32(2 gs[b]) g[b][i]) in g's shape, the bits of torch's g * (2 * gs).view(B, 1);
+    one launch.  ``out``: a contiguous fp32 tensor of g's shape to write into (any 4-byte alignment)"""
+    _chk('r1_sqnorm_bwd', g, gs, out)
+    b, n = _r1_rows('r1_sqnorm_bwd', g)
+    if gs.shape != (b, ):
+        raise ValueError(f'r1_sqnorm_bwd: gs {tuple(gs.shape)} for g {tuple(g.shape)}')
+    if out is not None and out.shape != g.shape:
+        raise ValueError(f'r1_sqnorm_bwd: out {tuple(out.shape)} for g {tuple(g.shape)}')
+    gg = torch.empty_like(g) if out is None else out
+    _lib.call('mrefsr_r1_sqnorm_bwd_f32', _p(g), _p(gs), b, n, _p(gg), _stream())
+    return gg
+
+
 def act_bwd_nhwc(g_out, out, act, slope=0.0, slope_ptr=None, want_bias=True, want_amax=False):
     """Backward of a fused convolution epilogue on [..., C] contiguous tensors: g_pre = g_out * act'(out) with act 0 none,
     1 LeakyReLU(slope) (0 = ReLU), 2 PReLU(slope_ptr).  Returns (g_pre [..., ld] with ld = C rounded up to 4 (extra channels

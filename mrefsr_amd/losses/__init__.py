@@ -1,14 +1,15 @@
 """Mirror of the loss module the reference model builds its criteria from (basicsr/models/losses.py, imported by
-multi_ref_restoration_model.py:17 -- not basicsr/losses/losses.py, which differs).  Classes register in LOSS_REGISTRY under the
+multi_ref_restoration_model.py:17 -- not basicsr/losses/losses.py, which differs; from that newer file come GANLoss's wgan_softplus
+type and r1_penalty, which every StyleGAN2Discriminator configuration sets).  Classes register in LOSS_REGISTRY under the
 reference's names; ``build_loss`` selects one by ``type`` (the contract of basicsr/losses/__init__.py)."""
 from copy import deepcopy
 
 from ..utils.registry import LOSS_REGISTRY
 from .losses import (CharbonnierLoss, GANLoss, GradientPenaltyLoss, L1Loss, MSELoss, PerceptualLoss,
-                     gradient_penalty_loss)
+                     gradient_penalty_loss, r1_penalty)
 
 __all__ = ['build_loss', 'LOSS_REGISTRY', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'PerceptualLoss', 'GANLoss', 'GradientPenaltyLoss',
-           'gradient_penalty_loss']
+           'gradient_penalty_loss', 'r1_penalty']
 
 
 def build_loss(opt):

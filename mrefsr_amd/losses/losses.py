@@ -1,11 +1,13 @@
 """L1Loss, MSELoss, CharbonnierLoss, PerceptualLoss, GANLoss and GradientPenaltyLoss with the reference's constructor signatures
-and values (basicsr/models/losses.py:17-124, 141-238, 275-427).
+and values (basicsr/models/losses.py:17-124, 141-238, 275-427), GANLoss's wgan_softplus type and r1_penalty from the newer
+basicsr/losses/losses.py:258-360, 391-405.
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
 what the model passes -- reduction='mean', no element weight -- and refuse the rest.  PerceptualLoss runs its VGG19 through ONE
 autograd node of the training engine (archs/nhwc_train.py: _VggLoss): output and GT as one batch through the HIP convolution
 kernels, the input-gradient pass of the output image back through the same kernels, pooling / criterion / Gram matrices on
-csrc/percep.hip.  GPU tensors only, like the ops.
+csrc/percep.hip.  GPU tensors only, like the ops.  r1_penalty's per-sample sum of squares and its backward are the kernels of
+csrc/gan_reg.hip for GPU tensors and the torch expression for CPU tensors.
 """
 import torch
 import torch.nn.functional as F
@@ -113,27 +115,36 @@ class PerceptualLoss(nn.Module):
 
 @LOSS_REGISTRY.register()
 class GANLoss(nn.Module):
-    """GAN loss of the adversarial step (basicsr/models/losses.py:275-356): gan_type 'vanilla', 'lsgan', 'wgan' or 'hinge'.
+    """GAN loss of the adversarial step (basicsr/models/losses.py:275-356; wgan_softplus: basicsr/losses/losses.py:284-318): gan_type
+    'vanilla', 'lsgan', 'wgan', 'wgan_softplus' or 'hinge'.
 
     forward(input, target_is_real, is_disc=False): vanilla = BCEWithLogits(input, label) (applied, as in the reference, to the
-    discriminator's sigmoid output), lsgan = mean (input - label)^2, wgan = -mean(input) for real, mean(input) for fake, hinge =
-    mean relu(1 -/+ input) for the discriminator and -mean(input) for the generator.  Labels are real_label_val / fake_label_val;
-    loss_weight multiplies the generator's loss only.  O(B) scalars: plain torch element-wise operations."""
+    discriminator's sigmoid output), lsgan = mean (input - label)^2, wgan = -mean(input) for real, mean(input) for fake,
+    wgan_softplus = mean softplus(-input) for real, mean softplus(input) for fake (StyleGAN2's logistic loss for the discriminator,
+    non-saturating loss for the generator), hinge = mean relu(1 -/+ input) for the discriminator and -mean(input) for the generator.
+    Labels are real_label_val / fake_label_val (wgan and wgan_softplus: the bool itself); loss_weight multiplies the generator's loss
+    only.  O(B) scalars: plain torch element-wise operations, which also gives every type its double backward towards the input
+    (WGAN-GP and R1 differentiate the discriminator twice, not the loss) and a CPU path."""
 
     def __init__(self, gan_type, real_label_val=1.0, fake_label_val=0.0, loss_weight=1.0):
         super().__init__()
-        if gan_type not in ('vanilla', 'lsgan', 'wgan', 'hinge'):
-            raise NotImplementedError(f'GAN type {gan_type} is not implemented.')
+        if gan_type not in ('vanilla', 'lsgan', 'wgan', 'wgan_softplus', 'hinge'):
+            raise NotImplementedError(f'GAN type {gan_type} is not implemented (vanilla, lsgan, wgan, wgan_softplus and hinge are).')
         self.gan_type, self.loss_weight = gan_type, loss_weight
         self.real_label_val, self.fake_label_val = real_label_val, fake_label_val
-        self.loss = {'vanilla': nn.BCEWithLogitsLoss(), 'lsgan': nn.MSELoss(), 'wgan': self._wgan_loss, 'hinge': nn.ReLU()}[gan_type]
+        self.loss = {'vanilla': nn.BCEWithLogitsLoss(), 'lsgan': nn.MSELoss(), 'wgan': self._wgan_loss,
+                     'wgan_softplus': self._wgan_softplus_loss, 'hinge': nn.ReLU()}[gan_type]
 
     @staticmethod
     def _wgan_loss(input, target):
         return -input.mean() if target else input.mean()
 
+    @staticmethod
+    def _wgan_softplus_loss(input, target):
+        return F.softplus(-input).mean() if target else F.softplus(input).mean()
+
     def get_target_label(self, input, target_is_real):
-        if self.gan_type == 'wgan':
+        if self.gan_type in ('wgan', 'wgan_softplus'):
             return target_is_real
         return input.new_ones(input.size()) * (self.real_label_val if target_is_real else self.fake_label_val)
 
@@ -162,6 +173,38 @@ def gradient_penalty_loss(discriminator, real_data, fake_data, mask=None):
         gradients = gradients * mask
     gradients = gradients.view(gradients.size(0), -1)
     return ((gradients.norm(2, dim=1) - 1)**2).mean()
+
+
+class _R1SqNorm(torch.autograd.Function):
+    """g [B, ...] -> [B]: the per-sample sum of squares of r1_penalty on the kernels of csrc/gan_reg.hip (fixed summation order).
+    Its backward, 2 gs[b] g, is a kernel too and is not differentiable again: nothing differentiates the penalty a third time."""
+
+    @staticmethod
+    def forward(ctx, g):
+        from .. import hip
+        g = g.contiguous()
+        ctx.save_for_backward(g)
+        return hip.r1_sqnorm(g)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gs):
+        from .. import hip
+        g, = ctx.saved_tensors
+        return hip.r1_sqnorm_bwd(g, gs.contiguous())
+
+
+def r1_penalty(real_pred, real_img):
+    """R1 regularisation mean_b ||d sum(D(x)) / d x_b||_2^2 on the real images (basicsr/losses/losses.py:391-405; Mescheder et al.,
+    "Which training methods for GANs do actually converge?", eq. 9).  real_img is a leaf that requires grad and real_pred =
+    D(real_img); the discriminator is differentiated twice (create_graph=True) through the nodes WGAN-GP uses.  GPU tensors: the sum
+    of squares is one autograd node over csrc/gan_reg.hip (fp32 only); CPU tensors: the torch expression."""
+    grad_real = torch.autograd.grad(outputs=real_pred.sum(), inputs=real_img, create_graph=True)[0]
+    if not grad_real.is_cuda:
+        return grad_real.pow(2).view(grad_real.shape[0], -1).sum(1).mean()
+    if grad_real.dtype != torch.float32:
+        raise NotImplementedError(f'r1_penalty: {grad_real.dtype} gradient; fp32 only on the GPU')
+    return _R1SqNorm.apply(grad_real).mean()
 
 
 @LOSS_REGISTRY.register()

@@ -12,7 +12,13 @@ Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLo
 (ImageDiscriminator, VGGStyleDiscriminator, UNetDiscriminatorSN or StyleGAN2Discriminator, on the kernels of csrc/disc.hip, disc_vgg.hip,
 disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
-:272-276.  texture_opt and other discriminators raise NotImplementedError instead of being silently skipped.
+:272-276.  gan_type wgan_softplus and the lazily applied R1 penalty on the real images (train.r1_reg_weight, train.net_d_reg_every) are
+those of basicsr/losses/losses.py:284-318, 391-405 and basicsr/models/stylegan2_model.py:75-79, 198-221; lr_d and beta_d are used as
+written (stylegan2_model.py:135-143 rescales them by every / (every + 1): left to the configuration).
+Refused, not silently skipped: texture_opt and other discriminators (NotImplementedError); gan_type without network_d and the
+reverse, r1_reg_weight without network_d (NotImplementedError); an r1_reg_weight that is not a finite number of at least 0, a
+net_d_reg_every that is not an int of at least 1 or that comes without r1_reg_weight, bools for either (ValueError); the clipping,
+EMA and hip_adam options together with train.hip_graph (ValueError).
 
 What differs underneath (SURVEY 7 "hard parts"):
   * the K references run as one k-major batch through extractor / matching / VGG19 / net_g;
@@ -157,7 +163,8 @@ class MultiRefRestorationModel:
 
     def _check_update_options(self):
         """train.ema_decay and train.hip_adam are not offered together with the (experimental) hipGraph replay of the training
-        step: refused, not one of them dropped"""
+        step: refused, not one of them dropped.  The values of the clipping options and of train.r1_reg_weight /
+        train.net_d_reg_every are checked here too."""
         train_opt = self.opt.get('train') or {}
         on = [f'train.{k}' for k in ('ema_decay', 'hip_adam') + self._CLIP_OPTIONS if train_opt.get(k)]
         if on and self._train_graph_wanted():
@@ -167,6 +174,16 @@ class MultiRefRestorationModel:
             v = train_opt.get(k)
             if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v > 0)):
                 raise ValueError(f'train.{k}: {v!r} is not a finite number above 0 (leave the option out for no clipping)')
+        v = train_opt.get('r1_reg_weight')
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not (math.isfinite(v) and v >= 0)):
+            raise ValueError(f'train.r1_reg_weight: {v!r} is not a finite number of at least 0 (0 or absent: no R1 regularisation)')
+        every = train_opt.get('net_d_reg_every')
+        if every is not None:
+            if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+                raise ValueError(f'train.net_d_reg_every: {every!r} is not an int of at least 1')
+            if not v:
+                raise ValueError('train.net_d_reg_every without train.r1_reg_weight: there is no regulariser to apply lazily; set '
+                                 'r1_reg_weight above 0 or drop net_d_reg_every')
         if train_opt.get('skip_nonfinite_steps') and not train_opt.get('fused_adam', True) and not train_opt.get('hip_adam'):
             raise ValueError("train.skip_nonfinite_steps cannot be combined with train.fused_adam: false unless train.hip_adam is on: "
                              "torch's non-fused Adam has no found_inf to skip an update by")
@@ -277,6 +294,12 @@ class MultiRefRestorationModel:
                                       'a missing grad_penalty_weight); give a network_d or drop gan_type')
         if net_d_opt and not train_opt.get('gan_type'):
             raise NotImplementedError('network_d without train.gan_type: the reference fails at its first D step; set gan_type')
+        if train_opt.get('r1_reg_weight') and not net_d_opt:
+            raise NotImplementedError('train.r1_reg_weight without network_d: R1 regularises a discriminator; give a network_d or drop '
+                                      'r1_reg_weight')
+        # R1 on the real images every net_d_reg_every-th D step (stylegan2_model.py:75-79); 0: none
+        self.r1_reg_weight = float(train_opt.get('r1_reg_weight') or 0)
+        self.net_d_reg_every = int(train_opt.get('net_d_reg_every') or 1)
         # discriminator (ref :98-113), built and loaded before the losses
         self.net_d = self.cri_gan = self.cri_grad_penalty = None
         if net_d_opt:
@@ -522,8 +545,14 @@ class MultiRefRestorationModel:
         torch.cuda.current_stream().synchronize()
         return True
 
-    def _discriminator_step(self):
-        """ref :219-245: D on the GT and on the detached output, the gradient penalty, backward, optimizer_d.step()"""
+    def _discriminator_step(self, step):
+        """ref :219-245: D on the GT and on the detached output, the gradient penalty, backward, optimizer_d.step().  With
+        train.r1_reg_weight, on the steps that net_d_reg_every divides, the R1 lines of stylegan2_model.py:208-219 stand between that
+        backward and the one optimizer_d.step(): the update, its clipping and its non-finite check see the sum of both gradients.
+        The extra forward on the real images moves ImageDiscriminator's and VGGStyleDiscriminator's BatchNorm running statistics and
+        UNetDiscriminatorSN's power-iteration vectors once more, as the torch modules would under the same lines.  log_dict holds
+        l_d_r1 after a regularised step only: a plain step takes the last one's value out (stylegan2_model.py builds its log anew
+        every iteration)."""
         self.optimizer_d.zero_grad()
         for p in self.net_d.parameters():
             p.requires_grad = True
@@ -541,6 +570,17 @@ class MultiRefRestorationModel:
             self.log_dict['l_grad_penalty'] = l_grad_penalty.detach()
             l_d_total = l_d_total + l_grad_penalty
         l_d_total.backward()
+        if self.r1_reg_weight > 0 and step % self.net_d_reg_every == 0:
+            from ..losses import r1_penalty
+            real_img = self.gt.detach().requires_grad_(True)   # a leaf of its own on self.gt's storage (D only reads it)
+            real_pred = self.net_d(real_img)
+            l_d_r1 = r1_penalty(real_pred, real_img)
+            # (0 * real_pred[0]: every output of D takes part in this backward, which is what DDP's reducer asks for)
+            l_d_r1 = self.r1_reg_weight / 2 * l_d_r1 * self.net_d_reg_every + 0 * real_pred[0]
+            self.log_dict['l_d_r1'] = l_d_r1.detach().mean()
+            l_d_r1.backward()
+        elif self.r1_reg_weight > 0:
+            self.log_dict.pop('l_d_r1', None)   # a plain step of the lazy schedule: not the value of an earlier regularised step
         self._step_d()
         for p in self.net_d.parameters():   # ref :249-251, before the G step
             p.requires_grad = False
@@ -589,7 +629,7 @@ class MultiRefRestorationModel:
             # of the reference.  Should net_g's backward trip the flag below, the G step is re-run with D's running statistics left as
             # they are (the D step is not repeated).
             self.output = self._rerun_range_free('optimize_parameters', self._forward, self.output)
-            self._discriminator_step()
+            self._discriminator_step(step)
         stepped = self._loss_and_backward(step)
         # (the frozen feature networks and the DCN forward run on the split kernels too)
         stepped = self._rerun_range_free('optimize_parameters', lambda: self._forward_backward(step), stepped, zero_grad=True,
