@@ -12,15 +12,9 @@
 //   head_*                      AdaptiveAvgPool2d(1) -> 1x1 conv + bias -> LeakyReLU -> 1x1 conv + bias -> Sigmoid: forward,
 //                               backward, double backward (a few MFLOP: one block per image, then one thread per weight)
 // No float atomics anywhere: two runs give the same bits.
-#include "common.h"
+#include "disc_common.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-inline int grid_of(long work, int cap) { return (int)(work < 1 ? 1 : (work < cap ? work : cap)); }
-
-__device__ inline float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // image packing: img [B][3][H][W] -> x4 [B][H][W][4] (channel 3 = 0); the gradient takes channels 0..2 back

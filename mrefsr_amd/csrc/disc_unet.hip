@@ -13,11 +13,9 @@
 //   add           out = a + b (the x6 + x0 skip)
 //   conv9_*       nn.Conv2d(C, 1, 3, 1, 1): forward (+ bias), input gradient, weight gradient as a fixed-order split over pixels
 // No float atomics anywhere: two runs give the same bits.
-#include "common.h"
+#include "disc_common.h"
 
 namespace {
-
-inline int grid_of(long work, int cap) { return (int)(work < 1 ? 1 : (work < cap ? work : cap)); }
 
 constexpr int SN_MAX = 8;     // layers per call
 constexpr int SN_RC = 32;     // rows per chunk of W^T u

@@ -1757,71 +1757,112 @@ def disc_head_dbl(ggf, gs, s, pooled, hidden, w1, w2, slope=0.2, want_gs=True, w
 
 
 # ------------------------------------------------------------------ VGGStyleDiscriminator (csrc/disc_vgg.hip)
-def _vout(n, ks):
-    return n // 2 if ks == 4 else n
+# The convolutions of disc_vgg.hip and disc_sg2.hip are one implicit GEMM (csrc/disc_conv_gemm.h) behind two families of entry
+# points, and one implementation here behind the two families of wrappers.
+class _ConvFamily:
+    """name: the prefix of the C symbols and of the _timed names; pack: the weight packing's name; layers: ks -> (stride, pad);
+    res: the forward entry point takes a residual.  (The symbols' names are put together once: the wrappers run hundreds of times
+    in a discriminator step that waits for the host.)"""
+
+    def __init__(self, name, pack, layers, res):
+        self.name, self.pack, self.layers, self.res = name, pack, layers, res
+        self.dgrad, self.wgrad = f'{name}_dgrad', f'{name}_wgrad'
+        self.sym_pack, self.sym_fwd, self.sym_dgrad, self.sym_wgrad = (f'mrefsr_{k}_f32' for k in (pack, name, self.dgrad, self.wgrad))
+        self.ws_bytes, self.wgrad_ws_bytes = f'mrefsr_{name}_workspace_bytes', f'mrefsr_{name}_wgrad_workspace_bytes'
+
+    def out(self, h, w, ks):
+        if ks not in self.layers:
+            return h, w   # (the library refuses the call and says why)
+        stride, pad = self.layers[ks]
+        return (h + 2 * pad - ks) // stride + 1, (w + 2 * pad - ks) // stride + 1
+
+
+_VCONV = _ConvFamily('disc_vconv', 'disc_vconv_pack_weight', {3: (1, 1), 4: (2, 1)}, res=False)
+_SG2CONV = _ConvFamily('disc_sg2_conv', 'disc_sg2_pack_weight', {3: (2, 0), 1: (1, 0)}, res=True)
+
+
+def _conv_ws(device, nbytes):
+    return _wgrad_workspace(device, nbytes) if nbytes > 0 else None
+
+
+def _conv_pack_weight(fam, w, cin, dgrad):
+    _chk(fam.pack, w)
+    cout, cinr, ks = w.shape[0], w.shape[1], w.shape[2]
+    if ks not in fam.layers or w.shape[3] != ks or cinr > cin:
+        raise ValueError(f'{fam.pack}: weight {tuple(w.shape)} for {cin} input channels')
+    out = torch.empty((cin, ks * ks, cout) if dgrad else (cout, ks * ks, cin), device=w.device, dtype=torch.float32)
+    _lib.call(fam.sym_pack, _p(w), _p(out), cout, cinr, cin, ks, 1 if dgrad else 0, _stream())
+    return out
+
+
+def _conv_fwd(fam, x, wpk, bias, ks, act_slope, res=None):
+    _chk(fam.name, x, wpk, bias, res)
+    n, h, w, cin = x.shape
+    cout = wpk.shape[0]
+    if tuple(wpk.shape) != (cout, ks * ks, cin):
+        raise ValueError(f'{fam.name}: packed weight does not match the input channels')
+    ho, wo = fam.out(h, w, ks)
+    y = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
+    if res is not None and res.shape != y.shape:
+        raise ValueError(f'{fam.name}: residual {tuple(res.shape)} for an output {tuple(y.shape)}')
+    ws = _conv_ws(x.device, getattr(_lib.load(), fam.ws_bytes)(n, h, w, cin, cout, ks, 0))
+    act, slope = 0 if act_slope is None else 1, C.c_float(0.0 if act_slope is None else act_slope)
+    nws = C.c_int64(0 if ws is None else ws.numel())
+    with _timed(f'{fam.name}{ks}', 2.0 * y.numel() * ks * ks * cin, detail=True):
+        if fam.res:
+            _lib.call(fam.sym_fwd, _p(x), _p(wpk), _p(bias), _p(res), _p(y), n, h, w, cin, cout, ks, act, slope, _p(ws), nws, _stream())
+        else:
+            _lib.call(fam.sym_fwd, _p(x), _p(wpk), _p(bias), _p(y), n, h, w, cin, cout, ks, act, slope, _p(ws), nws, _stream())
+    return y
+
+
+def _conv_dgrad(fam, dy, wpk_d, in_shape, ks, flop_div=1):
+    _chk(fam.dgrad, dy, wpk_d)
+    n, h, w, cin = in_shape
+    cout = dy.shape[3]
+    ho, wo = fam.out(h, w, ks)
+    if tuple(dy.shape) != (n, ho, wo, cout) or tuple(wpk_d.shape) != (cin, ks * ks, cout):
+        raise ValueError(f'{fam.dgrad}: inconsistent shapes')
+    dx = torch.empty((n, h, w, cin), device=dy.device, dtype=torch.float32)
+    ws = _conv_ws(dy.device, getattr(_lib.load(), fam.ws_bytes)(n, h, w, cin, cout, ks, 1))
+    with _timed(f'{fam.name}{ks}_dgrad', 2.0 * dy.numel() * ks * ks * cin / flop_div, detail=True):
+        _lib.call(fam.sym_dgrad, _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, ks, _p(ws), C.c_int64(0 if ws is None else ws.numel()), _stream())
+    return dx
+
+
+def _conv_wgrad(fam, x, dy, cin_real, ks):
+    _chk(fam.wgrad, x, dy)
+    n, h, w, cin = x.shape
+    cout = dy.shape[3]
+    ho, wo = fam.out(h, w, ks)
+    if tuple(dy.shape) != (n, ho, wo, cout):
+        raise ValueError(f'{fam.wgrad}: inconsistent shapes')
+    ws = _wgrad_workspace(x.device, getattr(_lib.load(), fam.wgrad_ws_bytes)(n, h, w, cin, cout, ks))
+    dw = torch.empty((cout, cin_real, ks, ks), device=x.device, dtype=torch.float32)
+    with _timed(f'{fam.name}{ks}_wgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
+        _lib.call(fam.sym_wgrad, _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, ks, _p(ws), C.c_int64(ws.numel()), _stream())
+    return dw
 
 
 def disc_vconv_pack_weight(w, cin, dgrad):
     """w [Cout,CinR,ks,ks] (ks 3 or 4) -> [Cout,ks*ks,cin] (dgrad False) or [cin,ks*ks,Cout] (dgrad True), channels CinR..cin-1 zero"""
-    _chk('disc_vconv_pack_weight', w)
-    cout, cinr, ks = w.shape[0], w.shape[1], w.shape[2]
-    if ks not in (3, 4) or w.shape[3] != ks or cinr > cin:
-        raise ValueError(f'disc_vconv_pack_weight: weight {tuple(w.shape)} for {cin} input channels')
-    out = torch.empty((cin, ks * ks, cout) if dgrad else (cout, ks * ks, cin), device=w.device, dtype=torch.float32)
-    _lib.call('mrefsr_disc_vconv_pack_weight_f32', _p(w), _p(out), cout, cinr, cin, ks, 1 if dgrad else 0, _stream())
-    return out
-
-
-def _vconv_ws(device, nbytes):
-    return _wgrad_workspace(device, nbytes) if nbytes > 0 else None
+    return _conv_pack_weight(_VCONV, w, cin, dgrad)
 
 
 def disc_vconv(x, wpk, bias, ks, act_slope=None):
     """x [N,H,W,Cin] -> [N,Ho,Wo,Cout]: ks 3 (stride 1) or 4 (stride 2), pad 1, + bias, then LeakyReLU(act_slope) unless it is None
     (wpk from disc_vconv_pack_weight(dgrad=False))"""
-    _chk('disc_vconv', x, wpk, bias)
-    n, h, w, cin = x.shape
-    cout = wpk.shape[0]
-    if tuple(wpk.shape) != (cout, ks * ks, cin):
-        raise ValueError('disc_vconv: packed weight does not match the input channels')
-    y = torch.empty((n, _vout(h, ks), _vout(w, ks), cout), device=x.device, dtype=torch.float32)
-    need = _lib.load().mrefsr_disc_vconv_workspace_bytes(n, h, w, cin, cout, ks, 0)
-    ws = _vconv_ws(x.device, need)
-    with _timed(f'disc_vconv{ks}', 2.0 * y.numel() * ks * ks * cin, detail=True):
-        _lib.call('mrefsr_disc_vconv_f32', _p(x), _p(wpk), _p(bias), _p(y), n, h, w, cin, cout, ks, 0 if act_slope is None else 1,
-                  C.c_float(0.0 if act_slope is None else act_slope), _p(ws), C.c_int64(0 if ws is None else ws.numel()), _stream())
-    return y
+    return _conv_fwd(_VCONV, x, wpk, bias, ks, act_slope)
 
 
 def disc_vconv_dgrad(dy, wpk_d, in_shape, ks):
     """input gradient: dy [N,Ho,Wo,Cout] -> dx [N,H,W,Cin] (in_shape = x's shape; wpk_d from disc_vconv_pack_weight(dgrad=True))"""
-    _chk('disc_vconv_dgrad', dy, wpk_d)
-    n, h, w, cin = in_shape
-    cout = dy.shape[3]
-    if tuple(dy.shape) != (n, _vout(h, ks), _vout(w, ks), cout) or tuple(wpk_d.shape) != (cin, ks * ks, cout):
-        raise ValueError('disc_vconv_dgrad: inconsistent shapes')
-    dx = torch.empty((n, h, w, cin), device=dy.device, dtype=torch.float32)
-    need = _lib.load().mrefsr_disc_vconv_workspace_bytes(n, h, w, cin, cout, ks, 1)
-    ws = _vconv_ws(dy.device, need)
-    with _timed(f'disc_vconv{ks}_dgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
-        _lib.call('mrefsr_disc_vconv_dgrad_f32', _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, ks, _p(ws), C.c_int64(0 if ws is None else ws.numel()),
-                  _stream())
-    return dx
+    return _conv_dgrad(_VCONV, dy, wpk_d, in_shape, ks)
 
 
 def disc_vconv_wgrad(x, dy, cin_real, ks):
     """weight gradient [Cout,cin_real,ks,ks] = sum over the output pixels of x (x) dy"""
-    _chk('disc_vconv_wgrad', x, dy)
-    n, h, w, cin = x.shape
-    cout = dy.shape[3]
-    if tuple(dy.shape) != (n, _vout(h, ks), _vout(w, ks), cout):
-        raise ValueError('disc_vconv_wgrad: inconsistent shapes')
-    need = _lib.load().mrefsr_disc_vconv_wgrad_workspace_bytes(n, h, w, cin, cout, ks)
-    ws = _wgrad_workspace(x.device, need)
-    dw = torch.empty((cout, cin_real, ks, ks), device=x.device, dtype=torch.float32)
-    with _timed(f'disc_vconv{ks}_wgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
-        _lib.call('mrefsr_disc_vconv_wgrad_f32', _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, ks, _p(ws), C.c_int64(ws.numel()), _stream())
-    return dw
+    return _conv_wgrad(_VCONV, x, dy, cin_real, ks)
 
 
 def disc_lrelu_mask(g, y, slope=0.2):
@@ -2058,10 +2099,6 @@ def disc_conv9_wgrad(x, gy):
 
 
 # ------------------------------------------------------------------ StyleGAN2Discriminator (csrc/disc_sg2.hip)
-def _sg2_out(n, ks):
-    return (n - 3) // 2 + 1 if ks == 3 else n
-
-
 def disc_sg2_fir_out(n, taps, pad, down):
     return (n + pad[0] + pad[1] - len(taps)) // down + 1
 
@@ -2085,61 +2122,20 @@ def disc_sg2_fir(x, taps, pad, down=1, adjoint_shape=None):
 
 def disc_sg2_pack_weight(w, cin, dgrad):
     """w [Cout,CinR,ks,ks] (ks 1 or 3) -> [Cout,ks*ks,cin] (dgrad False) or [cin,ks*ks,Cout] (dgrad True), channels CinR..cin-1 zero"""
-    _chk('disc_sg2_pack_weight', w)
-    cout, cinr, ks = w.shape[0], w.shape[1], w.shape[2]
-    if ks not in (1, 3) or w.shape[3] != ks or cinr > cin:
-        raise ValueError(f'disc_sg2_pack_weight: weight {tuple(w.shape)} for {cin} input channels')
-    out = torch.empty((cin, ks * ks, cout) if dgrad else (cout, ks * ks, cin), device=w.device, dtype=torch.float32)
-    _lib.call('mrefsr_disc_sg2_pack_weight_f32', _p(w), _p(out), cout, cinr, cin, ks, 1 if dgrad else 0, _stream())
-    return out
+    return _conv_pack_weight(_SG2CONV, w, cin, dgrad)
 
 
 def disc_sg2_conv(x, wpk, bias, ks, act_slope=None, res=None):
     """x [N,H,W,Cin] -> [N,Ho,Wo,Cout]: pad 0, ks 3 (stride 2) or 1 (stride 1); lrelu(conv + bias, act_slope) (no activation when
     act_slope is None) + res (wpk from disc_sg2_pack_weight(dgrad=False))"""
-    _chk('disc_sg2_conv', x, wpk, bias, res)
-    n, h, w, cin = x.shape
-    cout = wpk.shape[0]
-    if tuple(wpk.shape) != (cout, ks * ks, cin):
-        raise ValueError('disc_sg2_conv: packed weight does not match the input channels')
-    y = torch.empty((n, _sg2_out(h, ks), _sg2_out(w, ks), cout), device=x.device, dtype=torch.float32)
-    if res is not None and res.shape != y.shape:
-        raise ValueError(f'disc_sg2_conv: residual {tuple(res.shape)} for an output {tuple(y.shape)}')
-    need = _lib.load().mrefsr_disc_sg2_conv_workspace_bytes(n, h, w, cin, cout, ks, 0)
-    ws = _vconv_ws(x.device, need)
-    with _timed(f'disc_sg2_conv{ks}', 2.0 * y.numel() * ks * ks * cin, detail=True):
-        _lib.call('mrefsr_disc_sg2_conv_f32', _p(x), _p(wpk), _p(bias), _p(res), _p(y), n, h, w, cin, cout, ks, 0 if act_slope is None else 1,
-                  C.c_float(0.0 if act_slope is None else act_slope), _p(ws), C.c_int64(0 if ws is None else ws.numel()), _stream())
-    return y
+    return _conv_fwd(_SG2CONV, x, wpk, bias, ks, act_slope, res)
 
 
 def disc_sg2_conv_dgrad(dy, wpk_d, in_shape, ks):
     """input gradient: dy [N,Ho,Wo,Cout] -> dx [N,H,W,Cin] (in_shape = x's shape; wpk_d from disc_sg2_pack_weight(dgrad=True))"""
-    _chk('disc_sg2_conv_dgrad', dy, wpk_d)
-    n, h, w, cin = in_shape
-    cout = dy.shape[3]
-    if tuple(dy.shape) != (n, _sg2_out(h, ks), _sg2_out(w, ks), cout) or tuple(wpk_d.shape) != (cin, ks * ks, cout):
-        raise ValueError('disc_sg2_conv_dgrad: inconsistent shapes')
-    dx = torch.empty((n, h, w, cin), device=dy.device, dtype=torch.float32)
-    need = _lib.load().mrefsr_disc_sg2_conv_workspace_bytes(n, h, w, cin, cout, ks, 1)
-    ws = _vconv_ws(dy.device, need)
-    with _timed(f'disc_sg2_conv{ks}_dgrad', 2.0 * dy.numel() * ks * ks * cin / (4 if ks == 3 else 1), detail=True):
-        _lib.call('mrefsr_disc_sg2_conv_dgrad_f32', _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, ks, _p(ws),
-                  C.c_int64(0 if ws is None else ws.numel()), _stream())
-    return dx
+    return _conv_dgrad(_SG2CONV, dy, wpk_d, in_shape, ks, flop_div=4 if ks == 3 else 1)
 
 
 def disc_sg2_conv_wgrad(x, dy, cin_real, ks):
     """weight gradient [Cout,cin_real,ks,ks] = sum over the output pixels of x (x) dy"""
-    _chk('disc_sg2_conv_wgrad', x, dy)
-    n, h, w, cin = x.shape
-    cout = dy.shape[3]
-    if tuple(dy.shape) != (n, _sg2_out(h, ks), _sg2_out(w, ks), cout):
-        raise ValueError('disc_sg2_conv_wgrad: inconsistent shapes')
-    need = _lib.load().mrefsr_disc_sg2_conv_wgrad_workspace_bytes(n, h, w, cin, cout, ks)
-    ws = _wgrad_workspace(x.device, need)
-    dw = torch.empty((cout, cin_real, ks, ks), device=x.device, dtype=torch.float32)
-    with _timed(f'disc_sg2_conv{ks}_wgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
-        _lib.call('mrefsr_disc_sg2_conv_wgrad_f32', _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, ks, _p(ws), C.c_int64(ws.numel()),
-                  _stream())
-    return dw
+    return _conv_wgrad(_SG2CONV, x, dy, cin_real, ks)

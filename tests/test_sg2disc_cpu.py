@@ -160,8 +160,8 @@ def test_disc_sg2_kernels_compile_without_scratch(tmp_path):
     text = open(asm).read()
     kernels = re.findall(r'^(_ZN12_GLOBAL__N_1\d+(\w+?_kernel)\w*):', text, flags=re.M)
     names = sorted({k for _, k in kernels})
-    assert names == sorted(['sg2_fir_kernel', 'sconv_pack_weight_kernel', 'sconv_gemm_kernel', 'sconv_finish_kernel',
-                            'sconv_wgrad_finish_kernel']), names
+    assert names == sorted(['sg2_fir_kernel', 'dconv_pack_weight_kernel', 'dconv_gemm_kernel', 'dconv_finish_kernel',
+                            'dconv_wgrad_finish_kernel']), names
     assert len(kernels) == 2 + 1 + 6 + 2
     sizes = re.findall(r'; ScratchSize: (\d+)', text)
     assert len(sizes) == len(kernels) and set(sizes) == {'0'}, sizes

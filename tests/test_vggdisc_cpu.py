@@ -96,12 +96,12 @@ def test_disc_vgg_kernels_compile_without_scratch(tmp_path):
     text = open(asm).read()
     kernels = re.findall(r'^(_ZN12_GLOBAL__N_1\d+(\w+?_kernel)\w*):', text, flags=re.M)
     names = sorted({k for _, k in kernels})
-    for want in ('vconv_pack_weight_kernel', 'vconv_gemm_kernel', 'vconv_finish_kernel', 'vconv_wgrad_finish_kernel', 'lrelu_mask_kernel',
+    for want in ('dconv_pack_weight_kernel', 'dconv_gemm_kernel', 'dconv_finish_kernel', 'dconv_wgrad_finish_kernel', 'lrelu_mask_kernel',
                  'lin_rows_kernel', 'lin_out_kernel', 'lin_gf_kernel', 'lin_params_kernel'):
         assert want in names, (want, names)
-    assert sum(name == 'vconv_gemm_kernel' for _, name in kernels) == 6   # KS 3 and 4 x forward, input gradient, weight gradient
+    assert sum(name == 'dconv_gemm_kernel' for _, name in kernels) == 6   # KS 3 and 4 x forward, input gradient, weight gradient
     sizes = re.findall(r'; ScratchSize: (\d+)', text)
     assert len(sizes) == len(kernels) and set(sizes) == {'0'}, sizes
     for label, name in kernels:
         body = text.split(label + ':', 1)[1].split('s_endpgm', 1)[0]
-        assert ('v_mfma_f32_16x16x4_f32' in body) == (name == 'vconv_gemm_kernel'), label
+        assert ('v_mfma_f32_16x16x4_f32' in body) == (name == 'dconv_gemm_kernel'), label
