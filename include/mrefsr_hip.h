@@ -288,6 +288,23 @@ int mrefsr_mrattn_bwd_f32(const float *q, const float *emb, const float *ass, co
  * operation order as mrefsr_mrattn_fwd_nhwc_f32, fp32 math, the result rounded to bf16 (round-to-nearest-even). */
 int mrefsr_mrattn_fwd_nhwc_bf16(const void *q, const void *emb, const void *ass, void *out, int N, int T,
                                 int c, int HW, mrefsr_stream_t stream);
+/* Per-sample reference masks (mixed reference counts in one batch): the kernels above with
+ *   valid_bits [N]       one 32-bit word per sample, bit t set = reference t of the sample is present (bits >= T are ignored)
+ * An absent t is left out of the maximum, the denominator and the weighted sum; its emb / ass values are never read (inf or NaN
+ * there reaches no output); `prob` is written as exact 0 for it; mrefsr_mrattn_bwd_masked_f32 writes its g_emb / g_ass as exact
+ * zeros and sums g_q over the present t only.  The present terms run in ascending t with the operations of the unmasked kernels,
+ * so a sample's result is that of the unmasked kernel on its compacted references.  A word with no bit below T: out = 0, prob = 0
+ * and all three gradients 0 for that sample.  mrefsr_mrattn_fwd_nhwc_masked_f32 takes q_scale as
+ * mrefsr_mrattn_fwd_nhwc_scaled_f32 does (1 = none). */
+int mrefsr_mrattn_fwd_masked_f32(const float *q, const float *emb, const float *ass, const uint32_t *valid_bits, float *out,
+                                 float *prob, int N, int T, int c, int c2, int HW, int t_major, mrefsr_stream_t stream);
+int mrefsr_mrattn_bwd_masked_f32(const float *q, const float *emb, const float *ass, const float *prob, const float *g_out,
+                                 const uint32_t *valid_bits, float *g_q, float *g_emb, float *g_ass, int N, int T, int c, int c2,
+                                 int HW, int t_major, mrefsr_stream_t stream);
+int mrefsr_mrattn_fwd_nhwc_masked_f32(const float *q, const float *emb, const float *ass, const uint32_t *valid_bits, float *out,
+                                      int N, int T, int c, int HW, float q_scale, mrefsr_stream_t stream);
+int mrefsr_mrattn_fwd_nhwc_masked_bf16(const void *q, const void *emb, const void *ass, const uint32_t *valid_bits, void *out, int N,
+                                       int T, int c, int HW, mrefsr_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------
@@ -526,6 +543,12 @@ int mrefsr_conv_wgrad3x3_f32(const float *x, int ld_x, int Cin, const float *g, 
  * -> g_q [N][HW][c], g_emb [T*N][HW][c], g_ass [T*N][HW][2c]; the softmax is recomputed, nothing is saved by the forward. */
 int mrefsr_mrattn_bwd_nhwc_f32(const float *q, const float *emb, const float *ass, const float *g_out, float *g_q, float *g_emb,
                                float *g_ass, int N, int T, int c, int HW, mrefsr_stream_t stream);
+/* the same under per-sample reference masks (valid_bits [N] as mrefsr_mrattn_fwd_nhwc_masked_f32): the softmax is recomputed over
+ * the present references only, g_emb / g_ass of an absent reference are written as exact zeros without reading its emb / ass,
+ * g_q sums the present ones; a word with no bit below T gives zeros in all three. */
+int mrefsr_mrattn_bwd_nhwc_masked_f32(const float *q, const float *emb, const float *ass, const float *g_out,
+                                      const uint32_t *valid_bits, float *g_q, float *g_emb, float *g_ass, int N, int T, int c, int HW,
+                                      mrefsr_stream_t stream);
 /* gradient of refs * sigmoid(mul) * 2 + add (ref_mrapa_restoration_arch.py:343-345) w.r.t. refs and mul (d/d add = g);
  * `mul` is the value BEFORE mrefsr_attn_modulate_f32 overwrote it. */
 int mrefsr_attn_modulate_bwd_f32(const float *g, const float *refs, const float *mul, float *g_refs, float *g_mul, int64_t n,

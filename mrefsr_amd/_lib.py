@@ -84,6 +84,10 @@ SIGNATURES = {
     'mrefsr_mrattn_fwd_nhwc_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'mrefsr_mrattn_fwd_nhwc_scaled_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp]),
     'mrefsr_mrattn_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'mrefsr_mrattn_fwd_masked_f32': (_i, [_vp] * 6 + [_i] * 6 + [_vp]),
+    'mrefsr_mrattn_bwd_masked_f32': (_i, [_vp] * 9 + [_i] * 6 + [_vp]),
+    'mrefsr_mrattn_fwd_nhwc_masked_f32': (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _vp]),
+    'mrefsr_mrattn_fwd_nhwc_masked_bf16': (_i, [_vp] * 5 + [_i, _i, _i, _i, _vp]),
     'mrefsr_fused_bias_act': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, _i, _vp]),
     'mrefsr_bias_act_res_f32': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i, _i64, _f, _vp]),
     'mrefsr_tail_bilinear_add_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
@@ -105,6 +109,7 @@ SIGNATURES = {
     'mrefsr_conv_wgrad3x3_batch_workspace_bytes': (_i64, [_i, _i, _i, _i, _i, _i]),
     'mrefsr_conv_wgrad3x3_batch_f32': (_i, [_i, _vp, _i, _i, _vp, _i, _i, _vp, _i64, _i64, _i, _vp, _i, _i, _i, _vp, _i64, _vp, _vp]),
     'mrefsr_mrattn_bwd_nhwc_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'mrefsr_mrattn_bwd_nhwc_masked_f32': (_i, [_vp] * 8 + [_i, _i, _i, _i, _vp]),
     'mrefsr_attn_modulate_bwd_f32': (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     'mrefsr_reflect_pad_nhwc_f32': (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
     'mrefsr_reflect_pad_bwd_nhwc_f32': (_i, [_vp, _vp] + [_i] * 6 + [_vp]),

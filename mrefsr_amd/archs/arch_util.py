@@ -29,6 +29,40 @@ def conv_act(conv, x, slope=1.0, residual=None):
     return hip.bias_act_res_(y, conv.bias, slope, residual)
 
 
+def ref_valid_words(ref_valid, b=None, k=None):
+    """Host check of a per-sample reference mask: ``ref_valid`` [B, K] (bool or uint8; nonzero = reference k of sample b is
+    present) -> int32 [B] host tensor with bit k of word b set for a present reference, or None when every reference is present.
+    Refuses (ValueError) a wrong shape, K > 16 and a sample without a present reference.  A mask on the device is copied back
+    once (B * K bytes)."""
+    m = torch.as_tensor(ref_valid)
+    if m.dim() != 2 or (b is not None and m.shape[0] != b) or (k is not None and m.shape[1] != k):
+        raise ValueError(f'ref_valid: expected shape [{"B" if b is None else b}, {"K" if k is None else k}], got {list(m.shape)}')
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'ref_valid: expected a bool or uint8 tensor, got {m.dtype}')
+    if m.shape[1] > 16:
+        raise ValueError(f'ref_valid: K={m.shape[1]} references > 16')
+    m = (m.detach().cpu() != 0)
+    empty = (~m.any(dim=1)).nonzero().flatten().tolist()
+    if empty or m.shape[0] == 0:
+        raise ValueError(f'ref_valid: sample(s) {empty} have no valid reference')
+    if bool(m.all()):
+        return None
+    return (m.to(torch.int32) << torch.arange(m.shape[1], dtype=torch.int32)).sum(dim=1).to(torch.int32)
+
+
+def ref_valid_bits(ref_valid, b, k, device):
+    """what the networks take as ``ref_valid``: None, a [B, K] mask (checked and packed here) or the already packed int32 [B] words
+    -> the words on ``device``, or None when every reference is present"""
+    if ref_valid is None:
+        return None
+    if ref_valid.dtype == torch.int32 and ref_valid.dim() == 1:
+        if ref_valid.shape[0] != b:
+            raise ValueError(f'ref_valid: {ref_valid.shape[0]} mask words for a batch of {b}')
+        return ref_valid.to(device)
+    words = ref_valid_words(ref_valid, b, k)
+    return None if words is None else words.to(device)
+
+
 def run_conv_relu_stack(layers, x, taps=None):
     """nn.Sequential of Conv2d / ReLU / MaxPool2d (the VGG stacks) with every conv+ReLU pair fused
     through conv_act.  ``taps``: names whose output is returned in a dict (else the final tensor)."""

@@ -18,7 +18,8 @@ same graph is recorded over [N,H,W,C] tensors with one autograd node per FUSED l
   _Dcn           fused gather + MFMA deformable convolution on channels-last features (mrefsr_dcn_fwd_f32) with its LeakyReLU
                  -- backward: two fused launches (dcn_bwd_data: columns gradient with the offset / mask / input gradients as its
                  epilogue; dcn_bwd_weight: columns re-gathered inside the GEMM), no C*9*H*W buffer
-  _Attention     mrefsr_mrattn_fwd_nhwc_f32 / mrefsr_mrattn_bwd_nhwc_f32 (softmax recomputed, nothing extra saved)
+  _Attention     mrefsr_mrattn_fwd_nhwc_f32 / mrefsr_mrattn_bwd_nhwc_f32 (softmax recomputed, nothing extra saved); with a
+                 per-sample reference mask the _masked_ forms of both
   _Modulate      refs * sigmoid(mul) * 2 + add, one pass each way
   _Pad, _Crop    MRAPAFusion's reflect pad to a multiple of 4 and the crop back (csrc/pad.hip), one pass each way
   _VggLoss       the VGG of PerceptualLoss (losses/): output and GT as one batch forward, input gradients of the output image
@@ -533,16 +534,21 @@ class _Attention(Function):
     """softmax_t(<q, emb_t>) . ass_t per pixel on channels-last tensors (t-major references)   ref :321-335"""
 
     @staticmethod
-    def forward(ctx, q, emb, ass, t):
-        ctx.t = t
+    def forward(ctx, q, emb, ass, t, valid_bits=None):
+        """valid_bits ([n] int32, bit t = reference t of the sample is present) or None: all present, the unmasked kernels"""
+        ctx.t, ctx.valid_bits = t, valid_bits
         ctx.save_for_backward(q, emb, ass)
+        if valid_bits is not None:
+            return hip.mrattn_fwd_nhwc_masked(q, emb, ass, t, valid_bits)
         return hip.mrattn_fwd_nhwc(q, emb, ass, t)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g):
         q, emb, ass = ctx.saved_tensors
-        return hip.mrattn_bwd_nhwc(q, emb, ass, g.contiguous(), ctx.t) + (None,)
+        if ctx.valid_bits is not None:
+            return hip.mrattn_bwd_nhwc_masked(q, emb, ass, g.contiguous(), ctx.t, ctx.valid_bits) + (None, None)
+        return hip.mrattn_bwd_nhwc(q, emb, ass, g.contiguous(), ctx.t) + (None, None)
 
 
 class _Modulate(Function):

@@ -33,7 +33,7 @@ from .. import hip
 from ..ops.dcn import modulated_deform_conv
 from ..utils.registry import ARCH_REGISTRY
 from . import nhwc, nhwc_train
-from .arch_util import ResidualBlockNoBN, conv_act, default_init_weights, make_layer, srntt_init_weights
+from .arch_util import ResidualBlockNoBN, conv_act, default_init_weights, make_layer, ref_valid_bits, srntt_init_weights
 
 
 class _DynAggPrep(Function):
@@ -58,11 +58,15 @@ class _MultiRefAttention(Function):
     """softmax_t(<q, emb_t>) . ass_t per pixel   ref :321-335"""
 
     @staticmethod
-    def forward(ctx, q, emb, ass, t, t_major):
+    def forward(ctx, q, emb, ass, t, t_major, valid_bits=None):
+        """valid_bits ([n] int32, bit t = reference t of the sample is present) or None: all present, the unmasked kernels"""
         q, emb, ass = q.contiguous(), emb.contiguous(), ass.contiguous()
         need = q.requires_grad or emb.requires_grad or ass.requires_grad
-        out, prob = hip.mrattn_fwd(q, emb, ass, t, want_prob=need, t_major=t_major)
-        ctx.t, ctx.t_major = t, t_major
+        if valid_bits is not None:
+            out, prob = hip.mrattn_fwd_masked(q, emb, ass, t, valid_bits, want_prob=need, t_major=t_major)
+        else:
+            out, prob = hip.mrattn_fwd(q, emb, ass, t, want_prob=need, t_major=t_major)
+        ctx.t, ctx.t_major, ctx.valid_bits = t, t_major, valid_bits
         if need:
             ctx.save_for_backward(q, emb, ass, prob)
         return out
@@ -71,8 +75,11 @@ class _MultiRefAttention(Function):
     @once_differentiable
     def backward(ctx, g_out):
         q, emb, ass, prob = ctx.saved_tensors
-        g_q, g_emb, g_ass = hip.mrattn_bwd(q, emb, ass, prob, g_out.contiguous(), ctx.t, ctx.t_major)
-        return g_q, g_emb, g_ass, None, None
+        if ctx.valid_bits is not None:
+            g_q, g_emb, g_ass = hip.mrattn_bwd_masked(q, emb, ass, prob, g_out.contiguous(), ctx.t, ctx.valid_bits, ctx.t_major)
+        else:
+            g_q, g_emb, g_ass = hip.mrattn_bwd(q, emb, ass, prob, g_out.contiguous(), ctx.t, ctx.t_major)
+        return g_q, g_emb, g_ass, None, None, None
 
 
 class DynAgg(nn.Module):
@@ -212,25 +219,29 @@ class MRAPARestorationNet(nn.Module):
         for name in ('small_dyn_agg', 'medium_dyn_agg', 'large_dyn_agg'):
             getattr(self.dyn_agg_restore, name).init_offset()
 
-    def forward(self, x, pre_offset_list, img_ref_feat_list, k=None):
+    def forward(self, x, pre_offset_list, img_ref_feat_list, k=None, ref_valid=None):
         """x (B,3,h,w); pre_offset_list / img_ref_feat_list: K dicts as produced by
         CorrespondenceGenerationArch.forward -> (B,3,4h,4w)   (reference signature).
         With ``k`` given, the two arguments are single dicts of k-major stacked [K*B,...] tensors
-        (the batched path; goes through forward() so DistributedDataParallel hooks still run)."""
+        (the batched path; goes through forward() so DistributedDataParallel hooks still run).
+        ``ref_valid`` ([B,K] bool / uint8, or the packed words of arch_util.ref_valid_words): reference k of sample b takes
+        part in the fusion heads only where it is true -- sample b's output is that of the network run on it alone with its
+        valid references; None = all valid."""
         if k is not None:
-            return self.forward_stacked(x, pre_offset_list, img_ref_feat_list, k)
+            return self.forward_stacked(x, pre_offset_list, img_ref_feat_list, k, ref_valid)
         pre, feat, k = _stack_refs(pre_offset_list, img_ref_feat_list)
-        return self.forward_stacked(x, pre, feat, k)
+        return self.forward_stacked(x, pre, feat, k, ref_valid)
 
-    def forward_stacked(self, x, pre_offset, img_ref_feat, k):
+    def forward_stacked(self, x, pre_offset, img_ref_feat, k, ref_valid=None):
         """same with the K references already stacked k-major on the batch axis ([K*B,...])."""
+        ref_valid = ref_valid_bits(ref_valid, x.shape[0], k, x.device)   # (packed once; the heads pass the words to the kernels)
         if nhwc.BF16 and nhwc.active(x):
             x = x.bfloat16().float()
         if (nhwc.active(x) or (nhwc.train_active(x) and MRAPAFusion.pads_ok(x.shape[2], x.shape[3]))) and self.dyn_agg_restore.nhwc_ok(x):
             ce = self.content_extractor
             feat = nhwc.res_chain(ce.body, nhwc.conv(ce.conv_first, nhwc.image_to_nhwc4(x), slope=0.1))
             refs = {key: nhwc.to_nhwc(v if v.dtype == feat.dtype else v.to(feat.dtype)) for key, v in img_ref_feat.items()}
-            out = self.dyn_agg_restore.forward_nhwc(feat, pre_offset, refs, k)
+            out = self.dyn_agg_restore.forward_nhwc(feat, pre_offset, refs, k, ref_valid)
             if not nhwc.BF16 and out.dtype == torch.float32 and x.dtype == torch.float32 and not (out.requires_grad or x.requires_grad):
                 return hip.tail_bilinear_add(out, x, 4)   # F.interpolate + add + NCHW copy of :132-137 in one pass (torch's interpolation bits)
             base = F.interpolate(x, None, 4, 'bilinear', False)
@@ -239,7 +250,7 @@ class MRAPARestorationNet(nn.Module):
         # autograd / MIOpen path: NCHW storage (the frozen VGG taps arrive as channels-last views)
         img_ref_feat = {key: v.contiguous() for key, v in img_ref_feat.items()}
         content_feat = self.content_extractor(x)
-        return self.dyn_agg_restore.forward_stacked(content_feat, pre_offset, img_ref_feat, k) + base
+        return self.dyn_agg_restore.forward_stacked(content_feat, pre_offset, img_ref_feat, k, ref_valid) + base
 
 
 class DynamicAggregationRestoration(nn.Module):
@@ -306,12 +317,15 @@ class DynamicAggregationRestoration(nn.Module):
         off = nhwc.conv(conv2, off, slope=0.1)
         return dyn_agg.forward_nhwc(ref, off, pre_offset, act_slope=0.1)
 
-    def forward_nhwc(self, x, pre_offset, ref_feat, k):
-        """x [B,h,w,ngf]; ref_feat / pre_offset: k-major stacked, ref_feat as [K*B,H,W,C] -> [B,4h,4w,3]"""
+    def forward_nhwc(self, x, pre_offset, ref_feat, k, ref_valid=None):
+        """x [B,h,w,ngf]; ref_feat / pre_offset: k-major stacked, ref_feat as [K*B,H,W,C] -> [B,4h,4w,3]; ref_valid as
+        MRAPARestorationNet.forward (an absent reference still runs through the offset convolutions and the DCN: the stack is
+        not compacted)"""
+        ref_valid = ref_valid_bits(ref_valid, x.shape[0], k, x.device)
         for scale, key in (('small', 'relu3_1'), ('medium', 'relu2_1'), ('large', 'relu1_1')):
             swapped = self._swap_nhwc(x, ref_feat[key], pre_offset[key], getattr(self, f'{scale}_offset_conv1'),
                                       getattr(self, f'{scale}_offset_conv2'), getattr(self, f'{scale}_dyn_agg'))
-            h = getattr(self, f'head_{scale}').forward_nhwc(x, swapped, k)
+            h = getattr(self, f'head_{scale}').forward_nhwc(x, swapped, k, ref_valid)
             h = nhwc.res_chain(getattr(self, f'body_{scale}'), h)
             h = h + x if h.requires_grad else nhwc.rnd_(nhwc.add_(h, x))
             if scale == 'large':
@@ -325,24 +339,25 @@ class DynamicAggregationRestoration(nn.Module):
         it is fused into the convolution epilogue"""
         return tail[1](conv_act(tail[0], x, 0.1))
 
-    def forward(self, x, pre_offset_list, img_ref_feat_list):
+    def forward(self, x, pre_offset_list, img_ref_feat_list, ref_valid=None):
         pre, feat, k = _stack_refs(pre_offset_list, img_ref_feat_list)
-        return self.forward_stacked(x, pre, feat, k)
+        return self.forward_stacked(x, pre, feat, k, ref_valid)
 
-    def forward_stacked(self, x, pre_offset, img_ref_feat, k):
+    def forward_stacked(self, x, pre_offset, img_ref_feat, k, ref_valid=None):
+        ref_valid = ref_valid_bits(ref_valid, x.shape[0], k, x.device)
         swapped = self._swap(x, img_ref_feat['relu3_1'], pre_offset['relu3_1'], k, self.small_offset_conv1,
                              self.small_offset_conv2, self.small_dyn_agg)
-        h = self.head_small.forward_stacked(x, swapped, k)
+        h = self.head_small.forward_stacked(x, swapped, k, ref_valid)
         x = self._tail_up(self.tail_small, self.body_small(h) + x)
 
         swapped = self._swap(x, img_ref_feat['relu2_1'], pre_offset['relu2_1'], k, self.medium_offset_conv1,
                              self.medium_offset_conv2, self.medium_dyn_agg)
-        h = self.head_medium.forward_stacked(x, swapped, k)
+        h = self.head_medium.forward_stacked(x, swapped, k, ref_valid)
         x = self._tail_up(self.tail_medium, self.body_medium(h) + x)
 
         swapped = self._swap(x, img_ref_feat['relu1_1'], pre_offset['relu1_1'], k, self.large_offset_conv1,
                              self.large_offset_conv2, self.large_dyn_agg)
-        h = self.head_large.forward_stacked(x, swapped, k)
+        h = self.head_large.forward_stacked(x, swapped, k, ref_valid)
         h = self.body_large(h) + x
         return conv_act(self.tail_large[2], conv_act(self.tail_large[0], h, 0.1))
 
@@ -384,28 +399,31 @@ class MRAPAFusion(nn.Module):
             return feats
         return F.pad(feats, [0, pad_w, 0, pad_h], mode='reflect')
 
-    def forward(self, target, refs):
-        """target (n,nf,h,w); refs: list of t tensors (n,ref_nf,h,w)   (reference signature)"""
+    def forward(self, target, refs, ref_valid=None):
+        """target (n,nf,h,w); refs: list of t tensors (n,ref_nf,h,w)   (reference signature).  ref_valid ([n,t] bool / uint8 or
+        packed words, None = all): the softmax over t of :321-335 runs over sample n's valid references only; the absent ones
+        are not read by the attention core and receive exact zero gradients."""
         t = len(refs)
-        return self._fuse(target, torch.stack(refs, dim=1).flatten(0, 1), t, t_major=False)
+        return self._fuse(target, torch.stack(refs, dim=1).flatten(0, 1), t, t_major=False, ref_valid=ref_valid)
 
-    def forward_stacked(self, target, refs, t):
+    def forward_stacked(self, target, refs, t, ref_valid=None):
         """refs (t*n, ref_nf, h, w) stacked t-major (the batched path: no stack / permute copy)"""
-        return self._fuse(target, refs, t, t_major=True)
+        return self._fuse(target, refs, t, t_major=True, ref_valid=ref_valid)
 
-    def forward_nhwc(self, target, refs, t):
+    def forward_nhwc(self, target, refs, t, ref_valid=None):
         """channels-last form (inference and, under autograd, training): target [n,H,W,nf], refs [t*n,H,W,ref_nf] t-major ->
         [n,H,W,nf].  torch.cat of :339/:346 = two-source convolutions; H, W that are not multiples of 4 are reflect-padded
         and cropped back as in :306-311, :348 (CUFED5's 125 x 125 LR inputs need it at two scales) by the HIP kernels of
         csrc/pad.hip -- autograd nodes when a graph is recorded."""
         h_in, w_in = target.shape[1:3]
         ph, pw = self.pads(h_in, w_in)
+        vb = ref_valid_bits(ref_valid, target.shape[0], t, target.device)
         if ph or pw:
             if target.dtype != torch.float32:   # (bf16 storage: the kernels are fp32)
                 target = nhwc.to_nhwc(self.spatial_padding(nhwc.as_nchw(target)))
                 refs = nhwc.to_nhwc(self.spatial_padding(nhwc.as_nchw(refs)))
-                return self.forward_nhwc(target, refs, t)[:, :h_in, :w_in, :].contiguous()
-            out = self.forward_nhwc(nhwc.reflect_pad(target, ph, pw), nhwc.reflect_pad(refs, ph, pw), t)
+                return self.forward_nhwc(target, refs, t, vb)[:, :h_in, :w_in, :].contiguous()
+            out = self.forward_nhwc(nhwc.reflect_pad(target, ph, pw), nhwc.reflect_pad(refs, ph, pw), t, vb)
             return nhwc.crop(out, h_in, w_in)
         q = nhwc.conv(self.conv_emb1[0], target, prelu=self.conv_emb1[1], amax=False)   # (q, emb, ass: attention operands)
         train = q.requires_grad   # a graph is being recorded (archs/nhwc_train.py): no in-place edits of saved tensors
@@ -414,7 +432,12 @@ class MRAPAFusion(nn.Module):
             q = q * self.scale if train else nhwc.rnd_(q.mul_(self.scale))
         emb = nhwc.conv(self.conv_emb2[0], refs, prelu=self.conv_emb2[1], amax=False)
         ass = nhwc.conv(self.conv_ass, refs, amax=False)
-        if fold:
+        if vb is not None:   # per-sample reference masks: the masked forms of the same three kernels
+            if fold:
+                r = hip.mrattn_fwd_nhwc_masked(q, emb, ass, t, vb, q_scale=float(self.scale))
+            else:
+                r = nhwc_train.attention(q, emb, ass, t, vb) if train else nhwc.rnd_(hip.mrattn_fwd_nhwc_masked(q, emb, ass, t, vb))
+        elif fold:
             r = hip.mrattn_fwd_nhwc(q, emb, ass, t, q_scale=float(self.scale))
         else:
             r = nhwc_train.attention(q, emb, ass, t) if train else nhwc.rnd_(hip.mrattn_fwd_nhwc(q, emb, ass, t))
@@ -426,14 +449,15 @@ class MRAPAFusion(nn.Module):
         r = nhwc_train.modulate(r, attn_mul, attn_add) if train else nhwc.rnd_(hip.attn_modulate_(r, attn_mul, attn_add))
         return nhwc.conv(self.feat_fusion, target, x2=r, slope=0.1)
 
-    def _fuse(self, target, refs, t, t_major):
+    def _fuse(self, target, refs, t, t_major, ref_valid=None):
         h_input, w_input = target.shape[-2:]
+        vb = ref_valid_bits(ref_valid, target.shape[0], t, target.device)
         target = self.spatial_padding(target)
         refs = self.spatial_padding(refs)
         q = self.conv_emb1(target) * self.scale
         emb = self.conv_emb2(refs)
         ass = conv_act(self.conv_ass, refs)
-        refs = _MultiRefAttention.apply(q, emb, ass, t, t_major)
+        refs = _MultiRefAttention.apply(q, emb, ass, t, t_major) if vb is None else _MultiRefAttention.apply(q, emb, ass, t, t_major, vb)
         # spatial attention
         attn = conv_act(self.spatial_attn, torch.cat([target, refs], dim=1), 0.1)
         attn_mul = conv_act(self.spatial_attn_mul2, conv_act(self.spatial_attn_mul1, attn, 0.1))

@@ -10,13 +10,22 @@ namespace {
 
 constexpr int MAX_T = 16;
 
+// MASKED (per-sample reference masks): valid_bits[n] bit t set = reference t of sample n is present.  An absent t is left out of
+// the maximum, the denominator and the sums, its emb / ass values are never loaded (inf or NaN there reaches nothing), its prob and
+// its gradients are written as exact zeros; the present terms run in ascending t with the operations of the unmasked form.  A word
+// with no bit below T gives out = 0 and zero gradients.  MASKED = false is the unmasked kernel: every `on()` folds to true.
+template <bool MASKED> __device__ __forceinline__ bool on(unsigned int bits, int t) { return !MASKED || ((bits >> t) & 1u); }
+
+template <bool MASKED>
 __global__ __launch_bounds__(256) void mrattn_fwd_kernel(const float *__restrict__ q, const float *__restrict__ emb,
                                                          const float *__restrict__ ass, float *__restrict__ out,
-                                                         float *__restrict__ prob, int N, int T, int c, int c2, int HW, int t_major)
+                                                         float *__restrict__ prob, int N, int T, int c, int c2, int HW, int t_major,
+                                                         const unsigned int *__restrict__ valid_bits)
 {
     const long total = (long)N * HW;
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int n = (int)(e / HW), p = (int)(e - (long)n * HW);
+        const unsigned int vb = MASKED ? valid_bits[n] : 0u;
         float s[MAX_T];
 #pragma unroll
         for (int t = 0; t < MAX_T; ++t) s[t] = 0.f;
@@ -30,21 +39,21 @@ __global__ __launch_bounds__(256) void mrattn_fwd_kernel(const float *__restrict
             const float qv = qp[(size_t)k * HW];
 #pragma unroll
             for (int t = 0; t < MAX_T; ++t)
-                if (t < T) s[t] = fmaf(qv, ep[t * est + (size_t)k * HW], s[t]);
+                if (t < T && on<MASKED>(vb, t)) s[t] = fmaf(qv, ep[t * est + (size_t)k * HW], s[t]);
         }
-        float mx = s[0];
+        float mx = MASKED ? -3.4e38f : s[0];
 #pragma unroll
-        for (int t = 1; t < MAX_T; ++t)
-            if (t < T) mx = fmaxf(mx, s[t]);
+        for (int t = MASKED ? 0 : 1; t < MAX_T; ++t)
+            if (t < T && on<MASKED>(vb, t)) mx = fmaxf(mx, s[t]);
         float den = 0.f;
 #pragma unroll
         for (int t = 0; t < MAX_T; ++t)
-            if (t < T) { s[t] = expf(s[t] - mx); den += s[t]; }
-        const float rden = 1.0f / den;
+            if (t < T && on<MASKED>(vb, t)) { s[t] = expf(s[t] - mx); den += s[t]; }
+        const float rden = (!MASKED || den > 0.f) ? 1.0f / den : 0.f;   // (no present reference: every weight 0)
 #pragma unroll
         for (int t = 0; t < MAX_T; ++t)
             if (t < T) {
-                s[t] *= rden;
+                s[t] = on<MASKED>(vb, t) ? s[t] * rden : 0.f;
                 if (prob) prob[((size_t)n * T + t) * HW + p] = s[t];
             }
         const float *ap = ass + i0 * c2 * HW + p;
@@ -54,26 +63,29 @@ __global__ __launch_bounds__(256) void mrattn_fwd_kernel(const float *__restrict
             float a = 0.f;
 #pragma unroll
             for (int t = 0; t < MAX_T; ++t)
-                if (t < T) a = fmaf(s[t], ap[t * ast + (size_t)k * HW], a);
+                if (t < T && on<MASKED>(vb, t)) a = fmaf(s[t], ap[t * ast + (size_t)k * HW], a);
             op[(size_t)k * HW] = a;
         }
     }
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(256) void mrattn_bwd_kernel(const float *__restrict__ q, const float *__restrict__ emb,
                                                          const float *__restrict__ ass, const float *__restrict__ prob,
                                                          const float *__restrict__ g_out, float *__restrict__ g_q,
                                                          float *__restrict__ g_emb, float *__restrict__ g_ass, int N,
-                                                         int T, int c, int c2, int HW, int t_major)
+                                                         int T, int c, int c2, int HW, int t_major,
+                                                         const unsigned int *__restrict__ valid_bits)
 {
     const long total = (long)N * HW;
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int n = (int)(e / HW), p = (int)(e - (long)n * HW);
         const size_t i0 = t_major ? (size_t)n : (size_t)n * T, is = t_major ? (size_t)N : 1;
+        const unsigned int vb = MASKED ? valid_bits[n] : 0u;
         float a[MAX_T], da[MAX_T];
 #pragma unroll
         for (int t = 0; t < MAX_T; ++t) {
-            a[t] = (t < T) ? prob[((size_t)n * T + t) * HW + p] : 0.f;
+            a[t] = (t < T && on<MASKED>(vb, t)) ? prob[((size_t)n * T + t) * HW + p] : 0.f;
             da[t] = 0.f;
         }
         const float *ap = ass + i0 * c2 * HW + p;
@@ -86,16 +98,20 @@ __global__ __launch_bounds__(256) void mrattn_bwd_kernel(const float *__restrict
             for (int t = 0; t < MAX_T; ++t)
                 if (t < T) {
                     const size_t o = t * ast + (size_t)k * HW;
-                    da[t] = fmaf(g, ap[o], da[t]);
-                    gap[o] = g * a[t];
+                    if (on<MASKED>(vb, t)) {
+                        da[t] = fmaf(g, ap[o], da[t]);
+                        gap[o] = g * a[t];
+                    } else {
+                        gap[o] = 0.f;
+                    }
                 }
         }
         float dot = 0.f;
 #pragma unroll
         for (int t = 0; t < MAX_T; ++t)
-            if (t < T) dot = fmaf(a[t], da[t], dot);
+            if (t < T && on<MASKED>(vb, t)) dot = fmaf(a[t], da[t], dot);
 #pragma unroll
-        for (int t = 0; t < MAX_T; ++t) da[t] = a[t] * (da[t] - dot);  // d logits
+        for (int t = 0; t < MAX_T; ++t) da[t] = a[t] * (da[t] - dot);  // d logits (0 where a[t] = 0: t >= T, absent references)
         const float *qp = q + (size_t)n * c * HW + p;
         const float *ep = emb + i0 * c * HW + p;
         float *gqp = g_q + (size_t)n * c * HW + p;
@@ -107,8 +123,12 @@ __global__ __launch_bounds__(256) void mrattn_bwd_kernel(const float *__restrict
             for (int t = 0; t < MAX_T; ++t)
                 if (t < T) {
                     const size_t o = t * est + (size_t)k * HW;
-                    acc = fmaf(da[t], ep[o], acc);
-                    gep[o] = da[t] * qv;
+                    if (on<MASKED>(vb, t)) {
+                        acc = fmaf(da[t], ep[o], acc);
+                        gep[o] = da[t] * qv;
+                    } else {
+                        gep[o] = 0.f;
+                    }
                 }
             gqp[(size_t)k * HW] = acc;
         }
@@ -155,10 +175,13 @@ template <> struct Io4<true> {
     static __device__ __forceinline__ void st(unsigned short *p, float4 v) { *reinterpret_cast<uint2 *>(p) = make_uint2(rne(v.x, v.y), rne(v.z, v.w)); }
 };
 
-template <int CH, bool IO16>
+// MASKED: as in the NCHW kernels above.  The lanes of a group share a pixel, hence a sample and a mask, but the 4 or 2 groups of a
+// wave at CH = 64 / 128 may sit in different samples: the loads are predicated per lane, the xor shuffles run for every t < T
+// (wave-uniform control flow; an absent t reduces zeros that nothing reads).
+template <int CH, bool IO16, bool MASKED>
 __global__ __launch_bounds__(256) void mrattn_fwd_nhwc_kernel(const typename Io4<IO16>::T *__restrict__ q, const typename Io4<IO16>::T *__restrict__ emb,
                                                               const typename Io4<IO16>::T *__restrict__ ass, typename Io4<IO16>::T *__restrict__ out,
-                                                              int N, int T, long HW, float q_scale)
+                                                              int N, int T, long HW, float q_scale, const unsigned int *__restrict__ valid_bits)
 {
     typedef Io4<IO16> IO;
     constexpr int L = CH / 4, PPW = 64 / L;
@@ -170,6 +193,7 @@ __global__ __launch_bounds__(256) void mrattn_fwd_nhwc_kernel(const typename Io4
         const bool ok = gp < total;
         const long g = ok ? gp : total - 1;
         const long n = g / HW, p = g - n * HW;
+        const unsigned int vb = MASKED ? valid_bits[n] : 0u;
         float4 qv = IO::ld(q + g * CH + 4 * sub);
         if (!IO16) qv.x *= q_scale, qv.y *= q_scale, qv.z *= q_scale, qv.w *= q_scale;   // (q * scale of ref :323 as its own rounded product: the bits of the separate pass; 1 = none)
         float logit[16];
@@ -177,26 +201,29 @@ __global__ __launch_bounds__(256) void mrattn_fwd_nhwc_kernel(const typename Io4
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             if (t < T) {
-                const float4 e = IO::ld(emb + (((long)t * N + n) * HW + p) * CH + 4 * sub);
-                float d = qv.x * e.x + qv.y * e.y + qv.z * e.z + qv.w * e.w;
+                float d = 0.f;
+                if (on<MASKED>(vb, t)) {
+                    const float4 e = IO::ld(emb + (((long)t * N + n) * HW + p) * CH + 4 * sub);
+                    d = qv.x * e.x + qv.y * e.y + qv.z * e.z + qv.w * e.w;
+                }
 #pragma unroll
                 for (int o = L / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
                 logit[t] = d;
-                mx = fmaxf(mx, d);
+                if (on<MASKED>(vb, t)) mx = fmaxf(mx, d);
             }
         }
         float den = 0.f;
 #pragma unroll
         for (int t = 0; t < 16; ++t)
-            if (t < T) {
+            if (t < T && on<MASKED>(vb, t)) {
                 logit[t] = expf(logit[t] - mx);
                 den += logit[t];
             }
-        const float inv = 1.0f / den;
+        const float inv = (!MASKED || den > 0.f) ? 1.0f / den : 0.f;   // (no present reference: out = 0)
         float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
 #pragma unroll
         for (int t = 0; t < 16; ++t)
-            if (t < T) {
+            if (t < T && on<MASKED>(vb, t)) {
                 const float w = logit[t] * inv;
                 const typename IO::T *ap = ass + (((long)t * N + n) * HW + p) * (2 * CH) + 4 * sub;
                 const float4 a0 = IO::ld(ap), a1 = IO::ld(ap + CH);
@@ -211,8 +238,9 @@ __global__ __launch_bounds__(256) void mrattn_fwd_nhwc_kernel(const typename Io4
     }
 }
 
-template <bool IO16>
-int launch_mrattn_nhwc(const void *q, const void *emb, const void *ass, void *out, int N, int T, int c, int HW, float q_scale, hipStream_t st)
+template <bool IO16, bool MASKED>
+int launch_mrattn_nhwc(const void *q, const void *emb, const void *ass, const unsigned int *vb, void *out, int N, int T, int c, int HW, float q_scale,
+                       hipStream_t st)
 {
     typedef typename Io4<IO16>::T E;
     const long waves = ((long)N * HW * (c / 4) + 63) / 64;
@@ -220,9 +248,9 @@ int launch_mrattn_nhwc(const void *q, const void *emb, const void *ass, void *ou
     const dim3 grid((int)(blocks < 65536 ? blocks : 65536));
     const E *q_ = (const E *)q, *e_ = (const E *)emb, *a_ = (const E *)ass;
     E *o_ = (E *)out;
-    if (c == 256) hipLaunchKernelGGL((mrattn_fwd_nhwc_kernel<256, IO16>), grid, dim3(256), 0, st, q_, e_, a_, o_, N, T, (long)HW, q_scale);
-    else if (c == 128) hipLaunchKernelGGL((mrattn_fwd_nhwc_kernel<128, IO16>), grid, dim3(256), 0, st, q_, e_, a_, o_, N, T, (long)HW, q_scale);
-    else if (c == 64) hipLaunchKernelGGL((mrattn_fwd_nhwc_kernel<64, IO16>), grid, dim3(256), 0, st, q_, e_, a_, o_, N, T, (long)HW, q_scale);
+    if (c == 256) hipLaunchKernelGGL((mrattn_fwd_nhwc_kernel<256, IO16, MASKED>), grid, dim3(256), 0, st, q_, e_, a_, o_, N, T, (long)HW, q_scale, vb);
+    else if (c == 128) hipLaunchKernelGGL((mrattn_fwd_nhwc_kernel<128, IO16, MASKED>), grid, dim3(256), 0, st, q_, e_, a_, o_, N, T, (long)HW, q_scale, vb);
+    else if (c == 64) hipLaunchKernelGGL((mrattn_fwd_nhwc_kernel<64, IO16, MASKED>), grid, dim3(256), 0, st, q_, e_, a_, o_, N, T, (long)HW, q_scale, vb);
     else return mrefsr::fail(MREFSR_E_UNSUPPORTED, "mrattn_fwd_nhwc: c=%d (64, 128 or 256: the three MRAPAFusion heads)", c);
     return mrefsr::check_launch("mrattn_fwd_nhwc");
 }
@@ -234,7 +262,7 @@ MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_f32(const float *q, const float *emb, c
 {
     MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd_nhwc: null pointer");
     MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_fwd_nhwc: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
-    return launch_mrattn_nhwc<false>(q, emb, ass, out, N, T, c, HW, 1.0f, (hipStream_t)stream);
+    return launch_mrattn_nhwc<false, false>(q, emb, ass, nullptr, out, N, T, c, HW, 1.0f, (hipStream_t)stream);
 }
 
 // the same with `q * q_scale` (the 1 / sqrt(c) of ref_mrapa_restoration_arch.py:323) formed on the way in -- each product rounded on its
@@ -244,7 +272,7 @@ MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_scaled_f32(const float *q, const float 
 {
     MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd_nhwc_scaled: null pointer");
     MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_fwd_nhwc_scaled: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
-    return launch_mrattn_nhwc<false>(q, emb, ass, out, N, T, c, HW, q_scale, (hipStream_t)stream);
+    return launch_mrattn_nhwc<false, false>(q, emb, ass, nullptr, out, N, T, c, HW, q_scale, (hipStream_t)stream);
 }
 
 MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_bf16(const void *q, const void *emb, const void *ass, void *out, int N, int T, int c, int HW,
@@ -252,7 +280,7 @@ MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_bf16(const void *q, const void *emb, co
 {
     MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd_nhwc_bf16: null pointer");
     MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_fwd_nhwc_bf16: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
-    return launch_mrattn_nhwc<true>(q, emb, ass, out, N, T, c, HW, 1.0f, (hipStream_t)stream);
+    return launch_mrattn_nhwc<true, false>(q, emb, ass, nullptr, out, N, T, c, HW, 1.0f, (hipStream_t)stream);
 }
 
 MREFSR_EXPORT int mrefsr_mrattn_fwd_f32(const float *q, const float *emb, const float *ass, float *out, float *prob,
@@ -261,8 +289,8 @@ MREFSR_EXPORT int mrefsr_mrattn_fwd_f32(const float *q, const float *emb, const 
     MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd: null pointer");
     if (int e = check("mrattn_fwd", N, T, c, c2, HW)) return e;
     const long blocks = ((long)N * HW + 255) / 256;
-    hipLaunchKernelGGL(mrattn_fwd_kernel, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
-                       q, emb, ass, out, prob, N, T, c, c2, HW, t_major);
+    hipLaunchKernelGGL(mrattn_fwd_kernel<false>, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
+                       q, emb, ass, out, prob, N, T, c, c2, HW, t_major, (const unsigned int *)nullptr);
     return mrefsr::check_launch("mrattn_fwd");
 }
 
@@ -273,7 +301,51 @@ MREFSR_EXPORT int mrefsr_mrattn_bwd_f32(const float *q, const float *emb, const 
     MREFSR_REQUIRE(q && emb && ass && prob && g_out && g_q && g_emb && g_ass, "mrattn_bwd: null pointer");
     if (int e = check("mrattn_bwd", N, T, c, c2, HW)) return e;
     const long blocks = ((long)N * HW + 255) / 256;
-    hipLaunchKernelGGL(mrattn_bwd_kernel, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
-                       q, emb, ass, prob, g_out, g_q, g_emb, g_ass, N, T, c, c2, HW, t_major);
+    hipLaunchKernelGGL(mrattn_bwd_kernel<false>, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
+                       q, emb, ass, prob, g_out, g_q, g_emb, g_ass, N, T, c, c2, HW, t_major, (const unsigned int *)nullptr);
     return mrefsr::check_launch("mrattn_bwd");
+}
+
+// ---- per-sample reference masks: the same kernels with MASKED = true (valid_bits [N], bit t = reference t of the sample is present)
+MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_masked_f32(const float *q, const float *emb, const float *ass, const uint32_t *valid_bits, float *out,
+                                                    int N, int T, int c, int HW, float q_scale, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd_nhwc_masked: null pointer");
+    MREFSR_REQUIRE(valid_bits, "mrattn_fwd_nhwc_masked: null valid_bits");
+    MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_fwd_nhwc_masked: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
+    return launch_mrattn_nhwc<false, true>(q, emb, ass, valid_bits, out, N, T, c, HW, q_scale, (hipStream_t)stream);
+}
+
+MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_masked_bf16(const void *q, const void *emb, const void *ass, const uint32_t *valid_bits, void *out, int N,
+                                                     int T, int c, int HW, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd_nhwc_masked_bf16: null pointer");
+    MREFSR_REQUIRE(valid_bits, "mrattn_fwd_nhwc_masked_bf16: null valid_bits");
+    MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_fwd_nhwc_masked_bf16: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
+    return launch_mrattn_nhwc<true, true>(q, emb, ass, valid_bits, out, N, T, c, HW, 1.0f, (hipStream_t)stream);
+}
+
+MREFSR_EXPORT int mrefsr_mrattn_fwd_masked_f32(const float *q, const float *emb, const float *ass, const uint32_t *valid_bits, float *out,
+                                               float *prob, int N, int T, int c, int c2, int HW, int t_major, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd_masked: null pointer");
+    MREFSR_REQUIRE(valid_bits, "mrattn_fwd_masked: null valid_bits");
+    if (int e = check("mrattn_fwd_masked", N, T, c, c2, HW)) return e;
+    const long blocks = ((long)N * HW + 255) / 256;
+    hipLaunchKernelGGL(mrattn_fwd_kernel<true>, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
+                       q, emb, ass, out, prob, N, T, c, c2, HW, t_major, valid_bits);
+    return mrefsr::check_launch("mrattn_fwd_masked");
+}
+
+MREFSR_EXPORT int mrefsr_mrattn_bwd_masked_f32(const float *q, const float *emb, const float *ass, const float *prob, const float *g_out,
+                                               const uint32_t *valid_bits, float *g_q, float *g_emb, float *g_ass, int N, int T, int c, int c2,
+                                               int HW, int t_major, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(q && emb && ass && prob && g_out && g_q && g_emb && g_ass, "mrattn_bwd_masked: null pointer");
+    MREFSR_REQUIRE(valid_bits, "mrattn_bwd_masked: null valid_bits");
+    if (int e = check("mrattn_bwd_masked", N, T, c, c2, HW)) return e;
+    const long blocks = ((long)N * HW + 255) / 256;
+    hipLaunchKernelGGL(mrattn_bwd_kernel<true>, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
+                       q, emb, ass, prob, g_out, g_q, g_emb, g_ass, N, T, c, c2, HW, t_major, valid_bits);
+    return mrefsr::check_launch("mrattn_bwd_masked");
 }

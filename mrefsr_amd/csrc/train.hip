@@ -129,12 +129,16 @@ __global__ __launch_bounds__(256) void act_bwd_nhwc_kernel(const float *__restri
 // attention backward, channels-last: q [N][HW][c], emb [T*N][HW][c], ass [T*N][HW][2c] (t-major), g_out [N][HW][2c]
 // -> g_q, g_emb, g_ass.  c/4 lanes share a pixel (as mrattn_fwd_nhwc_kernel); the softmax is recomputed from q and emb
 // (they are read for their gradients anyway), the T embeddings of the pixel stay in registers.
+// MASKED (per-sample reference masks, as mrattn_fwd_nhwc_kernel): valid_bits[n] bit t = reference t of sample n is present.  The
+// softmax is recomputed over the present t only; an absent t's emb / ass are not loaded, its g_emb / g_ass are written as exact
+// zeros, g_q sums the present t.  Loads and stores are predicated per lane; the shuffles run for every t < T (the lane groups of
+// a wave may sit in samples with different masks).  MASKED = false is the unmasked kernel.
 // ---------------------------------------------------------------------------------------------------------------
-template <int CH>
+template <int CH, bool MASKED>
 __global__ __launch_bounds__(256) void mrattn_bwd_nhwc_kernel(const float *__restrict__ q, const float *__restrict__ emb,
                                                               const float *__restrict__ ass, const float *__restrict__ g_out,
                                                               float *__restrict__ g_q, float *__restrict__ g_emb, float *__restrict__ g_ass,
-                                                              int N, int T, long HW)
+                                                              int N, int T, long HW, const unsigned int *__restrict__ valid_bits)
 {
     constexpr int L = CH / 4, PPW = 64 / L, MT = 16;
     const int lane = threadIdx.x & 63, sub = lane % L, pw = lane / L;
@@ -145,6 +149,9 @@ __global__ __launch_bounds__(256) void mrattn_bwd_nhwc_kernel(const float *__res
         const bool ok = gp < total;
         const long g = ok ? gp : total - 1;
         const long n = g / HW, p = g - n * HW;
+        const unsigned int vb = MASKED ? valid_bits[n] : 0u;
+        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#define MREFSR_ON(t) (!MASKED || ((vb >> (t)) & 1u))
         const float4 qv = *reinterpret_cast<const float4 *>(q + g * CH + 4 * sub);
         const float4 g0 = *reinterpret_cast<const float4 *>(g_out + g * (2 * CH) + 4 * sub);
         const float4 g1 = *reinterpret_cast<const float4 *>(g_out + g * (2 * CH) + CH + 4 * sub);
@@ -154,49 +161,58 @@ __global__ __launch_bounds__(256) void mrattn_bwd_nhwc_kernel(const float *__res
 #pragma unroll
         for (int t = 0; t < MT; ++t)
             if (t < T) {
-                e[t] = *reinterpret_cast<const float4 *>(emb + (((long)t * N + n) * HW + p) * CH + 4 * sub);
-                float d = qv.x * e[t].x + qv.y * e[t].y + qv.z * e[t].z + qv.w * e[t].w;
+                float d = 0.f;
+                if (MREFSR_ON(t)) {
+                    e[t] = *reinterpret_cast<const float4 *>(emb + (((long)t * N + n) * HW + p) * CH + 4 * sub);
+                    d = qv.x * e[t].x + qv.y * e[t].y + qv.z * e[t].z + qv.w * e[t].w;
+                }
 #pragma unroll
                 for (int o = L / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
                 a[t] = d;
-                mx = fmaxf(mx, d);
+                if (MREFSR_ON(t)) mx = fmaxf(mx, d);
             }
         float den = 0.f;
 #pragma unroll
         for (int t = 0; t < MT; ++t)
-            if (t < T) {
+            if (t < T && MREFSR_ON(t)) {
                 a[t] = expf(a[t] - mx);
                 den += a[t];
             }
-        const float inv = 1.0f / den;
+        const float inv = (!MASKED || den > 0.f) ? 1.0f / den : 0.f;   // (no present reference: every gradient 0)
         float dot = 0.f;
 #pragma unroll
         for (int t = 0; t < MT; ++t)
             if (t < T) {
-                a[t] *= inv;
                 const size_t o = (size_t)((((long)t * N + n) * HW + p) * (2 * CH) + 4 * sub);
-                const float4 a0 = *reinterpret_cast<const float4 *>(ass + o), a1 = *reinterpret_cast<const float4 *>(ass + o + CH);
-                float d = g0.x * a0.x + g0.y * a0.y + g0.z * a0.z + g0.w * a0.w + g1.x * a1.x + g1.y * a1.y + g1.z * a1.z + g1.w * a1.w;
+                float d = 0.f;
+                if (MREFSR_ON(t)) {
+                    a[t] *= inv;
+                    const float4 a0 = *reinterpret_cast<const float4 *>(ass + o), a1 = *reinterpret_cast<const float4 *>(ass + o + CH);
+                    d = g0.x * a0.x + g0.y * a0.y + g0.z * a0.z + g0.w * a0.w + g1.x * a1.x + g1.y * a1.y + g1.z * a1.z + g1.w * a1.w;
+                }
 #pragma unroll
                 for (int s = L / 2; s > 0; s >>= 1) d += __shfl_xor(d, s, 64);
                 da[t] = d;
-                dot = fmaf(a[t], d, dot);
+                if (MREFSR_ON(t)) dot = fmaf(a[t], d, dot);
                 if (ok) {
-                    *reinterpret_cast<float4 *>(g_ass + o) = make_float4(g0.x * a[t], g0.y * a[t], g0.z * a[t], g0.w * a[t]);
-                    *reinterpret_cast<float4 *>(g_ass + o + CH) = make_float4(g1.x * a[t], g1.y * a[t], g1.z * a[t], g1.w * a[t]);
+                    *reinterpret_cast<float4 *>(g_ass + o) = MREFSR_ON(t) ? make_float4(g0.x * a[t], g0.y * a[t], g0.z * a[t], g0.w * a[t]) : z4;
+                    *reinterpret_cast<float4 *>(g_ass + o + CH) = MREFSR_ON(t) ? make_float4(g1.x * a[t], g1.y * a[t], g1.z * a[t], g1.w * a[t]) : z4;
                 }
             }
         float4 gq = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int t = 0; t < MT; ++t)
             if (t < T) {
-                const float dl = a[t] * (da[t] - dot);   // d logit_t
-                gq.x = fmaf(dl, e[t].x, gq.x), gq.y = fmaf(dl, e[t].y, gq.y), gq.z = fmaf(dl, e[t].z, gq.z), gq.w = fmaf(dl, e[t].w, gq.w);
-                if (ok)
-                    *reinterpret_cast<float4 *>(g_emb + (((long)t * N + n) * HW + p) * CH + 4 * sub) =
-                        make_float4(dl * qv.x, dl * qv.y, dl * qv.z, dl * qv.w);
+                float4 ge = z4;
+                if (MREFSR_ON(t)) {
+                    const float dl = a[t] * (da[t] - dot);   // d logit_t
+                    gq.x = fmaf(dl, e[t].x, gq.x), gq.y = fmaf(dl, e[t].y, gq.y), gq.z = fmaf(dl, e[t].z, gq.z), gq.w = fmaf(dl, e[t].w, gq.w);
+                    ge = make_float4(dl * qv.x, dl * qv.y, dl * qv.z, dl * qv.w);
+                }
+                if (ok) *reinterpret_cast<float4 *>(g_emb + (((long)t * N + n) * HW + p) * CH + 4 * sub) = ge;
             }
         if (ok) *reinterpret_cast<float4 *>(g_q + g * CH + 4 * sub) = gq;
+#undef MREFSR_ON
     }
 }
 
@@ -294,20 +310,37 @@ MREFSR_EXPORT int mrefsr_act_bwd_nhwc_det_f32(const float *g_out, const float *o
                           workspace_bytes, ticket, stream);
 }
 
-MREFSR_EXPORT int mrefsr_mrattn_bwd_nhwc_f32(const float *q, const float *emb, const float *ass, const float *g_out, float *g_q,
-                                             float *g_emb, float *g_ass, int N, int T, int c, int HW, mrefsr_stream_t stream)
+namespace {
+template <bool MASKED>
+int launch_mrattn_bwd_nhwc(const char *what, const float *q, const float *emb, const float *ass, const float *g_out, const unsigned int *vb, float *g_q,
+                           float *g_emb, float *g_ass, int N, int T, int c, int HW, mrefsr_stream_t stream)
 {
-    MREFSR_REQUIRE(q && emb && ass && g_out && g_q && g_emb && g_ass, "mrattn_bwd_nhwc: null pointer");
-    MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_bwd_nhwc: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
+    MREFSR_REQUIRE(q && emb && ass && g_out && g_q && g_emb && g_ass, "%s: null pointer", what);
+    MREFSR_REQUIRE(!MASKED || vb, "%s: null valid_bits", what);
+    MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "%s: N=%d T=%d HW=%d (T <= 16)", what, N, T, HW);
     const long waves = ((long)N * HW * (c / 4) + 63) / 64;
     const long blocks = (waves + 3) / 4;
     const dim3 grid((int)(blocks < 65536 ? blocks : 65536));
     hipStream_t st = (hipStream_t)stream;
-    if (c == 256) hipLaunchKernelGGL(mrattn_bwd_nhwc_kernel<256>, grid, dim3(256), 0, st, q, emb, ass, g_out, g_q, g_emb, g_ass, N, T, (long)HW);
-    else if (c == 128) hipLaunchKernelGGL(mrattn_bwd_nhwc_kernel<128>, grid, dim3(256), 0, st, q, emb, ass, g_out, g_q, g_emb, g_ass, N, T, (long)HW);
-    else if (c == 64) hipLaunchKernelGGL(mrattn_bwd_nhwc_kernel<64>, grid, dim3(256), 0, st, q, emb, ass, g_out, g_q, g_emb, g_ass, N, T, (long)HW);
-    else return mrefsr::fail(MREFSR_E_UNSUPPORTED, "mrattn_bwd_nhwc: c=%d (64, 128 or 256: the three MRAPAFusion heads)", c);
-    return mrefsr::check_launch("mrattn_bwd_nhwc");
+    if (c == 256) hipLaunchKernelGGL((mrattn_bwd_nhwc_kernel<256, MASKED>), grid, dim3(256), 0, st, q, emb, ass, g_out, g_q, g_emb, g_ass, N, T, (long)HW, vb);
+    else if (c == 128) hipLaunchKernelGGL((mrattn_bwd_nhwc_kernel<128, MASKED>), grid, dim3(256), 0, st, q, emb, ass, g_out, g_q, g_emb, g_ass, N, T, (long)HW, vb);
+    else if (c == 64) hipLaunchKernelGGL((mrattn_bwd_nhwc_kernel<64, MASKED>), grid, dim3(256), 0, st, q, emb, ass, g_out, g_q, g_emb, g_ass, N, T, (long)HW, vb);
+    else return mrefsr::fail(MREFSR_E_UNSUPPORTED, "%s: c=%d (64, 128 or 256: the three MRAPAFusion heads)", what, c);
+    return mrefsr::check_launch(what);
+}
+}  // namespace
+
+MREFSR_EXPORT int mrefsr_mrattn_bwd_nhwc_f32(const float *q, const float *emb, const float *ass, const float *g_out, float *g_q,
+                                             float *g_emb, float *g_ass, int N, int T, int c, int HW, mrefsr_stream_t stream)
+{
+    return launch_mrattn_bwd_nhwc<false>("mrattn_bwd_nhwc", q, emb, ass, g_out, nullptr, g_q, g_emb, g_ass, N, T, c, HW, stream);
+}
+
+MREFSR_EXPORT int mrefsr_mrattn_bwd_nhwc_masked_f32(const float *q, const float *emb, const float *ass, const float *g_out,
+                                                    const uint32_t *valid_bits, float *g_q, float *g_emb, float *g_ass, int N, int T, int c,
+                                                    int HW, mrefsr_stream_t stream)
+{
+    return launch_mrattn_bwd_nhwc<true>("mrattn_bwd_nhwc_masked", q, emb, ass, g_out, valid_bits, g_q, g_emb, g_ass, N, T, c, HW, stream);
 }
 
 MREFSR_EXPORT int mrefsr_attn_modulate_bwd_f32(const float *g, const float *refs, const float *mul, float *g_refs, float *g_mul, int64_t n,

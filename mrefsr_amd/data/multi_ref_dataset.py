@@ -9,6 +9,14 @@ Mirror of basicsr/data/multi_ref_dataset.py:
 Returned dict keys and tensor layouts are the reference's (:127-134, :215-225).
 Random draws are consumed in the reference's order (random.shuffle, then the three
 `flag and random.random() < 0.5` of transforms.augment :116-118), so seeding `random` reproduces it.
+
+Two options of this mirror (both off by default: the dict and the draws above are then unchanged) return samples with absent
+references -- zero images in `img_ref_list` / `img_ref_lq_list` / `img_ref_up_list` and a bool `ref_valid` [K], false for them,
+which MultiRefRestorationModel.feed_data reads:
+  MultiRefMegaDepthDataset  ref_drop_prob: p       each reference dropped with probability p (one random.random() per reference,
+                                                   drawn after the draws above; the first one is kept if all were dropped)
+  MultiRefCUFEDSet          allow_missing_refs     references looked up by name (<name>_k.png, k = 1..5) per input; a missing file
+                                                   is an absent reference, an input without any reference is refused
 """
 import glob
 import os.path as osp
@@ -102,8 +110,14 @@ class MultiRefMegaDepthDataset(data.Dataset):
         imgs = augment([img_in] + refs, self.opt['use_flip'], self.opt['use_rot'])
         img_in, refs = imgs[0], imgs[1:]
         in_lq, in_up = _bicubic_pair((img_in * 255).astype(np.uint8), scale)
+        drop_prob = self.opt.get('ref_drop_prob') or 0
+        if drop_prob:
+            valid = [not (random.random() < drop_prob) for _ in refs]
+            if not any(valid):
+                valid[0] = True
+            refs = [r if v else np.zeros_like(r) for r, v in zip(refs, valid)]
         pairs = [_bicubic_pair((r * 255).astype(np.uint8), scale) for r in refs]
-        return {
+        out = {
             'img_in': _to_tensor(img_in),
             'img_in_lq': _to_tensor(in_lq),
             'img_in_up': _to_tensor(in_up),
@@ -111,6 +125,9 @@ class MultiRefMegaDepthDataset(data.Dataset):
             'img_ref_lq_list': torch.stack([_to_tensor(p[0]) for p in pairs]),
             'img_ref_up_list': torch.stack([_to_tensor(p[1]) for p in pairs]),
         }
+        if drop_prob:
+            out['ref_valid'] = torch.tensor(valid, dtype=torch.bool)
+        return out
 
 
 @DATASET_REGISTRY.register()
@@ -120,7 +137,17 @@ class MultiRefCUFEDSet(data.Dataset):
         super().__init__()
         self.opt = opt
         self.input_list = sorted(glob.glob(osp.join(opt['dataroot_in'], '*_0.png')))
-        self.ref_lists = [sorted(glob.glob(osp.join(opt['dataroot_ref'], f'*_{k}.png'))) for k in range(1, 6)]
+        self.by_name = bool(opt.get('allow_missing_refs'))
+        if not self.by_name:
+            self.ref_lists = [sorted(glob.glob(osp.join(opt['dataroot_ref'], f'*_{k}.png'))) for k in range(1, 6)]
+            return
+        # <name>_0.png -> <name>_1.png .. <name>_5.png, each looked up by name: None where the file is missing
+        names = [osp.basename(p)[:-len('_0.png')] for p in self.input_list]
+        self.ref_paths = [[p if osp.exists(p) else None for p in (osp.join(opt['dataroot_ref'], f'{n}_{k}.png') for k in range(1, 6))]
+                          for n in names]
+        bare = [n for n, paths in zip(names, self.ref_paths) if not any(paths)]
+        if bare:
+            raise ValueError(f'MultiRefCUFEDSet: no reference image for input(s) {bare} in {opt["dataroot_ref"]}')
 
     def __len__(self):
         return len(self.input_list)
@@ -129,21 +156,28 @@ class MultiRefCUFEDSet(data.Dataset):
         scale = self.opt['scale']
         load = lambda p: np.array(Image.open(p).convert('RGB'))  # noqa: E731  (RGB; the reference loads BGR and swaps at the end)
         img_in = mod_crop(load(self.input_list[idx]), scale)
-        refs = [load(lst[idx]) for lst in self.ref_lists]
+        if self.by_name:
+            refs = [np.zeros((500, 500, 3), np.uint8) if p is None else load(p) for p in self.ref_paths[idx]]
+        else:
+            refs = [load(lst[idx]) for lst in self.ref_lists]
         img_in_gt = img_in.copy()
         img_in_h, img_in_w = img_in.shape[:2]
         img_in = impad(img_in, shape=(500, 500), pad_val=0)
         refs = [impad(r, shape=(500, 500), pad_val=0) for r in refs]
         in_lq, in_up = _bicubic_pair(img_in, scale)
         pairs = [_bicubic_pair(r, scale) for r in refs]
-        return {
+        out = {
             'img_in': _to_tensor(img_in_gt.astype(np.float32) / 255.),
             'img_in_lq': _to_tensor(in_lq),
             'img_in_up': _to_tensor(in_up),
             'img_ref_list': torch.stack([_to_tensor(r.astype(np.float32) / 255.) for r in refs]),
             'img_ref_lq_list': torch.stack([_to_tensor(p[0]) for p in pairs]),
             'img_ref_up_list': torch.stack([_to_tensor(p[1]) for p in pairs]),
-            'lq_path': self.ref_lists[0][idx].replace('_1.png', '_multi.png'),
+            'lq_path': (osp.join(self.opt['dataroot_ref'], osp.basename(self.input_list[idx])[:-len('_0.png')] + '_multi.png')
+                        if self.by_name else self.ref_lists[0][idx].replace('_1.png', '_multi.png')),
             'padding': True,
             'original_size': (img_in_h, img_in_w),
         }
+        if self.by_name:
+            out['ref_valid'] = torch.tensor([p is not None for p in self.ref_paths[idx]], dtype=torch.bool)
+        return out

@@ -617,6 +617,74 @@ def mrattn_bwd(q, emb, ass, prob, g_out, t, t_major=False):
     return g_q, g_emb, g_ass
 
 
+def _chk_valid_bits(name, valid_bits, n):
+    """valid_bits [N] int32 on the device: bit t of word n set = reference t of sample n is present"""
+    _chk(name, valid_bits, dtype=torch.int32)
+    if valid_bits is None or tuple(valid_bits.shape) != (n,):
+        raise ValueError(f'{name}: valid_bits must be an int32 tensor of shape ({n},)')
+
+
+def mrattn_fwd_masked(q, emb, ass, t, valid_bits, want_prob=True, t_major=False):
+    """mrattn_fwd under per-sample reference masks: reference t of sample n takes part only if bit t of valid_bits[n] is set; its
+    emb / ass are not read otherwise and its prob is exactly 0"""
+    _chk('mrattn_fwd_masked', q, emb, ass)
+    n, c, h, w = q.shape
+    c2 = ass.shape[1]
+    if emb.shape[0] != n * t or ass.shape[0] != n * t or emb.shape[1] != c:
+        raise ValueError('mrattn_fwd_masked: inconsistent shapes')
+    _chk_valid_bits('mrattn_fwd_masked', valid_bits, n)
+    out = torch.empty((n, c2, h, w), device=q.device, dtype=torch.float32)
+    prob = torch.empty((n, t, h, w), device=q.device, dtype=torch.float32) if want_prob else None
+    _lib.call('mrefsr_mrattn_fwd_masked_f32', _p(q), _p(emb), _p(ass), _p(valid_bits), _p(out), _p(prob), n, t, c, c2, h * w,
+              1 if t_major else 0, _stream())
+    return out, prob
+
+
+def mrattn_fwd_nhwc_masked(q, emb, ass, t, valid_bits, q_scale=None):
+    """mrattn_fwd_nhwc under per-sample reference masks (valid_bits [N] int32, bit t = reference t of the sample is present)"""
+    b16 = q.dtype == torch.bfloat16
+    if q_scale is not None and b16:
+        raise TypeError('mrattn_fwd_nhwc_masked: q_scale goes with fp32 tensors')
+    _chk('mrattn_fwd_nhwc_masked', q, emb, ass, dtype=q.dtype if b16 else torch.float32)
+    n, h, w, c = q.shape
+    if tuple(emb.shape) != (n * t, h, w, c) or tuple(ass.shape) != (n * t, h, w, 2 * c):
+        raise ValueError('mrattn_fwd_nhwc_masked: inconsistent shapes')
+    _chk_valid_bits('mrattn_fwd_nhwc_masked', valid_bits, n)
+    out = torch.empty((n, h, w, 2 * c), device=q.device, dtype=q.dtype)
+    with _timed('mrattn_fwd', (3.0 * t + 3.0) * c * h * w * q.element_size() * n, detail=True):
+        if b16:
+            _lib.call('mrefsr_mrattn_fwd_nhwc_masked_bf16', _p(q), _p(emb), _p(ass), _p(valid_bits), _p(out), n, t, c, h * w, _stream())
+        else:
+            _lib.call('mrefsr_mrattn_fwd_nhwc_masked_f32', _p(q), _p(emb), _p(ass), _p(valid_bits), _p(out), n, t, c, h * w,
+                      C.c_float(1.0 if q_scale is None else q_scale), _stream())
+    return out
+
+
+def mrattn_bwd_masked(q, emb, ass, prob, g_out, t, valid_bits, t_major=False, out=None):
+    """gradient of mrattn_fwd_masked -> (g_q, g_emb, g_ass); g_emb / g_ass of absent references are exact zeros.  out: the three
+    buffers to write into (every element is written)"""
+    _chk('mrattn_bwd_masked', q, emb, ass, prob, g_out)
+    n, c, h, w = q.shape
+    c2 = ass.shape[1]
+    if (emb.shape[0] != n * t or ass.shape[0] != n * t or emb.shape[1] != c or tuple(prob.shape) != (n, t, h, w)
+            or tuple(g_out.shape) != (n, c2, h, w)):
+        raise ValueError('mrattn_bwd_masked: inconsistent shapes')
+    _chk_valid_bits('mrattn_bwd_masked', valid_bits, n)
+    g_q, g_emb, g_ass = _grad_triple('mrattn_bwd_masked', out, q, emb, ass)
+    _lib.call('mrefsr_mrattn_bwd_masked_f32', _p(q), _p(emb), _p(ass), _p(prob), _p(g_out), _p(valid_bits), _p(g_q), _p(g_emb), _p(g_ass),
+              n, t, c, c2, h * w, 1 if t_major else 0, _stream())
+    return g_q, g_emb, g_ass
+
+
+def _grad_triple(name, out, q, emb, ass):
+    if out is None:
+        return torch.empty_like(q), torch.empty_like(emb), torch.empty_like(ass)
+    _chk(name, *out)
+    if [tuple(o.shape) for o in out] != [tuple(v.shape) for v in (q, emb, ass)]:
+        raise ValueError(f'{name}: out must be (g_q, g_emb, g_ass) shaped like (q, emb, ass)')
+    return tuple(out)
+
+
 # ------------------------------------------------------------------ fused_act / upfirdn2d
 _DT = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2, torch.float64: 3}
 
@@ -1188,6 +1256,20 @@ def mrattn_bwd_nhwc(q, emb, ass, g_out, t):
         raise ValueError('mrattn_bwd_nhwc: inconsistent shapes')
     g_q, g_emb, g_ass = torch.empty_like(q), torch.empty_like(emb), torch.empty_like(ass)
     _lib.call('mrefsr_mrattn_bwd_nhwc_f32', _p(q), _p(emb), _p(ass), _p(g_out), _p(g_q), _p(g_emb), _p(g_ass), n, t, c, h * w, _stream())
+    return g_q, g_emb, g_ass
+
+
+def mrattn_bwd_nhwc_masked(q, emb, ass, g_out, t, valid_bits, out=None):
+    """gradient of mrattn_fwd_nhwc_masked: -> (g_q, g_emb, g_ass), same layouts; g_emb / g_ass of absent references are exact
+    zeros.  out: the three buffers to write into (every element is written)"""
+    _chk('mrattn_bwd_nhwc_masked', q, emb, ass, g_out)
+    n, h, w, c = q.shape
+    if tuple(emb.shape) != (n * t, h, w, c) or tuple(ass.shape) != (n * t, h, w, 2 * c) or tuple(g_out.shape) != (n, h, w, 2 * c):
+        raise ValueError('mrattn_bwd_nhwc_masked: inconsistent shapes')
+    _chk_valid_bits('mrattn_bwd_nhwc_masked', valid_bits, n)
+    g_q, g_emb, g_ass = _grad_triple('mrattn_bwd_nhwc_masked', out, q, emb, ass)
+    _lib.call('mrefsr_mrattn_bwd_nhwc_masked_f32', _p(q), _p(emb), _p(ass), _p(g_out), _p(valid_bits), _p(g_q), _p(g_emb), _p(g_ass), n, t, c,
+              h * w, _stream())
     return g_q, g_emb, g_ass
 
 

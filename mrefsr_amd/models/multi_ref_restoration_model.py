@@ -349,12 +349,42 @@ class MultiRefRestorationModel:
         return net.module if isinstance(net, DistributedDataParallel) else net
 
     # ------------------------------------------------------------------ data
+    ref_valid_bits = None   # per-sample reference masks of the current batch: int32 [B] on the device (bit k = reference k present), None = all
+
+    @staticmethod
+    def check_ref_valid(ref_valid, b, k):
+        """the host check of data['ref_valid'] ([B,K] bool / uint8): ValueError for a wrong shape or a sample without a valid
+        reference; -> the packed int32 [B] words (host), or None for an all-true mask (archs/arch_util.ref_valid_words)"""
+        from ..archs.arch_util import ref_valid_words
+        return ref_valid_words(ref_valid, b, k)
+
+    _masked_eager_logged = False
+
+    def _masked_batch(self, what):
+        """True for a batch with an absent reference: it does not take the hipGraph paths (the mask is not part of a capture key)"""
+        if self.ref_valid_bits is None:
+            return False
+        if not MultiRefRestorationModel._masked_eager_logged:
+            MultiRefRestorationModel._masked_eager_logged = True
+            logging.getLogger('basicsr').info(f'{what}: batches with a ref_valid mask run eagerly (no hipGraph capture or replay)')
+        return True
+
     def feed_data(self, data):
         """data: img_in_lq (B,3,h,w), img_in_up (B,3,4h,4w), img_ref_list (B,K,3,4h,4w), img_in (B,3,4h,4w)
-        (the dict of multi_ref_dataset.py:127-134)."""
+        (the dict of multi_ref_dataset.py:127-134); optionally ref_valid (B,K) bool / uint8: reference k of sample b is absent
+        where it is false -- the sample is restored from its valid references alone, whatever the loader put in the absent slot."""
+        words = None
+        if data.get('ref_valid') is not None:   # (checked on the host before anything is launched)
+            words = self.check_ref_valid(data['ref_valid'], *data['img_ref_list'].shape[:2])
+        self.ref_valid_bits = None if words is None else words.to(self.device)
         self.img_in_lq = data['img_in_lq'].to(self.device, non_blocking=True)
         refs = data['img_ref_list'].to(self.device, non_blocking=True)
         self.num_refs = refs.shape[1]
+        if words is not None:
+            # absent references become zero images (a select, not a product: NaN filler goes too), so that the frozen networks, the
+            # fp16-range flag and the batch-wide input scales do not depend on the loader's filler
+            valid = ((self.ref_valid_bits[:, None] >> torch.arange(self.num_refs, device=self.device, dtype=torch.int32)) & 1).bool()
+            refs = torch.where(valid[:, :, None, None, None], refs, refs.new_zeros(()))
         # k-major stack [K*B,3,H,W]; the reference's list(torch.unbind(dim=1)) is its K slices
         self.img_ref_stack = refs.transpose(0, 1).reshape(-1, *refs.shape[2:]).contiguous()
         self.img_ref_list = list(self.img_ref_stack.view(self.num_refs, -1, *refs.shape[2:]).unbind(0))
@@ -371,6 +401,8 @@ class MultiRefRestorationModel:
             f1, f2 = self.net_extractor.forward_stacked(self.match_img_in, self.img_ref_stack)
             pre_offset, self.max_idx = self.net_map.offsets(f1, f2)
             img_ref_feat = self.net_map.vgg(self.img_ref_stack)
+        if self.ref_valid_bits is not None:
+            return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k, ref_valid=self.ref_valid_bits)
         return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k)
 
     range_fallbacks = 0   # batches re-run on the range-free kernels because an activation left the fp16 range
@@ -617,7 +649,7 @@ class MultiRefRestorationModel:
     def _optimize_parameters(self, step):
         from ..archs import nhwc_train
         nhwc_train.check_scales()   # cached fp16 weight scales of the training convolutions still valid? (device side)
-        if self._train_graph_wanted() and self._optimize_graphed(step):
+        if self._train_graph_wanted() and not self._masked_batch('train.hip_graph') and self._optimize_graphed(step):
             return
         self.optimizer_g.zero_grad()
         nhwc_train.begin_step()     # every packed copy of net_g's weights refreshed in one launch (they changed in optimizer_g.step())
@@ -651,7 +683,7 @@ class MultiRefRestorationModel:
         self.net_g.eval()
         with torch.no_grad():
             hip.verify_packed(self.device)   # packed weight copies still match their parameters? (one launch, read with the range flag)
-            self.output = self._forward_graphed() if self._use_graph() else self._forward()
+            self.output = self._forward_graphed() if (self._use_graph() and not self._masked_batch('val.hip_graph')) else self._forward()
             tripped = self._range_tripped('test')
             if hip.packed_stale():   # a parameter was edited through .data: drop every packed copy and repeat the pass
                 logging.getLogger('basicsr').warning('test: a parameter changed without a version bump (.data write?); packed weights rebuilt')
