@@ -926,6 +926,27 @@ int64_t mrefsr_r1_sqnorm_workspace_bytes(int batch, int64_t n);
 int mrefsr_r1_sqnorm_f32(const float *g, int batch, int64_t n, float *out, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
 int mrefsr_r1_sqnorm_bwd_f32(const float *g, const float *gs, int batch, int64_t n, float *gg, mrefsr_stream_t stream);
 
+/* ---- the x8 geometric self-ensemble of test() (csrc/selfens.hip; val.self_ensemble) ------------------------------------------------
+ * No reference counterpart: the "+" evaluation protocol of EDSR and its successors.  Copy j in 0..3 of a group has hf = j & 1,
+ * vf = (j >> 1) & 1; a group is untransposed (tr = 0) or transposed (tr = 1).  Copy j of src [..., H, W] is, in torch,
+ *     s = src;  if hf: s = s.flip(-1);  if vf: s = s.flip(-2);  if tr: s = s.transpose(-1, -2)
+ * (the order of data/multi_ref_dataset.py: augment), and the inverse x' of an output x of that copy is
+ *     o = x;    if tr: o = o.transpose(-1, -2);  if vf: o = o.flip(-2);  if hf: o = o.flip(-1).
+ * Contiguous fp32 at any 4-byte boundary, any H, W >= 1 with H W <= 2^30, at most 2^31 - 1 tiles of 32 x 32 per launch; 16-byte
+ * accesses when the pointers are 16-byte aligned, W % 4 == 0 and (tr = 1, merge) H % 4 == 0, 4-byte accesses otherwise; the
+ * transposed group goes through a 32 x 33-word LDS tile (global reads and writes both along rows).  Nothing is allocated, nothing
+ * is synchronised.
+ *
+ * mrefsr_dihedral_expand_f32: src [outer][inner][C][H][W] -> dst [outer][4][inner][C][Ho][Wo], (Ho, Wo) = tr ? (W, H) : (H, W);
+ *   dst[o][j][i] is copy j of src[o][i].  outer = K turns the k-major reference stack [K][B] into the k-major stack [K][4][B] of
+ *   the expanded batch in one launch; images and LR inputs take outer = 1.  A pure copy of 32-bit words: bit-identical to the
+ *   torch statement, NaN payloads, infinities and -0 included.  dst must not overlap src.
+ * mrefsr_dihedral_merge_f32: a [4][N][C][H][W] (outputs of the untransposed group), b [4][N][C][W][H] (of the transposed group)
+ *   -> out [N][C][H][W] = (((((((a0' + a1') + a2') + a3') + b0') + b1') + b2') + b3') * 0.125f: fp32 adds in exactly this order, one
+ *   multiply behind them; bit-identical to the same chain written in torch.  out must not overlap a or b. */
+int mrefsr_dihedral_expand_f32(const float *src, float *dst, int outer, int inner, int C, int H, int W, int tr, mrefsr_stream_t stream);
+int mrefsr_dihedral_merge_f32(const float *a, const float *b, float *out, int N, int C, int H, int W, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

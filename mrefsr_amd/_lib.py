@@ -199,6 +199,8 @@ SIGNATURES = {
     'mrefsr_r1_sqnorm_workspace_bytes': (_i64, [_i, _i64]),
     'mrefsr_r1_sqnorm_f32': (_i, [_vp, _i, _i64, _vp, _vp, _i64, _vp]),
     'mrefsr_r1_sqnorm_bwd_f32': (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    'mrefsr_dihedral_expand_f32': (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
+    'mrefsr_dihedral_merge_f32': (_i, [_vp, _vp, _vp] + [_i] * 4 + [_vp]),
 }
 
 _lib = None

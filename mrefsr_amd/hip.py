@@ -1160,6 +1160,38 @@ def r1_sqnorm_bwd(g, gs, out=None):
     return gg
 
 
+# ------------------------------------------------------------------ x8 geometric self-ensemble of test() (csrc/selfens.hip)
+def dihedral_expand(src, tr, outer=1):
+    """src [outer * inner, C, H, W] (contiguous fp32; the leading axis outer-major, e.g. the k-major reference stack with outer = K)
+    -> [outer * 4 * inner, C, Ho, Wo], (Ho, Wo) = (W, H) if tr else (H, W): row (o * 4 + j) * inner + i is copy j of row o * inner + i,
+    copy j = flip(-1) if j & 1, then flip(-2) if j & 2, then transpose(-1, -2) if tr.  A pure copy (the bits of the torch
+    statement); one launch"""
+    _chk('dihedral_expand', src)
+    if tr not in (0, 1):
+        raise ValueError(f'dihedral_expand: tr {tr!r} is not 0 or 1')
+    if src.dim() != 4 or src.numel() == 0 or not isinstance(outer, int) or outer < 1 or src.shape[0] % outer:
+        raise ValueError(f'dihedral_expand: a non-empty [outer * inner, C, H, W] tensor expected, got {tuple(src.shape)} with outer = {outer!r}')
+    n, c, h, w = src.shape
+    dst = torch.empty((4 * n, c, w, h) if tr else (4 * n, c, h, w), device=src.device, dtype=torch.float32)
+    with _timed('dihedral_expand', detail=True, nbytes=4.0 * (src.numel() + dst.numel())):
+        _lib.call('mrefsr_dihedral_expand_f32', _p(src), _p(dst), outer, n // outer, c, h, w, int(tr), _stream())
+    return dst
+
+
+def dihedral_merge(a, b):
+    """a [4 * N, C, H, W], b [4 * N, C, W, H] (contiguous fp32; row j * N + n is the output of copy j of sample n in the
+    untransposed / the transposed group) -> [N, C, H, W]: the eight outputs with their transforms undone, added in fp32 as
+    (((((((a0 + a1) + a2) + a3) + b0) + b1) + b2) + b3) * 0.125 (the bits of that chain in torch); one launch"""
+    _chk('dihedral_merge', a, b)
+    if a.dim() != 4 or a.numel() == 0 or a.shape[0] % 4 or tuple(b.shape) != (a.shape[0], a.shape[1], a.shape[3], a.shape[2]):
+        raise ValueError(f'dihedral_merge: a [4 N, C, H, W] and b [4 N, C, W, H] expected, got {tuple(a.shape)} and {tuple(b.shape)}')
+    n4, c, h, w = a.shape
+    out = torch.empty((n4 // 4, c, h, w), device=a.device, dtype=torch.float32)
+    with _timed('dihedral_merge', detail=True, nbytes=4.0 * (a.numel() + b.numel() + out.numel())):
+        _lib.call('mrefsr_dihedral_merge_f32', _p(a), _p(b), _p(out), n4 // 4, c, h, w, _stream())
+    return out
+
+
 def act_bwd_nhwc(g_out, out, act, slope=0.0, slope_ptr=None, want_bias=True, want_amax=False):
     """Backward of a fused convolution epilogue on [..., C] contiguous tensors: g_pre = g_out * act'(out) with act 0 none,
     1 LeakyReLU(slope) (0 = ReLU), 2 PReLU(slope_ptr).  Returns (g_pre [..., ld] with ld = C rounded up to 4 (extra channels

@@ -84,6 +84,7 @@ class MultiRefRestorationModel:
         self.opt = opt
         if opt.get('num_gpu', 1) == 0:
             raise NotImplementedError('mrefsr_amd has no CPU path: num_gpu must be >= 1')
+        self.check_self_ensemble(opt.get('val'))   # (a bad value is refused before anything is built; test() reads the option)
         self.device = torch.device('cuda', torch.cuda.current_device())
         self.is_train = opt['is_train']
         self.schedulers, self.optimizers = [], []
@@ -670,30 +671,92 @@ class MultiRefRestorationModel:
             self._step_g()
 
     def test(self):
+        run = self._test_self_ensemble if self.check_self_ensemble(self.opt.get('val')) else self._test
         if self.net_g_ema is None:
-            return self._test()
+            return run()
         net_g, self.net_g = self.net_g, self.net_g_ema   # sr_model.py:121-125: the EMA weights are the ones tested (and shipped)
         try:
-            self._test()
+            run()
         finally:
             self.net_g = net_g
 
     def _test(self):
-        from .. import hip
         self.net_g.eval()
         with torch.no_grad():
-            hip.verify_packed(self.device)   # packed weight copies still match their parameters? (one launch, read with the range flag)
-            self.output = self._forward_graphed() if (self._use_graph() and not self._masked_batch('val.hip_graph')) else self._forward()
-            tripped = self._range_tripped('test')
-            if hip.packed_stale():   # a parameter was edited through .data: drop every packed copy and repeat the pass
-                logging.getLogger('basicsr').warning('test: a parameter changed without a version bump (.data write?); packed weights rebuilt')
-                hip.invalidate_packed()
-                self.output = self._forward()
-                tripped = self._range_tripped('test')
-            if tripped:
-                self.output = self._rerun_range_free('test', self._forward, reset_scales=False, tripped=True)
+            self.output = self._test_pass()
         if self.net_g is not self.net_g_ema:   # (net_g_ema stays in eval mode)
             self.net_g.train()
+
+    def _test_pass(self, eager=False):
+        """one inference pass on the fed tensors -> the output; ``eager``: the hipGraph replay is not taken whatever the options say"""
+        from .. import hip
+        hip.verify_packed(self.device)   # packed weight copies still match their parameters? (one launch, read with the range flag)
+        out = self._forward_graphed() if (not eager and self._use_graph() and not self._masked_batch('val.hip_graph')) else self._forward()
+        tripped = self._range_tripped('test')
+        if hip.packed_stale():   # a parameter was edited through .data: drop every packed copy and repeat the pass
+            logging.getLogger('basicsr').warning('test: a parameter changed without a version bump (.data write?); packed weights rebuilt')
+            hip.invalidate_packed()
+            out = self._forward()
+            tripped = self._range_tripped('test')
+        if tripped:
+            out = self._rerun_range_free('test', self._forward, reset_scales=False, tripped=True)
+        return out
+
+    # ------------------------------------------------------------------ val.self_ensemble: the x8 geometric self-ensemble of test()
+    @staticmethod
+    def check_self_ensemble(val_opt):
+        """opt['val']['self_ensemble']: absent, None or False -> False, True -> True; anything else (ints and strings too) is a
+        ValueError: the ensemble has eight members, there is no other size to ask for"""
+        v = (val_opt or {}).get('self_ensemble')
+        if v is None or v is False:
+            return False
+        if v is True:
+            return True
+        raise ValueError(f'val.self_ensemble: {v!r} is not true or false (true: test() averages the eight flipped / transposed copies)')
+
+    _FED = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'img_ref_list', 'img_ref', 'ref_valid_bits')
+    _self_ensemble_logged = _self_ensemble_eager_logged = False
+
+    def _test_self_ensemble(self):
+        """test() under val.self_ensemble (the "+" protocol of EDSR): copy j in 0..3 of group tr in (0, 1) is the input flipped
+        along W if j & 1, along H if j & 2, then transposed if tr (data/multi_ref_dataset.py: augment).  Each group is ONE
+        ordinary pass of batch 4 B -- images in the order j B + b, the reference stack [K][4][B], the ref_valid words repeated --
+        on tensors written by hip.dihedral_expand; hip.dihedral_merge undoes the transforms and averages the eight outputs in a
+        fixed order.  Two passes also for square inputs; both eager (the groups differ in shape, the graph cache keeps one).
+        Afterwards the fed tensors are back in place and max_idx holds the rows of the identity copy."""
+        from .. import hip
+        if not MultiRefRestorationModel._self_ensemble_logged:
+            MultiRefRestorationModel._self_ensemble_logged = True
+            logging.getLogger('basicsr').info('val.self_ensemble: test() runs the x8 geometric self-ensemble (two passes of four '
+                                              'copies per sample)')
+        if self._use_graph() and not MultiRefRestorationModel._self_ensemble_eager_logged:
+            MultiRefRestorationModel._self_ensemble_eager_logged = True
+            logging.getLogger('basicsr').info('val.hip_graph: the passes of val.self_ensemble run eagerly (no hipGraph capture or replay)')
+        fed = {n: self.__dict__[n] for n in self._FED if n in self.__dict__}
+        k, b = self.num_refs, self.img_in_lq.shape[0]
+        outs, max_idx = [], None
+        self.net_g.eval()
+        try:
+            with torch.no_grad():
+                for tr in (0, 1):
+                    self.img_in_lq = hip.dihedral_expand(fed['img_in_lq'].contiguous(), tr)
+                    self.match_img_in = hip.dihedral_expand(fed['match_img_in'].contiguous(), tr)
+                    self.img_ref_stack = hip.dihedral_expand(fed['img_ref_stack'].contiguous(), tr, outer=k)
+                    self.img_ref_list = list(self.img_ref_stack.view(k, 4 * b, *self.img_ref_stack.shape[1:]).unbind(0))
+                    if 'img_ref' in fed:
+                        self.img_ref = self.img_ref_stack
+                    if fed.get('ref_valid_bits') is not None:
+                        self.ref_valid_bits = fed['ref_valid_bits'].repeat(4)
+                    outs.append(self._test_pass(eager=True).contiguous())
+                    if tr == 0:
+                        max_idx = self.max_idx
+                self.output = hip.dihedral_merge(*outs)
+                self.max_idx = max_idx.view(k, 4, b, *max_idx.shape[1:])[:, 0].reshape(k * b, *max_idx.shape[1:])
+        finally:
+            for n, t in fed.items():
+                setattr(self, n, t)
+            if self.net_g is not self.net_g_ema:
+                self.net_g.train()
 
     # ------------------------------------------------------------------ hipGraph replay of the inference pass
     _INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack')
