@@ -617,6 +617,9 @@ int mrefsr_tap_crit_f32(const mrefsr_tap_job *jobs, int n_jobs, int crit, float 
 int mrefsr_gram_splits(int N, int HW, int C);
 int64_t mrefsr_gram_workspace_bytes(int N, int HW, int C);
 int mrefsr_gram_nhwc_f32(const float *f, int N, int HW, int C, float *gram, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+/* the same sums times `scale` instead of 1 / (C HW) (scale = 1: the raw Gram matrix of the texture loss) */
+int mrefsr_gram_nhwc_scaled_f32(const float *f, int N, int HW, int C, float scale, float *gram, void *workspace, int64_t workspace_bytes,
+                                mrefsr_stream_t stream);
 int mrefsr_gram_bwd_nhwc_f32(const float *f, const float *gx, const float *gg, float *df, int N, int HW, int C, const float *gup,
                              float loss_weight, float weight, int accumulate, float *amax, mrefsr_stream_t stream);
 /* gradient of mrefsr_image_to_nhwc4_f32: g4 [N][HW][ld] (channels 0..2 read) -> g_img [N][3][HW] = g / std3[c] (std3 may be NULL),
@@ -946,6 +949,45 @@ int mrefsr_r1_sqnorm_bwd_f32(const float *g, const float *gs, int batch, int64_t
  *   multiply behind them; bit-identical to the same chain written in torch.  out must not overlap a or b. */
 int mrefsr_dihedral_expand_f32(const float *src, float *dst, int outer, int inner, int C, int H, int W, int tr, mrefsr_stream_t stream);
 int mrefsr_dihedral_merge_f32(const float *a, const float *b, float *out, int N, int C, int H, int W, mrefsr_stream_t stream);
+
+/* ---- the texture loss of the training step and its swapped reference maps (csrc/texture.hip; train.texture_opt) ---------------------
+ * TextureLoss.forward(x, maps, weights) of basicsr/models/losses.py:430-532 with use_weights and a tensor `weights`; the maps and
+ * weights themselves have no reference counterpart (the reference model reads them, nothing sets them): DESIGN 3.13.
+ * LR map h x w at relu3_1, match grid gh x gw = (h - 2) x (w - 2), P = gh gw, scales s = 1, 2, 4.
+ *
+ * mrefsr_texture_select_f32: idx (int64), val [K][B][P] -> sel [B][P] = the reference k whose bit is set in valid_bits[b] (NULL: all
+ *   present) with the largest val, the lowest such k among equal values; weights [B][P] = that value; pidx [B][P] = idx[sel].
+ * mrefsr_texture_swap_nhwc_f32: feat [K][B][s h][s w][C] (C % 4 == 0, 16-byte aligned) -> out [B][s h][s w][C]: every match position
+ *   (y, x) pastes the 3 s x 3 s reference patch at (s iy, s ix), (iy, ix) = divmod(pidx, gw), of reference sel over (s y, s x);
+ *   out = (sum of the 1..9 patches that cover the pixel, added in ascending (y, x) order in fp32) / their number, the division
+ *   correctly rounded.  sel and pidx are clamped to their ranges: no read leaves feat.
+ * mrefsr_texture_coeff_f32: weights [B][gh][gw] -> c_s [B][s h][s w] = sigmoid(-20 u + 0.65), u = bicubic resize by s with
+ *   align_corners (torch's upsample_bicubic2d: A = -0.75, clamped taps) of the weights replicate-padded by 1; evaluated in fp64 and
+ *   rounded once.  Any of c1, c2, c4 may be NULL.
+ * mrefsr_texture_scale_nhwc_f32: out [n_px][C] = f [n_px][C] * coeff [n_px].
+ * mrefsr_texture_crit_f32: per layer norms[l] = ||gx - gm||_F over its n = N C C elements (fp64 sums in a fixed order through
+ *   partial, a workspace of MREFSR_TEXTURE_MAX_LAYERS * MREFSR_TEXTURE_CRIT_BLOCKS doubles),
+ *   terms[l] = norms[l] / 4 / div, total = ((sum_l terms[l]) / 3) * loss_weight (fp32, layers in the given order).
+ * mrefsr_texture_gram_bwd_nhwc_f32: df [N][HW][C] (+)= coeff (.) (2 Fc (gx - gm)) * ((gup * scale) / norm), all zeros where
+ *   *norm == 0; fc = f (.) coeff, gx = its raw Gram matrix, scale = loss_weight / 3 / 4 / div of the layer, gup device (NULL = 1);
+ *   v_mfma_f32_16x16x4_f32, C a multiple of 64; amax (may be NULL): max |df| into a zeroed word. */
+#define MREFSR_TEXTURE_MAX_LAYERS 3
+#define MREFSR_TEXTURE_CRIT_BLOCKS 64
+typedef struct mrefsr_texture_layer {
+    const float *gx, *gm;
+    int64_t n;
+    float div;
+} mrefsr_texture_layer;
+int mrefsr_texture_select_f32(const int64_t *idx, const float *val, const int32_t *valid_bits, int32_t *sel, float *weights, int32_t *pidx, int K,
+                              int B, int64_t P, mrefsr_stream_t stream);
+int mrefsr_texture_swap_nhwc_f32(const float *feat, const int32_t *sel, const int32_t *pidx, float *out, int K, int B, int h, int w, int s, int C,
+                                 mrefsr_stream_t stream);
+int mrefsr_texture_coeff_f32(const float *weights, float *c1, float *c2, float *c4, int B, int h, int w, mrefsr_stream_t stream);
+int mrefsr_texture_scale_nhwc_f32(const float *f, const float *coeff, float *out, int64_t n_px, int C, mrefsr_stream_t stream);
+int mrefsr_texture_crit_f32(const mrefsr_texture_layer *layers, int n_layers, float loss_weight, double *partial, float *norms, float *terms,
+                            float *total, mrefsr_stream_t stream);
+int mrefsr_texture_gram_bwd_nhwc_f32(const float *fc, const float *gx, const float *gm, const float *coeff, const float *norm, const float *gup,
+                                     float *df, int N, int HW, int C, float scale, int accumulate, float *amax, mrefsr_stream_t stream);
 
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words

@@ -34,6 +34,11 @@ class TapJob(C.Structure):
                 ('group', C.c_int32)]
 
 
+class TextureLayer(C.Structure):
+    """mirror of mrefsr_texture_layer"""
+    _fields_ = [('gx', C.c_void_p), ('gm', C.c_void_p), ('n', C.c_int64), ('div', C.c_float)]
+
+
 class OptimJob(C.Structure):
     """mirror of mrefsr_optim_job"""
     _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('m', C.c_void_p), ('v', C.c_void_p), ('ema', C.c_void_p), ('n', C.c_int64),
@@ -134,6 +139,7 @@ SIGNATURES = {
     'mrefsr_gram_splits': (_i, [_i, _i, _i]),
     'mrefsr_gram_workspace_bytes': (_i64, [_i, _i, _i]),
     'mrefsr_gram_nhwc_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _i64, _vp]),
+    'mrefsr_gram_nhwc_scaled_f32': (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _i64, _vp]),
     'mrefsr_gram_bwd_nhwc_f32': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _f, _i, _vp, _vp]),
     'mrefsr_image_to_nhwc4_bwd_f32': (_i, [_vp, _i, _vp, _i64, _i64, _i, _vp, _vp]),
     'mrefsr_disc_pack_image_f32': (_i, [_vp, _vp, _i, _i, _i, _vp]),
@@ -201,6 +207,12 @@ SIGNATURES = {
     'mrefsr_r1_sqnorm_bwd_f32': (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
     'mrefsr_dihedral_expand_f32': (_i, [_vp, _vp] + [_i] * 6 + [_vp]),
     'mrefsr_dihedral_merge_f32': (_i, [_vp, _vp, _vp] + [_i] * 4 + [_vp]),
+    'mrefsr_texture_select_f32': (_i, [_vp] * 6 + [_i, _i, _i64, _vp]),
+    'mrefsr_texture_swap_nhwc_f32': (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
+    'mrefsr_texture_coeff_f32': (_i, [_vp] * 4 + [_i, _i, _i, _vp]),
+    'mrefsr_texture_scale_nhwc_f32': (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
+    'mrefsr_texture_crit_f32': (_i, [C.POINTER(TextureLayer), _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    'mrefsr_texture_gram_bwd_nhwc_f32': (_i, [_vp] * 7 + [_i, _i, _i, _f, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -31,11 +31,16 @@ class CorrespondenceGenerationArch(nn.Module):
         return hip.offsets_from_idx(max_idx.unsqueeze(0).contiguous(), ph + 2, pw + 2, scales=(1,))[1][:, 0]
 
     @torch.no_grad()
-    def offsets(self, feat_in, feat_ref):
-        """feat_in [B,256,h,w], feat_ref [K*B,256,h,w] k-major -> dict of [K*B,9,sh,sw,2]."""
+    def offsets(self, feat_in, feat_ref, want_val=False):
+        """feat_in [B,256,h,w], feat_ref [K*B,256,h,w] k-major -> (dict of [K*B,9,sh,sw,2], max_idx [K*B,h-2,w-2]); with want_val
+        also max_val (the winning scores, fp32 of max_idx's shape) as a third value -- the index bits are the same either way."""
         h, w = feat_in.shape[2:]
+        val = None
         if self.patch_size == 3 and self.stride == 1:
-            idx = match_normalised_batch(feat_in, feat_ref)
+            if want_val:
+                idx, val = match_normalised_batch(feat_in, feat_ref, want_val=True)
+            else:
+                idx = match_normalised_batch(feat_in, feat_ref)
         else:
             # any other patch size / stride (the reference's ctor takes them, :14-28; no shipped yml does): the general
             # kernel (mrefsr_feature_match_index_f32) pair by pair on the per-pixel-normalised maps (:57-68).  As in the
@@ -44,11 +49,13 @@ class CorrespondenceGenerationArch(nn.Module):
             from .ref_map_util import feature_match_index
             b = feat_in.shape[0]
             nrm = [torch.nn.functional.normalize(f.reshape(f.shape[0], f.shape[1], -1).float(), dim=1).view_as(f) for f in (feat_in, feat_ref)]
-            idx = torch.stack([feature_match_index(nrm[0][i % b], nrm[1][i], self.patch_size, self.stride, self.stride, True, True)[0]
-                               for i in range(feat_ref.shape[0])])
+            pairs = [feature_match_index(nrm[0][i % b], nrm[1][i], self.patch_size, self.stride, self.stride, True, True)
+                     for i in range(feat_ref.shape[0])]
+            idx, val = torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
             h, w = idx.shape[1] + 2, idx.shape[2] + 2
         offs = hip.offsets_from_idx(idx.contiguous(), h, w)
-        return {'relu3_1': offs[1], 'relu2_1': offs[2], 'relu1_1': offs[4]}, idx
+        out = {'relu3_1': offs[1], 'relu2_1': offs[2], 'relu1_1': offs[4]}
+        return (out, idx, val) if want_val else (out, idx)
 
     def forward(self, dense_features, img_ref_hr):
         pre_offset, _ = self.offsets(dense_features['dense_features1'], dense_features['dense_features2'])

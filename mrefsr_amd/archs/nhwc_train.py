@@ -655,6 +655,91 @@ class VggLossPlan:
         self.crit, self.pw, self.sw, self.norm_img = criterion, float(perceptual_weight), float(style_weight), bool(norm_img)
 
 
+def _vgg_stack_forward(plan, img, mean, std):
+    """the tapped VGG stack on the images img [N,3,H,W] -> (tap features [N,h,w,c] in the order of plan.taps, what the backward
+    needs per layer: (mask source, its ReLU not applied yet, pool plane, pool input shape))"""
+    h = hip.image_to_nhwc4(img, mean, std, plan.norm_img)
+    saved = []
+    tapv = {}           # (layer, kind) -> [N,h,w,c] tensor
+    last = len(plan.layers) - 1
+    tapped = {(i, k) for i, k, _ in plan.taps}
+    for i, l in enumerate(plan.layers):
+        conv, names = l['conv'], l['names']
+        relu, pool = 'relu' in names, 'pool' in names
+        tc, tr, tp = (i, 'conv') in tapped, (i, 'relu') in tapped, (i, 'pool') in tapped
+        need_t = tc or not relu
+        need_r = relu and (tr or (not pool and i < last) or not need_t)
+        cout = conv.out_channels
+        bias = conv.bias.detach() if conv.bias is not None else None
+        pk, _ = _vgg_pack(conv.weight, (0, conv.in_channels), False)
+        t = hip.conv_nhwc(h, pk, bias, cout, 3) if need_t else None
+        r = hip.conv_nhwc(h, pk, bias, cout, 3, act=True, slope=0.0) if need_r else None
+        src = r if r is not None else t
+        plane = None
+        if pool:
+            h, plane = hip.maxpool2_nhwc(src, relu=r is None, want_plane=POOL_PLANE)
+        else:
+            h = src
+        saved.append((src if (relu or pool) else None, r is None, plane, tuple(src.shape)))
+        if tc:
+            tapv[(i, 'conv')] = t
+        if tr:
+            tapv[(i, 'relu')] = r
+        if tp:
+            tapv[(i, 'pool')] = h
+    return [tapv[(i, k)] for i, k, _ in plan.taps], saved
+
+
+def _vgg_stack_backward(plan, b, saved, std, add_tap):
+    """input gradients of the first b images back through the stack (the VGG is frozen: no weight gradients) -> d loss / d image
+    [b,3,H,W], or None when no tap gave a gradient.  add_tap(g, i, kind) -> (g (None = zero) + the loss gradient of that tap,
+    max |g| or None) is called for every tap position in reverse network order."""
+    tapped = {(i, k) for i, k, _ in plan.taps}
+    g, amax, masked = None, None, False
+    for i in reversed(range(len(plan.layers))):
+        l = plan.layers[i]
+        conv, names = l['conv'], l['names']
+        src, relu_in, plane, shape = saved[i]
+        if 'pool' in names:
+            g, a = add_tap(g, i, 'pool')
+            amax = a if a is not None else amax
+            if g is not None:
+                tr = (i, 'relu') in tapped
+                g, amax = hip.maxpool2_bwd_nhwc(g, None if plane is not None else src[:b], plane[:b] if plane is not None else None,
+                                                relu=relu_in, mask=not tr, shape=(b,) + shape[1:])
+                if tr:
+                    g, _ = add_tap(g, i, 'relu')
+                    g, _, _, amax = hip.act_bwd_nhwc(g, src[:b], 1, 0.0, want_bias=False, want_amax=True)
+        elif 'relu' in names and not masked:
+            g, a = add_tap(g, i, 'relu')
+            amax = a if a is not None else amax
+            if g is not None:
+                g, _, _, amax = hip.act_bwd_nhwc(g, src[:b], 1, 0.0, want_bias=False, want_amax=True)
+        g, a = add_tap(g, i, 'conv')
+        amax = a if a is not None else amax
+        if g is None:
+            continue
+        cin = conv.in_channels
+        pk, terms = _vgg_pack(conv.weight, (0, cin), True)
+        masked = False
+        if i == 0:
+            g4 = torch.empty(g.shape[:3] + (4,), device=g.device, dtype=torch.float32)
+            hip.conv_nhwc(g, pk, None, cin, 3, out=g4[..., :cin], in_amax=amax if terms == 16 else None)
+            g_x = hip.image_to_nhwc4_bwd(g4, plan.norm_img, std)
+            return g_x
+        prev = plan.layers[i - 1]['names']
+        psrc = saved[i - 1][0]
+        if terms == 16 and 'relu' in prev and 'pool' not in prev and (i - 1, 'relu') not in tapped and cin % 4 == 0:
+            # the ReLU of the layer below rides on this input-gradient launch (its mask from the stored map), with max |g| of the
+            # result for the next input-gradient convolution (mrefsr_conv_nhwc_bwd_f32)
+            g, _, amax = hip.conv_nhwc_bwd(g, pk, cin, 3, residual=psrc[:b], residual_is_mask=True, in_amax=amax)
+            masked = True
+        else:
+            g = hip.conv_nhwc(g, pk, None, cin, 3, in_amax=amax if terms == 16 else None)
+            amax = None
+    return None
+
+
 class _VggLoss(Function):
     """(output x, gt) -> [perceptual total, style total] of PerceptualLoss with one VGG: the output and the GT run as ONE 2B batch
     through the convolution kernels (the same arithmetic for both feature sets, half the launches); the backward runs the input
@@ -664,36 +749,7 @@ class _VggLoss(Function):
     def forward(ctx, x, gt, plan, mean, std):
         b = x.shape[0]
         img = torch.cat([x.detach(), gt.detach()]).contiguous()
-        h = hip.image_to_nhwc4(img, mean, std, plan.norm_img)
-        saved = []          # per layer: (mask source, its ReLU not applied yet, pool plane, pool input shape)
-        tapv = {}           # (layer, kind) -> [2B,h,w,c] tensor
-        last = len(plan.layers) - 1
-        tapped = {(i, k) for i, k, _ in plan.taps}
-        for i, l in enumerate(plan.layers):
-            conv, names = l['conv'], l['names']
-            relu, pool = 'relu' in names, 'pool' in names
-            tc, tr, tp = (i, 'conv') in tapped, (i, 'relu') in tapped, (i, 'pool') in tapped
-            need_t = tc or not relu
-            need_r = relu and (tr or (not pool and i < last) or not need_t)
-            cout = conv.out_channels
-            bias = conv.bias.detach() if conv.bias is not None else None
-            pk, _ = _vgg_pack(conv.weight, (0, conv.in_channels), False)
-            t = hip.conv_nhwc(h, pk, bias, cout, 3) if need_t else None
-            r = hip.conv_nhwc(h, pk, bias, cout, 3, act=True, slope=0.0) if need_r else None
-            src = r if r is not None else t
-            plane = None
-            if pool:
-                h, plane = hip.maxpool2_nhwc(src, relu=r is None, want_plane=POOL_PLANE)
-            else:
-                h = src
-            saved.append((src if (relu or pool) else None, r is None, plane, tuple(src.shape)))
-            if tc:
-                tapv[(i, 'conv')] = t
-            if tr:
-                tapv[(i, 'relu')] = r
-            if tp:
-                tapv[(i, 'pool')] = h
-        feats = [tapv[(i, k)] for i, k, _ in plan.taps]
+        feats, saved = _vgg_stack_forward(plan, img, mean, std)
         if KEEP_TAPS is not None:
             KEEP_TAPS.append(feats)
         ws = [w for _, _, w in plan.taps]
@@ -745,49 +801,8 @@ class _VggLoss(Function):
                                          norm=losses[j:j + 1] if plan.crit == 'fro' else None, accumulate=acc)
             return g, amax
 
-        g, amax, masked = None, None, False
-        for i in reversed(range(len(plan.layers))):
-            l = plan.layers[i]
-            conv, names = l['conv'], l['names']
-            src, relu_in, plane, shape = saved[i]
-            if 'pool' in names:
-                g, a = add_tap(g, i, 'pool')
-                amax = a if a is not None else amax
-                if g is not None:
-                    tr = (i, 'relu') in tap_of
-                    g, amax = hip.maxpool2_bwd_nhwc(g, None if plane is not None else src[:b], plane[:b] if plane is not None else None,
-                                                    relu=relu_in, mask=not tr, shape=(b,) + shape[1:])
-                    if tr:
-                        g, _ = add_tap(g, i, 'relu')
-                        g, _, _, amax = hip.act_bwd_nhwc(g, src[:b], 1, 0.0, want_bias=False, want_amax=True)
-            elif 'relu' in names and not masked:
-                g, a = add_tap(g, i, 'relu')
-                amax = a if a is not None else amax
-                if g is not None:
-                    g, _, _, amax = hip.act_bwd_nhwc(g, src[:b], 1, 0.0, want_bias=False, want_amax=True)
-            g, a = add_tap(g, i, 'conv')
-            amax = a if a is not None else amax
-            if g is None:
-                continue
-            cin = conv.in_channels
-            pk, terms = _vgg_pack(conv.weight, (0, cin), True)
-            masked = False
-            if i == 0:
-                g4 = torch.empty(g.shape[:3] + (4,), device=g.device, dtype=torch.float32)
-                hip.conv_nhwc(g, pk, None, cin, 3, out=g4[..., :cin], in_amax=amax if terms == 16 else None)
-                g_x = hip.image_to_nhwc4_bwd(g4, plan.norm_img, std)
-                return g_x, None, None, None, None
-            prev = plan.layers[i - 1]['names']
-            psrc = saved[i - 1][0]
-            if terms == 16 and 'relu' in prev and 'pool' not in prev and (i - 1, 'relu') not in tap_of and cin % 4 == 0:
-                # the ReLU of the layer below rides on this input-gradient launch (its mask from the stored map), with max |g| of the
-                # result for the next input-gradient convolution (mrefsr_conv_nhwc_bwd_f32)
-                g, _, amax = hip.conv_nhwc_bwd(g, pk, cin, 3, residual=psrc[:b], residual_is_mask=True, in_amax=amax)
-                masked = True
-            else:
-                g = hip.conv_nhwc(g, pk, None, cin, 3, in_amax=amax if terms == 16 else None)
-                amax = None
-        return None, None, None, None, None
+        g_x = _vgg_stack_backward(plan, b, saved, std, add_tap)
+        return g_x, None, None, None, None
 
 
 def perceptual(vgg, x, gt, plan):
@@ -799,6 +814,102 @@ def perceptual(vgg, x, gt, plan):
     mean = vgg.mean.contiguous() if vgg.use_input_norm else None
     std = vgg.std.contiguous() if vgg.use_input_norm else None
     return _VggLoss.apply(x, gt, plan, mean, std)
+
+
+# ---- texture loss (TextureLoss, losses.py:430-532 of the reference model's loss module) -----------------------------
+TEXTURE_LAYERS = {'relu3_1': (1, 256), 'relu2_1': (2, 512), 'relu1_1': (4, 1024)}   # name -> (scale of its map, the reference's div_num)
+
+
+class TextureLossPlan(VggLossPlan):
+    """VggLossPlan of a TextureLoss: the taps are keys of TEXTURE_LAYERS (their weights are ignored, as in the reference); no image
+    range normalisation"""
+
+    def __init__(self, vgg_net, layer_names, loss_weight):
+        bad = [n for n in layer_names if n not in TEXTURE_LAYERS]
+        if bad or not layer_names:
+            raise NotImplementedError(f'TextureLoss: layers {sorted(layer_names)}; only relu1_1, relu2_1 and relu3_1 have a scale and a '
+                                      'divisor in the reference (it raises for any other)')
+        super().__init__(vgg_net, {n: 1.0 for n in layer_names}, 'texture', 0.0, 0.0, False)
+        self.names = [self.layers[i]['names'][kind] for i, kind, _ in self.taps]   # network order: the reference's summation order
+        self.loss_weight = float(loss_weight)
+
+
+class _VggTexture(Function):
+    """(output x, per tap: coeff [B,h,w] and the Gram matrix of the weighted swapped maps [B,C,C]) -> the texture loss [1]: x through
+    the VGG kernels, Fc = F * coeff, raw Gram matrices on the f32 MFMA, the Frobenius criterion of csrc/texture.hip; the backward
+    adds each tap's gradient where the style term adds its own and runs the input gradients back to x."""
+
+    @staticmethod
+    def forward(ctx, x, plan, mean, std, *cg):
+        import numpy as np
+        nt = len(plan.taps)
+        coeffs, gms = cg[:nt], cg[nt:]
+        feats, saved = _vgg_stack_forward(plan, x.detach().contiguous(), mean, std)
+        fcs = [hip.texture_scale_nhwc(f, c) for f, c in zip(feats, coeffs)]
+        gxs = [hip.gram_raw_nhwc(fc) for fc in fcs]
+        size = x.shape[-1]
+        # (input_size^2 div_num)^2: a Python int in the reference, which torch rounds to fp32 for the division
+        divs = [float(np.float32((size * size * TEXTURE_LAYERS[n][1]) ** 2)) for n in plan.names]
+        norms, terms, total = hip.texture_crit(gxs, gms, divs, plan.loss_weight)
+        ctx.plan, ctx.saved, ctx.divs = plan, saved, divs
+        ctx.save_for_backward(std, norms, *fcs, *gxs, *gms, *coeffs)
+        ctx.mark_non_differentiable(terms)
+        return total, terms
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_tot, _g_terms):
+        plan, saved = ctx.plan, ctx.saved
+        st = ctx.saved_tensors
+        std, norms = st[0], st[1]
+        nt = len(plan.taps)
+        fcs, gxs, gms, coeffs = (st[2 + j * nt:2 + (j + 1) * nt] for j in range(4))
+        g_tot = g_tot.contiguous()
+        tap_of = {(i, k): j for j, (i, k, _) in enumerate(plan.taps)}
+        b = fcs[0].shape[0]
+
+        def add_tap(g, i, kind):
+            j = tap_of.get((i, kind))
+            if j is None:
+                return g, None
+            acc = g is not None
+            if g is None:
+                g = torch.empty_like(fcs[j])
+            scale = plan.loss_weight / 3.0 / 4.0 / ctx.divs[j]
+            return g, hip.texture_gram_bwd_nhwc(fcs[j], gxs[j], gms[j], coeffs[j], norms[j:j + 1], g, scale, gup=g_tot, accumulate=acc)
+
+        g_x = _vgg_stack_backward(plan, b, saved, std, add_tap)
+        return (g_x,) + (None,) * (3 + 2 * nt)
+
+
+def texture_targets(plan, maps, weights):
+    """what TextureLoss needs of the swapped maps, computed once per step without autograd: per tap (network order) the coefficient map
+    coeff [B,h,w] and the raw Gram matrix of maps * coeff.  maps: name -> [B,C,h,w] (read, never written); weights [B,1,gh,gw]."""
+    with torch.no_grad():
+        coeff = hip.texture_coeff(weights.detach().contiguous())
+        coeffs, gms = [], []
+        for name in plan.names:
+            m = maps[name].detach().permute(0, 2, 3, 1)
+            c = coeff[TEXTURE_LAYERS[name][0]]
+            if tuple(m.shape[:3]) != tuple(c.shape):
+                raise ValueError(f'TextureLoss: maps[{name!r}] is {tuple(maps[name].shape)}, but the weights {tuple(weights.shape)} give a '
+                                 f'coefficient map of {tuple(c.shape)} at that layer')
+            coeffs.append(c)
+            gms.append(hip.gram_raw_nhwc(hip.texture_scale_nhwc(m.contiguous(), c)))
+    return coeffs, gms
+
+
+def texture(vgg, x, maps, weights, plan):
+    """TextureLoss.forward on the training engine: -> (loss [1], per-layer terms [L] in network order, detached); autograd reaches x"""
+    if not (x.is_cuda and weights.is_cuda and all(maps[n].is_cuda for n in plan.names)):
+        raise NotImplementedError('TextureLoss: mrefsr_amd has no CPU path (HIP kernels only)')
+    if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or weights.dtype != torch.float32 or \
+            any(maps[n].dtype != torch.float32 or maps[n].dim() != 4 or maps[n].shape[0] != x.shape[0] for n in plan.names):
+        raise ValueError(f'TextureLoss: a float32 [N,3,H,W] image, float32 [N,C,h,w] maps and float32 weights expected, got x {tuple(x.shape)}')
+    coeffs, gms = texture_targets(plan, maps, weights)
+    mean = vgg.mean.contiguous() if vgg.use_input_norm else None
+    std = vgg.std.contiguous() if vgg.use_input_norm else None
+    return _VggTexture.apply(x, plan, mean, std, *coeffs, *gms)
 
 
 def recording(*tensors):

@@ -50,10 +50,11 @@ def feature_match_index(feat_input, feat_ref, patch_size=3, input_stride=1, ref_
     return idx[0], val[0]
 
 
-def match_normalised_batch(feat_in, feat_ref):
+def match_normalised_batch(feat_in, feat_ref, want_val=False):
     """The batched form the path uses: feat_in [B,C,h,w], feat_ref [K*B,C,h,w] (k-major), raw
     extractor outputs.  Per-pixel normalisation (corres_generation_arch.py:57-59) is fused into
-    the layout pass.  Returns max_idx [K*B,h-2,w-2] int64."""
+    the layout pass.  Returns max_idx [K*B,h-2,w-2] int64; with want_val (max_idx, max_val fp32 of that shape): the same
+    launches and index bits, the kernels also store the winning score (the texture loss's match confidence)."""
     h, w = feat_in.shape[2:]
 
     # pre-filter operand: one fp16 plane (256 channels, the path) or the bf16 hi|lo split
@@ -81,5 +82,5 @@ def match_normalised_batch(feat_in, feat_ref):
     _, inv_ref = hip.patch_norm(n2_ref)
     if fmt == 'fp16' and not _EXACT_ONLY:
         tau = hip.prefilter_window(nrm_in, inv_ref, d2_in, d2_ref)   # data-dependent, proven window
-    idx, _ = hip.corr_top1(y_in, y_ref, inv_ref, nrm_in, h, w, want_val=False, ybf_in=bf_in, ybf_ref=bf_ref, tau=tau)
-    return idx
+    idx, val = hip.corr_top1(y_in, y_ref, inv_ref, nrm_in, h, w, want_val=bool(want_val), ybf_in=bf_in, ybf_ref=bf_ref, tau=tau)
+    return (idx, val) if want_val else idx

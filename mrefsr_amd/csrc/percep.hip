@@ -4,7 +4,7 @@
 //   maxpool2_nhwc        MaxPool2d(2, 2) (floor sizes, torch's tie rule), optional 3-bit arg-max / sign plane
 //   maxpool2_bwd_nhwc    its backward fused with the preceding ReLU's mask, + max |g| for the fp16-split dgrad
 //   tap_crit             L1 / Frobenius criterion of several taps: loss partials (fixed order) and / or the gradient
-//   gram_nhwc            G[n] = F^T F / (c h w) on v_mfma_f32_16x16x4_f32, upper tiles, split-K, fixed-order second stage
+//   gram_nhwc            G[n] = F^T F / (c h w) (or times a given scale: the texture loss's raw Gram, texture.hip) on v_mfma_f32_16x16x4_f32, upper tiles, split-K, fixed-order second stage
 //   gram_bwd_nhwc        dF += (2 / (c h w)) F S, S = d loss / d G formed inside from G(x) and G(gt), same MFMA
 //   image_to_nhwc4_bwd   gradient of the image packing + normalisation (fused_act.hip: image_to_nhwc4) -> [N][3][HW]
 // All element-wise / reduction kernels are HBM-bound; the Gram products are a few GFLOP per step.
@@ -461,8 +461,8 @@ MREFSR_EXPORT int64_t mrefsr_gram_workspace_bytes(int N, int HW, int C)
     return s < 0 ? -1 : (int64_t)s * N * C * C * 4;
 }
 
-MREFSR_EXPORT int mrefsr_gram_nhwc_f32(const float *f, int N, int HW, int C, float *gram, void *workspace, int64_t workspace_bytes,
-                                       mrefsr_stream_t stream)
+MREFSR_EXPORT int mrefsr_gram_nhwc_scaled_f32(const float *f, int N, int HW, int C, float scale, float *gram, void *workspace,
+                                              int64_t workspace_bytes, mrefsr_stream_t stream)
 {
     MREFSR_REQUIRE(f && gram && workspace, "gram_nhwc: null pointer");
     const int S = mrefsr_gram_splits(N, HW, C);
@@ -475,8 +475,14 @@ MREFSR_EXPORT int mrefsr_gram_nhwc_f32(const float *f, int N, int HW, int C, flo
     hipLaunchKernelGGL(gram_kernel, dim3(T * (T + 1) / 2, S_used, N), dim3(256), 0, st, f, N, HW, C, S_used, chunk, (float *)workspace);
     const long total = (long)N * C * C;
     hipLaunchKernelGGL(gram_finish_kernel, dim3(grid_of((total + 255) / 256, 4096)), dim3(256), 0, st, (const float *)workspace, gram, N, C,
-                       S_used, 1.0f / ((float)C * (float)HW));
+                       S_used, scale);
     return mrefsr::check_launch("gram_nhwc");
+}
+
+MREFSR_EXPORT int mrefsr_gram_nhwc_f32(const float *f, int N, int HW, int C, float *gram, void *workspace, int64_t workspace_bytes,
+                                       mrefsr_stream_t stream)
+{
+    return mrefsr_gram_nhwc_scaled_f32(f, N, HW, C, 1.0f / ((float)C * (float)HW), gram, workspace, workspace_bytes, stream);
 }
 
 MREFSR_EXPORT int mrefsr_gram_bwd_nhwc_f32(const float *f, const float *gx, const float *gg, float *df, int N, int HW, int C, const float *gup,

@@ -1673,6 +1673,122 @@ def gram_bwd_nhwc(f, gx, gg, df, loss_weight, weight, gup=None, accumulate=False
     return amax
 
 
+# ------------------------------------------------------------------ texture loss and its swapped maps (csrc/texture.hip)
+def texture_select(idx, val, valid_bits=None):
+    """idx int64, val fp32 [K,B,gh,gw] (the matcher's outputs, k-major) -> (sel int32 [B,gh,gw]: the present reference with the
+    largest val, the lowest k among equal ones; weights fp32 [B,1,gh,gw]: that value; pidx int32 [B,gh,gw]: idx[sel]).
+    valid_bits: int32 [B], bit k = reference k of the sample is present (None: all)."""
+    _chk('texture_select', idx, dtype=torch.int64)
+    _chk('texture_select', val)
+    if idx.dim() != 4 or idx.shape != val.shape or idx.shape[0] > 32:
+        raise ValueError(f'texture_select: idx / val must be [K,B,gh,gw] with K <= 32, got {tuple(idx.shape)} / {tuple(val.shape)}')
+    k, b, gh, gw = idx.shape
+    if valid_bits is not None:
+        _chk_valid_bits('texture_select', valid_bits, b)
+    sel = torch.empty((b, gh, gw), device=idx.device, dtype=torch.int32)
+    pidx = torch.empty_like(sel)
+    wts = torch.empty((b, 1, gh, gw), device=idx.device, dtype=torch.float32)
+    with _timed('texture_select', detail=True, nbytes=12.0 * idx.numel() + 12.0 * sel.numel()):
+        _lib.call('mrefsr_texture_select_f32', _p(idx), _p(val), _p(valid_bits), _p(sel), _p(wts), _p(pidx), k, b, C.c_int64(gh * gw), _stream())
+    return sel, wts, pidx
+
+
+def texture_swap_nhwc(feat, sel, pidx, k, s):
+    """feat [K*B,s*h,s*w,C] (the references' k-major NHWC maps, read in place), sel / pidx int32 [B,h-2,w-2] from texture_select ->
+    [B,s*h,s*w,C]: the matched 3s x 3s reference patches pasted at (s*y, s*x), overlaps averaged (ascending (y, x), fp32)"""
+    _chk('texture_swap_nhwc', feat)
+    _chk('texture_swap_nhwc', sel, pidx, dtype=torch.int32)
+    if sel.dim() != 3 or sel.shape != pidx.shape or feat.dim() != 4:
+        raise ValueError('texture_swap_nhwc: feat [K*B,sh,sw,C], sel / pidx [B,h-2,w-2] expected')
+    b, gh, gw = sel.shape
+    kb, sh, sw, c = feat.shape
+    if kb != k * b or sh != s * (gh + 2) or sw != s * (gw + 2) or c % 4 or gh < 1 or gw < 1:
+        raise ValueError(f'texture_swap_nhwc: feat {tuple(feat.shape)} does not fit K={k}, scale {s} and the match grid {(b, gh, gw)} '
+                         '(C a multiple of 4)')
+    out = torch.empty((b, sh, sw, c), device=feat.device, dtype=torch.float32)
+    with _timed('texture_swap_nhwc', detail=True, nbytes=4.0 * out.numel() * (1 + 9)):
+        _lib.call('mrefsr_texture_swap_nhwc_f32', _p(feat), _p(sel), _p(pidx), _p(out), k, b, gh + 2, gw + 2, s, c, _stream())
+    return out
+
+
+def texture_coeff(weights, scales=(1, 2, 4)):
+    """weights [B,1,gh,gw] -> {s: [B,s*(gh+2),s*(gw+2)]} = sigmoid(-20 * bicubic_s(replicate_pad(weights, 1)) + 0.65)
+    (align_corners=True, torch's upsample_bicubic2d), all scales in one launch"""
+    _chk('texture_coeff', weights)
+    if weights.dim() != 4 or weights.shape[1] != 1 or weights.shape[2] < 1 or weights.shape[3] < 1 or not set(scales) <= {1, 2, 4}:
+        raise ValueError(f'texture_coeff: weights [B,1,gh,gw] and scales out of (1, 2, 4) expected, got {tuple(weights.shape)} / {scales}')
+    b, _, gh, gw = weights.shape
+    h, w = gh + 2, gw + 2
+    outs = {s: torch.empty((b, s * h, s * w), device=weights.device, dtype=torch.float32) for s in scales}
+    with _timed('texture_coeff', detail=True, nbytes=4.0 * sum(o.numel() for o in outs.values())):
+        _lib.call('mrefsr_texture_coeff_f32', _p(weights), _p(outs.get(1)), _p(outs.get(2)), _p(outs.get(4)), b, h, w, _stream())
+    return outs
+
+
+def texture_scale_nhwc(f, coeff):
+    """f [N,H,W,C] * coeff [N,H,W] (broadcast over the channels) -> [N,H,W,C]"""
+    _chk('texture_scale_nhwc', f, coeff)
+    if f.dim() != 4 or tuple(coeff.shape) != tuple(f.shape[:3]) or f.shape[3] % 4:
+        raise ValueError(f'texture_scale_nhwc: f [N,H,W,C] (C a multiple of 4) and coeff [N,H,W] expected, got {tuple(f.shape)} / '
+                         f'{tuple(coeff.shape)}')
+    out = torch.empty_like(f)
+    with _timed('texture_scale_nhwc', detail=True, nbytes=8.0 * f.numel()):
+        _lib.call('mrefsr_texture_scale_nhwc_f32', _p(f), _p(coeff), _p(out), C.c_int64(coeff.numel()), f.shape[3], _stream())
+    return out
+
+
+def gram_raw_nhwc(f):
+    """f [N,H,W,C] (C a multiple of 64) -> [N,C,C] = F^T F per image, not normalised: gram_nhwc's kernels with scale 1"""
+    _chk('gram_raw_nhwc', f)
+    n, h, w, c = f.shape
+    lib = _lib.load()
+    need = lib.mrefsr_gram_workspace_bytes(n, h * w, c)
+    if need < 0:
+        raise ValueError(f'gram_raw_nhwc: C={c} (a multiple of 64)')
+    ws = _wgrad_workspace(f.device, need)
+    g = torch.empty((n, c, c), device=f.device, dtype=torch.float32)
+    with _timed('gram_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (f.numel() + g.numel())):
+        _lib.call('mrefsr_gram_nhwc_scaled_f32', _p(f), n, h * w, c, C.c_float(1.0), _p(g), _p(ws), C.c_int64(need), _stream())
+    return g
+
+
+def texture_crit(gxs, gms, divs, loss_weight):
+    """Gram matrices gxs[l], gms[l] [N,C_l,C_l] of up to three layers -> (norms [L] = ||gx - gm||_F over the whole tensor,
+    terms [L] = norms / 4 / divs[l], total [1] = (sum(terms) / 3) * loss_weight): fixed summation order, nothing read back"""
+    if not 1 <= len(gxs) <= 3 or len(gms) != len(gxs) or len(divs) != len(gxs):
+        raise ValueError('texture_crit: one to three layers, as many gms and divs as gxs')
+    layers = (_lib.TextureLayer * len(gxs))()
+    for l, (gx, gm) in enumerate(zip(gxs, gms)):
+        _chk('texture_crit', gx, gm)
+        if gx.shape != gm.shape:
+            raise ValueError(f'texture_crit: layer {l}: gx {tuple(gx.shape)} / gm {tuple(gm.shape)} differ')
+        layers[l] = _lib.TextureLayer(gx.data_ptr(), gm.data_ptr(), gx.numel(), float(divs[l]))
+    dev = gxs[0].device
+    norms = torch.empty(len(gxs), device=dev, dtype=torch.float32)
+    terms = torch.empty(len(gxs), device=dev, dtype=torch.float32)
+    total = torch.empty(1, device=dev, dtype=torch.float32)
+    part = torch.empty(3 * 64, device=dev, dtype=torch.float64)   # MREFSR_TEXTURE_MAX_LAYERS * MREFSR_TEXTURE_CRIT_BLOCKS
+    with _timed('texture_crit', detail=True, nbytes=8.0 * sum(g.numel() for g in gxs)):
+        _lib.call('mrefsr_texture_crit_f32', layers, len(gxs), C.c_float(loss_weight), _p(part), _p(norms), _p(terms), _p(total), _stream())
+    return norms, terms, total
+
+
+def texture_gram_bwd_nhwc(fc, gx, gm, coeff, norm, df, scale, gup=None, accumulate=False, want_amax=True):
+    """df [N,H,W,C] (+)= d total / d f of one layer of texture_crit: coeff * (2 fc (gx - gm)) * ((gup * scale) / norm), exactly 0 where
+    norm == 0.  fc = texture_scale_nhwc(f, coeff), gx = gram_raw_nhwc(fc), norm [1] the layer's entry of texture_crit's norms,
+    scale = loss_weight / 3 / 4 / div, gup a device scalar or None (= 1).  -> max |df| [1] | None"""
+    _chk('texture_gram_bwd_nhwc', fc, gx, gm, coeff, norm, df, gup)
+    n, h, w, c = fc.shape
+    if tuple(gx.shape) != (n, c, c) or tuple(gm.shape) != (n, c, c) or tuple(df.shape) != tuple(fc.shape) or \
+            tuple(coeff.shape) != (n, h, w) or norm.numel() != 1 or (gup is not None and gup.numel() != 1):
+        raise ValueError('texture_gram_bwd_nhwc: inconsistent shapes')
+    amax = zeros_f32(fc.device, 1) if want_amax else None
+    with _timed('texture_gram_bwd_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (2 + accumulate) * fc.numel()):
+        _lib.call('mrefsr_texture_gram_bwd_nhwc_f32', _p(fc), _p(gx), _p(gm), _p(coeff), _p(norm), _p(gup), _p(df), n, h * w, c,
+                  C.c_float(scale), 1 if accumulate else 0, _p(amax), _stream())
+    return amax
+
+
 def image_to_nhwc4_bwd(g4, range_norm=False, std=None):
     """gradient of image_to_nhwc4(img, mean, std, range_norm): g4 [N,H,W,ld>=3] (pixel-contiguous) -> [N,3,H,W]"""
     n, h, w, _ = g4.shape

@@ -5,10 +5,10 @@ reference's names; ``build_loss`` selects one by ``type`` (the contract of basic
 from copy import deepcopy
 
 from ..utils.registry import LOSS_REGISTRY
-from .losses import (CharbonnierLoss, GANLoss, GradientPenaltyLoss, L1Loss, MSELoss, PerceptualLoss,
+from .losses import (CharbonnierLoss, GANLoss, GradientPenaltyLoss, L1Loss, MSELoss, PerceptualLoss, TextureLoss,
                      gradient_penalty_loss, r1_penalty)
 
-__all__ = ['build_loss', 'LOSS_REGISTRY', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'PerceptualLoss', 'GANLoss', 'GradientPenaltyLoss',
+__all__ = ['build_loss', 'LOSS_REGISTRY', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'PerceptualLoss', 'TextureLoss', 'GANLoss', 'GradientPenaltyLoss',
            'gradient_penalty_loss', 'r1_penalty']
 
 

@@ -1,5 +1,5 @@
-"""L1Loss, MSELoss, CharbonnierLoss, PerceptualLoss, GANLoss and GradientPenaltyLoss with the reference's constructor signatures
-and values (basicsr/models/losses.py:17-124, 141-238, 275-427), GANLoss's wgan_softplus type and r1_penalty from the newer
+"""L1Loss, MSELoss, CharbonnierLoss, PerceptualLoss, TextureLoss, GANLoss and GradientPenaltyLoss with the reference's constructor signatures
+and values (basicsr/models/losses.py:17-124, 141-238, 275-532), GANLoss's wgan_softplus type and r1_penalty from the newer
 basicsr/losses/losses.py:258-360, 391-405.
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
@@ -111,6 +111,59 @@ class PerceptualLoss(nn.Module):
                                                 self.style_weight, self.norm_img)
         totals = nhwc_train.perceptual(self.vgg, x, gt.detach(), self._plan)
         return (totals[0] if self.perceptual_weight > 0 else None), (totals[1] if self.style_weight > 0 else None)
+
+
+@LOSS_REGISTRY.register()
+class TextureLoss(nn.Module):
+    """Texture loss of reference-based SR (basicsr/models/losses.py:430-532): the Gram matrices of the output's VGG features against
+    those of the swapped reference maps, both weighted by the match confidence.
+
+    forward(x, maps, weights) -> scalar.  maps: {layer: [B,C,s h,s w]} for the keys of layer_weights (relu3_1, relu2_1, relu1_1 at
+    s = 1, 2, 4; the values of layer_weights are ignored, as in the reference); weights [B,1,h-2,w-2]: replicate-padded by 1, resized
+    bicubically (align_corners) by s, coeff = sigmoid(-20 w + 0.65); per layer ||G(x_feat coeff) - G(maps coeff)||_F over the whole
+    [B,C,C] tensor (G = F F^T per image, not normalised) / 4 / (x.shape[-1]^2 div)^2 with div = 256, 512, 1024; their sum / 3 *
+    loss_weight.  The gradient reaches x only, and is exactly 0 for a layer whose norm is 0.  The caller's maps are not written to
+    (the reference multiplies them by coeff in place).  Everything runs on the kernels of csrc/texture.hip and the VGG node of the
+    training engine (archs/nhwc_train.py: _VggTexture); ``last_terms`` holds the per-layer terms of the last call (network order).
+
+    Refused: use_weights=False (the reference's forward then reads a divisor it never set: UnboundLocalError), a dict of weights,
+    other layers, batch-normalised VGGs, CPU tensors."""
+
+    def __init__(self, use_weights=False, loss_weight=1.0, vgg_type='vgg19', layer_weights={'relu1_1': 1.0, 'relu2_1': 1.0, 'relu3_1': 1.0},
+                 use_input_norm=True):
+        super().__init__()
+        if not use_weights:
+            raise NotImplementedError("TextureLoss / texture_opt: use_weights: true is required -- without it the reference's forward fails "
+                                      '(UnboundLocalError: div_num is only set on the use_weights path)')
+        if 'bn' in vgg_type:
+            raise NotImplementedError(f'TextureLoss: vgg_type {vgg_type} (batch-normalised VGGs have no kernel here)')
+        from ..archs.nhwc_train import TEXTURE_LAYERS
+        bad = [k for k in layer_weights if k not in TEXTURE_LAYERS]
+        if bad or not layer_weights:
+            raise NotImplementedError(f'TextureLoss: layers {sorted(layer_weights)}; only relu1_1, relu2_1 and relu3_1 have a scale and a '
+                                      'divisor in the reference (it raises for any other)')
+        self.use_weights = use_weights
+        self.loss_weight = loss_weight
+        self.vgg = VGGFeatureExtractor(layer_name_list=list(layer_weights.keys()), vgg_type=vgg_type, use_input_norm=use_input_norm)
+        self._plan = None
+        self.last_terms = None
+
+    def forward(self, x, maps, weights=0):
+        from ..archs import nhwc_train
+        if isinstance(weights, dict):
+            raise NotImplementedError('TextureLoss: a dict of per-layer weights is not implemented; pass the [B,1,h-2,w-2] tensor')
+        if not torch.is_tensor(weights):
+            raise NotImplementedError('TextureLoss: weights must be the [B,1,h-2,w-2] tensor of match values (use_weights)')
+        if not (x.is_cuda and weights.is_cuda and all(torch.is_tensor(m) and m.is_cuda for m in maps.values())):
+            raise NotImplementedError('TextureLoss: mrefsr_amd has no CPU path (HIP kernels only)')
+        if self._plan is None:
+            self._plan = nhwc_train.TextureLossPlan(self.vgg.vgg_net, list(self.vgg.layer_name_list), self.loss_weight)
+        missing = [n for n in self._plan.names if n not in maps]
+        if missing:
+            raise ValueError(f'TextureLoss: maps has no entry for {missing}')
+        total, terms = nhwc_train.texture(self.vgg, x, maps, weights, self._plan)
+        self.last_terms = terms
+        return total[0]
 
 
 @LOSS_REGISTRY.register()

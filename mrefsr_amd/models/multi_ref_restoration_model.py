@@ -8,14 +8,17 @@ layout: Adam with four parameter groups chosen by name (:60-89) --
     'offset' & 'small'  -> lr_relu3_offset     'offset' & 'medium' -> lr_relu2_offset
     other 'offset'      -> lr_offset           everything else     -> lr_g
 Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLoss), perceptual_opt and style_opt
-(PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), and the adversarial term: network_d
+(PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), texture_opt with use_weights: true (TextureLoss; its
+swapped reference maps and weights, which the reference model reads but never sets, are built from the matcher's indices and values
+on the kernels of csrc/texture.hip: _texture_targets), and the adversarial term: network_d
 (ImageDiscriminator, VGGStyleDiscriminator, UNetDiscriminatorSN or StyleGAN2Discriminator, on the kernels of csrc/disc.hip, disc_vgg.hip,
 disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
 :272-276.  gan_type wgan_softplus and the lazily applied R1 penalty on the real images (train.r1_reg_weight, train.net_d_reg_every) are
 those of basicsr/losses/losses.py:284-318, 391-405 and basicsr/models/stylegan2_model.py:75-79, 198-221; lr_d and beta_d are used as
 written (stylegan2_model.py:135-143 rescales them by every / (every + 1): left to the configuration).
-Refused, not silently skipped: texture_opt and other discriminators (NotImplementedError); gan_type without network_d and the
+Refused, not silently skipped: texture_opt without use_weights: true (the reference cannot evaluate it either) and other
+discriminators (NotImplementedError); gan_type without network_d and the
 reverse, r1_reg_weight without network_d (NotImplementedError); an r1_reg_weight that is not a finite number of at least 0, a
 net_d_reg_every that is not an int of at least 1 or that comes without r1_reg_weight, bools for either (ValueError); the clipping,
 EMA and hip_adam options together with train.hip_graph (ValueError).
@@ -231,6 +234,7 @@ class MultiRefRestorationModel:
             self.log_dict[f'skipped_steps_{which}'] = state.skipped
 
     net_g_ema = None
+    cri_texture = None   # TextureLoss of train.texture_opt (init_training_settings)
 
     def _setup_ema(self):
         """train.ema_decay > 0 (sr_model.py:39-53): net_g_ema, a second network_g in eval mode without gradients, never wrapped in
@@ -280,9 +284,9 @@ class MultiRefRestorationModel:
     def init_training_settings(self):
         from .. import losses
         train_opt = self.opt['train']
-        if train_opt.get('texture_opt'):
-            raise NotImplementedError('train.texture_opt: the texture loss is not implemented (pixel, perceptual, style and adversarial '
-                                      'losses are; the reference model never sets the maps / weights it reads)')
+        if train_opt.get('texture_opt') and not train_opt['texture_opt'].get('use_weights'):
+            raise NotImplementedError("train.texture_opt: use_weights: true is required (without it the reference's TextureLoss.forward "
+                                      'fails on a divisor it never sets; the weighted form is the one implemented)')
         net_d_opt = self.opt.get('network_d')
         if net_d_opt and net_d_opt.get('type') not in ('ImageDiscriminator', 'VGGStyleDiscriminator', 'UNetDiscriminatorSN',
                                                        'UNetDiscriminatorSN_basicsr', 'StyleGAN2Discriminator'):
@@ -329,6 +333,8 @@ class MultiRefRestorationModel:
         # two PerceptualLoss instances, each with its own VGG, as in the reference (:126-141)
         self.cri_perceptual = losses.PerceptualLoss(**train_opt['perceptual_opt']).to(self.device) if train_opt.get('perceptual_opt') else None
         self.cri_style = losses.PerceptualLoss(**train_opt['style_opt']).to(self.device) if train_opt.get('style_opt') else None
+        # TextureLoss (ref :142-147); its maps and weights are built from the matcher's outputs in _texture_targets
+        self.cri_texture = losses.TextureLoss(**train_opt['texture_opt']).to(self.device) if train_opt.get('texture_opt') else None
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
@@ -400,11 +406,22 @@ class MultiRefRestorationModel:
         hip.amax_pool_reset()   # the max |out| words of this pass's launches (archs/nhwc.py: Winograd input scales): zeroed, slot 0
         with torch.no_grad():
             f1, f2 = self.net_extractor.forward_stacked(self.match_img_in, self.img_ref_stack)
-            pre_offset, self.max_idx = self.net_map.offsets(f1, f2)
-            img_ref_feat = self.net_map.vgg(self.img_ref_stack)
+            pre_offset, img_ref_feat = self._match(f1, f2, self.img_ref_stack)
         if self.ref_valid_bits is not None:
             return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k, ref_valid=self.ref_valid_bits)
         return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k)
+
+    def _match(self, f1, f2, refs):
+        """net_map on the extractor's features and the reference images: -> (pre_offset, the references' VGG maps); max_idx is kept,
+        and with a texture loss also max_val and the maps (_texture_targets reads them)"""
+        if self.cri_texture is not None:
+            pre_offset, self.max_idx, self.max_val = self.net_map.offsets(f1, f2, want_val=True)
+        else:
+            pre_offset, self.max_idx = self.net_map.offsets(f1, f2)
+        img_ref_feat = self.net_map.vgg(refs)
+        if self.cri_texture is not None:
+            self.img_ref_feat = img_ref_feat
+        return pre_offset, img_ref_feat
 
     range_fallbacks = 0   # batches re-run on the range-free kernels because an activation left the fp16 range
 
@@ -438,6 +455,24 @@ class MultiRefRestorationModel:
         hip.conv_range_tripped()
         return out
 
+    def _texture_targets(self):
+        """(maps, weights) of TextureLoss.forward, which the reference model reads and never sets: per match position
+        the present reference with the largest match value (hip.texture_select), weights = that value, maps = its matched 3s x 3s
+        patches of net_map.vgg's reference maps pasted at the position, overlaps averaged (hip.texture_swap_nhwc, on the maps where
+        they lie).  maps: {layer: [B,C,s h,s w]} (NCHW views of channels-last storage), weights [B,1,h-2,w-2]."""
+        from .. import hip
+        from ..archs.nhwc_train import TEXTURE_LAYERS
+        k = self.num_refs
+        idx = self.max_idx.reshape(k, -1, *self.max_idx.shape[1:]).contiguous()
+        val = self.max_val.reshape(idx.shape).contiguous()
+        with torch.no_grad():
+            sel, weights, pidx = hip.texture_select(idx, val, self.ref_valid_bits)
+            maps = {}
+            for name in self.cri_texture.vgg.layer_name_list:
+                feat = self.img_ref_feat[name].permute(0, 2, 3, 1).contiguous()   # (no copy: the engine's maps are channels-last)
+                maps[name] = hip.texture_swap_nhwc(feat, sel, pidx, k, TEXTURE_LAYERS[name][0]).permute(0, 3, 1, 2)
+        return maps, weights
+
     def _loss_and_backward(self, step):
         """net_g's losses of ref :197-279 and their backward: returns True when a gradient was produced (the optimiser may step)"""
         if step <= self.net_g_pretrain_steps:
@@ -460,6 +495,10 @@ class MultiRefRestorationModel:
                 _, l_g_style = self.cri_style(self.output, self.gt)
                 l_g_total = l_g_total + l_g_style
                 self.log_dict['l_g_style'] = l_g_style.detach()
+            if self.cri_texture is not None:   # ref :265-269
+                l_g_texture = self.cri_texture(self.output, *self._texture_targets())
+                l_g_total = l_g_total + l_g_texture
+                self.log_dict['l_g_texture'] = l_g_texture.detach()
             if self.net_d is not None:   # ref :272-276 (D's parameters are frozen: no weight gradient of D is computed)
                 fake_g_pred = self.net_d(self.output)
                 l_g_gan = self.cri_gan(fake_g_pred, True, is_disc=False)
@@ -478,11 +517,11 @@ class MultiRefRestorationModel:
         """opt['train']['hip_graph'] or MREFSR_TRAIN_GRAPH=1 (EXPERIMENTAL, off by default: 1-2 % at the shipped patch size; see the
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
         a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
-        not with a perceptual or style loss (their VGG node is not captured), nor with a discriminator."""
+        not with a perceptual, style or texture loss (their VGG node is not captured), nor with a discriminator."""
         train_opt = self.opt.get('train') or {}
         return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
             and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt') \
-            and not self.opt.get('network_d')
+            and not train_opt.get('texture_opt') and not self.opt.get('network_d')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
     _GRAPH_WARMUP = 3   # eager steps per input shape before capture (lazy kernel attributes, workspaces, MIOpen find results)
@@ -1003,6 +1042,5 @@ class RefRestorationModel(MultiRefRestorationModel):
     def _forward(self):
         with torch.no_grad():   # frozen feature networks (:197-199, :278-280)
             features = self.net_extractor(self.match_img_in, self.img_ref)
-            pre_offset, self.max_idx = self.net_map.offsets(features['dense_features1'], features['dense_features2'])
-            img_ref_feat = self.net_map.vgg(self.img_ref)
+            pre_offset, img_ref_feat = self._match(features['dense_features1'], features['dense_features2'], self.img_ref)
         return self.net_g(self.img_in_lq, pre_offset, img_ref_feat)
