@@ -34,6 +34,14 @@
 // the epilogue, where the arriving data then landed in somebody else's values (wrong outputs), and every spill reload is a
 // `vmcnt(0)` behind the previous pass's output stores (16 k clocks per tile).  With the fragments on LDS-DMA only the six patch
 // registers are in flight, and they are pinned through every wait.
+// Output exchange and epilogue (stage 4 below; clocks per (tile, cout block) from the -DWINO_STAMP build, profiles/
+// wino4_epilogue_parent_vs_new.txt): four passes (cout half x output column parity) through one exchange region, seven barriers.  The
+// accumulators are read once per cout half for both column parities, the
+// second cout half's fold runs under the LDS latency of the first one's passes, both tile items of a thread are in flight together,
+// the added tensor is requested a pass ahead: 9.13 k -> 7.99 k clocks without an added tensor, 10.1 k -> 9.5 k with a residual.
+// Plain fp32 instructions only, as in the step: hand-written v_pk_add / v_pk_fma / v_pk_mul_f32 in the row fold and the bias / slope
+// step returned wrong values on the GPU (stale high halves in lanes 12-15 of every 16, cause not found), and in the
+// column fold, where they compared equal, they were worth 2 % of the phase.
 // Block = 256 threads, persistent (one per CU, XCD-contiguous band of the tile list), accumulators in the AGPR half of the file.
 // Served: whole tiles (H, W multiples of 16), whole cout blocks, the plain and the max-pool epilogue (wino4_serves); everything else is
 // conv_wino_kernel's.
@@ -495,55 +503,53 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const ConvArgs A)
         // Four passes (cout half hc x output column parity b) through the exchange buffer [wave = row i][tile][X_LD]; thread = (tile T,
         // 4 couts) for T = tid >> 3 and T + 32 adds the four rows up with the row signs -- y[a] = Z0 + Z1 + Z2 (a = 0), Z1 - Z2 - Z3
         // (a = 1) -- and runs the direct kernel's epilogue on the pixels (2 ty + a, 2 tx + b) of the pass.
+        //   * the column fold reads the four accumulators of an element ONCE per cout half and forms both column parities from them
+        //     (256 v_accvgpr_read per tile instead of 384); Z[1] waits in registers for its pass
+        //   * the fold of cout half 1 is issued between the exchange reads of the two hc = 0 passes and their use (tile half b in
+        //     pass b): it runs under the LDS latency, and the hc = 1 passes start with their values ready
+        //   * a pass requests the exchange rows of BOTH tile items of a thread before any arithmetic
+        //   * the added tensor (residual / pre) of a pass is requested one pass ahead, in front of the previous pass's stores
+        // A second exchange region, which would take a barrier out of every pass, does not fit: of the two raw-chunk slots only ONE is idle
+        // during the epilogue -- the other one holds the next tile's first chunk, stored by the tile's last step (first half, slots
+        // 6..11), whose tile half 1 the next tile's first step still has to transform -- and the idle slot (23 104 bytes) + the 7 040
+        // bytes past the exchange buffer are neither contiguous nor 36 864 bytes.
         // The exchange buffer is a region of its own (the ring is receiving the next tile's first fragments meanwhile); its readers of
         // the previous tile's last pass are n_ch step barriers behind.
         asm volatile("; W4MARK fast_begin");
         const int cb = cur.cb, n = cur.n, y0 = cur.y0, x0 = cur.x0;
         float *const xb = reinterpret_cast<float *>(smem + X_OFF);
         const int Cout = A.Cout;
-        const float oscale = oscale_in;
         // (per-thread addresses of the epilogue are formed here, per tile, from an opaque copy of the thread index instead of being kept
         // across the chunk loop)
         int tid_e = tid;
         asm volatile("" : "+v"(tid_e));
         const int c4 = (tid_e & 7) * 4, T0 = tid_e >> 3;
         float *const xrow0 = xb + ((size_t)wi * NTILE + (tid_e & 31)) * X_LD + 4 * ((tid_e >> 5) & 1);
-        // the column fold of one pass into this wave's row of the exchange buffer.  The accumulators are read where they are used, by
-        // hand: left to the compiler, all 256 of them are copied into vector registers at the top of the epilogue (and everything else
-        // that lives across it is spilled to make the room)
+        // The accumulators are read where they are used, by hand: left to the compiler, all 256 of them are copied into vector registers
+        // at the top of the epilogue (and everything else that lives across it is spilled to make the room)
         auto rd = [](const float &a) {
             float v;
             asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(v) : "a"(a));
             return v;
         };
-        auto publish = [&](const int hc, const int b) {
+        // the column fold of tile half t, cout half hc, BOTH column parities from one read of the four accumulators of an element
+        // (pairs: two neighbouring elements = half of a 16-byte exchange store)
+        auto colfold = [&](const int hc, const int t, f32x2 (&z0)[8], f32x2 (&z1)[8]) {
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                float *const xrow = xrow0 + t * 32 * X_LD;
-#pragma unroll
-                for (int qd = 0; qd < 4; ++qd) {
-                    float z[4];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int e = 4 * qd + r;
-                        if (b == 0) {
-                            const float m0 = rd(acc[0][t][hc][e]), m1 = rd(acc[1][t][hc][e]), m2 = rd(acc[2][t][hc][e]);
-                            z[r] = m0 + m1 + m2;
-                        } else {
-                            const float m1 = rd(acc[1][t][hc][e]), m2 = rd(acc[2][t][hc][e]), m3 = rd(acc[3][t][hc][e]);
-                            z[r] = m1 + (-m2 - m3);   // (conv_wino_kernel's association: same bits)
-                        }
-                    }
-                    *reinterpret_cast<float4 *>(xrow + 8 * qd) = make_float4(z[0], z[1], z[2], z[3]);
-                }
+            for (int p = 0; p < 8; ++p) {
+                const int e = 2 * p;
+                const f32x2 m0 = f32x2{rd(acc[0][t][hc][e]), rd(acc[0][t][hc][e + 1])}, m1 = f32x2{rd(acc[1][t][hc][e]), rd(acc[1][t][hc][e + 1])};
+                const f32x2 m2 = f32x2{rd(acc[2][t][hc][e]), rd(acc[2][t][hc][e + 1])}, m3 = f32x2{rd(acc[3][t][hc][e]), rd(acc[3][t][hc][e + 1])};
+                z0[p] = f32x2{m0[0] + m1[0] + m2[0], m0[1] + m1[1] + m2[1]};
+                z1[p] = f32x2{m1[0] + (-m2[0] - m3[0]), m1[1] + (-m2[1] - m3[1])};   // m1 + (-m2 - m3): conv_wino_kernel's association, same bits
             }
         };
-        auto gather = [&](const int T, float4 (&y)[2]) {   // the row fold for tile T, couts c4 .. c4 + 3 of the pass
-            float4 z[4];
+        auto publish = [&](const f32x2 (&z)[2][8]) {   // one pass's values into this wave's row of the exchange buffer
 #pragma unroll
-            for (int i = 0; i < 4; ++i) z[i] = *reinterpret_cast<const float4 *>(xb + ((size_t)i * NTILE + T) * X_LD + c4);
-            y[0] = make_float4(z[0].x + z[1].x + z[2].x, z[0].y + z[1].y + z[2].y, z[0].z + z[1].z + z[2].z, z[0].w + z[1].w + z[2].w);
-            y[1] = make_float4(z[1].x - z[2].x - z[3].x, z[1].y - z[2].y - z[3].y, z[1].z - z[2].z - z[3].z, z[1].w - z[2].w - z[3].w);
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int qd = 0; qd < 4; ++qd)
+                    *reinterpret_cast<f32x4 *>(xrow0 + t * 32 * X_LD + 8 * qd) = f32x4{z[t][2 * qd][0], z[t][2 * qd][1], z[t][2 * qd + 1][0], z[t][2 * qd + 1][1]};
         };
         // Every address is a scalar base (the tile's first pixel in `out` / the added tensor, a buffer descriptor without bounds) + one
         // per-thread offset that does not depend on the tile + a scalar offset per (pass, row, tile half): no 64-bit vector arithmetic.
@@ -568,66 +574,111 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const ConvArgs A)
 #pragma unroll
                     for (int t = 0; t < 4; ++t) nonfin = __builtin_fmaf(rd(acc[j][t >> 1][t & 1][0]), 0.f, nonfin);
             }
+            // the added tensor's pixels of a pass are requested ONE PASS AHEAD, in front of the stores of the pass before: loads and
+            // stores return in issue order, and a request behind the stores would wait for their round trip to memory
+            f32x4 rqn[2][2];
+            auto request = [&](const int hc, const int b) {
+                if constexpr (RES != 0) {
+#pragma unroll
+                    for (int it = 0; it < 2; ++it)
+#pragma unroll
+                        for (int a = 0; a < 2; ++a) {
+                            const unsigned int so = (unsigned int)(8 * it + a) * row_r + (unsigned int)(b * ld_r + hc * 32) * 4u;
+                            rqn[it][a] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_r, vo_r, so, aux));
+                        }
+                }
+            };
+            request(0, 0);
+            f32x2 zc[2][2][8];   // [column parity b][tile half][element pair] of the cout half in work
+            if constexpr (W4_ABL != 5) colfold(0, 0, zc[0][0], zc[1][0]), colfold(0, 1, zc[0][1], zc[1][1]);
+            const float oscale = oscale_in;
 #pragma unroll
             for (int hc = 0; hc < (W4_ABL == 5 ? 0 : 2); ++hc) {
-                const float4 bv = *reinterpret_cast<const float4 *>(smem + BIAS_OFF + (cb * NB + hc * 32 + c4) * 4);
-                float4 pool[2];   // epilogue 1: maximum of the tile's column 0 pixels, kept over the b = 1 pass
+                const f32x4 bv = *reinterpret_cast<const f32x4 *>(smem + BIAS_OFF + (cb * NB + hc * 32 + c4) * 4);
+                f32x2 zn[2][2][8];   // the next cout half's, folded while this one's exchange reads are in flight
+                float pool[2][4];    // epilogue 1: maximum of the tile's column 0 pixels, kept over the b = 1 pass
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {
                     if (hc | b) __syncthreads();   // the previous pass has been read
-                    f32x4 rq[2][2];
-                    if constexpr (RES != 0) {   // the added tensor's pixels of the pass, requested at its START: their latency lies under the
-                                                // exchange writes and the barrier
-#pragma unroll
-                        for (int it = 0; it < 2; ++it)
-#pragma unroll
-                            for (int a = 0; a < 2; ++a) {
-                                const unsigned int so = (unsigned int)(8 * it + a) * row_r + (unsigned int)(b * ld_r + hc * 32) * 4u;
-                                rq[it][a] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(srd_r, vo_r, so, aux));
-                            }
-                    }
-                    publish(hc, b);
+                    publish(zc[b]);
                     __syncthreads();
+                    f32x4 rq[2][2];
+                    if constexpr (RES != 0) {
+#pragma unroll
+                        for (int it = 0; it < 2; ++it) rq[it][0] = rqn[it][0], rq[it][1] = rqn[it][1];
+                        if (!(hc & b)) request(hc + b, b ^ 1);
+                    }
+                    // the four rows of BOTH tile items are requested before any arithmetic; the next cout half's column fold (tile half
+                    // b) runs under their latency
+                    f32x4 zr[2][4];
+#pragma unroll
+                    for (int it = 0; it < 2; ++it)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) zr[it][i] = *reinterpret_cast<const f32x4 *>(xb + ((size_t)i * NTILE + T0 + 32 * it) * X_LD + c4);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (hc == 0) {
+                        colfold(1, b, zn[0][b], zn[1][b]);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
 #pragma unroll
                     for (int it = 0; it < 2; ++it) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        float4 y[2];
-                        gather(T0 + 32 * it, y);
+                        // the row fold for tile T0 + 32 it, couts c4 .. c4 + 3 of the pass
+                        f32x4 y[2];
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            y[0][c] = zr[it][0][c] + zr[it][1][c] + zr[it][2][c];
+                            y[1][c] = zr[it][1][c] - zr[it][2][c] - zr[it][3][c];
+                        }
                         if constexpr (pooled) {   // MaxPool2d(2,2) of act(conv + bias) = act(max4 + bias): both monotone
                             // the range guard BEFORE the maximum: fmaxf drops a NaN, and a transform value that enters one output of the
                             // 2 x 2 tile only (V[0][0] -> Y[0][0]) makes just that pixel non-finite (inf - inf = NaN keeps the flag up)
-                            nonfin = __builtin_fmaf(y[0].x + y[1].x, 0.f, nonfin);
-                            float4 m = make_float4(fmaxf(y[0].x, y[1].x), fmaxf(y[0].y, y[1].y), fmaxf(y[0].z, y[1].z), fmaxf(y[0].w, y[1].w));
+                            nonfin = __builtin_fmaf(y[0][0] + y[1][0], 0.f, nonfin);
+                            f32x4 m;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c) m[c] = fmaxf(y[0][c], y[1][c]);
                             if (b == 0) {
-                                pool[it] = m;
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) pool[it][c] = m[c];
                             } else {
-                                m = make_float4(fmaxf(m.x, pool[it].x), fmaxf(m.y, pool[it].y), fmaxf(m.z, pool[it].z), fmaxf(m.w, pool[it].w));
-                                float4 v = make_float4(m.x * oscale + bv.x, m.y * oscale + bv.y, m.z * oscale + bv.z, m.w * oscale + bv.w);
-                                nonfin = __builtin_fmaf(v.x, 0.f, nonfin);   // (one cout of the pixel: see the plain epilogue)
-                                v.x = v.x > 0.f ? v.x : v.x * slope, v.y = v.y > 0.f ? v.y : v.y * slope;
-                                v.z = v.z > 0.f ? v.z : v.z * slope, v.w = v.w > 0.f ? v.w : v.w * slope;
+                                f32x4 v;
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) v[c] = fmaxf(m[c], pool[it][c]) * oscale + bv[c];
+                                nonfin = __builtin_fmaf(v[0], 0.f, nonfin);   // (one cout of the pixel: see the plain epilogue)
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) v[c] = v[c] > 0.f ? v[c] : v[c] * slope;
                                 const unsigned int so = (unsigned int)(4 * it) * row_o + (unsigned int)(hc * 32) * 4u;
-                                oamx = fmaxf(fmaxf(fmaxf(oamx, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v.x, v.y, v.z, v.w}), srd_o, vo_o, so, aux);
+                                oamx = fmaxf(fmaxf(fmaxf(oamx, fabsf(v[0])), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), srd_o, vo_o, so, aux);
                             }
                         } else {
 #pragma unroll
                             for (int a = 0; a < 2; ++a) {
-                                float4 v = y[a];
-                                v.x = v.x * oscale + bv.x, v.y = v.y * oscale + bv.y, v.z = v.z * oscale + bv.z, v.w = v.w * oscale + bv.w;
+                                f32x4 v;
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) v[c] = y[a][c] * oscale + bv[c];
                                 // the range guard: (inf, NaN) * 0 = NaN.  One cout of the pixel is enough: a transform value beyond the
                                 // fp16 range is an inf operand of EVERY cout's products (inf * u = +-inf, inf * 0 = NaN)
-                                nonfin = __builtin_fmaf(v.x, 0.f, nonfin);
-                                if constexpr (RES == 2) v.x += rq[it][a][0], v.y += rq[it][a][1], v.z += rq[it][a][2], v.w += rq[it][a][3];
-                                v.x = v.x > 0.f ? v.x : v.x * slope, v.y = v.y > 0.f ? v.y : v.y * slope;
-                                v.z = v.z > 0.f ? v.z : v.z * slope, v.w = v.w > 0.f ? v.w : v.w * slope;
-                                if constexpr (RES == 1) v.x += rq[it][a][0], v.y += rq[it][a][1], v.z += rq[it][a][2], v.w += rq[it][a][3];
+                                nonfin = __builtin_fmaf(v[0], 0.f, nonfin);
+#pragma unroll
+                                for (int c = 0; c < 4; ++c) {
+                                    if constexpr (RES == 2) v[c] += rq[it][a][c];
+                                    v[c] = v[c] > 0.f ? v[c] : v[c] * slope;
+                                    if constexpr (RES == 1) v[c] += rq[it][a][c];
+                                }
                                 const unsigned int so = (unsigned int)(8 * it + a) * row_o + (unsigned int)(b * A.ld_out + hc * 32) * 4u;
-                                oamx = fmaxf(fmaxf(fmaxf(oamx, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
-                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v.x, v.y, v.z, v.w}), srd_o, vo_o, so, aux);
+                                oamx = fmaxf(fmaxf(fmaxf(oamx, fabsf(v[0])), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+                                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), srd_o, vo_o, so, aux);
                             }
                         }
                     }
+                }
+                if (hc == 0) {
+#pragma unroll
+                    for (int b = 0; b < 2; ++b)
+#pragma unroll
+                        for (int t = 0; t < 2; ++t)
+#pragma unroll
+                            for (int p = 0; p < 8; ++p) zc[b][t][p] = zn[b][t][p];
                 }
             }
         }
