@@ -989,6 +989,33 @@ int mrefsr_texture_crit_f32(const mrefsr_texture_layer *layers, int n_layers, fl
 int mrefsr_texture_gram_bwd_nhwc_f32(const float *fc, const float *gx, const float *gm, const float *coeff, const float *norm, const float *gup,
                                      float *df, int N, int HW, int C, float scale, int accumulate, float *amax, mrefsr_stream_t stream);
 
+/* ---- reference pools: each sample's K best of N candidate references (csrc/refselect.hip; ref_select) -----------------------------
+ * No reference counterpart.  val [N][B][P]: the matcher's winning correlation of candidate n, sample b at match
+ * position p (k-major, as mrefsr_corr_top1_f32 writes it for the pool stack).  valid_bits [B] (NULL: all present): bit n of word b
+ * = candidate n of sample b is present; N = 32 uses bit 31.
+ *
+ * mrefsr_ref_select_f32: scores [B][N], sel [B][K], slot_bits [B]; workspace of mrefsr_ref_select_workspace_bytes(N, B, P) bytes.
+ *   score, mode MREFSR_REF_SCORE_MEAN: (sum_p val[n][b][p]) / P in fp32.  The sum's order depends on P alone, not on N, B or the
+ *     grid: chunks of MREFSR_REF_SELECT_CHUNK positions; inside a chunk thread t of 256 adds its positions t, t + 256, .. in
+ *     ascending order, the 256 sums are added by the tree a[t] += a[t + w], w = 128 .. 1, the chunks' results in ascending order;
+ *     one correctly rounded division by (float)P.  No float atomics: two calls return the same bits.
+ *   score, mode MREFSR_REF_SCORE_WINS: the number of positions at which n is the present candidate with the largest val, the lowest
+ *     n among equal values (the rule of mrefsr_texture_select_f32); a NaN never wins a position.  An exact integer (P <= 2^24).
+ *   scores[b][n] of an absent candidate is -inf.  The present candidates are ordered by (score descending, n ascending), a NaN
+ *   score behind every number; the first min(K, present) are kept and written to sel[b][0..] in ASCENDING n, -1 behind them;
+ *   slot_bits[b] has one bit set per filled slot ((1 << kept) - 1).  N, K in 1..32 (K may exceed N), B <= 65535.
+ * mrefsr_ref_gather: src [N][B] rows, dst [K][B] rows of row_bytes bytes each (whole 4-byte words): dst row k B + b = src row
+ *   sel[b][k] B + b, or zeros where sel[b][k] is outside 0..N-1 (no read leaves src).  Exactly the K B rows of dst are written.  16-byte
+ *   accesses when src, dst and row_bytes are multiples of 16, else 8-byte ones when they are multiples of 8 (int64 index maps with an
+ *   odd P), else 4-byte ones.  A copy of words: every bit pattern survives.  dst must not overlap src.  K B <= 65535. */
+#define MREFSR_REF_SELECT_CHUNK 1024
+#define MREFSR_REF_SCORE_MEAN 0
+#define MREFSR_REF_SCORE_WINS 1
+int64_t mrefsr_ref_select_workspace_bytes(int N, int B, int64_t P);
+int mrefsr_ref_select_f32(const float *val, const int32_t *valid_bits, float *scores, int32_t *sel, int32_t *slot_bits, int N, int B, int64_t P,
+                          int K, int mode, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_ref_gather(const void *src, void *dst, const int32_t *sel, int N, int B, int K, int64_t row_bytes, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

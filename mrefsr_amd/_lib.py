@@ -213,6 +213,9 @@ SIGNATURES = {
     'mrefsr_texture_scale_nhwc_f32': (_i, [_vp, _vp, _vp, _i64, _i, _vp]),
     'mrefsr_texture_crit_f32': (_i, [C.POINTER(TextureLayer), _i, _f, _vp, _vp, _vp, _vp, _vp]),
     'mrefsr_texture_gram_bwd_nhwc_f32': (_i, [_vp] * 7 + [_i, _i, _i, _f, _i, _vp, _vp]),
+    'mrefsr_ref_select_workspace_bytes': (_i64, [_i, _i, _i64]),
+    'mrefsr_ref_select_f32': (_i, [_vp] * 5 + [_i, _i, _i64, _i, _i, _vp, _i64, _vp]),
+    'mrefsr_ref_gather': (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
 }
 
 _lib = None

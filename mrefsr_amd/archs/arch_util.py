@@ -50,6 +50,29 @@ def ref_valid_words(ref_valid, b=None, k=None):
     return (m.to(torch.int32) << torch.arange(m.shape[1], dtype=torch.int32)).sum(dim=1).to(torch.int32)
 
 
+def ref_pool_words(ref_valid, b=None, n=None):
+    """ref_valid_words for a reference pool (ref_select): ``ref_valid`` [B, N] with N <= 32 candidates -> int32 [B] host tensor with
+    bit n of word b set for a present candidate (candidate 31 is the sign bit), or None when every candidate is present.  Refuses
+    (ValueError) a wrong shape, N > 32 and a sample without a present candidate.  The networks' own masks stay with
+    ref_valid_words and its K <= 16."""
+    m = torch.as_tensor(ref_valid)
+    if m.dim() != 2 or (b is not None and m.shape[0] != b) or (n is not None and m.shape[1] != n):
+        raise ValueError(f'ref_valid: expected shape [{"B" if b is None else b}, {"N" if n is None else n}], got {list(m.shape)}')
+    if m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'ref_valid: expected a bool or uint8 tensor, got {m.dtype}')
+    if m.shape[1] > 32:
+        raise ValueError(f'ref_valid: N={m.shape[1]} candidate references > 32')
+    m = (m.detach().cpu() != 0)
+    empty = (~m.any(dim=1)).nonzero().flatten().tolist()
+    if empty or m.shape[0] == 0 or m.shape[1] == 0:
+        raise ValueError(f'ref_valid: sample(s) {empty} have no valid reference')
+    if bool(m.all()):
+        return None
+    # (summed in int64 and wrapped: bit 31 makes the word negative)
+    words = (m.to(torch.int64) << torch.arange(m.shape[1], dtype=torch.int64)).sum(dim=1)
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32)
+
+
 def ref_valid_bits(ref_valid, b, k, device):
     """what the networks take as ``ref_valid``: None, a [B, K] mask (checked and packed here) or the already packed int32 [B] words
     -> the words on ``device``, or None when every reference is present"""

@@ -53,9 +53,23 @@ class CorrespondenceGenerationArch(nn.Module):
                      for i in range(feat_ref.shape[0])]
             idx, val = torch.stack([p[0] for p in pairs]), torch.stack([p[1] for p in pairs])
             h, w = idx.shape[1] + 2, idx.shape[2] + 2
-        offs = hip.offsets_from_idx(idx.contiguous(), h, w)
-        out = {'relu3_1': offs[1], 'relu2_1': offs[2], 'relu1_1': offs[4]}
+        out = self.offsets_from_idx(idx, h, w)
         return (out, idx, val) if want_val else (out, idx)
+
+    @torch.no_grad()
+    def match(self, feat_in, feat_ref):
+        """the matcher alone: feat_in [B,256,h,w], feat_ref [N*B,256,h,w] n-major -> (max_idx int64, max_val fp32), both
+        [N*B,h-2,w-2] -- the launches and bits of offsets(..., want_val=True) without the offsets (a reference pool is matched as a
+        whole, offsets are built for the chosen references only: offsets_from_idx)"""
+        if self.patch_size != 3 or self.stride != 1:
+            raise NotImplementedError(f'match: patch_size {self.patch_size} / stride {self.stride} (3 / 1 is what the batched matcher does)')
+        return match_normalised_batch(feat_in, feat_ref, want_val=True)
+
+    @torch.no_grad()
+    def offsets_from_idx(self, idx, h, w):
+        """max_idx [K*B,h-2,w-2] -> the pre_offset dict of offsets()"""
+        offs = hip.offsets_from_idx(idx.contiguous(), h, w)
+        return {'relu3_1': offs[1], 'relu2_1': offs[2], 'relu1_1': offs[4]}
 
     def forward(self, dense_features, img_ref_hr):
         pre_offset, _ = self.offsets(dense_features['dense_features1'], dense_features['dense_features2'])

@@ -17,6 +17,8 @@ which MultiRefRestorationModel.feed_data reads:
                                                    drawn after the draws above; the first one is kept if all were dropped)
   MultiRefCUFEDSet          allow_missing_refs     references looked up by name (<name>_k.png, k = 1..5) per input; a missing file
                                                    is an absent reference, an input without any reference is refused
+                            num_refs: N            (with allow_missing_refs only; default 5) the looked-up names run to <name>_N.png:
+                                                   [N, ...] stacks and a `ref_valid` [N] -- a reference pool for ref_select
 """
 import glob
 import os.path as osp
@@ -138,12 +140,18 @@ class MultiRefCUFEDSet(data.Dataset):
         self.opt = opt
         self.input_list = sorted(glob.glob(osp.join(opt['dataroot_in'], '*_0.png')))
         self.by_name = bool(opt.get('allow_missing_refs'))
+        self.num_refs = opt.get('num_refs', 5)
+        if isinstance(self.num_refs, bool) or not isinstance(self.num_refs, int) or not 1 <= self.num_refs <= 32:
+            raise ValueError(f'MultiRefCUFEDSet: num_refs {self.num_refs!r} is not an int in 1..32')
+        if not self.by_name and 'num_refs' in opt and self.num_refs != 5:
+            raise ValueError('MultiRefCUFEDSet: num_refs needs allow_missing_refs: true (the references are then looked up by name)')
         if not self.by_name:
             self.ref_lists = [sorted(glob.glob(osp.join(opt['dataroot_ref'], f'*_{k}.png'))) for k in range(1, 6)]
             return
-        # <name>_0.png -> <name>_1.png .. <name>_5.png, each looked up by name: None where the file is missing
+        # <name>_0.png -> <name>_1.png .. <name>_<num_refs>.png, each looked up by name: None where the file is missing
         names = [osp.basename(p)[:-len('_0.png')] for p in self.input_list]
-        self.ref_paths = [[p if osp.exists(p) else None for p in (osp.join(opt['dataroot_ref'], f'{n}_{k}.png') for k in range(1, 6))]
+        self.ref_paths = [[p if osp.exists(p) else None for p in (osp.join(opt['dataroot_ref'], f'{n}_{k}.png')
+                                                                  for k in range(1, self.num_refs + 1))]
                           for n in names]
         bare = [n for n, paths in zip(names, self.ref_paths) if not any(paths)]
         if bare:

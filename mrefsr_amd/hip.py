@@ -1693,6 +1693,65 @@ def texture_select(idx, val, valid_bits=None):
     return sel, wts, pidx
 
 
+# ------------------------------------------------------------------ reference pools: the K best of N candidates (csrc/refselect.hip)
+REF_SCORE_MODES = {'mean': 0, 'wins': 1}   # MREFSR_REF_SCORE_MEAN / _WINS
+
+
+def ref_select(val, valid_bits, k, score='mean'):
+    """val fp32 [N,B,gh,gw] (or [N,B,P]): the matcher's winning correlations of the N candidates (candidate-major);
+    valid_bits int32 [B] on the device, bit n = candidate n of the sample is present (None: all) -> (sel int32 [B,k]: per sample the
+    min(k, present) best candidates by (score descending, n ascending), written in ascending n, -1 behind them; slot_bits int32 [B]:
+    one bit per filled slot; scores fp32 [B,N], -inf for absent candidates).  score 'mean': the fp32 mean of val over the positions
+    in a fixed order that depends on P alone; 'wins': the number of positions the candidate wins (texture_select's rule).  Two
+    launches, no readback."""
+    if score not in REF_SCORE_MODES:
+        raise ValueError(f"ref_select: score {score!r} is not 'mean' or 'wins'")
+    _chk('ref_select', val)
+    if val.dim() not in (3, 4) or val.numel() == 0 or val.shape[0] > 32:
+        raise ValueError(f'ref_select: val must be a non-empty [N,B,gh,gw] or [N,B,P] tensor with N <= 32, got {tuple(val.shape)}')
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 32:
+        raise ValueError(f'ref_select: k {k!r} is not an int in 1..32')
+    n, b = val.shape[:2]
+    p = val[0, 0].numel()
+    if valid_bits is not None:
+        _chk_valid_bits('ref_select', valid_bits, b)
+    sel = torch.empty((b, k), device=val.device, dtype=torch.int32)
+    slot_bits = torch.empty((b,), device=val.device, dtype=torch.int32)
+    scores = torch.empty((b, n), device=val.device, dtype=torch.float32)
+    ws_bytes = _lib.load().mrefsr_ref_select_workspace_bytes(n, b, p)
+    ws = torch.empty(max(ws_bytes, 4) // 4, device=val.device, dtype=torch.int32)
+    with _timed('ref_select', detail=True, nbytes=4.0 * val.numel()):
+        _lib.call('mrefsr_ref_select_f32', _p(val), _p(valid_bits), _p(scores), _p(sel), _p(slot_bits), n, b, C.c_int64(p), k,
+                  REF_SCORE_MODES[score], _p(ws), C.c_int64(ws_bytes), _stream())
+    return sel, slot_bits, scores
+
+
+def ref_gather(src, sel, n, out=None):
+    """src [n*B, ...] (contiguous fp32 or int64, candidate-major), sel int32 [B,K] from ref_select -> [K*B, ...] (slot-major):
+    row k*B + b = src row sel[b,k]*B + b, zeros where sel[b,k] is -1.  A new tensor (not an engine product: no cached max |out|
+    travels with it), or ``out`` (its first K*B rows are written, nothing else).  One launch."""
+    if src.dtype not in (torch.float32, torch.int64):
+        raise TypeError(f'ref_gather: float32 or int64 rows expected, got {src.dtype}')
+    _chk('ref_gather', src, dtype=src.dtype)
+    _chk('ref_gather', sel, dtype=torch.int32)
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= 32 or src.dim() < 2 or src.numel() == 0 or src.shape[0] % n:
+        raise ValueError(f'ref_gather: a non-empty [n*B, ...] tensor with n in 1..32 expected, got {tuple(src.shape)} with n = {n!r}')
+    b = src.shape[0] // n
+    if sel.dim() != 2 or sel.shape[0] != b or not 1 <= sel.shape[1] <= 32:
+        raise ValueError(f'ref_gather: sel must be [{b}, K] with K in 1..32, got {tuple(sel.shape)}')
+    k = sel.shape[1]
+    if out is None:
+        out = torch.empty((k * b, *src.shape[1:]), device=src.device, dtype=src.dtype)
+    else:
+        _chk('ref_gather', out, dtype=src.dtype)
+        if out.dim() != src.dim() or out.shape[0] < k * b or out.shape[1:] != src.shape[1:]:
+            raise ValueError(f'ref_gather: out {tuple(out.shape)} does not hold {k * b} rows of {tuple(src.shape[1:])}')
+    row_bytes = src[0].numel() * src.element_size()
+    with _timed('ref_gather', detail=True, nbytes=2.0 * k * b * row_bytes):
+        _lib.call('mrefsr_ref_gather', _p(src), _p(out), _p(sel), n, b, k, C.c_int64(row_bytes), _stream())
+    return out
+
+
 def texture_swap_nhwc(feat, sel, pidx, k, s):
     """feat [K*B,s*h,s*w,C] (the references' k-major NHWC maps, read in place), sel / pidx int32 [B,h-2,w-2] from texture_select ->
     [B,s*h,s*w,C]: the matched 3s x 3s reference patches pasted at (s*y, s*x), overlaps averaged (ascending (y, x), fp32)"""

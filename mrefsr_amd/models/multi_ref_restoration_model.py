@@ -88,6 +88,10 @@ class MultiRefRestorationModel:
         if opt.get('num_gpu', 1) == 0:
             raise NotImplementedError('mrefsr_amd has no CPU path: num_gpu must be >= 1')
         self.check_self_ensemble(opt.get('val'))   # (a bad value is refused before anything is built; test() reads the option)
+        self.ref_select = self.check_ref_select(opt)   # None, or (top_k, score) of the ref_select option
+        if self.ref_select is not None and not self._REF_POOLS:
+            raise ValueError(f'ref_select: {type(self).__name__} takes one reference per sample; reference pools are '
+                             "MultiRefRestorationModel's")
         self.device = torch.device('cuda', torch.cuda.current_device())
         self.is_train = opt['is_train']
         self.schedulers, self.optimizers = [], []
@@ -365,6 +369,105 @@ class MultiRefRestorationModel:
         from ..archs.arch_util import ref_valid_words
         return ref_valid_words(ref_valid, b, k)
 
+    # ------------------------------------------------------------------ ref_select: each sample's K best of a pool of N references
+    _REF_POOLS = True
+    ref_pool = None        # the fed pool of a batch with N > top_k: dict(stack [N*B,3,H,W] n-major, bits int32 [B] / None, full, n)
+    ref_selection = None   # after a pass over a pool: int32 [B,K] on the device, the chosen candidates in ascending n, -1 = unused slot
+    ref_scores = None      # ... and fp32 [B,N], the candidates' scores (-inf: absent)
+
+    @staticmethod
+    def check_ref_select(opt):
+        """opt['ref_select']: absent or None -> None; {top_k: int in 1..16, score: 'mean' (default) | 'wins'} -> (top_k, score);
+        anything else -- a bool or non-int top_k, one outside 1..16, an unknown score, unknown keys -- is a ValueError"""
+        rs = (opt or {}).get('ref_select')
+        if rs is None:
+            return None
+        if not isinstance(rs, dict):
+            raise ValueError(f'ref_select: {rs!r} is not a mapping with top_k (and optionally score)')
+        unknown = sorted(set(rs) - {'top_k', 'score'})
+        if unknown:
+            raise ValueError(f'ref_select: unknown key(s) {unknown} (top_k and score are the options)')
+        k = rs.get('top_k')
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f'ref_select.top_k: {k!r} is not an int of at least 1')
+        if k > 16:
+            raise ValueError(f'ref_select.top_k: {k} > 16, the limit of the reference masks')
+        score = rs.get('score', 'mean')
+        if score not in ('mean', 'wins'):
+            raise ValueError(f"ref_select.score: {score!r} is not 'mean' or 'wins'")
+        return k, score
+
+    @staticmethod
+    def check_ref_pool_valid(ref_valid, b, n):
+        """check_ref_valid for a pool: [B,N] with N <= 32 -> the packed int32 [B] words (host; candidate 31 is the sign bit) or None
+        for an all-true mask (archs/arch_util.ref_pool_words)"""
+        from ..archs.arch_util import ref_pool_words
+        return ref_pool_words(ref_valid, b, n)
+
+    _pool_eager_logged = False
+
+    def _pool_batch(self, what):
+        """True for a batch with a reference pool: it does not take the hipGraph paths (the selection changes the pass's inputs)"""
+        if self.ref_pool is None:
+            return False
+        if not MultiRefRestorationModel._pool_eager_logged:
+            MultiRefRestorationModel._pool_eager_logged = True
+            logging.getLogger('basicsr').info(f'{what}: batches with a reference pool (ref_select) run eagerly (no hipGraph capture or replay)')
+        return True
+
+    def _feed_pool(self, data, top_k):
+        """feed_data's reference part for img_ref_list [B,N,...] with N > top_k: the pool is kept n-major, absent candidates as
+        zero images; what a pass reads (img_ref_stack, num_refs, ref_valid_bits) is written by the selection of that pass"""
+        b, n = data['img_ref_list'].shape[:2]
+        if n > 32:
+            raise ValueError(f'ref_select: a pool of N={n} candidate references > 32')
+        words, full = None, True
+        if data.get('ref_valid') is not None:
+            words = self.check_ref_pool_valid(data['ref_valid'], b, n)
+        if words is not None:   # does every sample fill its top_k slots?  (known here: the pass reads nothing back)
+            full = min(bin(w & 0xffffffff).count('1') for w in words.tolist()) >= top_k
+        bits = None if words is None else words.to(self.device)
+        refs = data['img_ref_list'].to(self.device, non_blocking=True)
+        if bits is not None:
+            valid = ((bits[:, None] >> torch.arange(n, device=self.device, dtype=torch.int32)) & 1).bool()
+            refs = torch.where(valid[:, :, None, None, None], refs, refs.new_zeros(()))
+        self.ref_pool = dict(stack=refs.transpose(0, 1).reshape(-1, *refs.shape[2:]).contiguous(), bits=bits, full=full, n=n)
+        self.num_refs, self.ref_valid_bits, self.img_ref_stack, self.img_ref_list = top_k, None, None, []
+
+    def _select_from_pool(self):
+        """extractor and matcher on the whole pool [N*B], scores and the per-sample choice on the device (hip.ref_select), the chosen
+        images gathered to the k-major stack [K*B] with zeros in unused slots: sets img_ref_stack / img_ref_list / ref_valid_bits (None
+        when every sample fills its K slots) / ref_selection / ref_scores -> (max_idx, max_val of the pool, for the caller to gather; the match maps' (h, w))"""
+        from .. import hip
+        pool, (k, score) = self.ref_pool, self.ref_select
+        with torch.no_grad():
+            f1, f2 = self.net_extractor.forward_stacked(self.match_img_in, pool['stack'])
+            idx, val = self.net_map.match(f1, f2)
+            idx, val = idx.contiguous(), val.contiguous()
+            sel, slot_bits, scores = hip.ref_select(val.view(pool['n'], -1, *val.shape[1:]), pool['bits'], k, score)
+            refs = hip.ref_gather(pool['stack'], sel, pool['n'])
+        self.ref_selection, self.ref_scores = sel, scores
+        self.num_refs, self.ref_valid_bits = k, None if pool['full'] else slot_bits
+        self.img_ref_stack = refs
+        self.img_ref_list = list(refs.view(k, -1, *refs.shape[1:]).unbind(0))
+        return idx, val, f1.shape[2:]
+
+    def _forward_pool(self):
+        """_forward over a reference pool: offsets, VGG19 maps and net_g run on the K chosen references of each sample only"""
+        from .. import hip
+        hip.amax_pool_reset()
+        idx, val, (h, w) = self._select_from_pool()
+        k, n = self.num_refs, self.ref_pool['n']
+        with torch.no_grad():
+            self.max_idx, self.max_val = hip.ref_gather(idx, self.ref_selection, n), hip.ref_gather(val, self.ref_selection, n)
+            pre_offset = self.net_map.offsets_from_idx(self.max_idx, h, w)
+            img_ref_feat = self.net_map.vgg(self.img_ref_stack)
+            if self.cri_texture is not None:
+                self.img_ref_feat = img_ref_feat
+        if self.ref_valid_bits is not None:
+            return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k, ref_valid=self.ref_valid_bits)
+        return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k)
+
     _masked_eager_logged = False
 
     def _masked_batch(self, what):
@@ -379,7 +482,17 @@ class MultiRefRestorationModel:
     def feed_data(self, data):
         """data: img_in_lq (B,3,h,w), img_in_up (B,3,4h,4w), img_ref_list (B,K,3,4h,4w), img_in (B,3,4h,4w)
         (the dict of multi_ref_dataset.py:127-134); optionally ref_valid (B,K) bool / uint8: reference k of sample b is absent
-        where it is false -- the sample is restored from its valid references alone, whatever the loader put in the absent slot."""
+        where it is false -- the sample is restored from its valid references alone, whatever the loader put in the absent slot.
+        With the ref_select option and K = N > top_k (N <= 32) the references are a pool: every pass picks each sample's top_k best
+        present candidates on the device (_forward_pool) and restores from those."""
+        self.ref_pool = self.ref_selection = self.ref_scores = None
+        if self.ref_select is not None and data['img_ref_list'].shape[1] > self.ref_select[0]:
+            self._feed_pool(data, self.ref_select[0])   # (checked on the host before anything is launched)
+            self.img_in_lq = data['img_in_lq'].to(self.device, non_blocking=True)
+            if 'img_in' in data:
+                self.gt = data['img_in'].to(self.device, non_blocking=True)
+            self.match_img_in = data['img_in_up'].to(self.device, non_blocking=True)
+            return
         words = None
         if data.get('ref_valid') is not None:   # (checked on the host before anything is launched)
             words = self.check_ref_valid(data['ref_valid'], *data['img_ref_list'].shape[:2])
@@ -401,6 +514,8 @@ class MultiRefRestorationModel:
 
     # ------------------------------------------------------------------ the hot path
     def _forward(self):
+        if self.ref_pool is not None:
+            return self._forward_pool()
         k = self.num_refs
         from .. import hip
         hip.amax_pool_reset()   # the max |out| words of this pass's launches (archs/nhwc.py: Winograd input scales): zeroed, slot 0
@@ -689,7 +804,8 @@ class MultiRefRestorationModel:
     def _optimize_parameters(self, step):
         from ..archs import nhwc_train
         nhwc_train.check_scales()   # cached fp16 weight scales of the training convolutions still valid? (device side)
-        if self._train_graph_wanted() and not self._masked_batch('train.hip_graph') and self._optimize_graphed(step):
+        if self._train_graph_wanted() and not self._pool_batch('train.hip_graph') and not self._masked_batch('train.hip_graph') \
+                and self._optimize_graphed(step):
             return
         self.optimizer_g.zero_grad()
         nhwc_train.begin_step()     # every packed copy of net_g's weights refreshed in one launch (they changed in optimizer_g.step())
@@ -730,7 +846,8 @@ class MultiRefRestorationModel:
         """one inference pass on the fed tensors -> the output; ``eager``: the hipGraph replay is not taken whatever the options say"""
         from .. import hip
         hip.verify_packed(self.device)   # packed weight copies still match their parameters? (one launch, read with the range flag)
-        out = self._forward_graphed() if (not eager and self._use_graph() and not self._masked_batch('val.hip_graph')) else self._forward()
+        out = self._forward_graphed() if (not eager and self._use_graph() and not self._pool_batch('val.hip_graph')
+                                          and not self._masked_batch('val.hip_graph')) else self._forward()
         tripped = self._range_tripped('test')
         if hip.packed_stale():   # a parameter was edited through .data: drop every packed copy and repeat the pass
             logging.getLogger('basicsr').warning('test: a parameter changed without a version bump (.data write?); packed weights rebuilt')
@@ -771,11 +888,17 @@ class MultiRefRestorationModel:
         if self._use_graph() and not MultiRefRestorationModel._self_ensemble_eager_logged:
             MultiRefRestorationModel._self_ensemble_eager_logged = True
             logging.getLogger('basicsr').info('val.hip_graph: the passes of val.self_ensemble run eagerly (no hipGraph capture or replay)')
+        pool = self.ref_pool
+        if pool is not None:   # a matching pre-pass over the pool, once, on the untransformed batch: the ensemble runs on its choice
+            hip.amax_pool_reset()
+            self._select_from_pool()
+            self._rerun_range_free('test', self._select_from_pool, reset_scales=False)   # (the extractor left the fp16 range: choose again)
         fed = {n: self.__dict__[n] for n in self._FED if n in self.__dict__}
         k, b = self.num_refs, self.img_in_lq.shape[0]
         outs, max_idx = [], None
         self.net_g.eval()
         try:
+            self.ref_pool = None
             with torch.no_grad():
                 for tr in (0, 1):
                     self.img_in_lq = hip.dihedral_expand(fed['img_in_lq'].contiguous(), tr)
@@ -794,6 +917,7 @@ class MultiRefRestorationModel:
         finally:
             for n, t in fed.items():
                 setattr(self, n, t)
+            self.ref_pool = pool
             if self.net_g is not self.net_g_ema:
                 self.net_g.train()
 
@@ -1028,6 +1152,7 @@ class RefRestorationModel(MultiRefRestorationModel):
     `network_extractor` = ContrasExtractorSep, data dict with one `img_ref` (B,3,4h,4w) (:190-194).  Same
     optimizer groups, schedulers, losses, validation and checkpoint layout as the multi-reference model."""
     _INPUTS = ('img_in_lq', 'match_img_in', 'img_ref')
+    _REF_POOLS = False   # (the ref_select option is refused at construction)
 
     def feed_data(self, data):
         self.img_in_lq = data['img_in_lq'].to(self.device, non_blocking=True)
