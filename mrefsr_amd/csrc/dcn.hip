@@ -51,6 +51,7 @@ struct Tap {
     bool inside;
 };
 
+// (one rule, three set-ups that move together: this, make_corner in dcn_bwd.hip, Bil in dcn_any.hip -- tests/test_dcn_edges_gpu.py)
 __device__ __forceinline__ Tap make_tap(float hi, float wi, int H, int W)
 {
     Tap t;

@@ -37,6 +37,7 @@ template <typename T, typename A> __device__ __forceinline__ void stt(T *p, size
 template <> __device__ __forceinline__ void stt<__half, float>(__half *p, size_t i, float v) { p[i] = __float2half(v); }
 
 // bilinear setup: clamped corner offsets, corner validity (position in range and sample inside (-1,H) x (-1,W)), fractions
+// (one rule, three set-ups that move together: this, make_tap in dcn.hip, make_corner in dcn_bwd.hip -- tests/test_dcn_edges_gpu.py)
 template <typename A>
 struct Bil {
     int o[4];

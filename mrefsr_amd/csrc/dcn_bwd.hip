@@ -38,6 +38,7 @@ struct Corner {
     float w[4];      // bilinear weights, 0 where the corner is out of range or the sample outside the validity window
     float dh[4], dw[4];   // d(sample) / d(h), d(w) coefficients of the four corner values (0 for a corner out of range)
 };
+// (one rule, three set-ups that move together: this, make_tap in dcn.hip, Bil in dcn_any.hip -- tests/test_dcn_edges_gpu.py)
 __device__ __forceinline__ Corner make_corner(const float hi, const float wi, const int H, const int W)
 {
     Corner c;

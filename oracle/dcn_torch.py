@@ -39,10 +39,13 @@ def deform_columns(x, offset, mask, kh, kw, stride, padding, dilation, deform_gr
     uh, uw = 1 - lh, 1 - lw
     hl, wl = hl.long(), wl.long()
     hh, wh = hl + 1, wl + 1
+    # the validity window (-1, H) x (-1, W) of :618 and :531: a sample ON its boundary (-1 or H) is empty, value AND derivatives -- the
+    # value is 0 either way (the one corner in range has weight 0), the offset gradient is not (tests/test_dcn_edges_cpu.py)
+    inside = (pos_h > -1) & (pos_w > -1) & (pos_h < h) & (pos_w < w)
     xg = x.view(b, dg, cpg, h * w)
 
     def corner(hi, wi):
-        ok = (hi >= 0) & (hi <= h - 1) & (wi >= 0) & (wi <= w - 1)
+        ok = inside & (hi >= 0) & (hi <= h - 1) & (wi >= 0) & (wi <= w - 1)
         lin = (hi.clamp(0, h - 1) * w + wi.clamp(0, w - 1)).view(b, dg, 1, kk * ho * wo).expand(-1, -1, cpg, -1)
         v = torch.gather(xg, 3, lin).view(b, dg, cpg, kk, ho, wo)
         return v * ok.view(b, dg, 1, kk, ho, wo).to(dt)

@@ -511,6 +511,8 @@ def test_dcn_backward_pieces_vs_oracle(hip, case):
     ho = (h + 2 * pad - (dil * 2 + 1)) // stride + 1
     wo = (w + 2 * pad - (dil * 2 + 1)) // stride + 1
     off = (rng.standard_normal((b, dg * 18, ho, wo)) * 3).astype(np.float32)
+    off[:, :, 0, 0] = 0.0           # integer positions
+    off[:, 0, 1, 1] = -50.0         # far outside
     msk = rng.random((b, dg * 9, ho, wo)).astype(np.float32) if with_mask else None
     gout = rng.standard_normal((b, co, ho, wo)).astype(np.float32)
     gx, goff, gm, gw, gb = orc.dcnv2_bwd(x, off, msk, wgt, gout, stride, pad, dil, groups, dg)
