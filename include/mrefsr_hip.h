@@ -1016,6 +1016,29 @@ int mrefsr_ref_select_f32(const float *val, const int32_t *valid_bits, float *sc
                           int K, int mode, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
 int mrefsr_ref_gather(const void *src, void *dst, const int32_t *sel, int N, int B, int K, int64_t row_bytes, mrefsr_stream_t stream);
 
+/* ---- SSIM loss of the training step (csrc/ssim_loss.hip; losses.SSIMLoss, train.ssim_opt) -------------------------------------
+ * No reference counterpart: loss_weight (1 - mean m), m the SSIM map of the validation metric (11-tap Gaussian window,
+ * sigma 1.5, valid region, C1 = (0.01 255)^2, C2 = (0.03 255)^2) in fp32 on the images as they are (nominal range [0, 1], nothing
+ * clamped or quantised).  pred, target [batch][3][h][w] contiguous; rgb = 0: one plane per image, X = 65.481 R + 128.553 G +
+ * 24.966 B + 16; rgb = 1: three planes per image, X = 255 x.  planes = (rgb ? 3 : 1) batch; the map is (h - 10) x (w - 10).
+ * batch <= 21845, 11 <= h, w <= 2^19, h w <= 2^30.
+ *
+ * mrefsr_ssim_loss_blocks: the blocks of the forward launch = the floats of `partial` (16 x 32 map positions per block); -1 for a
+ *   shape outside the limits.
+ * mrefsr_ssim_loss_fwd_f32: loss[0] = fl32(loss_weight (1 - sum m / count)).  Second moments are taken about a per-tile reference
+ *   value, so flat regions do not cancel at 255 scale.  The sum: fixed order inside a block (fp32), one partial per block, the
+ *   partials in ascending block order in double by the block that draws the last `ticket` (one zeroed word; left zero): no float
+ *   atomics, the same bits from call to call.  a, b, c (all three or all NULL): the coefficient maps [planes][h - 10][w - 10]
+ *   dm/d mu_x, dm/d E[x^2], dm/d E[xy] the backward reads.  pred and target are only read.
+ * mrefsr_ssim_loss_bwd_f32: grad_pred [batch][3][h][w], every element written once: (-loss_weight / count) grad_loss[0] times
+ *   ((G^T a) + 2 X (G^T b) + Y (G^T c)) mapped back to R, G, B with the plane's coefficients; G^T = the window over the maps
+ *   zero-extended by 10.  grad_loss: the upstream gradient, one float in device memory.  One launch. */
+int mrefsr_ssim_loss_blocks(int batch, int h, int w, int rgb);
+int mrefsr_ssim_loss_fwd_f32(const float *pred, const float *target, int batch, int h, int w, int rgb, float loss_weight, float *a, float *b,
+                             float *c, float *partial, uint32_t *ticket, float *loss, mrefsr_stream_t stream);
+int mrefsr_ssim_loss_bwd_f32(const float *pred, const float *target, const float *a, const float *b, const float *c, const float *grad_loss,
+                             int batch, int h, int w, int rgb, float loss_weight, float *grad_pred, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -216,6 +216,9 @@ SIGNATURES = {
     'mrefsr_ref_select_workspace_bytes': (_i64, [_i, _i, _i64]),
     'mrefsr_ref_select_f32': (_i, [_vp] * 5 + [_i, _i, _i64, _i, _i, _vp, _i64, _vp]),
     'mrefsr_ref_gather': (_i, [_vp, _vp, _vp, _i, _i, _i, _i64, _vp]),
+    'mrefsr_ssim_loss_blocks': (_i, [_i, _i, _i, _i]),
+    'mrefsr_ssim_loss_fwd_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _f] + [_vp] * 7),
+    'mrefsr_ssim_loss_bwd_f32': (_i, [_vp] * 6 + [_i, _i, _i, _i, _f, _vp, _vp]),
 }
 
 _lib = None

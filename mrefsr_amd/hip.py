@@ -1752,6 +1752,53 @@ def ref_gather(src, sel, n, out=None):
     return out
 
 
+# ------------------------------------------------------------------ SSIM loss of the training step (csrc/ssim_loss.hip)
+SSIM_TILE = (16, 32)   # map positions per forward block / pixels per backward block (rows, columns)
+
+
+def _ssim_shape(name, pred, target, rgb):
+    _chk(name, pred, target)
+    if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != target.shape:
+        raise ValueError(f'{name}: pred and target must be [B,3,H,W] of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}')
+    b, _, h, w = pred.shape
+    blocks = _lib.load().mrefsr_ssim_loss_blocks(b, h, w, int(bool(rgb)))
+    if blocks <= 0:
+        raise ValueError(f'{name}: unsupported shape {tuple(pred.shape)} (B <= 21845, 11 <= H, W <= 2^19, H W <= 2^30)')
+    return b, h, w, blocks
+
+
+def ssim_loss_fwd(pred, target, rgb=False, loss_weight=1.0, want_grad=False):
+    """pred, target [B,3,H,W] (contiguous fp32) -> (loss, maps): loss a 0-dim tensor = loss_weight (1 - mean SSIM map) over the Y
+    plane of every image (rgb=False) or its three colour planes at 255 scale (rgb=True); maps: None, or with want_grad the
+    coefficient maps (a, b, c), each [planes,H-10,W-10], that ssim_loss_bwd reads.  One launch, a fixed summation order (the same
+    bits from call to call), nothing read back; pred and target are only read"""
+    b, h, w, blocks = _ssim_shape('ssim_loss_fwd', pred, target, rgb)
+    planes = (3 if rgb else 1) * b
+    maps = tuple(torch.empty((planes, h - 10, w - 10), device=pred.device, dtype=torch.float32) for _ in range(3)) if want_grad else None
+    loss = torch.empty((), device=pred.device, dtype=torch.float32)
+    part, ticket = _det_scratch(pred.device, 4 * blocks)
+    a, bb, c = maps if want_grad else (None, None, None)
+    with _timed('ssim_loss_fwd', detail=True, nbytes=4.0 * (2 * pred.numel() + (3 * planes * (h - 10) * (w - 10) if want_grad else 0))):
+        _lib.call('mrefsr_ssim_loss_fwd_f32', _p(pred), _p(target), b, h, w, int(bool(rgb)), C.c_float(loss_weight), _p(a), _p(bb), _p(c),
+                  _p(part), _p(ticket), _p(loss), _stream())
+    return loss, maps
+
+
+def ssim_loss_bwd(pred, target, maps, grad_loss, rgb=False, loss_weight=1.0):
+    """d (grad_loss * loss) / d pred [B,3,H,W] of ssim_loss_fwd from its coefficient maps; grad_loss: the upstream gradient, a
+    one-element fp32 device tensor (read by the kernel, not by the host).  One launch; every element is written once"""
+    b, h, w, _ = _ssim_shape('ssim_loss_bwd', pred, target, rgb)
+    _chk('ssim_loss_bwd', grad_loss, *maps)
+    planes = (3 if rgb else 1) * b
+    if grad_loss.numel() != 1 or len(maps) != 3 or any(m.shape != (planes, h - 10, w - 10) for m in maps):
+        raise ValueError(f'ssim_loss_bwd: one upstream value and three maps of {(planes, h - 10, w - 10)} expected')
+    grad = torch.empty_like(pred)
+    with _timed('ssim_loss_bwd', detail=True, nbytes=4.0 * (3 * pred.numel() + 3 * maps[0].numel())):
+        _lib.call('mrefsr_ssim_loss_bwd_f32', _p(pred), _p(target), _p(maps[0]), _p(maps[1]), _p(maps[2]), _p(grad_loss), b, h, w,
+                  int(bool(rgb)), C.c_float(loss_weight), _p(grad), _stream())
+    return grad
+
+
 def texture_swap_nhwc(feat, sel, pidx, k, s):
     """feat [K*B,s*h,s*w,C] (the references' k-major NHWC maps, read in place), sel / pidx int32 [B,h-2,w-2] from texture_select ->
     [B,s*h,s*w,C]: the matched 3s x 3s reference patches pasted at (s*y, s*x), overlaps averaged (ascending (y, x), fp32)"""

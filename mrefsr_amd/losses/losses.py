@@ -1,6 +1,7 @@
 """L1Loss, MSELoss, CharbonnierLoss, PerceptualLoss, TextureLoss, GANLoss and GradientPenaltyLoss with the reference's constructor signatures
 and values (basicsr/models/losses.py:17-124, 141-238, 275-532), GANLoss's wgan_softplus type and r1_penalty from the newer
-basicsr/losses/losses.py:258-360, 391-405.
+basicsr/losses/losses.py:258-360, 391-405.  SSIMLoss has no counterpart in the reference: it is the structural-similarity term the
+validation metric (mrefsr_amd/metrics.py: calculate_ssim) measures, as a criterion, on the kernels of csrc/ssim_loss.hip.
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
 what the model passes -- reduction='mean', no element weight -- and refuse the rest.  PerceptualLoss runs its VGG19 through ONE
@@ -164,6 +165,88 @@ class TextureLoss(nn.Module):
         total, terms = nhwc_train.texture(self.vgg, x, maps, weights, self._plan)
         self.last_terms = terms
         return total[0]
+
+
+def ssim_loss_torch(pred, target, channel='y'):
+    """1 - mean SSIM map of [B,3,H,W] images in the nominal range [0, 1], as torch operations in the tensors' dtype and on their
+    device: the definition SSIMLoss implements (and what it runs for CPU tensors).  Planes: channel 'y', X = 65.481 R + 128.553 G +
+    24.966 B + 16 (metrics.rgb_to_y without its float32 round trip); 'rgb', X = 255 x per colour plane.  Per plane the five moments
+    under the normalised 11-tap Gaussian of metrics._gaussian_window, applied separably on the valid region (metrics._filter_valid),
+    and the map of metrics._ssim with C1 = (0.01 255)^2, C2 = (0.03 255)^2.  Nothing is clamped or quantised."""
+    from ..metrics import _gaussian_window
+    if channel == 'y':
+        coef = pred.new_tensor([65.481, 128.553, 24.966]).view(1, 3, 1, 1)
+        x, y = (pred * coef).sum(1, keepdim=True) + 16.0, (target * coef).sum(1, keepdim=True) + 16.0
+    else:
+        x, y = 255.0 * pred, 255.0 * target
+    x, y = x.reshape(-1, 1, *x.shape[2:]), y.reshape(-1, 1, *y.shape[2:])
+    k = torch.from_numpy(_gaussian_window(11, 1.5)).to(device=pred.device, dtype=pred.dtype)
+
+    def filt(z):
+        return F.conv2d(F.conv2d(z, k.view(1, 1, 11, 1)), k.view(1, 1, 1, 11))
+    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    mu1, mu2 = filt(x), filt(y)
+    mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+    s1, s2, s12 = filt(x * x) - mu1_sq, filt(y * y) - mu2_sq, filt(x * y) - mu1_mu2
+    return 1.0 - (((2 * mu1_mu2 + c1) * (2 * s12 + c2)) / ((mu1_sq + mu2_sq + c1) * (s1 + s2 + c2))).mean()
+
+
+class _SSIMLossFn(torch.autograd.Function):
+    """(pred, target) [B,3,H,W] contiguous fp32 on the GPU -> loss_weight (1 - mean SSIM map), one launch of csrc/ssim_loss.hip; when
+    pred needs a gradient the same launch writes the three coefficient maps its backward launch reads.  Differentiable once, towards
+    pred only; the upstream gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rgb, loss_weight):
+        from .. import hip
+        ctx.rgb, ctx.loss_weight = rgb, loss_weight
+        loss, maps = hip.ssim_loss_fwd(pred, target, rgb, loss_weight, want_grad=ctx.needs_input_grad[0])
+        if maps is not None:
+            ctx.save_for_backward(pred, target, *maps)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        from .. import hip
+        pred, target, *maps = ctx.saved_tensors
+        return hip.ssim_loss_bwd(pred, target, maps, grad_loss.contiguous().float(), ctx.rgb, ctx.loss_weight), None, None, None
+
+
+@LOSS_REGISTRY.register()
+class SSIMLoss(nn.Module):
+    """loss_weight * (1 - mean SSIM) between [B,3,H,W] images in the nominal range [0, 1]: the structural similarity the validation
+    loop reports (metrics.calculate_ssim: 11 x 11 Gaussian window, sigma 1.5, valid region), as a differentiable criterion on the
+    unquantised, unclamped images.  channel 'y': on the Y plane of every image (the SSIM-Y of validation); 'rgb': on the three colour
+    planes at 255 scale.  The mean runs over images, planes and the (H - 10) x (W - 10) map positions; ssim_loss_torch spells the
+    definition out.  target is a constant (detached); the gradient reaches pred, once.
+
+    GPU fp32 tensors run on the kernels of csrc/ssim_loss.hip (one forward and one backward launch, a fixed summation order); CPU
+    tensors of any float dtype take ssim_loss_torch.  Refused: window_size other than 11, sigma other than 1.5, another channel,
+    inputs that are not 3-channel (NotImplementedError); H or W below 11, differing shapes (ValueError)."""
+
+    def __init__(self, loss_weight=1.0, channel='y', window_size=11, sigma=1.5):
+        super().__init__()
+        if window_size != 11 or sigma != 1.5:
+            raise NotImplementedError(f'SSIMLoss: window_size={window_size!r}, sigma={sigma!r}; only the 11-tap window with sigma 1.5 of '
+                                      'the validation metric is implemented')
+        if channel not in ('y', 'rgb'):
+            raise NotImplementedError(f"SSIMLoss: channel={channel!r}; 'y' or 'rgb'")
+        self.loss_weight, self.channel, self.window_size, self.sigma = loss_weight, channel, window_size, sigma
+
+    def forward(self, pred, target, **kwargs):
+        if pred.dim() != 4 or pred.shape[1] != 3:
+            raise NotImplementedError(f'SSIMLoss: [B,3,H,W] images expected, got {tuple(pred.shape)}')
+        if target.shape != pred.shape:
+            raise ValueError(f'SSIMLoss: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
+        if pred.shape[2] < self.window_size or pred.shape[3] < self.window_size:
+            raise ValueError(f'SSIMLoss: {pred.shape[2]} x {pred.shape[3]} images are smaller than the {self.window_size}-tap window')
+        target = target.detach()
+        if not pred.is_cuda:
+            return self.loss_weight * ssim_loss_torch(pred, target, self.channel)
+        if pred.dtype != torch.float32 or target.dtype != torch.float32:
+            raise NotImplementedError(f'SSIMLoss: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
+        return _SSIMLossFn.apply(pred.contiguous(), target.contiguous(), self.channel == 'rgb', float(self.loss_weight))
 
 
 @LOSS_REGISTRY.register()

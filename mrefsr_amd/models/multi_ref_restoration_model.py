@@ -10,7 +10,8 @@ layout: Adam with four parameter groups chosen by name (:60-89) --
 Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLoss), perceptual_opt and style_opt
 (PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), texture_opt with use_weights: true (TextureLoss; its
 swapped reference maps and weights, which the reference model reads but never sets, are built from the matcher's indices and values
-on the kernels of csrc/texture.hip: _texture_targets), and the adversarial term: network_d
+on the kernels of csrc/texture.hip: _texture_targets), ssim_opt (SSIMLoss: 1 - SSIM on the Y or the colour planes, the quantity
+validation reports, on the kernels of csrc/ssim_loss.hip; no counterpart in the reference), and the adversarial term: network_d
 (ImageDiscriminator, VGGStyleDiscriminator, UNetDiscriminatorSN or StyleGAN2Discriminator, on the kernels of csrc/disc.hip, disc_vgg.hip,
 disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
@@ -239,6 +240,7 @@ class MultiRefRestorationModel:
 
     net_g_ema = None
     cri_texture = None   # TextureLoss of train.texture_opt (init_training_settings)
+    cri_ssim = None      # SSIMLoss of train.ssim_opt
 
     def _setup_ema(self):
         """train.ema_decay > 0 (sr_model.py:39-53): net_g_ema, a second network_g in eval mode without gradients, never wrapped in
@@ -339,6 +341,8 @@ class MultiRefRestorationModel:
         self.cri_style = losses.PerceptualLoss(**train_opt['style_opt']).to(self.device) if train_opt.get('style_opt') else None
         # TextureLoss (ref :142-147); its maps and weights are built from the matcher's outputs in _texture_targets
         self.cri_texture = losses.TextureLoss(**train_opt['texture_opt']).to(self.device) if train_opt.get('texture_opt') else None
+        # SSIMLoss: train.ssim_opt holds its constructor's keys (loss_weight, channel, window_size, sigma)
+        self.cri_ssim = losses.SSIMLoss(**train_opt['ssim_opt']).to(self.device) if train_opt.get('ssim_opt') else None
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
@@ -614,6 +618,10 @@ class MultiRefRestorationModel:
                 l_g_texture = self.cri_texture(self.output, *self._texture_targets())
                 l_g_total = l_g_total + l_g_texture
                 self.log_dict['l_g_texture'] = l_g_texture.detach()
+            if self.cri_ssim is not None:
+                l_g_ssim = self.cri_ssim(self.output, self.gt)
+                l_g_total = l_g_total + l_g_ssim
+                self.log_dict['l_g_ssim'] = l_g_ssim.detach()
             if self.net_d is not None:   # ref :272-276 (D's parameters are frozen: no weight gradient of D is computed)
                 fake_g_pred = self.net_d(self.output)
                 l_g_gan = self.cri_gan(fake_g_pred, True, is_disc=False)
@@ -632,11 +640,11 @@ class MultiRefRestorationModel:
         """opt['train']['hip_graph'] or MREFSR_TRAIN_GRAPH=1 (EXPERIMENTAL, off by default: 1-2 % at the shipped patch size; see the
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
         a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
-        not with a perceptual, style or texture loss (their VGG node is not captured), nor with a discriminator."""
+        not with a perceptual, style or texture loss (their VGG node is not captured), an SSIM loss, nor with a discriminator."""
         train_opt = self.opt.get('train') or {}
         return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
             and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt') \
-            and not train_opt.get('texture_opt') and not self.opt.get('network_d')
+            and not train_opt.get('texture_opt') and not train_opt.get('ssim_opt') and not self.opt.get('network_d')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
     _GRAPH_WARMUP = 3   # eager steps per input shape before capture (lazy kernel attributes, workspaces, MIOpen find results)
