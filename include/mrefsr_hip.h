@@ -1039,6 +1039,35 @@ int mrefsr_ssim_loss_fwd_f32(const float *pred, const float *target, int batch, 
 int mrefsr_ssim_loss_bwd_f32(const float *pred, const float *target, const float *a, const float *b, const float *c, const float *grad_loss,
                              int batch, int h, int w, int rgb, float loss_weight, float *grad_pred, mrefsr_stream_t stream);
 
+/* ---- LDL artifact loss of the training step (csrc/ldl_loss.hip; losses.LDLLoss, train.ldl_opt) -----------------------
+ * basicsr/losses/loss_util.py:99-145 as used by basicsr/models/realesrgan_model.py:211-226, the weight map NOT detached.  pred,
+ * target, ema [batch][3][h][w] contiguous fp32; r = sum_c |target - pred|, r_e = sum_c |target - ema| (channels added 0, 1, 2);
+ * g_b = Var(r_b)^(1/5) (unbiased over h w; 0 for a variance of exactly 0), v = the unbiased variance of r over the 7 x 7 window of
+ * the image reflect-padded by 3, m = [r >= r_e]; loss = loss_weight / (3 batch h w) sum_b g_b sum_p v m r.
+ * batch <= 65535, 4 <= h, w <= 2^19, h w <= 2^30.
+ *
+ * mrefsr_ldl_loss_blocks: the blocks of the forward launch (16 x 32 pixels each); `partial` holds 4 floats per block.  -1 for a
+ *   shape outside the limits.
+ * mrefsr_ldl_loss_fwd_f32: one launch.  Window variances in two passes over the 49 taps (the mean from the deviations about the
+ *   centre tap, then the squares about it); per block
+ *   (count, mean, M2) of r and sum v m r in fp32 by a fixed tree, merged per sample in ascending block order in double (the mean, then
+ *   M2 about it) by the block that
+ *   draws the last `ticket` (one zeroed word; left zero), which writes stats [batch][4] = (g_b, mean(r_b), k_b, S_b) with
+ *   S_b = sum_p v m r and k_b = S_b (1/5) Var_b^(-4/5) 2 / (h w - 1) (0 for a variance of 0), and loss[0].  No float atomics, the
+ *   same bits from call to call.  mr, mu (both or both NULL): the maps [batch][h][w] m r and the window means the backward reads;
+ *   vm (or NULL): v m, read by the backward and by mrefsr_ldl_loss_map_f32.  The inputs are only read.
+ * mrefsr_ldl_loss_bwd_f32: one launch; grad_pred [batch][3][h][w], every element written once:
+ *   sign(pred_c - target_c) s [g v m + (2 / 48) g sum_q mult(q, p) (m r)_q (r_p - mu_q) + k_b (r_p - mean_b)], s = loss_weight /
+ *   (3 batch h w) grad_loss[0]; mult(q, p): the positions of q's padded window that reflect onto p.  grad_loss: the upstream
+ *   gradient, one float in device memory.  A sample with a variance of 0 gets a gradient of 0.
+ * mrefsr_ldl_loss_map_f32: w [batch][h][w] = g_b (v m), the artifact map.  One launch. */
+int mrefsr_ldl_loss_blocks(int batch, int h, int w);
+int mrefsr_ldl_loss_fwd_f32(const float *pred, const float *target, const float *ema, int batch, int h, int w, float loss_weight, float *mr,
+                            float *mu, float *vm, float *stats, float *partial, uint32_t *ticket, float *loss, mrefsr_stream_t stream);
+int mrefsr_ldl_loss_bwd_f32(const float *pred, const float *target, const float *mr, const float *mu, const float *vm, const float *stats,
+                            const float *grad_loss, int batch, int h, int w, float loss_weight, float *grad_pred, mrefsr_stream_t stream);
+int mrefsr_ldl_loss_map_f32(const float *vm, const float *stats, int batch, int h, int w, float *wmap, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -219,6 +219,10 @@ SIGNATURES = {
     'mrefsr_ssim_loss_blocks': (_i, [_i, _i, _i, _i]),
     'mrefsr_ssim_loss_fwd_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _f] + [_vp] * 7),
     'mrefsr_ssim_loss_bwd_f32': (_i, [_vp] * 6 + [_i, _i, _i, _i, _f, _vp, _vp]),
+    'mrefsr_ldl_loss_blocks': (_i, [_i, _i, _i]),
+    'mrefsr_ldl_loss_fwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _f] + [_vp] * 8),
+    'mrefsr_ldl_loss_bwd_f32': (_i, [_vp] * 7 + [_i, _i, _i, _f, _vp, _vp]),
+    'mrefsr_ldl_loss_map_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -1377,6 +1377,12 @@ def amax_pool_reset():
         st[1] = 0
 
 
+def amax_pool_used(device):
+    """the slots handed out on ``device`` since the pool was last reset or wrapped around"""
+    st = _amax_pool.get(device)
+    return 0 if st is None else st[1]
+
+
 def amax_slot(device):
     """a zeroed 1-element float32 device tensor for one launch's max |out|"""
     st = _amax_state(device)
@@ -1796,6 +1802,58 @@ def ssim_loss_bwd(pred, target, maps, grad_loss, rgb=False, loss_weight=1.0):
     with _timed('ssim_loss_bwd', detail=True, nbytes=4.0 * (3 * pred.numel() + 3 * maps[0].numel())):
         _lib.call('mrefsr_ssim_loss_bwd_f32', _p(pred), _p(target), _p(maps[0]), _p(maps[1]), _p(maps[2]), _p(grad_loss), b, h, w,
                   int(bool(rgb)), C.c_float(loss_weight), _p(grad), _stream())
+    return grad
+
+
+# ------------------------------------------------------------------ LDL artifact loss of the training step (csrc/ldl_loss.hip)
+LDL_TILE = (16, 32)   # pixels per block of the forward and the backward launch (rows, columns)
+
+
+def _ldl_shape(name, pred, *others):
+    _chk(name, pred, *others)
+    if pred.dim() != 4 or pred.shape[1] != 3 or any(t.shape != pred.shape for t in others):
+        raise ValueError(f'{name}: [B,3,H,W] images of one shape expected, got {[tuple(t.shape) for t in (pred, *others)]}')
+    b, _, h, w = pred.shape
+    blocks = _lib.load().mrefsr_ldl_loss_blocks(b, h, w)
+    if blocks <= 0:
+        raise ValueError(f'{name}: unsupported shape {tuple(pred.shape)} (B <= 65535, 4 <= H, W <= 2^19, H W <= 2^30)')
+    return b, h, w, blocks
+
+
+def ldl_loss_fwd(pred, target, ema, loss_weight=1.0, want_grad=False, want_map=False):
+    """pred, target, ema [B,3,H,W] (contiguous fp32) -> (loss, saved, w): loss a 0-dim tensor = loss_weight mean |w pred - w target|
+    with the LDL artifact map w of the three images; saved: None, or with want_grad what ldl_loss_bwd reads, (m r, mu, v m) each
+    [B,H,W] and the per-sample scalars [B,4]; w: None, or with want_map the map [B,1,H,W] (a second launch).  Without either the
+    one launch writes no map.  Fixed summation orders (the same bits from call to call), nothing read back; the inputs are only read"""
+    b, h, w, blocks = _ldl_shape('ldl_loss_fwd', pred, target, ema)
+    dev = pred.device
+    mr, mu = (torch.empty((b, h, w), device=dev, dtype=torch.float32) for _ in range(2)) if want_grad else (None, None)
+    vm = torch.empty((b, h, w), device=dev, dtype=torch.float32) if want_grad or want_map else None
+    stats = torch.empty((b, 4), device=dev, dtype=torch.float32)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    part, ticket = _det_scratch(dev, 16 * blocks)
+    with _timed('ldl_loss_fwd', detail=True, nbytes=4.0 * (3 * pred.numel() + (3 if want_grad else 1 if want_map else 0) * b * h * w)):
+        _lib.call('mrefsr_ldl_loss_fwd_f32', _p(pred), _p(target), _p(ema), b, h, w, C.c_float(loss_weight), _p(mr), _p(mu), _p(vm), _p(stats),
+                  _p(part), _p(ticket), _p(loss), _stream())
+    wmap = None
+    if want_map:
+        wmap = torch.empty((b, 1, h, w), device=dev, dtype=torch.float32)
+        with _timed('ldl_loss_map', detail=True, nbytes=8.0 * b * h * w):
+            _lib.call('mrefsr_ldl_loss_map_f32', _p(vm), _p(stats), b, h, w, _p(wmap), _stream())
+    return loss, ((mr, mu, vm, stats) if want_grad else None), wmap
+
+
+def ldl_loss_bwd(pred, target, saved, grad_loss, loss_weight=1.0):
+    """d (grad_loss * loss) / d pred [B,3,H,W] of ldl_loss_fwd from what it saved; grad_loss: the upstream gradient, a one-element
+    fp32 device tensor (read by the kernel, not by the host).  One launch; every element is written once"""
+    b, h, w, _ = _ldl_shape('ldl_loss_bwd', pred, target)
+    _chk('ldl_loss_bwd', grad_loss, *saved)
+    if grad_loss.numel() != 1 or len(saved) != 4 or any(m.shape != (b, h, w) for m in saved[:3]) or saved[3].shape != (b, 4):
+        raise ValueError(f'ldl_loss_bwd: one upstream value, three maps of {(b, h, w)} and the scalars {(b, 4)} expected')
+    grad = torch.empty_like(pred)
+    with _timed('ldl_loss_bwd', detail=True, nbytes=4.0 * (3 * pred.numel() + 3 * b * h * w)):
+        _lib.call('mrefsr_ldl_loss_bwd_f32', _p(pred), _p(target), _p(saved[0]), _p(saved[1]), _p(saved[2]), _p(saved[3]), _p(grad_loss),
+                  b, h, w, C.c_float(loss_weight), _p(grad), _stream())
     return grad
 
 

@@ -1,6 +1,7 @@
 """L1Loss, MSELoss, CharbonnierLoss, PerceptualLoss, TextureLoss, GANLoss and GradientPenaltyLoss with the reference's constructor signatures
 and values (basicsr/models/losses.py:17-124, 141-238, 275-532), GANLoss's wgan_softplus type and r1_penalty from the newer
-basicsr/losses/losses.py:258-360, 391-405.  SSIMLoss has no counterpart in the reference: it is the structural-similarity term the
+basicsr/losses/losses.py:258-360, 391-405.  LDLLoss is the artifact loss of LDL (basicsr/losses/loss_util.py:99-145 as used by
+basicsr/models/realesrgan_model.py:211-226), on the kernels of csrc/ldl_loss.hip.  SSIMLoss has no counterpart in the reference: it is the structural-similarity term the
 validation metric (mrefsr_amd/metrics.py: calculate_ssim) measures, as a criterion, on the kernels of csrc/ssim_loss.hip.
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
@@ -247,6 +248,115 @@ class SSIMLoss(nn.Module):
         if pred.dtype != torch.float32 or target.dtype != torch.float32:
             raise NotImplementedError(f'SSIMLoss: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
         return _SSIMLossFn.apply(pred.contiguous(), target.contiguous(), self.channel == 'rgb', float(self.loss_weight))
+
+
+def _ldl_residuals(gt, out, ema):
+    """r = sum_c |gt - out| and r_e = sum_c |gt - ema|, [B,1,H,W], the channels added in the order 0, 1, 2"""
+    d, e = (gt - out).abs(), (gt - ema).abs()
+    return d[:, 0:1] + d[:, 1:2] + d[:, 2:3], e[:, 0:1] + e[:, 1:2] + e[:, 2:3]
+
+
+def ldl_artifact_map_torch(gt, out, ema, ksize=7):
+    """The artifact map w [B,1,H,W] of LDL (Liang et al., "Details or Artifacts: A Locally Discriminative Learning Approach to
+    Realistic Image Super-Resolution", CVPR 2022; get_refined_artifact_map of basicsr/losses/loss_util.py) as torch operations in
+    the tensors' dtype and on their device, differentiable towards ``out``: with r = sum_c |gt - out| and r_e = sum_c |gt - ema|,
+        w = g v m,   g_b = Var(r_b)^(1/5) (unbiased, over the H W pixels of sample b),
+                     v_p = the unbiased variance of r over the ksize x ksize window at p of the image reflect-padded by ksize // 2
+                           (two passes: the window mean, then the squares about it),
+                     m_p = [r_p >= r_e,p] (a constant).
+    One deviation: a sample whose residual has exactly zero variance has g = 0 AND a zero gradient through g (the reference's
+    autograd gives 0 * 0^(-4/5) = NaN there)."""
+    if ksize % 2 != 1 or ksize < 3:
+        raise ValueError(f'ldl_artifact_map_torch: ksize={ksize!r} is not an odd window size of at least 3')
+    pad = ksize // 2
+    if gt.dim() != 4 or min(gt.shape[2:]) <= pad:
+        raise ValueError(f'ldl_artifact_map_torch: [B,C,H,W] images with H, W > {pad} expected, got {tuple(gt.shape)}')
+    r, r_e = _ldl_residuals(gt, out, ema)
+    flat = r.flatten(1)
+    var = ((flat - flat.mean(1, keepdim=True)) ** 2).sum(1) / (flat.shape[1] - 1)
+    positive = var > 0
+    g = torch.where(positive, torch.where(positive, var, torch.ones_like(var)) ** 0.2, torch.zeros_like(var)).view(-1, 1, 1, 1)
+    win = F.pad(r, [pad] * 4, mode='reflect').unfold(2, ksize, 1).unfold(3, ksize, 1).flatten(4)   # [B,1,H,W,ksize^2]
+    v = ((win - win.mean(4, keepdim=True)) ** 2).sum(4) / (ksize * ksize - 1)
+    return g * v * (r >= r_e).to(r.dtype)
+
+
+def ldl_loss_torch(pred, target, pred_ema, ksize=7):
+    """mean over [B,3,H,W] of |w pred - w target|, w = ldl_artifact_map_torch(target, pred, pred_ema, ksize) NOT detached (the
+    reference differentiates through the map: realesrgan_model.py:211-226): the definition LDLLoss implements and what it runs for
+    CPU tensors.  As w >= 0 this is sum_p w_p r_p / (3 B H W)."""
+    w = ldl_artifact_map_torch(target, pred, pred_ema, ksize)
+    return (w * pred - w * target).abs().mean()
+
+
+class _LDLLossFn(torch.autograd.Function):
+    """(pred, target, pred_ema) [B,3,H,W] contiguous fp32 on the GPU -> loss_weight mean |w pred - w target|, one launch of
+    csrc/ldl_loss.hip; when pred needs a gradient the same launch writes the maps (m r, the window means, v m) and the per-sample
+    scalars its backward launch reads.  Differentiable once, towards pred only; the upstream gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, pred_ema, loss_weight):
+        from .. import hip
+        ctx.loss_weight = loss_weight
+        loss, saved, _ = hip.ldl_loss_fwd(pred, target, pred_ema, loss_weight, want_grad=ctx.needs_input_grad[0])
+        if saved is not None:
+            ctx.save_for_backward(pred, target, *saved)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        from .. import hip
+        pred, target, *saved = ctx.saved_tensors
+        return hip.ldl_loss_bwd(pred, target, saved, grad_loss.contiguous().float(), ctx.loss_weight), None, None, None
+
+
+@LOSS_REGISTRY.register()
+class LDLLoss(nn.Module):
+    """The artifact loss of LDL (train.ldl_opt): loss_weight * mean |w pred - w target| with the artifact map w of
+    ldl_artifact_map_torch built from pred, target and pred_ema, the output of the EMA network on the same input.  It penalises the
+    pixels where pred is further from target than pred_ema is, each by how irregular the residual is around it.  w is not detached:
+    the gradient towards pred flows through the local variances and the per-sample variance as well (DESIGN 3.16 has the closed
+    form); target and pred_ema are constants.  A sample with a residual of exactly zero variance contributes no loss and no gradient.
+
+    GPU fp32 tensors run on the kernels of csrc/ldl_loss.hip (one forward and one backward launch, fixed summation orders); CPU
+    tensors of any float dtype take ldl_loss_torch.  ``artifact_map`` returns w [B,1,H,W] without a gradient.  Refused: ksize other
+    than 7, inputs that are not [B,3,H,W], non-fp32 tensors on the GPU (NotImplementedError); H or W below 4, differing shapes
+    (ValueError)."""
+
+    def __init__(self, loss_weight=1.0, ksize=7):
+        super().__init__()
+        if isinstance(ksize, bool) or ksize != 7:
+            raise NotImplementedError(f'LDLLoss: ksize={ksize!r}; only the 7 x 7 window of the paper is implemented')
+        self.loss_weight, self.ksize = loss_weight, 7
+
+    def _checked(self, pred, target, pred_ema):
+        if pred.dim() != 4 or pred.shape[1] != 3:
+            raise NotImplementedError(f'LDLLoss: [B,3,H,W] images expected, got {tuple(pred.shape)}')
+        if target.shape != pred.shape or pred_ema.shape != pred.shape:
+            raise ValueError(f'LDLLoss: pred {tuple(pred.shape)}, target {tuple(target.shape)} and pred_ema {tuple(pred_ema.shape)} differ')
+        if pred.shape[2] < 4 or pred.shape[3] < 4:
+            raise ValueError(f'LDLLoss: {pred.shape[2]} x {pred.shape[3]} images; H and W of at least 4 (the reflect padding of 3)')
+        on_gpu = pred.is_cuda
+        if on_gpu and not (pred.dtype == target.dtype == pred_ema.dtype == torch.float32):
+            raise NotImplementedError(f'LDLLoss: {pred.dtype} / {target.dtype} / {pred_ema.dtype} images; fp32 only on the GPU')
+        return on_gpu, target.detach(), pred_ema.detach()
+
+    def forward(self, pred, target, pred_ema, **kwargs):
+        on_gpu, target, pred_ema = self._checked(pred, target, pred_ema)
+        if not on_gpu:
+            return self.loss_weight * ldl_loss_torch(pred, target, pred_ema, self.ksize)
+        return _LDLLossFn.apply(pred.contiguous(), target.contiguous(), pred_ema.contiguous(), float(self.loss_weight))
+
+    def artifact_map(self, pred, target, pred_ema):
+        """w [B,1,H,W] of the three images, without a gradient (the forward launch plus one that scales v m by g)"""
+        on_gpu, target, pred_ema = self._checked(pred, target, pred_ema)
+        with torch.no_grad():
+            if not on_gpu:
+                return ldl_artifact_map_torch(target, pred, pred_ema, self.ksize)
+            from .. import hip
+            return hip.ldl_loss_fwd(pred.detach().contiguous(), target.contiguous(), pred_ema.contiguous(), float(self.loss_weight),
+                                    want_map=True)[2]
 
 
 @LOSS_REGISTRY.register()

@@ -11,7 +11,9 @@ Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLo
 (PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), texture_opt with use_weights: true (TextureLoss; its
 swapped reference maps and weights, which the reference model reads but never sets, are built from the matcher's indices and values
 on the kernels of csrc/texture.hip: _texture_targets), ssim_opt (SSIMLoss: 1 - SSIM on the Y or the colour planes, the quantity
-validation reports, on the kernels of csrc/ssim_loss.hip; no counterpart in the reference), and the adversarial term: network_d
+validation reports, on the kernels of csrc/ssim_loss.hip; no counterpart in the reference), ldl_opt (LDLLoss: the artifact loss of
+LDL between the output, the GT and the output of net_g_ema on the same input, basicsr/models/realesrgan_model.py:211-226, on the
+kernels of csrc/ldl_loss.hip; needs train.ema_decay: _ema_pass), and the adversarial term: network_d
 (ImageDiscriminator, VGGStyleDiscriminator, UNetDiscriminatorSN or StyleGAN2Discriminator, on the kernels of csrc/disc.hip, disc_vgg.hip,
 disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
@@ -241,6 +243,8 @@ class MultiRefRestorationModel:
     net_g_ema = None
     cri_texture = None   # TextureLoss of train.texture_opt (init_training_settings)
     cri_ssim = None      # SSIMLoss of train.ssim_opt
+    cri_ldl = None       # LDLLoss of train.ldl_opt
+    output_ema = None    # net_g_ema's output on this step's input (steps that evaluate the LDL term)
 
     def _setup_ema(self):
         """train.ema_decay > 0 (sr_model.py:39-53): net_g_ema, a second network_g in eval mode without gradients, never wrapped in
@@ -343,6 +347,7 @@ class MultiRefRestorationModel:
         self.cri_texture = losses.TextureLoss(**train_opt['texture_opt']).to(self.device) if train_opt.get('texture_opt') else None
         # SSIMLoss: train.ssim_opt holds its constructor's keys (loss_weight, channel, window_size, sigma)
         self.cri_ssim = losses.SSIMLoss(**train_opt['ssim_opt']).to(self.device) if train_opt.get('ssim_opt') else None
+        self.cri_ldl = self._build_ldl(train_opt)
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
@@ -358,6 +363,28 @@ class MultiRefRestorationModel:
             raise NotImplementedError(f'Scheduler {stype} is not implemented yet.')
         for optimizer in self.optimizers:
             self.schedulers.append((_CosineAnnealingRestartLR if stype == 'CosineAnnealingRestartLR' else _MultiStepRestartLR)(optimizer, **sched))
+
+    @staticmethod
+    def _build_ldl(train_opt):
+        """train.ldl_opt in basicsr's form {type: L1Loss, loss_weight, reduction: mean} (sr_model.py builds an L1Loss that
+        realesrgan_model.py:211-226 applies to the weighted images), plus an optional ksize: 7 -> LDLLoss, or None without the
+        option.  It needs the EMA network: refused here, not at the first step, without train.ema_decay > 0."""
+        from .. import losses
+        ldl_opt = train_opt.get('ldl_opt')
+        if not ldl_opt:
+            return None
+        unknown = sorted(set(ldl_opt) - {'type', 'loss_weight', 'reduction', 'ksize'})
+        if unknown:
+            raise ValueError(f'train.ldl_opt: unknown key(s) {unknown} (type, loss_weight, reduction and ksize are the options)')
+        if ldl_opt.get('type', 'L1Loss') != 'L1Loss':
+            raise NotImplementedError(f"train.ldl_opt: type {ldl_opt.get('type')!r}; the artifact loss is implemented as the L1 form "
+                                      "(type: L1Loss) of the LDL paper and of basicsr's configurations")
+        if ldl_opt.get('reduction', 'mean') != 'mean':
+            raise NotImplementedError(f"train.ldl_opt: reduction {ldl_opt.get('reduction')!r}; only 'mean' is implemented")
+        if not (train_opt.get('ema_decay') or 0) > 0:
+            raise ValueError('train.ldl_opt without train.ema_decay > 0: the artifact loss compares the output with that of net_g_ema; '
+                             'set ema_decay (e.g. 0.999) or drop ldl_opt')
+        return losses.LDLLoss(loss_weight=ldl_opt.get('loss_weight', 1.0), ksize=ldl_opt.get('ksize', 7))
 
     @staticmethod
     def get_bare_model(net):
@@ -469,8 +496,8 @@ class MultiRefRestorationModel:
             if self.cri_texture is not None:
                 self.img_ref_feat = img_ref_feat
         if self.ref_valid_bits is not None:
-            return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k, ref_valid=self.ref_valid_bits)
-        return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k)
+            return self._run_net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k, ref_valid=self.ref_valid_bits)
+        return self._run_net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k)
 
     _masked_eager_logged = False
 
@@ -527,8 +554,38 @@ class MultiRefRestorationModel:
             f1, f2 = self.net_extractor.forward_stacked(self.match_img_in, self.img_ref_stack)
             pre_offset, img_ref_feat = self._match(f1, f2, self.img_ref_stack)
         if self.ref_valid_bits is not None:
-            return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k, ref_valid=self.ref_valid_bits)
-        return self.net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k)
+            return self._run_net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k, ref_valid=self.ref_valid_bits)
+        return self._run_net_g(self.img_in_lq, pre_offset, img_ref_feat, k=k)
+
+    def _run_net_g(self, *args, **kwargs):
+        """net_g on what the frozen networks produced; with an LDL loss the arguments are kept for the EMA pass of this step
+        (_ema_pass), as _match keeps the reference maps for the texture loss"""
+        if self.cri_ldl is not None:
+            self._net_g_inputs = (args, kwargs)
+        return self.net_g(*args, **kwargs)
+
+    def _ema_pass(self):
+        """net_g_ema, in eval mode and without a graph, on the inputs net_g has just had in this step's _forward: the same LR
+        images, pre_offset, reference VGG maps, k and ref_valid words (the matcher is frozen: recomputing them, as
+        realesrgan_model.py:211-226 does, would give the same tensors) -> its output, the bits test() would produce for this batch.
+        It runs on the inference engine with the weights net_g_ema has BEFORE this step's update; their packed copies come from
+        the versioned cache of hip.packed_weight, re-packed here because the last step's EMA update moved every version.
+        Left alone: net_g (its train mode, the _offset_count guards of its DynAgg modules -- net_g_ema has its own) and the
+        max |out| words of the recorded forward: the pass takes fresh slots of hip's pool behind them, without resetting it."""
+        from .. import hip
+        if self.net_g_ema is None:
+            raise RuntimeError('train.ldl_opt: there is no net_g_ema (train.ema_decay > 0 is required)')
+        args, kwargs = self._net_g_inputs
+        start = hip.amax_pool_used(self.device)
+        with torch.no_grad():
+            out = self.net_g_ema(*args, **kwargs)
+        # a slot counter that wrapped, or ran into the pool's second half, would zero words in use: the second half is what the
+        # backward pass may still take before the first one, which the recorded graph reads, is handed out again
+        used = hip.amax_pool_used(self.device)
+        if used < start or used > hip.AMAX_POOL // 2:
+            raise RuntimeError(f'train.ldl_opt: the forward and the EMA pass took {used} max |out| words (the pass from {start} on); a '
+                               f'step has {hip.AMAX_POOL // 2} of them, half of hip.AMAX_POOL = {hip.AMAX_POOL}')
+        return out.detach()
 
     def _match(self, f1, f2, refs):
         """net_map on the extractor's features and the reference images: -> (pre_offset, the references' VGG maps); max_idx is kept,
@@ -622,6 +679,11 @@ class MultiRefRestorationModel:
                 l_g_ssim = self.cri_ssim(self.output, self.gt)
                 l_g_total = l_g_total + l_g_ssim
                 self.log_dict['l_g_ssim'] = l_g_ssim.detach()
+            if self.cri_ldl is not None:   # realesrgan_model.py:211-226
+                self.output_ema = self._ema_pass()
+                l_g_ldl = self.cri_ldl(self.output, self.gt, self.output_ema)
+                l_g_total = l_g_total + l_g_ldl
+                self.log_dict['l_g_ldl'] = l_g_ldl.detach()
             if self.net_d is not None:   # ref :272-276 (D's parameters are frozen: no weight gradient of D is computed)
                 fake_g_pred = self.net_d(self.output)
                 l_g_gan = self.cri_gan(fake_g_pred, True, is_disc=False)
@@ -640,11 +702,13 @@ class MultiRefRestorationModel:
         """opt['train']['hip_graph'] or MREFSR_TRAIN_GRAPH=1 (EXPERIMENTAL, off by default: 1-2 % at the shipped patch size; see the
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
         a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
-        not with a perceptual, style or texture loss (their VGG node is not captured), an SSIM loss, nor with a discriminator."""
+        not with a perceptual, style or texture loss (their VGG node is not captured), an SSIM loss, an LDL loss (its EMA pass is not
+        captured), nor with a discriminator."""
         train_opt = self.opt.get('train') or {}
         return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
             and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt') \
-            and not train_opt.get('texture_opt') and not train_opt.get('ssim_opt') and not self.opt.get('network_d')
+            and not train_opt.get('texture_opt') and not train_opt.get('ssim_opt') and not train_opt.get('ldl_opt') \
+            and not self.opt.get('network_d')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
     _GRAPH_WARMUP = 3   # eager steps per input shape before capture (lazy kernel attributes, workspaces, MIOpen find results)
@@ -1176,4 +1240,4 @@ class RefRestorationModel(MultiRefRestorationModel):
         with torch.no_grad():   # frozen feature networks (:197-199, :278-280)
             features = self.net_extractor(self.match_img_in, self.img_ref)
             pre_offset, img_ref_feat = self._match(features['dense_features1'], features['dense_features2'], self.img_ref)
-        return self.net_g(self.img_in_lq, pre_offset, img_ref_feat)
+        return self._run_net_g(self.img_in_lq, pre_offset, img_ref_feat)
