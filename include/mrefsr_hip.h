@@ -1068,6 +1068,45 @@ int mrefsr_ldl_loss_bwd_f32(const float *pred, const float *target, const float 
                             const float *grad_loss, int batch, int h, int w, float loss_weight, float *grad_pred, mrefsr_stream_t stream);
 int mrefsr_ldl_loss_map_f32(const float *vm, const float *stats, int batch, int h, int w, float *wmap, mrefsr_stream_t stream);
 
+/* ---- Real-ESRGAN second-order degradation (csrc/degrade.hip; mrefsr_amd/degradation.py, opt['degradation']) ------------
+ * Forward only.  Images [batch][c][h][w] contiguous fp32; batch c <= 65535, h, w <= 2^19, h w <= 2^30.  Every shape is checked
+ * before any launch.  No entry works in place.
+ *
+ * mrefsr_degrade_filter2d_f32: filter2D of basicsr/utils/img_process_util.py:7-31: the k x k correlation (k odd, 3 ... 21) of the
+ *   image reflect-padded by k / 2 (by index arithmetic; h, w > k / 2), kernels [batch][k][k], or [1][k][k] with shared != 0.
+ *   One launch, a halo tile in LDS.
+ * mrefsr_degrade_usm_f32: USMSharp.forward of img_process_util.py:63-83: blur = the separable Gaussian `taps` (k floats in HOST
+ *   memory, k odd, 3 ... 51, h, w > k / 2; cv2.getGaussianKernel(k, 0)'s values) over the reflect-padded image, r = img - blur,
+ *   soft = blur([|r| 255 > threshold]), out = soft clip(img + weight r, 0, 1) + (1 - soft) img.  Two launches; `residual`
+ *   (the image's size) holds r between them.
+ * mrefsr_degrade_resize_f32: F.interpolate(align_corners=False, no antialiasing) to oh x ow as realesrgan_model.py:95, 126, 151,
+ *   164 call it; mode 0 area (adaptive_avg_pool2d's windows floor(i in / out) ... ceil((i + 1) in / out); the scales are not read),
+ *   1 bilinear, 2 bicubic (A = -0.75).  scale_h, scale_w map output to input coordinates, src = scale (dst + 0.5) - 0.5: torch takes
+ *   1 / scale_factor when it is called with scale_factor, in / out when it is called with size.
+ * mrefsr_degrade_noise_f32: basicsr/data/degradations.py:461-514 (mode 0) and :610-684 (mode 1) on c = 3 images, in the
+ *   reference's operation order.  noise [batch][3][h][w], noise_gray [batch][1][h][w]; param, gray [batch] (sigma_b or scale_b; the
+ *   gray flag 0 or 1).  mode 0: out = clamp(img + ((n sigma / 255) (1 - gray) + (n_gray sigma / 255) gray), 0, 1), n standard
+ *   normal draws.  mode 1: n, n_gray are Poisson draws of rate l vals_b0 and l_gray vals_b1, l = clamp(round(img 255), 0, 255) / 255
+ *   (l_gray: of 0.2989 R + 0.587 G + 0.114 B); out = clamp(img + ((n / vals_b0 - l) (1 - gray) + (n_gray / vals_b1 - l_gray) gray)
+ *   scale, 0, 1); vals [batch][2] from mrefsr_degrade_levels_f32.
+ * mrefsr_degrade_levels_f32: vals[b] = (2^ceil(log2(#distinct levels of the three channels)), the same of the gray image), what
+ *   degradations.py:630-648 reads back per sample with len(torch.unique(...)).  One launch, no readback.  sets:
+ *   mrefsr_degrade_levels_workspace_words(batch) 32-bit words, zero on entry and left zero.
+ * mrefsr_degrade_jpeg_f32: DiffJPEG(differentiable=False) of basicsr/utils/diffjpeg.py:449-491 on c = 3 images in [0, 1];
+ *   quality [batch] in device memory (0 < quality <= 100; the factor as diffjpeg.py:32-45).  One launch, one block per 16 x 16
+ *   macroblock, nothing intermediate in device memory; the zero padding to multiples of 16 is a predicate. */
+int mrefsr_degrade_filter2d_f32(const float *img, const float *kernels, int batch, int c, int h, int w, int k, int shared, float *out,
+                                mrefsr_stream_t stream);
+int mrefsr_degrade_usm_f32(const float *img, const float *taps, int batch, int c, int h, int w, int k, float weight, float threshold,
+                           float *residual, float *out, mrefsr_stream_t stream);
+int mrefsr_degrade_resize_f32(const float *in, int batch, int c, int h, int w, int oh, int ow, int mode, float scale_h, float scale_w,
+                              float *out, mrefsr_stream_t stream);
+int mrefsr_degrade_noise_f32(const float *img, const float *noise, const float *noise_gray, const float *param, const float *gray,
+                             const float *vals, int batch, int h, int w, int mode, float *out, mrefsr_stream_t stream);
+int64_t mrefsr_degrade_levels_workspace_words(int batch);
+int mrefsr_degrade_levels_f32(const float *img, int batch, int h, int w, uint32_t *sets, float *vals, mrefsr_stream_t stream);
+int mrefsr_degrade_jpeg_f32(const float *img, const float *quality, int batch, int h, int w, float *out, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

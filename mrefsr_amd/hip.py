@@ -1857,6 +1857,125 @@ def ldl_loss_bwd(pred, target, saved, grad_loss, loss_weight=1.0):
     return grad
 
 
+# ------------------------------------------------------------------ second-order degradation (csrc/degrade.hip; degradation.py)
+DEGRADE_MODES = {'area': 0, 'bilinear': 1, 'bicubic': 2}
+_levels_sets = {}
+
+
+def _degrade_image(name, img, channels=None):
+    _chk(name, img)
+    if img.dim() != 4 or (channels is not None and img.shape[1] != channels) or img.numel() == 0:
+        raise ValueError(f'{name}: a [B,{channels or "C"},H,W] image expected, got {tuple(img.shape)}')
+    return tuple(img.shape)
+
+
+def degrade_filter2d(img, kernel):
+    """filter2D (basicsr/utils/img_process_util.py:7-31): img [B,C,H,W], kernel [B,k,k] or [1,k,k] (one for the batch), k odd,
+    3 ... 21, H, W > k // 2 -> the k x k correlation of the reflect-padded image.  One launch"""
+    b, c, h, w = _degrade_image('degrade_filter2d', img)
+    _chk('degrade_filter2d', kernel)
+    k = kernel.shape[-1]
+    if kernel.dim() != 3 or kernel.shape[1] != k or kernel.shape[0] not in (1, b):
+        raise ValueError(f'degrade_filter2d: kernels [{b},k,k] or [1,k,k] expected, got {tuple(kernel.shape)}')
+    out = torch.empty_like(img)
+    with _timed('degrade_filter2d', detail=True, flops=2.0 * img.numel() * k * k, nbytes=8.0 * img.numel()):
+        _lib.call('mrefsr_degrade_filter2d_f32', _p(img), _p(kernel), b, c, h, w, k, int(kernel.shape[0] == 1 and b > 1), _p(out), _stream())
+    return out
+
+
+def degrade_usm(img, radius=51, weight=0.5, threshold=10.0):
+    """USMSharp.forward (img_process_util.py:63-83; an even radius is raised by one, as there): the Gaussian as a row and a column
+    pass in LDS.  img [B,C,H,W], H, W > radius // 2.  Two launches"""
+    from .degradation import gaussian_kernel1d
+    b, c, h, w = _degrade_image('degrade_usm', img)
+    k = int(radius) + (1 if int(radius) % 2 == 0 else 0)
+    if k < 3 or k > 51:
+        raise ValueError(f'degrade_usm: radius {radius} outside 3 ... 51')
+    taps = (C.c_float * k)(*gaussian_kernel1d(k).tolist())
+    residual, out = torch.empty_like(img), torch.empty_like(img)
+    with _timed('degrade_usm', detail=True, flops=8.0 * img.numel() * k, nbytes=20.0 * img.numel()):
+        _lib.call('mrefsr_degrade_usm_f32', _p(img), taps, b, c, h, w, k, C.c_float(weight), C.c_float(threshold), _p(residual), _p(out),
+                  _stream())
+    return out
+
+
+def degrade_resize_geometry(in_hw, size=None, scale_factor=None):
+    """((out_h, out_w), (scale_h, scale_w)) of F.interpolate(size=... | scale_factor=..., align_corners=False): the output size and
+    the output -> input coordinate scales torch uses -- 1 / scale_factor when called with scale_factor (the output size is
+    floor(in * scale_factor)), in / out when called with size"""
+    if (size is None) == (scale_factor is None):
+        raise ValueError('degrade_resize: exactly one of size and scale_factor')
+    if size is not None:
+        oh, ow = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+        if oh < 1 or ow < 1:
+            raise ValueError(f'degrade_resize: output size {(oh, ow)}')
+        return (oh, ow), (in_hw[0] / oh, in_hw[1] / ow)
+    sf = (float(scale_factor),) * 2 if isinstance(scale_factor, (int, float)) else (float(scale_factor[0]), float(scale_factor[1]))
+    if not all(s > 0 and math.isfinite(s) for s in sf):
+        raise ValueError(f'degrade_resize: scale_factor {scale_factor}')
+    oh, ow = int(math.floor(in_hw[0] * sf[0])), int(math.floor(in_hw[1] * sf[1]))
+    if oh < 1 or ow < 1:
+        raise ValueError(f'degrade_resize: scale_factor {scale_factor} leaves no pixel of {tuple(in_hw)}')
+    return (oh, ow), (1.0 / sf[0], 1.0 / sf[1])
+
+
+def degrade_resize(img, size=None, scale_factor=None, mode='bicubic'):
+    """F.interpolate(img, size=... | scale_factor=..., mode='area' | 'bilinear' | 'bicubic') with align_corners=False and no
+    antialiasing (cubic A = -0.75; area = adaptive_avg_pool2d).  One launch"""
+    b, c, h, w = _degrade_image('degrade_resize', img)
+    if mode not in DEGRADE_MODES:
+        raise ValueError(f'degrade_resize: mode {mode!r} not in {sorted(DEGRADE_MODES)}')
+    (oh, ow), (sh, sw) = degrade_resize_geometry((h, w), size, scale_factor)
+    out = torch.empty((b, c, oh, ow), device=img.device, dtype=torch.float32)
+    with _timed('degrade_resize', detail=True, nbytes=4.0 * (img.numel() + out.numel())):
+        _lib.call('mrefsr_degrade_resize_f32', _p(img), b, c, h, w, oh, ow, DEGRADE_MODES[mode], C.c_float(sh), C.c_float(sw), _p(out),
+                  _stream())
+    return out
+
+
+def degrade_levels(img):
+    """img [B,3,H,W] -> vals [B,2] fp32 on the device: 2^ceil(log2(n)) for n = the distinct values of clamp(round(img 255), 0, 255)
+    over the three channels, and over the gray image 0.2989 R + 0.587 G + 0.114 B (degradations.py:630-648 without its host loop)"""
+    b, _, h, w = _degrade_image('degrade_levels', img, 3)
+    key = (img.device.index, torch.cuda.current_stream().cuda_stream, torch.cuda.is_current_stream_capturing(), b)
+    sets = _levels_sets.get(key)
+    if sets is None:   # zeroed once; every launch leaves it zero
+        sets = _levels_sets[key] = torch.zeros(_lib.load().mrefsr_degrade_levels_workspace_words(b), device=img.device, dtype=torch.int32)
+    vals = torch.empty((b, 2), device=img.device, dtype=torch.float32)
+    with _timed('degrade_levels', detail=True, nbytes=4.0 * img.numel()):
+        _lib.call('mrefsr_degrade_levels_f32', _p(img), b, h, w, _p(sets), _p(vals), _stream())
+    return vals
+
+
+def degrade_noise(img, noise, noise_gray, param, gray, vals=None, poisson=False):
+    """The noise models of degradations.py on drawn tensors: img, noise [B,3,H,W], noise_gray [B,1,H,W], param (sigma_b, or scale_b
+    with poisson), gray (flags 0 / 1) [B], vals [B,2] from degrade_levels (Poisson only).  One launch; see degradation.noise_torch"""
+    b, _, h, w = _degrade_image('degrade_noise', img, 3)
+    _chk('degrade_noise', noise, noise_gray, param, gray, vals)
+    if noise.shape != img.shape or tuple(noise_gray.shape) != (b, 1, h, w) or tuple(param.shape) != (b,) or tuple(gray.shape) != (b,):
+        raise ValueError(f'degrade_noise: noise {tuple(img.shape)}, noise_gray {(b, 1, h, w)}, param and gray {(b,)} expected')
+    if poisson and (vals is None or tuple(vals.shape) != (b, 2)):
+        raise ValueError(f'degrade_noise: the Poisson model needs vals {(b, 2)} (degrade_levels)')
+    out = torch.empty_like(img)
+    with _timed('degrade_noise', detail=True, nbytes=4.0 * (3 * img.numel() + noise_gray.numel())):
+        _lib.call('mrefsr_degrade_noise_f32', _p(img), _p(noise), _p(noise_gray), _p(param), _p(gray), _p(vals if poisson else None), b, h, w,
+                  1 if poisson else 0, _p(out), _stream())
+    return out
+
+
+def degrade_jpeg(img, quality):
+    """DiffJPEG(differentiable=False) (basicsr/utils/diffjpeg.py:449-491): img [B,3,H,W] in [0, 1], quality [B] on the device
+    (0 < q <= 100; not modified, where the reference overwrites it with the factors).  One launch"""
+    b, _, h, w = _degrade_image('degrade_jpeg', img, 3)
+    _chk('degrade_jpeg', quality)
+    if tuple(quality.shape) != (b,):
+        raise ValueError(f'degrade_jpeg: quality {(b,)} expected, got {tuple(quality.shape)}')
+    out = torch.empty_like(img)
+    with _timed('degrade_jpeg', detail=True, nbytes=8.0 * img.numel()):
+        _lib.call('mrefsr_degrade_jpeg_f32', _p(img), _p(quality), b, h, w, _p(out), _stream())
+    return out
+
+
 def texture_swap_nhwc(feat, sel, pidx, k, s):
     """feat [K*B,s*h,s*w,C] (the references' k-major NHWC maps, read in place), sel / pidx int32 [B,h-2,w-2] from texture_select ->
     [B,s*h,s*w,C]: the matched 3s x 3s reference patches pasted at (s*y, s*x), overlaps averaged (ascending (y, x), fp32)"""

@@ -97,6 +97,7 @@ class MultiRefRestorationModel:
                              "MultiRefRestorationModel's")
         self.device = torch.device('cuda', torch.cuda.current_device())
         self.is_train = opt['is_train']
+        self._setup_degradation(opt)
         self.schedulers, self.optimizers = [], []
         logger = logging.getLogger('basicsr')
 
@@ -156,6 +157,76 @@ class MultiRefRestorationModel:
                 self.optimizer_g.ema_decay = self.ema_decay
             self.optimizers.append(self.optimizer_g)
             self.init_training_settings()
+
+    # ------------------------------------------------------------------ opt['degradation']: the LQ input synthesised on the device
+    _GT_USM_KEYS = ('l1_gt_usm', 'percep_gt_usm', 'gan_gt_usm')
+    # (the state of a model without the option; _setup_degradation sets the instance's)
+    degradation = pair_pool = gt_usm = None
+    _synthesise = False
+    _gt_usm = dict.fromkeys(_GT_USM_KEYS, False)
+
+    def _setup_degradation(self, opt):
+        """opt['degradation'] (a dict of degradation.OPTION_KEYS: the reference yml's degradation and blur-kernel keys, plus an
+        optional queue_size): training batches get their LQ input from Real-ESRGAN's second-order degradation of the GT
+        (realesrgan_model.py:68-179) on the kernels of csrc/degrade.hip, see _degrade.  Validation and test() never synthesise
+        (:187-191).  l1_gt_usm / percep_gt_usm / gan_gt_usm (top level, as in the reference's yml) make the pixel, SSIM and LDL
+        losses / the perceptual and style losses / the discriminator's real images take the USM-sharpened GT; the texture loss has no
+        GT.  They are refused without `degradation`.  train.hip_graph stays allowed: the synthesis runs in feed_data, outside the
+        captured region (the sharpened GT is one more static input of the capture).  Without the option nothing changes."""
+        self.degradation = self.pair_pool = self.gt_usm = None
+        self._synthesise = False
+        self._gt_usm = {k: bool(opt.get(k, False)) for k in self._GT_USM_KEYS}
+        deg_opt = opt.get('degradation')
+        if deg_opt is None or deg_opt is False:   # ({} is the option with every default)
+            wanted = [k for k in self._GT_USM_KEYS if self._gt_usm[k]]
+            if wanted:
+                raise ValueError(f'{wanted} without the degradation option: the USM-sharpened GT is made by the degradation chain; set '
+                                 'degradation or drop them')
+            return
+        if not self._REF_POOLS:
+            raise NotImplementedError(f"degradation: {type(self).__name__} does not synthesise its input; MultiRefRestorationModel does")
+        from ..degradation import HighOrderDegradation, TrainingPairPool
+        if not isinstance(deg_opt, dict):
+            raise ValueError(f'degradation: a dict of options expected ({{}} for the defaults), got {deg_opt!r}')
+        deg_opt = dict(deg_opt)
+        deg_opt.setdefault('scale', opt['scale'])
+        if deg_opt['scale'] != opt['scale']:
+            raise ValueError(f"degradation.scale {deg_opt['scale']} differs from the model's scale {opt['scale']}")
+        self.degradation = HighOrderDegradation(deg_opt)
+        if self.degradation.queue_size is not None:
+            self.pair_pool = TrainingPairPool(self.degradation.queue_size)
+        import numpy as np
+        seed = opt.get('manual_seed')
+        if seed is None:   # (from torch's global generator: reproducible behind torch.manual_seed)
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        self._degrade_rng = np.random.default_rng(seed)
+        self._degrade_gen = torch.Generator(device=self.device).manual_seed(seed)
+        self._pool_gen = torch.Generator().manual_seed(seed)
+        self._synthesise = bool(self.is_train)
+
+    def _degrade(self, data):
+        """feed_data's dict with img_in_lq replaced by the synthesised LQ of data['img_in'] (on the 1/255 grid) and img_in_up by its
+        bicubic x scale up-sampling clamped to [0, 1] -- the frozen extractor is fed from the degraded image, as it would be at
+        deployment; sets gt_usm.  With queue_size the (lq, gt, references, ref_valid) of the batch go through the training pair pool
+        first (realesrgan_model.py:31-66, :176-178).  The GT sides must be multiples of 4 * scale."""
+        from .. import hip
+        gt = data['img_in'].to(self.device, non_blocking=True).float().contiguous()
+        plan = self.degradation.sample(gt.shape[0], gt.shape[2:], self._degrade_rng)
+        lq, gt_usm = self.degradation.apply(gt, plan, self._degrade_gen)
+        data = dict(data, img_in=gt, img_in_lq=lq)
+        if self.pair_pool is not None:
+            keys = [k for k in ('img_in_lq', 'img_in', 'img_ref_list', 'ref_valid') if data.get(k) is not None]
+            data.update(self.pair_pool.step({k: data[k] for k in keys}, self._pool_gen))
+            gt_usm = hip.degrade_usm(data['img_in'].contiguous())
+        self.gt_usm = gt_usm
+        with torch.no_grad():
+            data['img_in_up'] = torch.clamp(hip.degrade_resize(data['img_in_lq'].contiguous(), scale_factor=self.degradation.scale,
+                                                               mode='bicubic'), 0, 1)
+        return data
+
+    def _gt_for(self, which):
+        """the GT of a loss family: 'l1' (pixel, SSIM, LDL), 'percep' (perceptual, style) or 'gan' (D's real images)"""
+        return self.gt_usm if self._gt_usm[which + '_gt_usm'] and self.gt_usm is not None else self.gt
 
     # ------------------------------------------------------------------ the parameter update: train.hip_adam, train.ema_decay
     def _hip_adam_wanted(self):
@@ -517,6 +588,9 @@ class MultiRefRestorationModel:
         With the ref_select option and K = N > top_k (N <= 32) the references are a pool: every pass picks each sample's top_k best
         present candidates on the device (_forward_pool) and restores from those."""
         self.ref_pool = self.ref_selection = self.ref_scores = None
+        self.gt_usm = None
+        if self._synthesise:   # opt['degradation'], training batches only: img_in_lq and img_in_up are made from img_in
+            data = self._degrade(data)
         if self.ref_select is not None and data['img_ref_list'].shape[1] > self.ref_select[0]:
             self._feed_pool(data, self.ref_select[0])   # (checked on the host before anything is launched)
             self.img_in_lq = data['img_in_lq'].to(self.device, non_blocking=True)
@@ -652,7 +726,7 @@ class MultiRefRestorationModel:
     def _loss_and_backward(self, step):
         """net_g's losses of ref :197-279 and their backward: returns True when a gradient was produced (the optimiser may step)"""
         if step <= self.net_g_pretrain_steps:
-            l_pix = self.cri_pix(self.output, self.gt)
+            l_pix = self.cri_pix(self.output, self._gt_for('l1'))
             l_pix.backward()
             self.log_dict['l_pix'] = l_pix.detach()
             return True
@@ -660,15 +734,15 @@ class MultiRefRestorationModel:
                 (step - self.net_g_pretrain_steps) > self.net_d_init_steps:
             l_g_total = 0
             if self.cri_pix is not None:
-                l_g_pix = self.cri_pix(self.output, self.gt)
+                l_g_pix = self.cri_pix(self.output, self._gt_for('l1'))
                 l_g_total = l_g_total + l_g_pix
                 self.log_dict['l_g_pix'] = l_g_pix.detach()
             if self.cri_perceptual is not None:
-                l_g_percep, _ = self.cri_perceptual(self.output, self.gt)
+                l_g_percep, _ = self.cri_perceptual(self.output, self._gt_for('percep'))
                 l_g_total = l_g_total + l_g_percep
                 self.log_dict['l_g_percep'] = l_g_percep.detach()
             if self.cri_style is not None:
-                _, l_g_style = self.cri_style(self.output, self.gt)
+                _, l_g_style = self.cri_style(self.output, self._gt_for('percep'))
                 l_g_total = l_g_total + l_g_style
                 self.log_dict['l_g_style'] = l_g_style.detach()
             if self.cri_texture is not None:   # ref :265-269
@@ -676,12 +750,12 @@ class MultiRefRestorationModel:
                 l_g_total = l_g_total + l_g_texture
                 self.log_dict['l_g_texture'] = l_g_texture.detach()
             if self.cri_ssim is not None:
-                l_g_ssim = self.cri_ssim(self.output, self.gt)
+                l_g_ssim = self.cri_ssim(self.output, self._gt_for('l1'))
                 l_g_total = l_g_total + l_g_ssim
                 self.log_dict['l_g_ssim'] = l_g_ssim.detach()
             if self.cri_ldl is not None:   # realesrgan_model.py:211-226
                 self.output_ema = self._ema_pass()
-                l_g_ldl = self.cri_ldl(self.output, self.gt, self.output_ema)
+                l_g_ldl = self.cri_ldl(self.output, self._gt_for('l1'), self.output_ema)
                 l_g_total = l_g_total + l_g_ldl
                 self.log_dict['l_g_ldl'] = l_g_ldl.detach()
             if self.net_d is not None:   # ref :272-276 (D's parameters are frozen: no weight gradient of D is computed)
@@ -711,6 +785,10 @@ class MultiRefRestorationModel:
             and not self.opt.get('network_d')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
+
+    def _train_inputs(self):
+        """the tensors a captured training step reads: with a synthesised batch the USM-sharpened GT as well"""
+        return self._TRAIN_INPUTS + (('gt_usm',) if self.gt_usm is not None else ())
     _GRAPH_WARMUP = 3   # eager steps per input shape before capture (lazy kernel attributes, workspaces, MIOpen find results)
 
     def _optimize_graphed(self, step):
@@ -721,7 +799,7 @@ class MultiRefRestorationModel:
             return False   # (the phases of ref :197-279 differ in what they run and log: only the steady one is captured)
         # (the learning rates are NOT part of the key: the captured update reads them from device tensors, refreshed below when a
         # scheduler has moved them -- update_learning_rate with warm-up, base_model.py:172-193, moves them every iteration)
-        key = (tuple(tuple(getattr(self, n).shape) for n in self._TRAIN_INPUTS), self.num_refs, hip.packed_epoch(), nhwc_train.scale_epoch())
+        key = (self._train_inputs(), tuple(tuple(getattr(self, n).shape) for n in self._train_inputs()), self.num_refs, hip.packed_epoch(), nhwc_train.scale_epoch())
         st = self.__dict__.setdefault('_tgraph', {'key': None})
         if st['key'] != key:
             changes = st.get('changes', 0) + (st['key'] is not None)
@@ -735,7 +813,7 @@ class MultiRefRestorationModel:
             if st['eager'] < self._GRAPH_WARMUP:
                 st['eager'] += 1
                 return False
-            static = {n: getattr(self, n).clone() for n in self._TRAIN_INPUTS}
+            static = {n: getattr(self, n).clone() for n in self._train_inputs()}
             for n, t in static.items():
                 setattr(self, n, t)
             dyn = [m for m in self.net_g.modules() if hasattr(m, '_offset_count')]
@@ -773,7 +851,7 @@ class MultiRefRestorationModel:
                 st.clear()
                 st.update(key=None)
                 return False
-            for n in self._TRAIN_INPUTS:
+            for n in self._train_inputs():
                 st['static'][n].copy_(getattr(self, n))
                 setattr(self, n, st['static'][n])
             for m, c in zip(st['dyn'], st['counts']):
@@ -815,7 +893,8 @@ class MultiRefRestorationModel:
         self.optimizer_d.zero_grad()
         for p in self.net_d.parameters():
             p.requires_grad = True
-        real_d_pred = self.net_d(self.gt)
+        gan_gt = self._gt_for('gan')
+        real_d_pred = self.net_d(gan_gt)
         l_d_real = self.cri_gan(real_d_pred, True, is_disc=True)
         self.log_dict['l_d_real'] = l_d_real.detach()
         self.log_dict['out_d_real'] = torch.mean(real_d_pred.detach())
@@ -825,13 +904,13 @@ class MultiRefRestorationModel:
         self.log_dict['out_d_fake'] = torch.mean(fake_d_pred.detach())
         l_d_total = l_d_real + l_d_fake
         if self.cri_grad_penalty is not None:
-            l_grad_penalty = self.cri_grad_penalty(self.net_d, self.gt, self.output)
+            l_grad_penalty = self.cri_grad_penalty(self.net_d, gan_gt, self.output)
             self.log_dict['l_grad_penalty'] = l_grad_penalty.detach()
             l_d_total = l_d_total + l_grad_penalty
         l_d_total.backward()
         if self.r1_reg_weight > 0 and step % self.net_d_reg_every == 0:
             from ..losses import r1_penalty
-            real_img = self.gt.detach().requires_grad_(True)   # a leaf of its own on self.gt's storage (D only reads it)
+            real_img = gan_gt.detach().requires_grad_(True)   # a leaf of its own on the GT's storage (D only reads it)
             real_pred = self.net_d(real_img)
             l_d_r1 = r1_penalty(real_pred, real_img)
             # (0 * real_pred[0]: every output of D takes part in this backward, which is what DDP's reducer asks for)
@@ -1069,6 +1148,14 @@ class MultiRefRestorationModel:
         return bool((self.opt.get('val') or {}).get('metrics_on_device'))
 
     def nondist_validation(self, dataloader, current_iter, tb_logger, save_img):
+        """validation never synthesises its input (realesrgan_model.py:187-191): the flag is put back behind it"""
+        synthesise, self._synthesise = self._synthesise, False
+        try:
+            return self._nondist_validation(dataloader, current_iter, tb_logger, save_img)
+        finally:
+            self._synthesise = synthesise
+
+    def _nondist_validation(self, dataloader, current_iter, tb_logger, save_img):
         """per image: feed_data -> test -> uint8 image -> crop the dataset's zero padding -> [PNG] -> PSNR (RGB), PSNR (Y),
         SSIM (Y) with crop_border from the options (ref :324-386).  save_img writes
         path.visualization/<img>/<img>_<iter>.png while training, path.visualization/<dataset>/<img>_<name>[_suffix].png when testing.
