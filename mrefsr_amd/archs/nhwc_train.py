@@ -229,7 +229,7 @@ def capture_state():
         for e in st['rows']:
             w = e[0]()
             ptrs.append((e[1].data.data_ptr(), w.data_ptr() if w is not None else -1))
-    ptrs.append(hip.capture_ptrs())   # workspaces (DCN, zero chunks, weight-gradient partials): a regrown one has moved
+    ptrs.append(hip.capture_ptrs())   # the capture's cached scratch, ticket words and zero chunks: a regrown one has moved
     return objs, tuple(ptrs)
 
 

@@ -72,6 +72,140 @@ def _p(t):
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _chk(name, *tensors, dtype=torch.float32):
+    for t in tensors:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise NotImplementedError(f'{name}: tensor on {t.device}; mrefsr_amd has no CPU path (HIP kernels only)')
+        if t.dtype != dtype:
+            raise TypeError(f'{name}: expected {dtype}, got {t.dtype}')
+        if not t.is_contiguous():
+            raise ValueError(f'{name}: tensor must be contiguous')
+
+
+def _c(t):
+    return t if t is None or t.is_contiguous() else t.contiguous()
+
+
+def _ptrs(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+# ------------------------------------------------------------------ cached device memory
+# Device memory that outlives a wrapper call (scratch, zeroed ticket / level-set words, zero-filled accumulator chunks) is cached
+# per (device, stream, side of a hipGraph capture boundary[, extra key]) in instances of ONE class, and the capture bookkeeping
+# (release_capture_workspaces, capture_refs, capture_ptrs) runs over all of them: a new cache is an instance, nothing else.
+def _stream_side():
+    """(handle of torch's current stream, whether it is capturing): the caches and capture_epoch() read both here, nowhere else"""
+    # (the raw handle, 0.7 us for the pair: torch.cuda.current_stream() builds a Stream object per call, 2.7 us, and capture_epoch()
+    #  is asked once per packed weight, ~340 times per training step)
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()), torch.cuda.is_current_stream_capturing()
+
+
+_caches = []
+
+
+class _StreamCache:
+    """entries per (device index, stream handle, capturing, extra).  Per stream: launches on ONE stream are ordered, two eager
+    streams sharing a buffer would overwrite each other's contents.  Per side: a buffer handed out under a capture comes from the
+    graph's pool and its address is baked into the graph -- the graph's owner keeps it (capture_refs), it is dropped with the
+    graph (release_capture_workspaces), and nothing an eager call does replaces it.  tensor: entry -> its buffer"""
+
+    def __init__(self, tensor=lambda e: e):
+        self.entries, self.tensor = {}, tensor
+        _caches.append(self)
+
+    def key(self, device, extra=None):
+        return (device.index, *_stream_side(), extra)
+
+    def captured(self):
+        return [k for k in self.entries if k[2]]
+
+
+_scratch_bufs, _zeroed, _zero_chunks = _StreamCache(), _StreamCache(), _StreamCache(tensor=lambda ch: ch[0])
+
+
+def _scratch(device, nbytes):
+    """>= nbytes of uint8 scratch (256-byte aligned; at least 1 MiB, so that warm-up does not reallocate at every slightly larger
+    request), one growing buffer per cache key.  THE RULE: its contents are dead once the launches of the wrapper call that asked
+    for it are enqueued -- launches on a stream are ordered, and the next wrapper call on that stream may take the same bytes.
+    So a wrapper asks ONCE per call (two regions at once: one request, sliced at 256-byte alignment), reads nothing a previous
+    call left here, and passes the library the byte count it asked for, not the buffer's size"""
+    key = _scratch_bufs.key(device)
+    buf = _scratch_bufs.entries.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _scratch_bufs.entries[key] = torch.empty(max(nbytes, 1 << 20), device=device, dtype=torch.uint8)
+    return buf
+
+
+def _zeroed_words(device, name, n):
+    """n int32 words zeroed once that every launch using them leaves zero again (tickets, level sets), per cache key and (name, n)"""
+    key = _zeroed.key(device, (name, n))
+    t = _zeroed.entries.get(key)
+    if t is None:
+        t = _zeroed.entries[key] = torch.zeros(n, device=device, dtype=torch.int32)
+    return t
+
+
+def release_capture_workspaces():
+    """drop every cached buffer that was handed out under a capture (call when the graphs that used them are destroyed)"""
+    for c in _caches:
+        for k in c.captured():
+            del c.entries[k]
+
+
+def capture_refs():
+    """the cached buffers whose addresses a hipGraph captured now may have baked in: whoever owns the graph keeps this list as
+    long as the graph lives"""
+    # (only the buffers that were handed out UNDER a capture: an eager regrowth of some other stream's scratch -- validation at
+    #  another size, the correlation call's scratch -- does not move anything a graph baked in, and must not force a recapture)
+    return [c.tensor(c.entries[k]) for c in _caches for k in c.captured()]
+
+
+def capture_ptrs():
+    """addresses of the cached buffers of capture_refs(): a graph owner compares them before a replay (a regrown buffer has moved)"""
+    return tuple(t.data_ptr() for t in capture_refs())
+
+
+_cap_state = [False, 0]
+
+
+def _epoch(cap):
+    if cap != _cap_state[0]:
+        _cap_state[0] = cap
+        _cap_state[1] += 1
+    return cap, _cap_state[1]
+
+
+def capture_epoch():
+    """(capturing, epoch): the epoch moves every time this is called on the other side of a hipGraph capture boundary than
+    the call before -- device state prepared on one side (zero-filled accumulators, packed weight copies) is not replayed with
+    a graph captured on the other, so its users key it by this epoch"""
+    return _epoch(_stream_side()[1])
+
+
+_ZCHUNK = 1 << 18
+_ZALIGN = 128         # floats: slices start on 512-byte boundaries like allocations of their own (float atomics into a slice at
+                      # 16-byte granularity ran 17 % slower: act_bwd_nhwc 5.66 -> 4.87 ms per training step)
+
+
+def zeros_f32(device, n):
+    """n zero float32 (512-byte aligned) carved from a chunk that ONE fill launch zeroed: the accumulators of act_bwd_nhwc (bias
+    gradient, PReLU slope gradient, max |g|: ~70 floats, 174 times per training step) each had a fill launch of their own.  A
+    slice is handed out once and never re-zeroed, so it may be kept (autograd adopts the bias gradient as ``.grad``); the chunk
+    lives as long as any of its slices.  Chunks are per stream and per side of a capture boundary (the fill that zeroes a chunk
+    has to be part of the graph whose kernels accumulate into it)."""
+    key = _zero_chunks.key(device)
+    _, epoch = _epoch(key[2])
+    n4 = (n + _ZALIGN - 1) // _ZALIGN * _ZALIGN
+    ch = _zero_chunks.entries.get(key)
+    if ch is None or ch[2] != epoch or ch[1] + n4 > ch[0].numel():
+        ch = _zero_chunks.entries[key] = [torch.zeros(max(_ZCHUNK, n4), device=device, dtype=torch.float32), 0, epoch]
+    out = ch[0][ch[1]:ch[1] + n]
+    ch[1] += n4
+    return out
+
 # ------------------------------------------------------------------ deterministic mode
 # net_g's backward adds three kinds of per-channel sums over blocks with float atomics (bias gradients and the PReLU slope gradient
 # in act_bwd_nhwc, conv_offset_mask's bias gradient in dynagg_prep_bwd_nhwc, the per-cout sums in the epilogue of conv_nhwc_bwd):
@@ -127,31 +261,9 @@ def nondeterministic_alert(what):
         raise RuntimeError(msg)
 
 
-_det_tickets = {}
-
-
 def _det_scratch(device, nbytes):
-    """(partials workspace, ticket word) of one deterministic reduction launch: the workspace is the stream's cached one (launches
-    on a stream are ordered, a launch has consumed its partials when it ends), the ticket a zeroed word per stream and side of a
-    capture boundary that every launch leaves zero again"""
-    ws = _workspace(device, max(int(nbytes), 4))
-    key = (device.index, torch.cuda.current_stream().cuda_stream, torch.cuda.is_current_stream_capturing())
-    t = _det_tickets.get(key)
-    if t is None:
-        t = _det_tickets[key] = torch.zeros(1, device=device, dtype=torch.int32)
-    return ws, t
-
-
-def _chk(name, *tensors, dtype=torch.float32):
-    for t in tensors:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise NotImplementedError(f'{name}: tensor on {t.device}; mrefsr_amd has no CPU path (HIP kernels only)')
-        if t.dtype != dtype:
-            raise TypeError(f'{name}: expected {dtype}, got {t.dtype}')
-        if not t.is_contiguous():
-            raise ValueError(f'{name}: tensor must be contiguous')
+    """(partials scratch, ticket word) of one deterministic reduction launch: every launch leaves the ticket zero again"""
+    return _scratch(device, max(int(nbytes), 4)), _zeroed_words(device, 'ticket', 1)
 
 
 # ------------------------------------------------------------------ correlation path
@@ -242,9 +354,9 @@ def corr_top1(y_in, y_ref, inv_ref, nrm_in, h, w, want_val=True, ybf_in=None, yb
             if not fmt or tuple(tau.shape) != (n_pair, h - 2, w - 2):
                 raise ValueError('corr_top1: tau is [n_pair,h-2,w-2] and belongs to the fp16 pre-filter operand')
         need = _lib.load().mrefsr_corr_workspace_bytes(n_pair, h, w)
-        ws = _workspace(y_in.device, need)   # (pooled per device and stream with the DCN's: ~400 MB at the benchmark size, used
-                                             #  and dropped within this call; a fresh torch.empty per call held a second copy
-                                             #  of it alive in the allocator across the whole pass)
+        ws = _scratch(y_in.device, need)   # (~400 MB at the benchmark size, used and dropped within this call; a fresh torch.empty
+                                           #  per call held a second copy of it alive in the allocator across the whole pass)
+        # diagnostic hook (tools/corr_diag.py): the bytes last only until the next scratch user on this stream -- read them at once
         _timing['last_corr_ws'] = (ws, n_pair, (h - 2) * (w - 2)) if _timing.get('keep_ws') else None
         with _timed('corr_top1'):
             _lib.call('mrefsr_corr_top1_prefilter_f32', _p(y_in), _p(y_ref), _p(ybf_in), _p(ybf_ref), _p(inv_ref),
@@ -320,9 +432,10 @@ def dynagg_prep_bwd_nhwc(g_offset, g_mask, mask, dg, want_bias=True):
     g_om = torch.empty((b, h, w, nc), device=mask.device, dtype=torch.float32)
     z = zeros_f32(mask.device, nc + 1)
     if want_bias and is_deterministic():   # the bias gradient added in block order (bitwise reproducible)
-        ws, ticket = _det_scratch(mask.device, _lib.load().mrefsr_dynagg_prep_bwd_det_workspace_bytes(b, dg, h, w))
+        need = _lib.load().mrefsr_dynagg_prep_bwd_det_workspace_bytes(b, dg, h, w)
+        ws, ticket = _det_scratch(mask.device, need)
         _lib.call('mrefsr_dynagg_prep_bwd_nhwc_det_f32', _p(g_offset), _p(g_mask), _p(mask), _p(g_om), _p(z[:nc]), _p(z[nc:]), b, dg, h, w,
-                  _p(ws), C.c_int64(ws.numel()), _p(ticket), _stream())
+                  _p(ws), C.c_int64(need), _p(ticket), _stream())
         return g_om, z[:nc], z[nc:]
     _lib.call('mrefsr_dynagg_prep_bwd_nhwc_f32', _p(g_offset), _p(g_mask), _p(mask), _p(g_om), _p(z[:nc]) if want_bias else None, _p(z[nc:]), b, dg, h, w,
               _stream())
@@ -342,83 +455,6 @@ def dcn_shape(x, weight, stride, padding, dilation, groups, dg):
     ho = (h + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
     wo = (w + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
     return s, ho, wo
-
-
-_ws_cache = {}
-
-
-def _workspace(device, nbytes):
-    # one buffer per (device, stream): dcn_fwd re-packs its split weights into this buffer on every call and then reads them,
-    # which is ordered on ONE stream only -- two eager streams sharing a buffer would overwrite each other's packed weights.
-    # Buffers of streams that were under hipGraph capture are flagged so that they can be freed with their graphs.
-    capturing = torch.cuda.is_current_stream_capturing()
-    key = (device.index, torch.cuda.current_stream().cuda_stream, capturing)
-    buf = _ws_cache.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1), device=device, dtype=torch.uint8)
-        _ws_cache[key] = buf
-    return buf
-
-
-def release_capture_workspaces():
-    """drop the DCN workspaces that belonged to capture streams (call when the graphs that used them are destroyed)"""
-    for k in [k for k in _ws_cache if k[2]]:
-        del _ws_cache[k]
-    for k in [k for k in _zero_chunks if k[2]]:
-        del _zero_chunks[k]
-    for k in [k for k in _det_tickets if k[2]]:
-        del _det_tickets[k]
-
-
-def capture_refs():
-    """the cached buffers (DCN workspaces, zero-filled accumulator chunks) whose addresses a hipGraph captured now may have baked
-    in: whoever owns the graph keeps this list as long as the graph lives"""
-    # (only the buffers that were handed out UNDER a capture: an eager regrowth of some other stream's workspace -- validation at
-    #  another size, the correlation call's scratch -- does not move anything a graph baked in, and must not force a recapture)
-    return [[t for k, t in _ws_cache.items() if k[2]] + [t for k, t in _det_tickets.items() if k[2]],
-            [c[0] for k, c in _zero_chunks.items() if k[2]], list(_wgrad_ws.values())]
-
-
-def capture_ptrs():
-    """addresses of the cached buffers of capture_refs(): a graph owner compares them before a replay (a regrown workspace has moved)"""
-    return tuple(t.data_ptr() for group in capture_refs() for t in group)
-
-
-_cap_state = [False, 0]
-
-
-def capture_epoch():
-    """(capturing, epoch): the epoch moves every time this is called on the other side of a hipGraph capture boundary than
-    the call before -- device state prepared on one side (zero-filled accumulators, packed weight copies) is not replayed with
-    a graph captured on the other, so its users key it by this epoch"""
-    cap = torch.cuda.is_current_stream_capturing()
-    if cap != _cap_state[0]:
-        _cap_state[0] = cap
-        _cap_state[1] += 1
-    return cap, _cap_state[1]
-
-
-_zero_chunks = {}
-_ZCHUNK = 1 << 18
-_ZALIGN = 128         # floats: slices start on 512-byte boundaries like allocations of their own (float atomics into a slice at
-                      # 16-byte granularity ran 17 % slower: act_bwd_nhwc 5.66 -> 4.87 ms per training step)
-
-
-def zeros_f32(device, n):
-    """n zero float32 (512-byte aligned) carved from a chunk that ONE fill launch zeroed: the accumulators of act_bwd_nhwc (bias
-    gradient, PReLU slope gradient, max |g|: ~70 floats, 174 times per training step) each had a fill launch of their own.  A
-    slice is handed out once and never re-zeroed, so it may be kept (autograd adopts the bias gradient as ``.grad``); the chunk
-    lives as long as any of its slices.  Chunks are per stream and per side of a capture boundary (the fill that zeroes a chunk
-    has to be part of the graph whose kernels accumulate into it)."""
-    cap, epoch = capture_epoch()
-    key = (device.index, torch.cuda.current_stream().cuda_stream, cap)
-    n4 = (n + _ZALIGN - 1) // _ZALIGN * _ZALIGN
-    ch = _zero_chunks.get(key)
-    if ch is None or ch[2] != epoch or ch[1] + n4 > ch[0].numel():
-        ch = _zero_chunks[key] = [torch.zeros(max(_ZCHUNK, n4), device=device, dtype=torch.float32), 0, epoch]
-    out = ch[0][ch[1]:ch[1] + n]
-    ch[1] += n4
-    return out
 
 
 def dcn_mfma_eligible(c, co, dg, k=3):
@@ -461,7 +497,7 @@ def dcn_fwd(x, offset, mask, weight, bias, stride, padding, dilation, groups, dg
         out = torch.empty((s.B, ho, wo, s.Co), device=x.device, dtype=x.dtype)
         with _timed('dcn_fwd', 2.0 * s.B * ho * wo * s.C * s.Co * 9, detail=True):
             _lib.call('mrefsr_dcn_fwd_amax_f32', _p(x), _p(offset), _p(mask), _p(weight), _p(bias), _p(out), C.byref(s),
-                      C.c_float(act_slope), (23 if io16 else 7) if bf16_arith else (11 if range_free else 3), _p(_workspace(x.device, need)), C.c_int64(need),
+                      C.c_float(act_slope), (23 if io16 else 7) if bf16_arith else (11 if range_free else 3), _p(_scratch(x.device, need)), C.c_int64(need),
                       _p(_range_flag(x.device)), _p(out_amax), _stream())
         return out
     s, ho, wo = dcn_shape(x, weight, stride, padding, dilation, groups, dg)
@@ -472,7 +508,7 @@ def dcn_fwd(x, offset, mask, weight, bias, stride, padding, dilation, groups, dg
         raise RuntimeError(f'dcn_fwd: mask shape {tuple(mask.shape)} != {(s.B, dg * kk, ho, wo)}')
     out = torch.empty((s.B, s.Co, ho, wo), device=x.device, dtype=torch.float32)
     need = _lib.load().mrefsr_dcn_fwd_workspace_bytes(C.byref(s))
-    ws = _workspace(x.device, need) if need > 0 else None
+    ws = _scratch(x.device, need) if need > 0 else None
     nhwc = (9 if range_free else 1) if (need > 0 and nhwc_gather) else 0
     xin = x.permute(0, 2, 3, 1).contiguous() if nhwc else x
     _lib.call('mrefsr_dcn_fwd_f32', _p(xin), _p(offset), _p(mask), _p(weight), _p(bias), _p(out), C.byref(s),
@@ -552,7 +588,7 @@ def conv_wgrad1x1(x, g, cin, cout, g_amax):
     ld_x, ld_g = _nhwc_ld('x', x), _nhwc_ld('g', g)
     pixels = x.shape[0] * x.shape[1] * x.shape[2]
     nbytes = _lib.load().mrefsr_conv_wgrad1x1_workspace_bytes(pixels, cout, cin)
-    ws = _wgrad_workspace(x.device, nbytes)
+    ws = _scratch(x.device, nbytes)
     gw = torch.empty((cout, cin, 1, 1), device=x.device, dtype=torch.float32)
     _lib.call('mrefsr_conv_wgrad1x1_f32', _p(g), _p(x), _p(g_amax), _p(gw), _p(ws), nbytes, pixels, cout, ld_g, cin, ld_x,
               _p(_range_flag(x.device)), _stream())
@@ -567,7 +603,7 @@ def dcn_bwd_weight(g_out, x, offset, mask, cout, dg, g_amax=None):
     _dcn_bwd_shapes('dcn_bwd_weight', g_out, x, offset, mask, dg)
     s = _lib.DcnShape(b, c, h, w, cout, 3, 3, 1, 1, 1, 1, 1, 1, 1, dg)
     nbytes = _lib.load().mrefsr_dcn_bwd_weight_workspace_bytes(C.byref(s))
-    ws = _wgrad_workspace(x.device, nbytes)
+    ws = _scratch(x.device, nbytes)
     gw = torch.empty((cout, c, 3, 3), device=x.device, dtype=torch.float32)
     _lib.call('mrefsr_dcn_bwd_weight_f32', _p(g_out), _p(x), _p(offset), _p(mask), _p(g_amax), _p(gw), _p(ws), nbytes, C.byref(s),
               _p(_range_flag(x.device)), _stream())
@@ -1218,28 +1254,16 @@ def act_bwd_nhwc(g_out, out, act, slope=0.0, slope_ptr=None, want_bias=True, wan
     amax = z[c + 1:c + 2] if want_amax else None
     flag = _p(_range_flag(g_out.device)) if act == 2 else None
     if (g_bias is not None or g_slope is not None) and is_deterministic():   # the sums added in block order (bitwise reproducible)
-        ws, ticket = _det_scratch(g_out.device, blocks * (c + 1) * 4)
+        need = blocks * (c + 1) * 4
+        ws, ticket = _det_scratch(g_out.device, need)
         _lib.call('mrefsr_act_bwd_nhwc_det_f32', _p(g_out), _p(out if act else None), _p(g_pre), ld, _p(g_bias), _p(g_slope), _p(amax),
-                  C.c_int64(npix), c, act, C.c_float(slope), _p(slope_ptr), flag, _p(ws), C.c_int64(ws.numel()), _p(ticket), _stream())
+                  C.c_int64(npix), c, act, C.c_float(slope), _p(slope_ptr), flag, _p(ws), C.c_int64(need), _p(ticket), _stream())
     else:
         _lib.call('mrefsr_act_bwd_nhwc_f32', _p(g_out), _p(out if act else None), _p(g_pre), ld, _p(g_bias), _p(g_slope), _p(amax), C.c_int64(npix), c,
                   act, C.c_float(slope), _p(slope_ptr), flag, _stream())
     if want_amax:
         return (g_out if g_pre is None else g_pre), g_bias, g_slope, amax
     return (g_out if g_pre is None else g_pre), g_bias, g_slope
-
-
-_wgrad_ws = {}
-
-
-def _wgrad_workspace(device, nbytes):
-    """one growing scratch buffer per device and stream (launches on a stream are ordered: the partials of one weight gradient
-    are consumed by its reduction before the next one writes)"""
-    key = (device.index, torch.cuda.current_stream().cuda_stream)
-    buf = _wgrad_ws.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = _wgrad_ws[key] = torch.empty(max(nbytes, 1 << 20), device=device, dtype=torch.uint8)
-    return buf
 
 
 def conv_wgrad3x3(x, g, cin, cout, g_amax):
@@ -1252,7 +1276,7 @@ def conv_wgrad3x3(x, g, cin, cout, g_amax):
     _chk('conv_wgrad3x3', g_amax)
     dw = torch.empty((cout, cin, 3, 3), device=x.device, dtype=torch.float32)
     need = _lib.load().mrefsr_conv_wgrad3x3_workspace_bytes(n, h, w, cin, cout)
-    ws = _wgrad_workspace(x.device, need)
+    ws = _scratch(x.device, need)
     _lib.call('mrefsr_conv_wgrad3x3_f32', _p(x), ldx, cin, _p(g), ldg, cout, _p(dw), C.c_int64(cin * 9), C.c_int64(9), 0, _p(g_amax), n, h, w,
               _p(ws), C.c_int64(need), _p(_range_flag(x.device)), _stream())
     return dw
@@ -1272,7 +1296,7 @@ def conv_wgrad3x3_batch(xs, gs, cin, cout, g_amaxes):
     _chk('conv_wgrad3x3_batch', *g_amaxes)
     dw = torch.empty((nj, cout, cin, 3, 3), device=xs[0].device, dtype=torch.float32)
     need = _lib.load().mrefsr_conv_wgrad3x3_batch_workspace_bytes(nj, n, h, w, cin, cout)
-    ws = _wgrad_workspace(xs[0].device, need)
+    ws = _scratch(xs[0].device, need)
     arr = C.c_void_p * nj
     _lib.call('mrefsr_conv_wgrad3x3_batch_f32', nj, arr(*[t.data_ptr() for t in xs]), ldx, cin, arr(*[t.data_ptr() for t in gs]), ldg, cout,
               arr(*[dw[j].data_ptr() for j in range(nj)]), C.c_int64(cin * 9), C.c_int64(9), 0, arr(*[t.data_ptr() for t in g_amaxes]), n, h, w,
@@ -1364,10 +1388,10 @@ _amax_pool = {}
 
 
 def _amax_state(device):
-    st = _amax_pool.get(device)
+    st = _amax_pool.get(device.index)
     if st is None:
         buf = torch.zeros(AMAX_POOL, device=device, dtype=torch.float32)
-        st = _amax_pool[device] = [buf, 0, list(buf.split(1))]   # (the one-element views are made once: a slice per launch costs microseconds)
+        st = _amax_pool[device.index] = [buf, 0, list(buf.split(1))]   # (the one-element views are made once: a slice per launch costs microseconds)
     return st
 
 
@@ -1379,7 +1403,7 @@ def amax_pool_reset():
 
 def amax_pool_used(device):
     """the slots handed out on ``device`` since the pool was last reset or wrapped around"""
-    st = _amax_pool.get(device)
+    st = _amax_pool.get(device.index)
     return 0 if st is None else st[1]
 
 
@@ -1487,9 +1511,10 @@ def conv_nhwc_bwd(x, packed, cout, ksize, residual=None, residual_is_mask=False,
     _chk('conv_nhwc_bwd', x, residual, in_amax)
     z = zeros_f32(x.device, cout + 1) if want_stats else None
     if want_stats and is_deterministic():   # the per-cout sums added in tile order (bitwise reproducible)
-        ws, ticket = _det_scratch(x.device, _lib.load().mrefsr_conv_nhwc_bwd_det_workspace_bytes(C.byref(d)))
+        need = _lib.load().mrefsr_conv_nhwc_bwd_det_workspace_bytes(C.byref(d))
+        ws, ticket = _det_scratch(x.device, need)
         _lib.call('mrefsr_conv_nhwc_bwd_det_f32', C.byref(d), _p(x), _p(packed.data), _p(residual), 1 if residual_is_mask else 0, _p(out),
-                  _p(_range_flag(x.device)), _p(in_amax), _p(z[:cout]), _p(z[cout:]), _p(ws), C.c_int64(ws.numel()), _p(ticket), _stream())
+                  _p(_range_flag(x.device)), _p(in_amax), _p(z[:cout]), _p(z[cout:]), _p(ws), C.c_int64(need), _p(ticket), _stream())
         return out, z[:cout], z[cout:]
     _lib.call('mrefsr_conv_nhwc_bwd_f32', C.byref(d), _p(x), _p(packed.data), _p(residual), 1 if residual_is_mask else 0, _p(out),
               _p(_range_flag(x.device)), _p(in_amax), _p(z[:cout]) if want_stats else None, _p(z[cout:]) if want_stats else None, _stream())
@@ -1657,7 +1682,7 @@ def gram_nhwc(f):
     need = lib.mrefsr_gram_workspace_bytes(n, h * w, c)
     if need < 0:
         raise ValueError(f'gram_nhwc: C={c} (a multiple of 64)')
-    ws = _wgrad_workspace(f.device, need)
+    ws = _scratch(f.device, need)
     g = torch.empty((n, c, c), device=f.device, dtype=torch.float32)
     with _timed('gram_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (f.numel() + g.numel())):
         _lib.call('mrefsr_gram_nhwc_f32', _p(f), n, h * w, c, _p(g), _p(ws), C.c_int64(need), _stream())
@@ -1859,7 +1884,6 @@ def ldl_loss_bwd(pred, target, saved, grad_loss, loss_weight=1.0):
 
 # ------------------------------------------------------------------ second-order degradation (csrc/degrade.hip; degradation.py)
 DEGRADE_MODES = {'area': 0, 'bilinear': 1, 'bicubic': 2}
-_levels_sets = {}
 
 
 def _degrade_image(name, img, channels=None):
@@ -1937,10 +1961,7 @@ def degrade_levels(img):
     """img [B,3,H,W] -> vals [B,2] fp32 on the device: 2^ceil(log2(n)) for n = the distinct values of clamp(round(img 255), 0, 255)
     over the three channels, and over the gray image 0.2989 R + 0.587 G + 0.114 B (degradations.py:630-648 without its host loop)"""
     b, _, h, w = _degrade_image('degrade_levels', img, 3)
-    key = (img.device.index, torch.cuda.current_stream().cuda_stream, torch.cuda.is_current_stream_capturing(), b)
-    sets = _levels_sets.get(key)
-    if sets is None:   # zeroed once; every launch leaves it zero
-        sets = _levels_sets[key] = torch.zeros(_lib.load().mrefsr_degrade_levels_workspace_words(b), device=img.device, dtype=torch.int32)
+    sets = _zeroed_words(img.device, 'levels', _lib.load().mrefsr_degrade_levels_workspace_words(b))
     vals = torch.empty((b, 2), device=img.device, dtype=torch.float32)
     with _timed('degrade_levels', detail=True, nbytes=4.0 * img.numel()):
         _lib.call('mrefsr_degrade_levels_f32', _p(img), b, h, w, _p(sets), _p(vals), _stream())
@@ -2028,7 +2049,7 @@ def gram_raw_nhwc(f):
     need = lib.mrefsr_gram_workspace_bytes(n, h * w, c)
     if need < 0:
         raise ValueError(f'gram_raw_nhwc: C={c} (a multiple of 64)')
-    ws = _wgrad_workspace(f.device, need)
+    ws = _scratch(f.device, need)
     g = torch.empty((n, c, c), device=f.device, dtype=torch.float32)
     with _timed('gram_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (f.numel() + g.numel())):
         _lib.call('mrefsr_gram_nhwc_scaled_f32', _p(f), n, h * w, c, C.c_float(1.0), _p(g), _p(ws), C.c_int64(need), _stream())
@@ -2155,10 +2176,10 @@ def disc_conv3x3_wgrad(x, dy, cin_real, stride):
         raise ValueError('disc_conv3x3_wgrad: inconsistent shapes')
     lib = _lib.load()
     need = lib.mrefsr_disc_conv3x3_wgrad_workspace_bytes(n, h, w, cin, cout, stride)
-    ws = _wgrad_workspace(x.device, need)
+    ws = _scratch(x.device, need)
     dw = torch.empty((cout, cin_real, 3, 3), device=x.device, dtype=torch.float32)
     with _timed('disc_conv3x3_wgrad', 2.0 * dy.numel() * 9 * cin, detail=True):
-        _lib.call('mrefsr_disc_conv3x3_wgrad_f32', _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, stride, _p(ws), C.c_int64(ws.numel()),
+        _lib.call('mrefsr_disc_conv3x3_wgrad_f32', _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, stride, _p(ws), C.c_int64(need),
                   _stream())
     return dw
 
@@ -2166,15 +2187,15 @@ def disc_conv3x3_wgrad(x, dy, cin_real, stride):
 def _chan_ws(t):
     p, c = t.numel() // t.shape[-1], t.shape[-1]
     need = _lib.load().mrefsr_disc_chan_workspace_bytes(p, c)
-    return p, c, _wgrad_workspace(t.device, need)
+    return p, c, _scratch(t.device, need), C.c_int64(need)
 
 
 def disc_bias_grad(dy):
     """[..., C] -> [C] sum over every other dimension"""
     _chk('disc_bias_grad', dy)
-    p, c, ws = _chan_ws(dy)
+    p, c, ws, need = _chan_ws(dy)
     db = torch.empty(c, device=dy.device, dtype=torch.float32)
-    _lib.call('mrefsr_disc_bias_grad_f32', _p(dy), _p(db), C.c_int64(p), c, _p(ws), C.c_int64(ws.numel()), _stream())
+    _lib.call('mrefsr_disc_bias_grad_f32', _p(dy), _p(db), C.c_int64(p), c, _p(ws), need, _stream())
     return db
 
 
@@ -2184,13 +2205,13 @@ def disc_bn_lrelu(x, gamma, beta, running_mean=None, running_var=None, num_batch
     _chk('disc_bn_lrelu', x, gamma, beta, running_mean, running_var)
     if num_batches_tracked is not None:
         _chk('disc_bn_lrelu', num_batches_tracked, dtype=torch.int64)
-    p, c, ws = _chan_ws(x)
+    p, c, ws, need = _chan_ws(x)
     y = torch.empty_like(x)
     mean = torch.empty(c, device=x.device, dtype=torch.float32)
     invstd = torch.empty(c, device=x.device, dtype=torch.float32)
     with _timed('disc_bn_lrelu', detail=True):
         _lib.call('mrefsr_disc_bn_lrelu_f32', _p(x), _p(gamma), _p(beta), _p(y), _p(mean), _p(invstd), _p(running_mean), _p(running_var),
-                  _p(num_batches_tracked), C.c_int64(p), c, C.c_float(eps), C.c_float(momentum), C.c_float(slope), _p(ws), C.c_int64(ws.numel()),
+                  _p(num_batches_tracked), C.c_int64(p), c, C.c_float(eps), C.c_float(momentum), C.c_float(slope), _p(ws), need,
                   _stream())
     return y, mean, invstd
 
@@ -2198,33 +2219,27 @@ def disc_bn_lrelu(x, gamma, beta, running_mean=None, running_var=None, num_batch
 def disc_bn_lrelu_bwd(gy, y, x, mean, invstd, gamma, slope=0.2, want_gx=True, want_params=True):
     """-> (gx | None, ggamma | None, gbeta | None)"""
     _chk('disc_bn_lrelu_bwd', gy, y, x, mean, invstd, gamma)
-    p, c, ws = _chan_ws(x)
+    p, c, ws, need = _chan_ws(x)
     gx = torch.empty_like(x) if want_gx else None
     gg = torch.empty(c, device=x.device, dtype=torch.float32) if want_params else None
     gb = torch.empty(c, device=x.device, dtype=torch.float32) if want_params else None
     with _timed('disc_bn_lrelu_bwd', detail=True):
         _lib.call('mrefsr_disc_bn_lrelu_bwd_f32', _p(gy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(gx), _p(gg), _p(gb), C.c_int64(p), c,
-                  C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+                  C.c_float(slope), _p(ws), need, _stream())
     return gx, gg, gb
 
 
 def disc_bn_lrelu_dbl(ggx, ggamma, gbeta, gy, y, x, mean, invstd, gamma, slope=0.2, want=(True, True, True)):
     """double backward: (ggx [N,H,W,C], ggamma [C] | None, gbeta [C] | None) -> (d gy, d x, d gamma), each None unless wanted"""
     _chk('disc_bn_lrelu_dbl', ggx, ggamma, gbeta, gy, y, x, mean, invstd, gamma)
-    p, c, ws = _chan_ws(x)
+    p, c, ws, need = _chan_ws(x)
     d_gy = torch.empty_like(x) if want[0] else None
     d_x = torch.empty_like(x) if want[1] else None
     d_g = torch.empty(c, device=x.device, dtype=torch.float32) if want[2] else None
     with _timed('disc_bn_lrelu_dbl', detail=True):
         _lib.call('mrefsr_disc_bn_lrelu_dbl_f32', _p(ggx), _p(ggamma), _p(gbeta), _p(gy), _p(y), _p(x), _p(mean), _p(invstd), _p(gamma), _p(d_gy),
-                  _p(d_x), _p(d_g), C.c_int64(p), c, C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+                  _p(d_x), _p(d_g), C.c_int64(p), c, C.c_float(slope), _p(ws), need, _stream())
     return d_gy, d_x, d_g
-
-
-def _head_ws(f, w1):
-    n, c, j = f.shape[0], f.shape[3], w1.shape[0]
-    need = _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j)
-    return _wgrad_workspace(f.device, need)
 
 
 def disc_head(f, w1, b1, w2, b2, slope=0.2):
@@ -2248,9 +2263,9 @@ def disc_head_bwd(gs, s, pooled, hidden, w1, w2, f_shape, slope=0.2, want_params
     dev = gs.device
     gf = torch.empty((n, h, w, c), device=dev, dtype=torch.float32)
     pw = [torch.empty(sh, device=dev, dtype=torch.float32) for sh in ((j, c), (j, ), (j, ), (1, ))] if want_params else [None] * 4
-    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j))
+    need = _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j)
     _lib.call('mrefsr_disc_head_bwd_f32', _p(gs), _p(s), _p(pooled), _p(hidden), _p(w1), _p(w2), _p(gf), *[_p(t) for t in pw], n, h * w, c, j,
-              C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+              C.c_float(slope), _p(_scratch(dev, need)), C.c_int64(need), _stream())
     return (gf, *pw)
 
 
@@ -2263,9 +2278,9 @@ def disc_head_dbl(ggf, gs, s, pooled, hidden, w1, w2, slope=0.2, want_gs=True, w
     d_gs = torch.empty(n, device=dev, dtype=torch.float32) if want_gs else None
     d_f = torch.empty_like(ggf) if want_f else None
     pw = [torch.empty(sh, device=dev, dtype=torch.float32) for sh in ((j, c), (j, ), (j, ), (1, ))] if want_params else [None] * 4
-    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j))
+    need = _lib.load().mrefsr_disc_head_workspace_bytes(n, c, j)
     _lib.call('mrefsr_disc_head_dbl_f32', _p(ggf), _p(gs), _p(s), _p(pooled), _p(hidden), _p(w1), _p(w2), _p(d_gs), _p(d_f), *[_p(t) for t in pw], n,
-              h * w, c, j, C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+              h * w, c, j, C.c_float(slope), _p(_scratch(dev, need)), C.c_int64(need), _stream())
     return (d_gs, d_f, *pw)
 
 
@@ -2294,10 +2309,6 @@ _VCONV = _ConvFamily('disc_vconv', 'disc_vconv_pack_weight', {3: (1, 1), 4: (2, 
 _SG2CONV = _ConvFamily('disc_sg2_conv', 'disc_sg2_pack_weight', {3: (2, 0), 1: (1, 0)}, res=True)
 
 
-def _conv_ws(device, nbytes):
-    return _wgrad_workspace(device, nbytes) if nbytes > 0 else None
-
-
 def _conv_pack_weight(fam, w, cin, dgrad):
     _chk(fam.pack, w)
     cout, cinr, ks = w.shape[0], w.shape[1], w.shape[2]
@@ -2318,9 +2329,9 @@ def _conv_fwd(fam, x, wpk, bias, ks, act_slope, res=None):
     y = torch.empty((n, ho, wo, cout), device=x.device, dtype=torch.float32)
     if res is not None and res.shape != y.shape:
         raise ValueError(f'{fam.name}: residual {tuple(res.shape)} for an output {tuple(y.shape)}')
-    ws = _conv_ws(x.device, getattr(_lib.load(), fam.ws_bytes)(n, h, w, cin, cout, ks, 0))
+    need = getattr(_lib.load(), fam.ws_bytes)(n, h, w, cin, cout, ks, 0)   # (may be 0: no workspace, a null pointer)
+    ws, nws = (_scratch(x.device, need) if need > 0 else None), C.c_int64(max(need, 0))
     act, slope = 0 if act_slope is None else 1, C.c_float(0.0 if act_slope is None else act_slope)
-    nws = C.c_int64(0 if ws is None else ws.numel())
     with _timed(f'{fam.name}{ks}', 2.0 * y.numel() * ks * ks * cin, detail=True):
         if fam.res:
             _lib.call(fam.sym_fwd, _p(x), _p(wpk), _p(bias), _p(res), _p(y), n, h, w, cin, cout, ks, act, slope, _p(ws), nws, _stream())
@@ -2337,9 +2348,10 @@ def _conv_dgrad(fam, dy, wpk_d, in_shape, ks, flop_div=1):
     if tuple(dy.shape) != (n, ho, wo, cout) or tuple(wpk_d.shape) != (cin, ks * ks, cout):
         raise ValueError(f'{fam.dgrad}: inconsistent shapes')
     dx = torch.empty((n, h, w, cin), device=dy.device, dtype=torch.float32)
-    ws = _conv_ws(dy.device, getattr(_lib.load(), fam.ws_bytes)(n, h, w, cin, cout, ks, 1))
+    need = getattr(_lib.load(), fam.ws_bytes)(n, h, w, cin, cout, ks, 1)
+    ws = _scratch(dy.device, need) if need > 0 else None
     with _timed(f'{fam.name}{ks}_dgrad', 2.0 * dy.numel() * ks * ks * cin / flop_div, detail=True):
-        _lib.call(fam.sym_dgrad, _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, ks, _p(ws), C.c_int64(0 if ws is None else ws.numel()), _stream())
+        _lib.call(fam.sym_dgrad, _p(dy), _p(wpk_d), _p(dx), n, h, w, cin, cout, ks, _p(ws), C.c_int64(max(need, 0)), _stream())
     return dx
 
 
@@ -2350,10 +2362,10 @@ def _conv_wgrad(fam, x, dy, cin_real, ks):
     ho, wo = fam.out(h, w, ks)
     if tuple(dy.shape) != (n, ho, wo, cout):
         raise ValueError(f'{fam.wgrad}: inconsistent shapes')
-    ws = _wgrad_workspace(x.device, getattr(_lib.load(), fam.wgrad_ws_bytes)(n, h, w, cin, cout, ks))
+    need = getattr(_lib.load(), fam.wgrad_ws_bytes)(n, h, w, cin, cout, ks)
     dw = torch.empty((cout, cin_real, ks, ks), device=x.device, dtype=torch.float32)
     with _timed(f'{fam.name}{ks}_wgrad', 2.0 * dy.numel() * ks * ks * cin, detail=True):
-        _lib.call(fam.sym_wgrad, _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, ks, _p(ws), C.c_int64(ws.numel()), _stream())
+        _lib.call(fam.sym_wgrad, _p(x), _p(dy), _p(dw), n, h, w, cin, cin_real, cout, ks, _p(_scratch(x.device, need)), C.c_int64(need), _stream())
     return dw
 
 
@@ -2425,15 +2437,14 @@ def disc_linear_head_dbl(ggf, gs, hidden, w1, w2, slope=0.2, want_gs=True, want_
     d_gs = torch.empty(n, device=dev, dtype=torch.float32) if want_gs else None
     d_w1 = torch.empty((j, c * h * w), device=dev, dtype=torch.float32) if want_params else None
     d_w2 = torch.empty(j, device=dev, dtype=torch.float32) if want_params else None
-    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_linear_head_workspace_bytes(n, j))
+    need = _lib.load().mrefsr_disc_linear_head_workspace_bytes(n, j)
     _lib.call('mrefsr_disc_linear_head_dbl_f32', _p(ggf), _p(gs), _p(hidden), _p(w1), _p(w2), _p(d_gs), _p(d_w1), _p(d_w2), n, h * w, c, j,
-              C.c_float(slope), _p(ws), C.c_int64(ws.numel()), _stream())
+              C.c_float(slope), _p(_scratch(dev, need)), C.c_int64(need), _stream())
     return d_gs, d_w1, d_w2
 
 
 # ------------------------------------------------------------------ validation metrics (csrc/metrics.hip)
 VALM_SSIM_Y, VALM_SSIM_RGB = 1, 2
-_metrics_ws = {}
 
 
 def tensor2img_u8(x):
@@ -2464,26 +2475,14 @@ def val_metrics(out, gt, crop_border, sizes=None, flags=VALM_SSIM_Y, want_img=Fa
         sz = C.cast(sz_host, C.c_void_p)
     lib = _lib.load()
     need = lib.mrefsr_val_metrics_workspace_bytes(n, h, w)
-    key = (out.device.index, torch.cuda.current_stream().cuda_stream)
-    ws = _metrics_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _metrics_ws[key] = torch.empty(need, device=out.device, dtype=torch.uint8)
     res = torch.empty((n, 8), device=out.device, dtype=torch.int64)
     img = torch.empty((n, h, w, 3), device=out.device, dtype=torch.uint8) if want_img else None
-    _lib.call('mrefsr_val_metrics_f32', _p(out), _p(gt), n, h, w, hg, wg, sz, int(crop_border), int(flags), _p(img), _p(res), _p(ws),
-              C.c_int64(ws.numel()), _stream())
+    _lib.call('mrefsr_val_metrics_f32', _p(out), _p(gt), n, h, w, hg, wg, sz, int(crop_border), int(flags), _p(img), _p(res),
+              _p(_scratch(out.device, need)), C.c_int64(need), _stream())
     return res, img
 
 
 # ------------------------------------------------------------------ UNetDiscriminatorSN (csrc/disc_unet.hip)
-def _c(t):
-    return t if t is None or t.is_contiguous() else t.contiguous()
-
-
-def _ptrs(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-
-
 def _sn_geometry(ws):
     return (C.c_int * len(ws))(*[w.shape[0] for w in ws]), (C.c_int * len(ws))(*[w[0].numel() for w in ws])
 
@@ -2502,10 +2501,10 @@ def disc_sn_power(w_origs, us, vs, update, eps=1e-12):
     snap_u = torch.empty(sum(rows), device=dev, dtype=torch.float32)
     snap_v = torch.empty(sum(cols), device=dev, dtype=torch.float32)
     sigma = torch.empty(len(w_origs), device=dev, dtype=torch.float32)
-    ws = _wgrad_workspace(dev, _lib.load().mrefsr_disc_sn_workspace_bytes(rows, cols, len(w_origs)))
+    need = _lib.load().mrefsr_disc_sn_workspace_bytes(rows, cols, len(w_origs))
     with _timed('disc_sn_power', 4.0 * sum(r * c for r, c in zip(rows, cols)), detail=True):
         _lib.call('mrefsr_disc_sn_power_f32', _ptrs(w_origs), _ptrs(us), _ptrs(vs), rows, cols, len(w_origs), 1 if update else 0, C.c_float(eps),
-                  _p(snap_u), _p(snap_v), _p(sigma), _p(ws), C.c_int64(ws.numel()), _stream())
+                  _p(snap_u), _p(snap_v), _p(sigma), _p(_scratch(dev, need)), C.c_int64(need), _stream())
     return snap_u, snap_v, sigma
 
 
@@ -2525,10 +2524,10 @@ def disc_sn_bwd(gs, w_origs, snap_u, snap_v, sigma):
         raise ValueError('disc_sn_bwd: gradients must be contiguous and shaped like the weights')
     rows, cols = _sn_geometry(w_origs)
     dws = [torch.empty_like(w) for w in w_origs]
-    ws = _wgrad_workspace(gs[0].device, _lib.load().mrefsr_disc_sn_bwd_workspace_bytes(rows, cols, len(w_origs)))
+    need = _lib.load().mrefsr_disc_sn_bwd_workspace_bytes(rows, cols, len(w_origs))
     with _timed('disc_sn_bwd', 4.0 * sum(r * c for r, c in zip(rows, cols)), detail=True):
-        _lib.call('mrefsr_disc_sn_bwd_f32', _ptrs(gs), _ptrs(w_origs), _ptrs(dws), rows, cols, len(w_origs), _p(snap_u), _p(snap_v), _p(sigma), _p(ws),
-                  C.c_int64(ws.numel()), _stream())
+        _lib.call('mrefsr_disc_sn_bwd_f32', _ptrs(gs), _ptrs(w_origs), _ptrs(dws), rows, cols, len(w_origs), _p(snap_u), _p(snap_v), _p(sigma),
+                  _p(_scratch(gs[0].device, need)), C.c_int64(need), _stream())
     return dws
 
 
@@ -2604,10 +2603,10 @@ def disc_conv9_wgrad(x, gy):
     n, h, wd, c = x.shape
     if tuple(gy.shape) != (n, h, wd, 1):
         raise ValueError('disc_conv9_wgrad: inconsistent shapes')
-    ws = _wgrad_workspace(x.device, _lib.load().mrefsr_disc_conv9_wgrad_workspace_bytes(n, h, wd, c))
+    need = _lib.load().mrefsr_disc_conv9_wgrad_workspace_bytes(n, h, wd, c)
     dw = torch.empty((1, c, 3, 3), device=x.device, dtype=torch.float32)
     with _timed('disc_conv9_wgrad', 2.0 * x.numel() * 9, detail=True):
-        _lib.call('mrefsr_disc_conv9_wgrad_f32', _p(x), _p(_c(gy)), _p(dw), n, h, wd, c, _p(ws), C.c_int64(ws.numel()), _stream())
+        _lib.call('mrefsr_disc_conv9_wgrad_f32', _p(x), _p(_c(gy)), _p(dw), n, h, wd, c, _p(_scratch(x.device, need)), C.c_int64(need), _stream())
     return dw
 
 

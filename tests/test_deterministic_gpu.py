@@ -133,9 +133,16 @@ def test_conv_bwd_channel_sums_are_reproducible_and_right(n, h, w, c):
 
 
 # ------------------------------------------------------------------ captured and replayed
+def _wgrad_close(got, want):
+    """the assertion of test_train_engine_gpu.test_batched_wgrad_equals_the_single_launches for this wrapper"""
+    err = float((got.double() - want.double()).abs().max()) / (float(want.double().abs().max()) + 1e-30)
+    assert err <= 2e-6, err
+
+
 def test_ticket_resets_itself_across_eager_launches_and_graph_replays():
     """one ticket word per stream serves every launch: five eager launches above already share it; here one linear capture of the
-    three reductions is replayed twice and gives the eager deterministic bits each time"""
+    three reductions and of a weight gradient (its partial tiles in the same cached scratch) is replayed twice and gives the eager
+    deterministic bits each time; the capture's cached buffers are listed while the graph lives and gone once they are released"""
     from mrefsr_amd import hip
     npix, c = 73728, 64                                   # 288 blocks
     g, out, slope_ptr = _act_inputs(npix, c, 2)
@@ -147,12 +154,20 @@ def test_ticket_resets_itself_across_eager_launches_and_graph_replays():
     tc = torch.randn(2, 48, 48, 64, device='cuda')
     amax = gc.abs().max().reshape(1)
     pk = hip.conv_pack_view(torch.randn(64, 64, 3, 3, device='cuda') * 0.05, None, 16, dgrad=True, wscale=2.0 ** 12)
+    xw = torch.randn(1, 16, 16, 16, device='cuda')        # the smallest weight gradient with a partial tile and a reduction
+    gw = torch.randn(1, 16, 16, 16, device='cuda') * 1e-3
+    amax_w = gw.abs().max().reshape(1)
 
     def body():
         _, bias, slope, _ = hip.act_bwd_nhwc(g, out, 2, 0.0, slope_ptr, want_bias=True, want_amax=True)
         _, dyn, _ = hip.dynagg_prep_bwd_nhwc(g_off, g_m, mask, 8)
         _, csum, _ = hip.conv_nhwc_bwd(gc, pk, 64, 3, residual=tc, residual_is_mask=True, in_amax=amax)
-        return bias, slope, dyn, csum
+        return bias, slope, dyn, csum, hip.conv_wgrad3x3(xw, gw, 16, 16, amax_w)
+
+    def check(got, want):
+        for a, b in zip(got[:4], want[:4]):
+            assert torch.equal(a, b)
+        _wgrad_close(got[4], want[4])
 
     with hip.deterministic():
         want = [t.clone() for t in body()]
@@ -160,17 +175,54 @@ def test_ticket_resets_itself_across_eager_launches_and_graph_replays():
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             got = body()
-        keep = hip.capture_refs()                         # the workspaces and the ticket the graph baked in
+        keep = hip.capture_refs()                         # the scratch, the ticket and the zero chunk the graph baked in
+        assert len(keep) >= 3
         for _ in range(2):
             graph.replay()
             torch.cuda.synchronize()
-            for a, b in zip(got, want):
-                assert torch.equal(a, b)
-        eager = body()                                    # and the eager stream's ticket is still good
-    for a, b in zip(eager, want):
-        assert torch.equal(a, b)
+            check(got, want)
+        check(body(), want)                               # and the eager stream's ticket is still good
     del graph, keep
     hip.release_capture_workspaces()
+    assert len(hip.capture_refs()) == 0 and hip.capture_ptrs() == ()
+    with hip.deterministic():
+        check(body(), want)
+    hip.check_conv_range()
+
+
+def test_eager_regrowth_leaves_a_captured_graph_alone():
+    """an eager call that regrows the eager stream's scratch moves nothing the graph baked in: capture_ptrs() is unchanged (the
+    training graph's owner would recapture otherwise) and a replay still gives the eager bits"""
+    from mrefsr_amd import hip
+    g, out, slope_ptr = _act_inputs(4096, 64, 2)
+    call = lambda: hip.act_bwd_nhwc(g, out, 2, 0.0, slope_ptr, want_bias=True, want_amax=True)   # noqa: E731
+    wgrad = lambda x, gr: hip.conv_wgrad3x3(x, gr, x.shape[3], x.shape[3], gr.abs().max().reshape(1))   # noqa: E731
+    torch.manual_seed(5)
+    small = [torch.randn(1, 16, 16, 16, device='cuda') for _ in range(2)]
+    large = [torch.randn(2, 32, 32, 64, device='cuda') for _ in range(2)]
+    with hip.deterministic():
+        want = [t.clone() for t in call()]
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            got = call()
+        keep, ptrs = hip.capture_refs(), hip.capture_ptrs()
+        assert len(keep) >= 3 and len(ptrs) == len(keep)
+        hip._scratch_bufs.entries.pop(hip._scratch_bufs.key(g.device), None)   # (whatever size earlier tests left: start at the floor)
+        wgrad(*small)
+        before = hip._scratch(g.device, 1)
+        dw = wgrad(*large)
+        assert hip._scratch(g.device, 1) is not before, 'the second weight gradient was meant to regrow the eager scratch'
+        assert hip.capture_ptrs() == ptrs
+        graph.replay()
+        torch.cuda.synchronize()
+        for a, b in zip(got, want):
+            assert torch.equal(a, b)
+    want_dw = torch.nn.grad.conv2d_weight(large[0].permute(0, 3, 1, 2).double(), (64, 64, 3, 3), large[1].permute(0, 3, 1, 2).double(), padding=1)
+    assert float((dw.double() - want_dw).abs().max()) <= 2e-5 * float(want_dw.abs().max())   # (the regrown scratch serves its call)
+    del graph, keep
+    hip.release_capture_workspaces()
+    hip.check_conv_range()
 
 
 # ------------------------------------------------------------------ whole steps
