@@ -1107,6 +1107,35 @@ int64_t mrefsr_degrade_levels_workspace_words(int batch);
 int mrefsr_degrade_levels_f32(const float *img, int batch, int h, int w, uint32_t *sets, float *vals, mrefsr_stream_t stream);
 int mrefsr_degrade_jpeg_f32(const float *img, const float *quality, int batch, int h, int w, float *out, mrefsr_stream_t stream);
 
+/* ---- Frequency-domain losses of the training step (csrc/freq_loss.hip; losses.FFTLoss, losses.FocalFrequencyLoss, train.freq_opt;
+ * DESIGN 3.18).  No reference counterpart.  pred, target [planes][h][w] contiguous fp32 (planes = batch x channels), X = pred -
+ * target; D = the 2-D DFT of every plane of X, computed densely on the f32 MFMA for the wh = w/2 + 1 non-redundant columns, the
+ * others counted through the multiplicity mult (1 for column 0 and for column w/2 with w even, 2 otherwise).  1 <= h, w <= 1024,
+ * planes <= 65535, planes h w <= 2^30.  tab_h / tab_w: the twiddle tables [h][2] / [w][2] in device memory, tab_n[r] = (cos, sin)
+ * (2 pi r / n) as the fp32 rounding of the float64 values (both may be one table when h = w).
+ *
+ * mrefsr_freq_loss_blocks: planes ceil(h / 32) ceil(wh / 32), the blocks of the column pass; `partial` holds TWICE as many floats.
+ *   -1 for a shape outside the limits.
+ * mrefsr_freq_loss_fwd_f32: t: scratch of planes h wh 2 floats (the row pass T = X F_W).
+ *   focal = 0 (FFTLoss): loss[0] = fl32(loss_weight s sum mult (|Re D| + |Im D|) / (2 planes h w)), s = 1 (ortho = 0, the
+ *     unnormalised transform) or 1 / sqrt(h w) (ortho = 1); with write_g the map g [planes][h][wh][2] = sign(D) mult s /
+ *     (2 planes h w) (sign(0) = 0); g may be NULL without write_g.  Two launches.
+ *   focal = 1 (FocalFrequencyLoss, the ortho transform; `ortho` is not read): m = |D|^2, w = sqrt(m)^alpha over its maximum in the
+ *     plane, NaN -> 0, clamped to [0, 1]; loss[0] = fl32(loss_weight sum mult w m / (planes h w)).  g is always needed (it holds D
+ *     between the launches); with write_g it leaves as 2 w D mult / (planes h w sqrt(h w)).  alpha finite, >= 0.  Three launches.
+ *   The imaginary part of a self-conjugate bin (ky in {0, h/2}, kx in {0, w/2}) counts as exactly 0.  Sums: fixed order inside a
+ *   block, one partial per block, the partials in ascending block order in double by the block that draws the last `ticket` (one
+ *   zeroed word; left zero): no float atomics, the same bits from call to call.  pred and target are only read.
+ * mrefsr_freq_loss_bwd_f32: grad_pred [planes][h][w], every element written once: loss_weight grad_loss[0] Re(F_H^H g F_W^H) over
+ *   the wh stored columns.  grad_loss: the upstream gradient, one float in device memory.  u: scratch of planes h wh 2 floats.
+ *   Two launches. */
+int mrefsr_freq_loss_blocks(int planes, int h, int w);
+int mrefsr_freq_loss_fwd_f32(const float *pred, const float *target, int planes, int h, int w, int focal, int ortho, float alpha,
+                             float loss_weight, const float *tab_h, const float *tab_w, float *t, float *g, int write_g, float *partial,
+                             uint32_t *ticket, float *loss, mrefsr_stream_t stream);
+int mrefsr_freq_loss_bwd_f32(const float *g, const float *grad_loss, int planes, int h, int w, float loss_weight, const float *tab_h,
+                             const float *tab_w, float *u, float *grad_pred, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

@@ -1882,6 +1882,86 @@ def ldl_loss_bwd(pred, target, saved, grad_loss, loss_weight=1.0):
     return grad
 
 
+# ------------------------------------------------------------------ frequency-domain losses of the training step (csrc/freq_loss.hip)
+FREQ_TILE = (32, 32)    # outputs per block of every pass (rows, columns): rows of X / D, columns of D (W/2 + 1 of them) / of grad
+FREQ_MAX_SIDE = 1024
+_freq_tables = {}       # (device index, n) -> [n,2] fp32 (cos, sin)(2 pi r / n): constants, built once, never part of a step
+
+
+def freq_twiddles(device, n):
+    """[n,2] fp32 on ``device``: (cos, sin)(2 pi r / n), r = 0 .. n-1, each the fp32 rounding of the float64 value.  Built on the
+    host at the first request for (device, n) and kept; the kernels index it by (j k) mod n, reduced in integers"""
+    key = (device.index, int(n))
+    t = _freq_tables.get(key)
+    if t is None:
+        ang = [2.0 * math.pi * r / n for r in range(n)]
+        t = _freq_tables[key] = torch.tensor([[math.cos(a), math.sin(a)] for a in ang], dtype=torch.float64).float().to(device)
+    return t
+
+
+def _freq_shape(name, pred, target=None):
+    _chk(name, pred, target)
+    if pred.dim() != 4 or (target is not None and target.shape != pred.shape):
+        raise ValueError(f'{name}: [B,C,H,W] tensors of one shape expected, got {tuple(pred.shape)}'
+                         + ('' if target is None else f' and {tuple(target.shape)}'))
+    b, c, h, w = pred.shape
+    blocks = _lib.load().mrefsr_freq_loss_blocks(b * c, h, w)
+    if blocks <= 0:
+        raise ValueError(f'{name}: unsupported shape {tuple(pred.shape)} (1 <= H, W <= {FREQ_MAX_SIDE}, 1 <= B C <= 65535, B C H W <= 2^30)')
+    return b * c, h, w, blocks
+
+
+def _align256(n):
+    return (n + 255) // 256 * 256
+
+
+def freq_loss_fwd(pred, target, focal=False, norm='backward', alpha=1.0, loss_weight=1.0, want_grad=False):
+    """pred, target [B,C,H,W] (contiguous fp32) -> (loss, g): loss a 0-dim tensor, with D = fft2(pred - target) over the last two
+    dimensions: focal=False, loss_weight mean(|Re D| + |Im D|) / 2 in the given norm ('backward' or 'ortho'); focal=True,
+    loss_weight mean(w |D|^2) in the ortho norm, w = |D|^alpha over its per-plane maximum (NaN -> 0, clamped to [0, 1]; a constant).
+    g: None, or with want_grad the coefficient-gradient map [B C,H,W/2+1,2] freq_loss_bwd reads.  A dense DFT on the f32 MFMA over
+    the W/2 + 1 non-redundant columns; two launches (three with focal), fixed summation orders (the same bits from call to call),
+    nothing read back; pred and target are only read"""
+    planes, h, w, blocks = _freq_shape('freq_loss_fwd', pred, target)
+    if norm not in ('backward', 'ortho'):
+        raise ValueError(f"freq_loss_fwd: norm={norm!r}; 'backward' or 'ortho'")
+    dev, wh = pred.device, w // 2 + 1
+    tab_h, tab_w = freq_twiddles(dev, h), freq_twiddles(dev, w)
+    g = torch.empty((planes, h, wh, 2), device=dev, dtype=torch.float32) if want_grad else None
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    # one scratch request: T | the block partials | (focal without a map: D)
+    nt, npart = _align256(8 * planes * h * wh), _align256(8 * blocks)
+    buf = _scratch(dev, nt + npart + (nt if focal and not want_grad else 0))
+    t, part = buf[:nt], buf[nt:nt + npart]
+    gbuf = g if want_grad or not focal else buf[nt + npart:]
+    ticket = _zeroed_words(dev, 'ticket', 1)
+    flops = 2.0 * planes * h * w * 2 * wh + 8.0 * planes * h * h * wh
+    with _timed('freq_loss_fwd', detail=True, flops=flops, nbytes=4.0 * (2 * pred.numel() + (4 + (2 if want_grad else 0)) * planes * h * wh)):
+        _lib.call('mrefsr_freq_loss_fwd_f32', _p(pred), _p(target), planes, h, w, int(bool(focal)), int(norm == 'ortho'),
+                  C.c_float(alpha), C.c_float(loss_weight), _p(tab_h), _p(tab_w), _p(t), _p(gbuf), int(bool(want_grad)), _p(part),
+                  _p(ticket), _p(loss), _stream())
+    return loss, g
+
+
+def freq_loss_bwd(g, grad_loss, shape, loss_weight=1.0):
+    """d (grad_loss * loss) / d pred [B,C,H,W] (``shape``) of freq_loss_fwd from its map g: loss_weight grad_loss times the adjoint
+    transform Re(F_H^H g F_W^H).  grad_loss: the upstream gradient, a one-element fp32 device tensor (read by the kernel, not by the
+    host).  Two launches; every element is written once"""
+    _chk('freq_loss_bwd', g, grad_loss)
+    grad = torch.empty(tuple(shape), device=g.device, dtype=torch.float32)
+    planes, h, w, _ = _freq_shape('freq_loss_bwd', grad)
+    wh = w // 2 + 1
+    if grad_loss.numel() != 1 or g.shape != (planes, h, wh, 2):
+        raise ValueError(f'freq_loss_bwd: one upstream value and a map of {(planes, h, wh, 2)} expected, got {tuple(g.shape)}')
+    tab_h, tab_w = freq_twiddles(g.device, h), freq_twiddles(g.device, w)
+    u = _scratch(g.device, 8 * planes * h * wh)
+    flops = 8.0 * planes * h * h * wh + 4.0 * planes * h * w * wh
+    with _timed('freq_loss_bwd', detail=True, flops=flops, nbytes=4.0 * (grad.numel() + 6 * planes * h * wh)):
+        _lib.call('mrefsr_freq_loss_bwd_f32', _p(g), _p(grad_loss), planes, h, w, C.c_float(loss_weight), _p(tab_h), _p(tab_w), _p(u),
+                  _p(grad), _stream())
+    return grad
+
+
 # ------------------------------------------------------------------ second-order degradation (csrc/degrade.hip; degradation.py)
 DEGRADE_MODES = {'area': 0, 'bilinear': 1, 'bicubic': 2}
 

@@ -2,7 +2,8 @@
 and values (basicsr/models/losses.py:17-124, 141-238, 275-532), GANLoss's wgan_softplus type and r1_penalty from the newer
 basicsr/losses/losses.py:258-360, 391-405.  LDLLoss is the artifact loss of LDL (basicsr/losses/loss_util.py:99-145 as used by
 basicsr/models/realesrgan_model.py:211-226), on the kernels of csrc/ldl_loss.hip.  SSIMLoss has no counterpart in the reference: it is the structural-similarity term the
-validation metric (mrefsr_amd/metrics.py: calculate_ssim) measures, as a criterion, on the kernels of csrc/ssim_loss.hip.
+validation metric (mrefsr_amd/metrics.py: calculate_ssim) measures, as a criterion, on the kernels of csrc/ssim_loss.hip.  FFTLoss and FocalFrequencyLoss have none either: the L1 distance of the spectra
+(MIMO-UNet, DeepRFT) and the focal frequency loss (Jiang et al., ICCV 2021), on the dense-DFT kernels of csrc/freq_loss.hip.
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
 what the model passes -- reduction='mean', no element weight -- and refuse the rest.  PerceptualLoss runs its VGG19 through ONE
@@ -248,6 +249,130 @@ class SSIMLoss(nn.Module):
         if pred.dtype != torch.float32 or target.dtype != torch.float32:
             raise NotImplementedError(f'SSIMLoss: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
         return _SSIMLossFn.apply(pred.contiguous(), target.contiguous(), self.channel == 'rgb', float(self.loss_weight))
+
+
+def _freq_residual_spectrum(pred, target, norm):
+    return torch.fft.fft2(pred, norm=norm) - torch.fft.fft2(target, norm=norm)
+
+
+def fft_loss_torch(pred, target, norm='backward'):
+    """mean(|Re D| + |Im D|) / 2, D = fft2(pred, norm) - fft2(target, norm) over the last two dimensions of [B,C,H,W] tensors, full
+    spectrum: F.l1_loss over the stacked real and imaginary parts, the FFT loss of MIMO-UNet / DeepRFT.  torch operations in the
+    tensors' dtype and on their device: the definition FFTLoss implements (and what it runs for CPU tensors).  The subgradient at a
+    zero component is 0."""
+    d = torch.view_as_real(_freq_residual_spectrum(pred, target, norm))
+    return d.abs().mean()
+
+
+def focal_frequency_weight_torch(pred, target, alpha=1.0):
+    """the spectrum weight matrix of the focal frequency loss [B,C,H,W], detached: |D|^alpha over its maximum in each (b, c) plane,
+    NaN -> 0 (0 / 0 for equal images), clamped to [0, 1]; D the ortho-normalised residual spectrum"""
+    d = torch.view_as_real(_freq_residual_spectrum(pred, target, 'ortho')).detach()
+    w = torch.sqrt(d[..., 0] ** 2 + d[..., 1] ** 2) ** alpha
+    w = w / w.amax(dim=(-2, -1), keepdim=True)
+    w = torch.where(torch.isnan(w), torch.zeros_like(w), w)
+    return w.clamp(0.0, 1.0)
+
+
+def focal_frequency_loss_torch(pred, target, alpha=1.0, weight=None):
+    """mean(w (Re D^2 + Im D^2)) with D = fft2(pred, 'ortho') - fft2(target, 'ortho') and w = focal_frequency_weight_torch (a
+    constant), the focal frequency loss of Jiang et al. ("Focal Frequency Loss for Image Reconstruction and Synthesis", ICCV 2021)
+    with patch_factor 1 and without ave_spectrum / log_matrix / batch_matrix.  torch operations in the tensors' dtype and on their
+    device: the definition FocalFrequencyLoss implements (and what it runs for CPU tensors).  ``weight``: a given weight matrix
+    held fixed in place of the computed one."""
+    d = torch.view_as_real(_freq_residual_spectrum(pred, target, 'ortho'))
+    w = focal_frequency_weight_torch(pred, target, alpha) if weight is None else weight.detach()
+    return (w * (d[..., 0] ** 2 + d[..., 1] ** 2)).mean()
+
+
+class _FreqLossFn(torch.autograd.Function):
+    """(pred, target) [B,C,H,W] contiguous fp32 on the GPU -> the frequency-domain loss on the kernels of csrc/freq_loss.hip; when
+    pred needs a gradient the forward writes the coefficient-gradient map its backward transforms back.  Differentiable once,
+    towards pred only; the upstream gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, focal, norm, alpha, loss_weight):
+        from .. import hip
+        ctx.loss_weight, ctx.shape = loss_weight, tuple(pred.shape)
+        loss, g = hip.freq_loss_fwd(pred, target, focal, norm, alpha, loss_weight, want_grad=ctx.needs_input_grad[0])
+        if g is not None:
+            ctx.save_for_backward(g)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        from .. import hip
+        g, = ctx.saved_tensors
+        return hip.freq_loss_bwd(g, grad_loss.contiguous().float(), ctx.shape, ctx.loss_weight), None, None, None, None, None
+
+
+def _freq_checked(name, pred, target):
+    if pred.dim() != 4:
+        raise ValueError(f'{name}: [B,C,H,W] images expected, got {tuple(pred.shape)}')
+    if target.shape != pred.shape:
+        raise ValueError(f'{name}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
+    if not (1 <= pred.shape[2] <= 1024 and 1 <= pred.shape[3] <= 1024):
+        raise ValueError(f'{name}: {pred.shape[2]} x {pred.shape[3]} images; H and W of 1 ... 1024')
+    if pred.is_cuda and not (pred.dtype == target.dtype == torch.float32):
+        raise NotImplementedError(f'{name}: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
+    return pred.is_cuda, target.detach()
+
+
+@LOSS_REGISTRY.register()
+class FFTLoss(nn.Module):
+    """loss_weight * mean(|Re D| + |Im D|) / 2 with D = fft2(pred, norm) - fft2(target, norm) over the last two dimensions of
+    [B,C,H,W] images (any C): the L1 distance of the stacked real and imaginary parts of the spectra (fft_loss_torch spells the
+    definition out).  norm 'backward' (unnormalised, the widespread default) or 'ortho'.  target is a constant (detached); the
+    gradient reaches pred, once; the subgradient at a zero component is 0.
+
+    GPU fp32 tensors run on the kernels of csrc/freq_loss.hip (a dense DFT of pred - target on the f32 MFMA: two forward and two
+    backward launches, fixed summation orders, no FFT library); CPU tensors of any float dtype take fft_loss_torch.  Refused: a
+    reduction other than 'mean', another norm, non-fp32 tensors on the GPU (NotImplementedError); inputs that are not [B,C,H,W],
+    differing shapes, H or W outside 1 ... 1024 (ValueError)."""
+
+    def __init__(self, loss_weight=1.0, reduction='mean', norm='backward'):
+        super().__init__()
+        _only_mean('FFTLoss', reduction)
+        if norm not in ('backward', 'ortho'):
+            raise NotImplementedError(f"FFTLoss: norm={norm!r}; 'backward' or 'ortho'")
+        self.loss_weight, self.reduction, self.norm = loss_weight, reduction, norm
+
+    def forward(self, pred, target, **kwargs):
+        on_gpu, target = _freq_checked('FFTLoss', pred, target)
+        if not on_gpu:
+            return self.loss_weight * fft_loss_torch(pred, target, self.norm)
+        return _FreqLossFn.apply(pred.contiguous(), target.contiguous(), False, self.norm, 1.0, float(self.loss_weight))
+
+
+@LOSS_REGISTRY.register()
+class FocalFrequencyLoss(nn.Module):
+    """loss_weight * mean(w |D|^2), the focal frequency loss (Jiang et al., ICCV 2021) of [B,C,H,W] images (any C): D the difference
+    of the ortho-normalised spectra, w = |D|^alpha over its maximum in each (b, c) plane, NaN -> 0, clamped to [0, 1], a constant
+    (focal_frequency_loss_torch spells the definition out).  alpha: any finite float >= 0 (0: w = 1, the mean squared error by
+    Parseval).  target is a constant (detached); the gradient reaches pred, once.
+
+    GPU fp32 tensors run on the kernels of csrc/freq_loss.hip (three forward and two backward launches, fixed orders); CPU tensors
+    of any float dtype take focal_frequency_loss_torch.  Refused: patch_factor other than 1, ave_spectrum, log_matrix, batch_matrix,
+    non-fp32 tensors on the GPU (NotImplementedError); an alpha that is not a finite number >= 0, inputs that are not [B,C,H,W],
+    differing shapes, H or W outside 1 ... 1024 (ValueError)."""
+
+    def __init__(self, loss_weight=1.0, alpha=1.0, patch_factor=1, ave_spectrum=False, log_matrix=False, batch_matrix=False):
+        super().__init__()
+        if isinstance(patch_factor, bool) or patch_factor != 1 or ave_spectrum or log_matrix or batch_matrix:
+            raise NotImplementedError(f'FocalFrequencyLoss: patch_factor={patch_factor!r}, ave_spectrum={ave_spectrum!r}, log_matrix='
+                                      f'{log_matrix!r}, batch_matrix={batch_matrix!r}; only patch_factor 1 with the three switches off '
+                                      'is implemented')
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not (0.0 <= alpha < float('inf')):
+            raise ValueError(f'FocalFrequencyLoss: alpha={alpha!r} is not a finite number >= 0')
+        self.loss_weight, self.alpha = loss_weight, float(alpha)
+        self.patch_factor, self.ave_spectrum, self.log_matrix, self.batch_matrix = 1, False, False, False
+
+    def forward(self, pred, target, **kwargs):
+        on_gpu, target = _freq_checked('FocalFrequencyLoss', pred, target)
+        if not on_gpu:
+            return self.loss_weight * focal_frequency_loss_torch(pred, target, self.alpha)
+        return _FreqLossFn.apply(pred.contiguous(), target.contiguous(), True, 'ortho', self.alpha, float(self.loss_weight))
 
 
 def _ldl_residuals(gt, out, ema):

@@ -13,7 +13,8 @@ swapped reference maps and weights, which the reference model reads but never se
 on the kernels of csrc/texture.hip: _texture_targets), ssim_opt (SSIMLoss: 1 - SSIM on the Y or the colour planes, the quantity
 validation reports, on the kernels of csrc/ssim_loss.hip; no counterpart in the reference), ldl_opt (LDLLoss: the artifact loss of
 LDL between the output, the GT and the output of net_g_ema on the same input, basicsr/models/realesrgan_model.py:211-226, on the
-kernels of csrc/ldl_loss.hip; needs train.ema_decay: _ema_pass), and the adversarial term: network_d
+kernels of csrc/ldl_loss.hip; needs train.ema_decay: _ema_pass), freq_opt (FFTLoss or FocalFrequencyLoss: a distance between the
+spectra of the output and the GT, on the dense-DFT kernels of csrc/freq_loss.hip; no counterpart in the reference), and the adversarial term: network_d
 (ImageDiscriminator, VGGStyleDiscriminator, UNetDiscriminatorSN or StyleGAN2Discriminator, on the kernels of csrc/disc.hip, disc_vgg.hip,
 disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
@@ -169,7 +170,7 @@ class MultiRefRestorationModel:
         """opt['degradation'] (a dict of degradation.OPTION_KEYS: the reference yml's degradation and blur-kernel keys, plus an
         optional queue_size): training batches get their LQ input from Real-ESRGAN's second-order degradation of the GT
         (realesrgan_model.py:68-179) on the kernels of csrc/degrade.hip, see _degrade.  Validation and test() never synthesise
-        (:187-191).  l1_gt_usm / percep_gt_usm / gan_gt_usm (top level, as in the reference's yml) make the pixel, SSIM and LDL
+        (:187-191).  l1_gt_usm / percep_gt_usm / gan_gt_usm (top level, as in the reference's yml) make the pixel, SSIM, LDL and frequency
         losses / the perceptual and style losses / the discriminator's real images take the USM-sharpened GT; the texture loss has no
         GT.  They are refused without `degradation`.  train.hip_graph stays allowed: the synthesis runs in feed_data, outside the
         captured region (the sharpened GT is one more static input of the capture).  Without the option nothing changes."""
@@ -225,7 +226,7 @@ class MultiRefRestorationModel:
         return data
 
     def _gt_for(self, which):
-        """the GT of a loss family: 'l1' (pixel, SSIM, LDL), 'percep' (perceptual, style) or 'gan' (D's real images)"""
+        """the GT of a loss family: 'l1' (pixel, SSIM, LDL, frequency), 'percep' (perceptual, style) or 'gan' (D's real images)"""
         return self.gt_usm if self._gt_usm[which + '_gt_usm'] and self.gt_usm is not None else self.gt
 
     # ------------------------------------------------------------------ the parameter update: train.hip_adam, train.ema_decay
@@ -314,6 +315,7 @@ class MultiRefRestorationModel:
     net_g_ema = None
     cri_texture = None   # TextureLoss of train.texture_opt (init_training_settings)
     cri_ssim = None      # SSIMLoss of train.ssim_opt
+    cri_freq = None      # FFTLoss / FocalFrequencyLoss of train.freq_opt
     cri_ldl = None       # LDLLoss of train.ldl_opt
     output_ema = None    # net_g_ema's output on this step's input (steps that evaluate the LDL term)
 
@@ -419,6 +421,7 @@ class MultiRefRestorationModel:
         # SSIMLoss: train.ssim_opt holds its constructor's keys (loss_weight, channel, window_size, sigma)
         self.cri_ssim = losses.SSIMLoss(**train_opt['ssim_opt']).to(self.device) if train_opt.get('ssim_opt') else None
         self.cri_ldl = self._build_ldl(train_opt)
+        self.cri_freq = self._build_freq(train_opt)
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
@@ -434,6 +437,18 @@ class MultiRefRestorationModel:
             raise NotImplementedError(f'Scheduler {stype} is not implemented yet.')
         for optimizer in self.optimizers:
             self.schedulers.append((_CosineAnnealingRestartLR if stype == 'CosineAnnealingRestartLR' else _MultiStepRestartLR)(optimizer, **sched))
+
+    @staticmethod
+    def _build_freq(train_opt):
+        """train.freq_opt {type: FFTLoss | FocalFrequencyLoss, ...its constructor's keys} -> the criterion, or None without the option"""
+        from .. import losses
+        freq_opt = dict(train_opt.get('freq_opt') or {})
+        if not freq_opt:
+            return None
+        kind = freq_opt.pop('type', None)
+        if kind not in ('FFTLoss', 'FocalFrequencyLoss'):
+            raise ValueError(f'train.freq_opt: type {kind!r}; FFTLoss or FocalFrequencyLoss')
+        return losses.LOSS_REGISTRY.get(kind)(**freq_opt)
 
     @staticmethod
     def _build_ldl(train_opt):
@@ -758,6 +773,10 @@ class MultiRefRestorationModel:
                 l_g_ldl = self.cri_ldl(self.output, self._gt_for('l1'), self.output_ema)
                 l_g_total = l_g_total + l_g_ldl
                 self.log_dict['l_g_ldl'] = l_g_ldl.detach()
+            if self.cri_freq is not None:
+                l_g_freq = self.cri_freq(self.output, self._gt_for('l1'))
+                l_g_total = l_g_total + l_g_freq
+                self.log_dict['l_g_freq'] = l_g_freq.detach()
             if self.net_d is not None:   # ref :272-276 (D's parameters are frozen: no weight gradient of D is computed)
                 fake_g_pred = self.net_d(self.output)
                 l_g_gan = self.cri_gan(fake_g_pred, True, is_disc=False)
@@ -777,11 +796,12 @@ class MultiRefRestorationModel:
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
         a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
         not with a perceptual, style or texture loss (their VGG node is not captured), an SSIM loss, an LDL loss (its EMA pass is not
-        captured), nor with a discriminator."""
+        captured), a frequency-domain loss, nor with a discriminator."""
         train_opt = self.opt.get('train') or {}
         return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
             and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt') \
             and not train_opt.get('texture_opt') and not train_opt.get('ssim_opt') and not train_opt.get('ldl_opt') \
+            and not train_opt.get('freq_opt') \
             and not self.opt.get('network_d')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
