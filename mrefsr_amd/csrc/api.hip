@@ -35,8 +35,7 @@ __global__ __launch_bounds__(256) void weights_checksum_kernel(const long long *
     }
     for (long long i = 4 * n4 + blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
         s += (unsigned long long)w[i] * (unsigned long long)(2 * i + 1);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+    s = mrefsr::wave_sum(s);
     __shared__ unsigned long long part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();

@@ -7,6 +7,9 @@
 #include <stdlib.h>
 
 #include "../../include/mrefsr_hip.h"
+#ifdef __HIPCC__
+#include "reduce.h"   // wave, block and last-block reductions (device code)
+#endif
 
 #define MREFSR_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -52,52 +55,6 @@ inline bool ab_flag(const char *name, bool dflt) { const char *e = getenv(name);
 #else
 constexpr long ab_int(const char *, long dflt) { return dflt; }
 constexpr bool ab_flag(const char *, bool dflt) { return dflt; }
-#endif
-
-#ifdef __HIPCC__
-// The fixed-order ("deterministic") reductions of the training step (train.hip, dynagg.hip, conv_nhwc.hip): every block writes
-// its partial sums to its own row of a workspace with store_partial (write-through stores: they reach memory without a release
-// of the block's other, much larger output from L2); the block that draws the last ticket adds the rows in ascending row order.
-// last_block_by_ticket is called by ALL threads of the block behind those stores; true in every thread of the one block that
-// arrived last, whose loads then see every row: every wave waits for its own stores, the block meets, lane 0 draws the ticket and
-// -- last -- acquires at agent scope (the XCDs' L2s are not coherent with each other, nor is this CU's L1) before anyone reads.
-// The last block puts the ticket word back to 0, so a launch needs no memset in front of it and can be replayed from a graph.
-// `lds_flag`: one word of the block's LDS that nothing else uses across this call.
-__device__ __forceinline__ void store_partial(float *p, const float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ bool last_block_by_ticket(unsigned int *ticket, const unsigned int nblocks, int *lds_flag)
-{
-    constexpr int VMCNT0 = 0x0F70;   // s_waitcnt vmcnt(0) alone (gfx9 encoding: expcnt and lgkmcnt left at their maxima)
-    __builtin_amdgcn_s_waitcnt(VMCNT0);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const bool last = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblocks - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            __builtin_amdgcn_s_waitcnt(VMCNT0);   // (the invalidate has completed before the block is let through the barrier)
-            __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        *lds_flag = last ? 1 : 0;
-    }
-    __syncthreads();
-    return *lds_flag != 0;
-}
-
-// rows [n_rows] of `ld` floats each: column c added in ascending row order, eight loads in flight
-__device__ __forceinline__ float sum_rows_in_order(const float *part, const int n_rows, const long ld, const int c)
-{
-    float s = 0.f;
-    int r = 0;
-    for (; r + 8 <= n_rows; r += 8) {
-        float v[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = part[(long)(r + k) * ld + c];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) s += v[k];
-    }
-    for (; r < n_rows; ++r) s += part[(long)r * ld + c];
-    return s;
-}
 #endif
 
 // corr.hip: exact correlation kernel on the query tiles flagged by the pre-filter (corr_prefilter.hip)

@@ -197,7 +197,7 @@ __device__ unsigned long long g_conv_stamp[1024][8];   // 1024 slots: no hot spo
 #endif
 
 // max |out| of a launch (ConvArgs::stat_amax as the forward launches' `out_amax`: the input scale of the Winograd layer that reads
-// this tensor next, archs/nhwc.py): a lane's running maximum over the values it stores, one wave reduction and one atomic per wave
+// this tensor next, archs/nhwc.py): a lane's running maximum over the values it stores, then mrefsr::publish_amax<true> (reduce.h)
 __device__ __forceinline__ float amax4(float m, const float4 &v, int co, int Cout)
 {
     if (co + 3 < Cout) return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));   // (two v_max3 with |.| modifiers)
@@ -205,15 +205,6 @@ __device__ __forceinline__ float amax4(float m, const float4 &v, int co, int Cou
     if (co + 1 < Cout) m = fmaxf(m, fabsf(v.y));
     if (co + 2 < Cout) m = fmaxf(m, fabsf(v.z));
     return m;
-}
-__device__ __forceinline__ void publish_amax(unsigned int *dst, float m)
-{
-    if (!dst) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    // (one plain read first: after the first blocks most waves' maxima are below the word already -- tens of thousands of atomics
-    //  on ONE address cost the bandwidth-bound launches 0.3 ms)
-    if ((threadIdx.x & 63) == 0 && m > 0.f && m < 3.0e38f && __float_as_uint(m) > __builtin_nontemporal_load(dst)) atomicMax(dst, __float_as_uint(m));
 }
 
 // The epilogue of both convolution kernels.  `acc`: the wave's RPW x 2 accumulator tiles (rows wrow * RPW .. + RPW of the block's
@@ -334,8 +325,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &A, f32x16 (&acc)[R
             }
         }
         if (A.dyn_abs) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
+            local = mrefsr::wave_sum(local);
             if (lane == 0 && local != 0.f) atomicAdd(A.dyn_abs, (double)local);
         }
         return;
@@ -394,7 +384,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &A, f32x16 (&acc)[R
             }
             __builtin_amdgcn_wave_barrier();
         }
-        if (MODE == 2 && !IO16) publish_amax(A.stat_amax, pamx);
+        if (MODE == 2 && !IO16 && A.stat_amax) mrefsr::publish_amax<true>(A.stat_amax, pamx);
         return;
     }
     }
@@ -543,8 +533,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &A, f32x16 (&acc)[R
             ssum.x += __shfl_xor(ssum.x, o, 64), ssum.y += __shfl_xor(ssum.y, o, 64);
             ssum.z += __shfl_xor(ssum.z, o, 64), ssum.w += __shfl_xor(ssum.w, o, 64);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) samx = fmaxf(samx, __shfl_xor(samx, o, 64));
+        samx = mrefsr::wave_max(samx);
         constexpr int NWV = NTHR / 64;
         float *red = reinterpret_cast<float *>(smem);   // [NWV][64] sums, then [NWV] maxima
         __syncthreads();                                 // every wave is done with its slab
@@ -579,8 +568,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &A, f32x16 (&acc)[R
                 for (int c = tid; c < Cout; c += NTHR)
                     A.stat_sum[c] += mrefsr::sum_rows_in_order(A.stat_part + (long)(c / NB) * n_sp * NB, n_sp, NB, c % NB);
         }
-    } else if (MODE == 2 && !IO16) {
-        publish_amax(A.stat_amax, samx);
+    } else if (MODE == 2 && !IO16 && A.stat_amax) {
+        mrefsr::publish_amax<true>(A.stat_amax, samx);
     }
 }
 

@@ -684,11 +684,8 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const ConvArgs A)
 #pragma unroll
             for (int sp = 0; sp < 2; ++sp) asm volatile("" ::"v"(uq[jj][ct][sp]) : "memory");
     if (A.range_flag && !(amax <= 16000.f)) atomicOr(A.range_flag, 1);
-    if (A.stat_amax) {   // max |out| of the launch: the next Winograd layer's input scale (ConvArgs::stat_amax as out_amax)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) oamx = fmaxf(oamx, __shfl_xor(oamx, o, 64));
-        if (lane == 0 && oamx > 0.f && oamx < 3.0e38f && __float_as_uint(oamx) > __builtin_nontemporal_load(A.stat_amax)) atomicMax(A.stat_amax, __float_as_uint(oamx));
-    }
+    // max |out| of the launch: the next Winograd layer's input scale (ConvArgs::stat_amax as out_amax)
+    if (A.stat_amax) mrefsr::publish_amax<true>(A.stat_amax, oamx);
 #ifdef WINO_STAMP
     WSTAMP(6)
     st_acc[7] = 1;

@@ -696,11 +696,8 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const ConvArgs A)
     // the fp16 range guard: an activation so large that a transform value leaves the fp16 range makes that value +-inf and every output it
     // enters inf or NaN (the eight-wave kernel compares the raw activations with 16000 instead: here they never pass through registers)
     if (A.range_flag && !(nonfin == nonfin)) atomicOr(A.range_flag, 1);
-    if (A.stat_amax) {   // (a non-finite output raised the flag above: the batch is re-run, this value is not used)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) oamx = fmaxf(oamx, __shfl_xor(oamx, o, 64));
-        if (lane == 0 && oamx > 0.f && oamx < 3.0e38f && __float_as_uint(oamx) > __builtin_nontemporal_load(A.stat_amax)) atomicMax(A.stat_amax, __float_as_uint(oamx));
-    }
+    // (a non-finite output raised the flag above: the batch is re-run, this value is not used)
+    if (A.stat_amax) mrefsr::publish_amax<true>(A.stat_amax, oamx);
 #ifdef WINO_STAMP
     W4STAMP(10)
     st_acc[11] = 1;

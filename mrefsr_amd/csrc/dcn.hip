@@ -376,8 +376,7 @@ __global__ void dcn_weight_amax_kernel(const float *__restrict__ w, unsigned int
 {
     float m = 0.f;
     for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(w[e]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    m = mrefsr::wave_max(m);
     if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(scal, __float_as_uint(m));  // non-negative floats order like their bits
 }
 
@@ -670,10 +669,7 @@ __global__ __launch_bounds__(256) void dcn_fwd_bf16_kernel(const float *__restri
     const float oscale = NT == 16 ? scal[2] : 1.f;  // 1 / S of the weight scaling
     float oamx = 0.f;   // max |out| of the launch -> out_amax
     auto publish = [&]() {
-        if (!out_amax) return;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) oamx = fmaxf(oamx, __shfl_xor(oamx, o, 64));
-        if (lane == 0 && oamx > 0.f && oamx < 3.0e38f && __float_as_uint(oamx) > __builtin_nontemporal_load(out_amax)) atomicMax(out_amax, __float_as_uint(oamx));
+        if (out_amax) mrefsr::publish_amax<true>(out_amax, oamx);
     };
     if (out_nhwc) {
 #pragma unroll
@@ -1117,11 +1113,7 @@ __global__ __launch_bounds__(256, T == 2 && MB * NB == 1 ? 3 : 2) void dcn_fwd_p
                     }
                 }
             }
-    if (out_amax) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) oamx = fmaxf(oamx, __shfl_xor(oamx, o, 64));
-        if (lane == 0 && oamx > 0.f && oamx < 3.0e38f && __float_as_uint(oamx) > __builtin_nontemporal_load(out_amax)) atomicMax(out_amax, __float_as_uint(oamx));
-    }
+    if (out_amax) mrefsr::publish_amax<true>(out_amax, oamx);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -466,19 +466,6 @@ __global__ __launch_bounds__(256) void bn_dbl_apply_kernel(const float *__restri
 #define HEAD_MAXC 2048
 #define HEAD_MAXJ 4096
 
-__device__ inline float block_sum_256(float v, float *red)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ __launch_bounds__(256) void head_fwd_kernel(const float *__restrict__ f, const float *__restrict__ w1, const float *__restrict__ b1,
                                                        const float *__restrict__ w2, const float *__restrict__ b2, float *__restrict__ out,
                                                        float *__restrict__ Pp, float *__restrict__ Hh, int HW, int C, int J, float slope)
@@ -503,7 +490,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const float *__restrict__
         Hh[(long)n * J + j] = h;
         part += w2[j] * lrelu(h, slope);
     }
-    const float o = block_sum_256(part, red) + b2[0];
+    const float o = mrefsr::block_sum<256>(red, part) + b2[0];
     if (threadIdx.x == 0) out[n] = 1.f / (1.f + expf(-o));
 }
 
@@ -559,7 +546,7 @@ __global__ __launch_bounds__(256) void head_dbl_kernel(const float *__restrict__
         V[(long)n * J + j] = v;
         part += w2[j] * (Hh[(long)n * J + j] > 0.f ? 1.f : slope) * v;
     }
-    const float u = block_sum_256(part, red);
+    const float u = mrefsr::block_sum<256>(red, part);
     const float sv = s[n], ds = sv * (1.f - sv), go = gs[n] * ds, e = go * (1.f - 2.f * sv) * u;
     if (threadIdx.x == 0) {
         if (d_gs) d_gs[n] = ds * u;

@@ -41,19 +41,6 @@ __device__ inline int layer_of(const SnTab &t, int b)
     return l;
 }
 
-__device__ inline float block_sum_256(float v, float *red)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // block b of layer l = (row chunk rc, column block cb): part[rc][k] = sum over the chunk's rows of W[r][k] u[r]
 __global__ __launch_bounds__(256) void sn_wtu_kernel(const SnTab t, float *__restrict__ part)
 {
@@ -82,7 +69,7 @@ __global__ __launch_bounds__(256) void sn_v_kernel(const SnTab t, const float *_
         for (int rc = 0; rc < nrc; ++rc) tk += p[(long)rc * K + k];
         ss += tk * tk;
     }
-    const float inv = 1.f / fmaxf(sqrtf(block_sum_256(ss, red)), eps);
+    const float inv = 1.f / fmaxf(sqrtf(mrefsr::block_sum<256>(red, ss)), eps);
     float *v = t.v[l], *sv = snap_v + t.voff[l];
     for (int k = threadIdx.x; k < K; k += 256) {
         float tk = 0.f;
@@ -102,7 +89,7 @@ __global__ __launch_bounds__(256) void sn_wv_kernel(const SnTab t, const float *
     const float *w = t.w[l] + (long)r * K, *v = use_snap ? snap_v + t.voff[l] : t.v[l];
     float acc = 0.f;
     for (int k = threadIdx.x; k < K; k += 256) acc += w[k] * v[k];
-    const float sr = block_sum_256(acc, red);
+    const float sr = mrefsr::block_sum<256>(red, acc);
     if (threadIdx.x == 0) s[t.uoff[l] + r] = sr;
 }
 
@@ -118,7 +105,7 @@ __global__ __launch_bounds__(256) void sn_u_kernel(const SnTab t, const float *_
     if (update) {
         float ss = 0.f;
         for (int r = threadIdx.x; r < R; r += 256) ss += sl[r] * sl[r];
-        const float inv = 1.f / fmaxf(sqrtf(block_sum_256(ss, red)), eps);
+        const float inv = 1.f / fmaxf(sqrtf(mrefsr::block_sum<256>(red, ss)), eps);
         for (int r = threadIdx.x; r < R; r += 256) {
             const float ur = sl[r] * inv;
             t.u[l][r] = ur;
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(256) void sn_u_kernel(const SnTab t, const float *_
     }
     float d = 0.f;
     for (int r = threadIdx.x; r < R; r += 256) d += su[r] * sl[r];   // (each thread reads back its own writes)
-    const float sg = block_sum_256(d, red);
+    const float sg = mrefsr::block_sum<256>(red, d);
     if (threadIdx.x == 0) sigma[l] = sg;
 }
 
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(256) void sn_dot_kernel(const SnTab t, float *__res
     const float *w = t.w[l], *gl = t.g[l];
     float acc = 0.f;
     for (long i = i0 + threadIdx.x; i < i1; i += 256) acc += gl[i] * w[i];
-    const float sc = block_sum_256(acc, red);
+    const float sc = mrefsr::block_sum<256>(red, acc);
     if (threadIdx.x == 0) part[blockIdx.x] = sc;
 }
 

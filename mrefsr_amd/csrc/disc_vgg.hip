@@ -28,19 +28,6 @@ __global__ __launch_bounds__(256) void lrelu_mask_kernel(const float *__restrict
 // dW2[j] = sum_n gs[n] lrelu(h[n][j]); db2 = sum_n gs.  Double backward for an upstream ggf of gf alone: V = W1 ggf;
 // d gs[n] = sum_j W2[j] lrelu'(h) V; dW1 = GH (x) ggf; dW2[j] = sum_n gs[n] lrelu'(h[n][j]) V[n][j]; d f, d b1, d b2 = 0.
 // ---------------------------------------------------------------------------------------------------------------
-__device__ inline float block_sum_256(float v, float *red)
-{
-    red[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
 __device__ inline long feat_index(long k, int HW, int C) { return (k % HW) * C + k / HW; }   // NCHW feature k -> [HW][C] offset
 
 // one block per j: rows[n][j] = sum_k W1[j][k] F[n][k] (+ b1[j]), per thread over k = tid + 256 i, then a fixed tree
@@ -55,7 +42,7 @@ __global__ __launch_bounds__(256) void lin_rows_kernel(const float *__restrict__
         const float *fn = F + (long)n * K;
         float part = 0.f;
         for (long k = threadIdx.x; k < K; k += 256) part += wr[k] * fn[feat_index(k, HW, C)];
-        const float s = block_sum_256(part, red);
+        const float s = mrefsr::block_sum<256>(red, part);
         if (threadIdx.x == 0) rows[(long)n * J + j] = b1 ? s + b1[j] : s;
     }
 }

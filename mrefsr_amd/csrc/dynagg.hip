@@ -38,8 +38,7 @@ __global__ __launch_bounds__(256) void dynagg_prep_kernel(const float *__restric
     }
     if (abs_sum) {
         __shared__ float red[4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
+        local = mrefsr::wave_sum(local);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
         __syncthreads();
         if (threadIdx.x == 0) atomicAdd(abs_sum, (double)(red[0] + red[1] + red[2] + red[3]));
@@ -88,8 +87,7 @@ __global__ __launch_bounds__(256) void dynagg_prep_nhwc_kernel(const float *__re
     }
     if (abs_sum) {
         __shared__ float red[4];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) local += __shfl_down(local, o, 64);
+        local = mrefsr::wave_sum(local);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = local;
         __syncthreads();
         if (threadIdx.x == 0) atomicAdd(abs_sum, (double)(red[0] + red[1] + red[2] + red[3]));
@@ -197,11 +195,7 @@ __global__ __launch_bounds__(256) void dynagg_prep_bwd_nhwc_kernel(const float *
     } else {
         if (bias_grad && t < nc) atomicAdd(bias_grad + t, sum);
     }
-    if (amax_bits) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
-        if ((t & 63) == 0 && amx > 0.f && amx < 3.0e38f) atomicMax(amax_bits, __float_as_uint(amx));
-    }
+    if (amax_bits) mrefsr::publish_amax<false>(amax_bits, amx);
 }
 
 }  // namespace

@@ -25,7 +25,7 @@
 // kx in {0, W/2}) is structurally zero and is set to zero.
 //
 // Sums: a thread adds its four values r = 0..3, the 256 threads by an LDS tree, one fp32 partial per block (write-through); the
-// block that draws the last ticket (common.h) adds the partials in ascending block order in double and writes the loss.  No float
+// block that draws the last ticket (reduce.h) adds the partials in ascending block order in double and writes the loss.  No float
 // atomics, no readback, the same bits from call to call.  The maximum is order-free.
 #include <math.h>
 
@@ -61,36 +61,6 @@ __device__ __forceinline__ float weight_of(const float m, const float alpha)
 {
     const float a = __fsqrt_rn(m);
     return alpha == 1.f ? a : powf(a, alpha);   // (powf(0, 0) = 1, as torch)
-}
-
-// the block's 256 values added by a tree in `red`, its partial written through, and in the block that arrives last the partials
-// added in ascending block order in double: loss[0] = fl32(factor total)
-__device__ __forceinline__ void block_sum_and_finish(float *red, int *last, const float v, float *partial, unsigned int *ticket,
-                                                     const unsigned int nblocks, const unsigned int bid, const double factor,
-                                                     float *__restrict__ loss)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int o = THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) mrefsr::store_partial(partial + bid, red[0]);
-    if (!mrefsr::last_block_by_ticket(ticket, nblocks, last)) return;
-    double total = 0.0;
-    for (unsigned int base = 0; base < nblocks; base += THREADS) {
-        __syncthreads();
-        red[tid] = base + tid < nblocks ? __hip_atomic_load(partial + base + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-        __syncthreads();
-        if (tid == 0) {
-            const int n = (int)min((unsigned int)THREADS, nblocks - base);
-            for (int q = 0; q < n; ++q) total += (double)red[q];
-        }
-    }
-    if (tid == 0) loss[0] = (float)(factor * total);
 }
 
 // T[row][kx] = sum_x (pred - target)[row][x] (cos, -sin)(2 pi kx x / W); rows = planes H.  grid (row tiles, column tiles)
@@ -197,18 +167,17 @@ __global__ __launch_bounds__(THREADS) void col_kernel(const float2 *__restrict__
         }
         const unsigned int nblocks = gridDim.x * gridDim.y * gridDim.z;
         const unsigned int bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        const int tid = threadIdx.x;
         if constexpr (MODE == MODE_FFT) {
-            block_sum_and_finish(red, &last, v, partial, ticket, nblocks, bid, factor, loss);
+            // the block's tree sum written through; the block that arrives last adds the partials in block order: fl32(factor total)
+            const float bsum = mrefsr::block_sum<THREADS>(red, v);
+            if (tid == 0) mrefsr::store_partial(partial + bid, bsum);
+            if (!mrefsr::last_block_by_ticket(ticket, nblocks, &last)) return;
+            const double total = mrefsr::sum_partials_in_order(partial, nblocks, red);
+            if (tid == 0) loss[0] = (float)(factor * total);
         } else {
-            const int tid = threadIdx.x;
-            red[tid] = v;
-            __syncthreads();
-#pragma unroll
-            for (int o = THREADS / 2; o > 0; o >>= 1) {
-                if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
-                __syncthreads();
-            }
-            if (tid == 0) partial[bid] = red[0];
+            const float bmax = mrefsr::block_max<THREADS>(red, v);
+            if (tid == 0) partial[bid] = bmax;
         }
     }
 }
@@ -225,14 +194,7 @@ __global__ __launch_bounds__(THREADS) void focal_fin_kernel(float2 *__restrict__
     const int tid = threadIdx.x;
     float mx = 0.f;
     for (int i = tid; i < per_plane; i += THREADS) mx = fmaxf(mx, wmax[(long)blockIdx.y * per_plane + i]);
-    red[tid] = mx;
-    __syncthreads();
-#pragma unroll
-    for (int o = THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]);
-        __syncthreads();
-    }
-    mx = red[0];
+    mx = mrefsr::block_max<THREADS>(red, mx);
     const int n = H * Wh;
     float2 *dp = d + (long)blockIdx.y * n;
     float v = 0.f;
@@ -251,7 +213,13 @@ __global__ __launch_bounds__(THREADS) void focal_fin_kernel(float2 *__restrict__
             dp[e] = make_float2(f * c.x, f * c.y);
         }
     }
-    block_sum_and_finish(red, &last, v, partial, ticket, gridDim.x * gridDim.y, blockIdx.y * gridDim.x + blockIdx.x, factor, loss);
+    // as col<FFT>: tree sum, partial written through, the last block's ordered total in double
+    const unsigned int nblocks = gridDim.x * gridDim.y;
+    const float bsum = mrefsr::block_sum<THREADS>(red, v);
+    if (tid == 0) mrefsr::store_partial(partial + blockIdx.y * gridDim.x + blockIdx.x, bsum);
+    if (!mrefsr::last_block_by_ticket(ticket, nblocks, &last)) return;
+    const double total = mrefsr::sum_partials_in_order(partial, nblocks, red);
+    if (tid == 0) loss[0] = (float)(factor * total);
 }
 
 // grad[row][x] = f sum_kx (Re U[row][kx] cos(2 pi kx x / W) - Im U[row][kx] sin(2 pi kx x / W)); grid (row tiles, column tiles)

@@ -66,18 +66,9 @@ __global__ __launch_bounds__(THREADS) void r1_sqnorm_partial_kernel(const float 
         const float q0 = v[0] * v[0], q1 = v[1] * v[1], q2 = v[2] * v[2], q3 = v[3] * v[3];
         acc += (q0 + q1) + (q2 + q3);
     }
-    double d = (double)acc;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) d += __shfl_down(d, off, 64);
-    __shared__ double wave_sum[THREADS / 64];
-    if ((tid & 63) == 0) wave_sum[tid >> 6] = d;
-    __syncthreads();
-    if (tid == 0) {
-        double s = wave_sum[0];
-#pragma unroll
-        for (int w = 1; w < THREADS / 64; ++w) s += wave_sum[w];
-        ((gf64 *)partial_)[b * gridDim.x + blockIdx.x] = s;
-    }
+    __shared__ double wsum[THREADS / 64];
+    const double s = mrefsr::block_sum_by_waves<THREADS>((double)acc, wsum);
+    if (tid == 0) ((gf64 *)partial_)[b * gridDim.x + blockIdx.x] = s;
 }
 
 // one block per row: the row's partials in ascending block order

@@ -17,7 +17,7 @@
 // Both sums run row by row (seven sums of seven, then their sum).  With maps wanted it stores
 // m r, mu and v m.  Block sums by an LDS tree (128, 64, ... 1) in fp32: sum r -> the block's mean, sum (r - mean)^2 -> its M2 (two
 // passes again), sum v m r; with the block's pixel count the three go to its row of `partial`.  The block that draws the last
-// ticket (common.h) finalises: thread t takes samples t, t + 256, ...; per sample it merges the blocks' (count, mean, M2) in double,
+// ticket (reduce.h) finalises: thread t takes samples t, t + 256, ...; per sample it merges the blocks' (count, mean, M2) in double,
 // in ascending block order and again in two passes -- mean = sum count_b mean_b / (H W), M2 = sum M2_b + count_b (mean_b - mean)^2:
 // one dependent fp64 add per block, where the pairwise update of (count, mean, M2) has two divisions in its chain -- adds their
 // sum v m r in the same order, and writes stats[b] = (g_b, mean_b, k_b, S_b), k_b = S_b (1/5) Var_b^(-4/5) 2 / (H W - 1), or 0 for
@@ -54,21 +54,6 @@ __device__ __forceinline__ int reflect(const int i, const int n) { return i < 0 
 __device__ __forceinline__ float residual(const float *__restrict__ a, const float *__restrict__ b, const long hw, const long off)
 {
     return (fabsf(a[off] - b[off]) + fabsf(a[off + hw] - b[off + hw])) + fabsf(a[off + 2 * hw] - b[off + 2 * hw]);
-}
-
-// the sum of v over the block in a fixed order, known to every thread; red: THREADS floats of LDS nothing else uses across the call
-__device__ __forceinline__ float block_sum(float *red, const float v)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-    red[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int o = THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) red[tid] += red[tid + o];
-        __syncthreads();
-    }
-    return red[0];
 }
 
 __device__ __forceinline__ int tile_count(const int t, const int n, const int size) { return min(size, n - t * size); }
@@ -140,13 +125,13 @@ __global__ __launch_bounds__(THREADS) void ldl_loss_fwd_kernel(const float *__re
         }
     }
     const int count = tile_count(blockIdx.y, H, TH) * tile_count(blockIdx.x, W, TW);
-    const float bmean = block_sum(red, rsum) / (float)count;
+    const float bmean = mrefsr::block_sum<THREADS>(red, rsum) / (float)count;
     float dev = 0.f;
 #pragma unroll
     for (int k = 0; k < PER_THREAD; ++k)
         if (inside[k]) dev += (rp[k] - bmean) * (rp[k] - bmean);
-    const float bm2 = block_sum(red, dev);
-    const float bsvr = block_sum(red, svr);
+    const float bm2 = mrefsr::block_sum<THREADS>(red, dev);
+    const float bsvr = mrefsr::block_sum<THREADS>(red, svr);
     const unsigned int per_sample = gridDim.x * gridDim.y, nblocks = per_sample * gridDim.z;
     const unsigned int bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     if (tid == 0) {

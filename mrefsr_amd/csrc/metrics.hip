@@ -71,21 +71,6 @@ __device__ __forceinline__ double y_of(const double *tab, int r, int g, int b)
     return (d + 16.0) / 255.0 * 255.0;
 }
 
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T *red)
-{
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = VM_THREADS / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const T r = red[0];
-    __syncthreads();
-    return r;
-}
-
 // grid (nblk1, images of the chunk).  Pixels of one image are visited p = blockIdx.x * 256 + tid + k * nblk1 * 256.
 template <bool IMG>
 __global__ __launch_bounds__(VM_THREADS) void quant_kernel(const float *__restrict__ out, const float *__restrict__ gt,
@@ -133,9 +118,9 @@ __global__ __launch_bounds__(VM_THREADS) void quant_kernel(const float *__restri
         const double dy = y_of(ytab, uo[0], uo[1], uo[2]) - y_of(ytab, ug[0], ug[1], ug[2]);
         sse_y += dy * dy;
     }
-    sse = block_sum(sse, red_i);
-    bad = block_sum(bad, red_i);
-    sse_y = block_sum(sse_y, red_d);
+    sse = mrefsr::block_sum<VM_THREADS>(red_i, sse);
+    bad = mrefsr::block_sum<VM_THREADS>(red_i, bad);
+    sse_y = mrefsr::block_sum<VM_THREADS>(red_d, sse_y);
     if (threadIdx.x == 0) part[(long)i * g.nblk1 + blockIdx.x] = Part1{sse, sse_y, bad};
 }
 
@@ -216,7 +201,7 @@ __global__ __launch_bounds__(VM_THREADS) void ssim_kernel(const unsigned char *_
         const double s1 = f[2] - mu1_sq, s2 = f[3] - mu2_sq, s12 = f[4] - mu1_mu2;
         acc += ((2.0 * mu1_mu2 + sc.c1) * (2.0 * s12 + sc.c2)) / ((mu1_sq + mu2_sq + sc.c1) * (s1 + s2 + sc.c2));
     }
-    acc = block_sum(acc, red);
+    acc = mrefsr::block_sum<VM_THREADS>(red, acc);
     if (threadIdx.x == 0) *dst = acc;
 }
 
@@ -235,15 +220,15 @@ __global__ __launch_bounds__(VM_THREADS) void finish_kernel(const Part1 *__restr
         bad += p1[b].nonfinite;
         sse_y += p1[b].sse_y;
     }
-    sse = block_sum(sse, red_i);
-    bad = block_sum(bad, red_i);
-    sse_y = block_sum(sse_y, red_d);
+    sse = mrefsr::block_sum<VM_THREADS>(red_i, sse);
+    bad = mrefsr::block_sum<VM_THREADS>(red_i, bad);
+    sse_y = mrefsr::block_sum<VM_THREADS>(red_d, sse_y);
     double ssim[4] = {0.0, 0.0, 0.0, 0.0};
     for (int s = slot0; s < slot1; ++s) {
         const double *p2 = part2 + ((long)i * 4 + s) * g.tile_stride;
         double a = 0.0;
         for (int b = threadIdx.x; b < ntiles; b += VM_THREADS) a += p2[b];
-        ssim[s] = block_sum(a, red_d);
+        ssim[s] = mrefsr::block_sum<VM_THREADS>(red_d, a);
     }
     if (threadIdx.x == 0) {
         long long *row = res + (long)i * RES_WORDS;

@@ -231,18 +231,9 @@ __global__ __launch_bounds__(THREADS) void grad_walk_kernel(const mrefsr_optim_j
         }
     }
     if (SCALE) return;
-    double d = (double)acc;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) d += __shfl_down(d, off, 64);
-    __shared__ double wave_sum[THREADS / 64];
-    if ((tid & 63) == 0) wave_sum[tid >> 6] = d;
-    __syncthreads();
-    if (tid == 0) {
-        double s = wave_sum[0];
-#pragma unroll
-        for (int w = 1; w < THREADS / 64; ++w) s += wave_sum[w];
-        partial[blockIdx.x] = s;
-    }
+    __shared__ double wsum[THREADS / 64];
+    const double s = mrefsr::block_sum_by_waves<THREADS>((double)acc, wsum);
+    if (tid == 0) partial[blockIdx.x] = s;
 }
 
 // one block: the partials in index order, then the state.  torch's clip_grad_norm_: coef = min(max_norm / (norm + 1e-6), 1) in

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(256) void reflect_pad_bwd_nhwc_kernel(const float4 
 }
 
 // top-left H0 x W0 window of x [N][H][W][C]; amax_bits (may be NULL): max |out| as the convolution epilogues publish it
-// (conv_nhwc.hip publish_amax: one wave reduction, one atomic per wave that raises the word)
+// (mrefsr::publish_amax<true>, reduce.h: one wave reduction, one atomic per wave that raises the word)
 __global__ __launch_bounds__(256) void crop_nhwc_kernel(const float4 *__restrict__ x, float4 *__restrict__ out,
                                                         unsigned int *__restrict__ amax_bits, int H, int W, int H0, int W0, int C4)
 {
@@ -65,11 +65,7 @@ __global__ __launch_bounds__(256) void crop_nhwc_kernel(const float4 *__restrict
         out[(long)row * W0 * C4 + j] = v;
         m = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
-    if (!amax_bits) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0 && m > 0.f && m < 3.0e38f && __float_as_uint(m) > __builtin_nontemporal_load(amax_bits))
-        atomicMax(amax_bits, __float_as_uint(m));
+    if (amax_bits) mrefsr::publish_amax<true>(amax_bits, m);
 }
 
 // adjoint of the crop: g [N][H0][W0][C] into the window of gx [N][H][W][C], zeros in the band to its right and below

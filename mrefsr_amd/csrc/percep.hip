@@ -14,14 +14,6 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ inline void amax_store(unsigned int *amax_bits, float amx)
-{
-    // max |g| of the wave into the zero-initialised word (non-negative floats order like their bit patterns)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
-    if ((threadIdx.x & 63) == 0 && amx > 0.f && amx < 3.0e38f) atomicMax(amax_bits, __float_as_uint(amx));
-}
-
 __device__ inline float relu_in(float v, int relu) { return (relu && v < 0.f) ? 0.f : v; }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -122,7 +114,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float *__restri
         if (has_d) dst[(long)W * C4] = make_float4(o[2][0], o[2][1], o[2][2], o[2][3]);
         if (has_r && has_d) dst[(long)W * C4 + C4] = make_float4(o[3][0], o[3][1], o[3][2], o[3][3]);
     }
-    if (amax_bits) amax_store(amax_bits, amx);
+    if (amax_bits) mrefsr::publish_amax<false>(amax_bits, amx);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -186,15 +178,10 @@ __global__ __launch_bounds__(256) void tap_crit_kernel(const TapArgs a)
         }
     }
     if (a.partial) {
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) {
-            if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) a.partial[blockIdx.x] = red[0];
+        s = mrefsr::block_sum<256>(red, s);
+        if (threadIdx.x == 0) a.partial[blockIdx.x] = s;
     }
-    if (gr && a.amax_bits) amax_store(a.amax_bits, amx);
+    if (gr && a.amax_bits) mrefsr::publish_amax<false>(a.amax_bits, amx);
 }
 
 // second stage: loss_k = sum / n (l1) or sqrt(sum) (fro), totals[g] = (sum over the jobs of group g, in order, of loss_k * w_k)
@@ -346,7 +333,7 @@ __global__ __launch_bounds__(256) void gram_bwd_kernel(const float *__restrict__
             amx = fmaxf(amx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
         }
     }
-    if (amax_bits) amax_store(amax_bits, amx);
+    if (amax_bits) mrefsr::publish_amax<false>(amax_bits, amx);
 }
 
 // gradient of image_to_nhwc4: g4 [N][HW][ld] (channels 0..2) -> g_img [N][3][HW] = (g / std) * 0.5 (torch's order: the division's

@@ -30,13 +30,8 @@ __global__ __launch_bounds__(THREADS) void mean_partial_kernel(const float *__re
     float a = 0.f;
 #pragma unroll 4
     for (long p = (long)c * CHUNK + threadIdx.x; p < p1; p += THREADS) a = __fadd_rn(a, v[p]);
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int w = THREADS / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] = __fadd_rn(red[threadIdx.x], red[threadIdx.x + w]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[((long)n * B + b) * chunks + c] = red[0];
+    a = mrefsr::block_sum<THREADS>(red, a);   // (additions alone: under -ffp-contract=off a plain + is __fadd_rn)
+    if (threadIdx.x == 0) part[((long)n * B + b) * chunks + c] = a;
 }
 
 // block (c, b): per position of the chunk the present candidate with the largest val -- a later one replaces the best only when

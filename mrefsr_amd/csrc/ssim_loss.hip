@@ -19,7 +19,7 @@
 // (derivatives at fixed RAW second moments; A1 = 2 mu_x mu_y + C1, A2 = 2 sigma_xy + C2, B1 = mu_x^2 + mu_y^2 + C1,
 // B2 = sigma_x^2 + sigma_y^2 + C2, D = 1 / (B1 B2), m = A1 A2 D) into three [planes, MH, MW] maps.  Sum of m: per thread k = 0 then
 // k = 1 (a position outside the map counts 0), the 256 threads by an LDS tree (128, 64, ... 1), one fp32 partial per block written
-// through to `partial`; the block that draws the last ticket (common.h) adds the partials in ascending block order
+// through to `partial`; the block that draws the last ticket (reduce.h) adds the partials in ascending block order
 // ((plane, ty, tx) row-major) in double and writes loss = fl32(loss_weight (1 - sum / count)).  No float atomics, no readback.
 //
 // Backward, one launch over 16 x 32 tiles of the INPUT: d(sum m)/dX(p) = (G^T a)(p) + 2 X(p) (G^T b)(p) + Y(p) (G^T c)(p), G^T the
@@ -157,28 +157,12 @@ __global__ __launch_bounds__(THREADS) void ssim_loss_fwd_kernel(const float *__r
             }
         }
     }
-    __syncthreads();                         // every thread has read v: it becomes the tree
-    v[tid] = msum;
-    __syncthreads();
-#pragma unroll
-    for (int o = THREADS / 2; o > 0; o >>= 1) {
-        if (tid < o) v[tid] += v[tid + o];
-        __syncthreads();
-    }
+    const float bsum = mrefsr::block_sum<THREADS>(v, msum);   // (meets first: every thread has read v, it becomes the tree)
     const unsigned int nblocks = gridDim.x * gridDim.y * gridDim.z;
     const unsigned int bid = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    if (tid == 0) mrefsr::store_partial(partial + bid, v[0]);
+    if (tid == 0) mrefsr::store_partial(partial + bid, bsum);
     if (!mrefsr::last_block_by_ticket(ticket, nblocks, &last)) return;
-    double total = 0.0;
-    for (unsigned int base = 0; base < nblocks; base += THREADS) {
-        __syncthreads();
-        v[tid] = base + tid < nblocks ? __hip_atomic_load(partial + base + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
-        __syncthreads();
-        if (tid == 0) {
-            const int n = (int)min((unsigned int)THREADS, nblocks - base);
-            for (int q = 0; q < n; ++q) total += (double)v[q];
-        }
-    }
+    const double total = mrefsr::sum_partials_in_order(partial, nblocks, v);
     if (tid == 0) loss[0] = (float)((double)loss_weight * (1.0 - total * inv_count));
 }
 

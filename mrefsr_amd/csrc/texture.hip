@@ -175,13 +175,8 @@ __global__ __launch_bounds__(256) void crit_kernel(const CritArgs a, double *__r
         const double d = (double)(gx[i] - gm[i]);
         s += d * d;
     }
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partial[l * MREFSR_TEXTURE_CRIT_BLOCKS + blockIdx.x] = red[0];
+    s = mrefsr::block_sum<256>(red, s);
+    if (threadIdx.x == 0) partial[l * MREFSR_TEXTURE_CRIT_BLOCKS + blockIdx.x] = s;
 }
 
 __global__ __launch_bounds__(64) void crit_finish_kernel(const CritArgs a, const double *__restrict__ partial, float *__restrict__ norms,
@@ -260,12 +255,7 @@ __global__ __launch_bounds__(256) void gram_bwd_kernel(const float *__restrict__
             amx = fmaxf(amx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
         }
     }
-    if (amax_bits) {
-        // max |dF| of the wave into the zero-initialised word (non-negative floats order like their bit patterns)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
-        if (lane == 0 && amx > 0.f && amx < 3.0e38f) atomicMax(amax_bits, __float_as_uint(amx));
-    }
+    if (amax_bits) mrefsr::publish_amax<false>(amax_bits, amx);   // max |dF|
 }
 
 }  // namespace

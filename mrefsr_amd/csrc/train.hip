@@ -18,7 +18,7 @@ namespace {
 // x = out / slope for out < 0, which needs slope > 0 -- `flag` is raised otherwise and the caller re-runs unfused)
 // ---------------------------------------------------------------------------------------------------------------
 // DET: the blocks' sums go to row blockIdx.x of `part` ([gridDim.x][C + 1] floats: C channel sums, the slope sum) instead of
-// into atomics; the block that draws the last `ticket` adds the rows in ascending block order (common.h) -- bitwise reproducible.
+// into atomics; the block that draws the last `ticket` adds the rows in ascending block order (reduce.h) -- bitwise reproducible.
 template <int V, bool DET>
 __global__ __launch_bounds__(256) void act_bwd_nhwc_kernel(const float *__restrict__ g_out, const float *__restrict__ out,
                                                            float *__restrict__ g_pre, int ld_pre, float *__restrict__ bias_grad,
@@ -118,11 +118,7 @@ __global__ __launch_bounds__(256) void act_bwd_nhwc_kernel(const float *__restri
             }
         }
     }
-    if (amax_bits) {   // max |g_pre| (non-negative floats order like their bit patterns): the scale of the fp16-split dgrad
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amx = fmaxf(amx, __shfl_xor(amx, o, 64));
-        if ((t & 63) == 0 && amx > 0.f && amx < 3.0e38f) atomicMax(amax_bits, __float_as_uint(amx));
-    }
+    if (amax_bits) mrefsr::publish_amax<false>(amax_bits, amx);   // max |g_pre|: the scale of the fp16-split dgrad
 }
 
 // ---------------------------------------------------------------------------------------------------------------

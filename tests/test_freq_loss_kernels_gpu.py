@@ -261,3 +261,43 @@ def test_the_planes_are_independent(variant):
         err = float((3.0 * grad[i].double() - alone[0].double()).abs().max() / alone.double().abs().max())
         print(f'  {variant:12s} image {i}: |3 grad[batch] - grad[alone]| / max = {err:.2e} (bar {2 * bars["generic"][1]:.2e})')
         assert err <= 2 * bars['generic'][1]
+
+
+CHUNKED = (257, 1, 5, 8)
+
+
+@functools.lru_cache(maxsize=None)
+def chunked_reference():
+    """the one case of CHUNKED, as reference() holds its cases: {variant: (loss64, grad64)}, the inputs, and the (relative loss bar,
+    gradient bar) of the file's rule on this case -- FACTOR x the largest yardstick error over the four variants"""
+    pred, target = make_inputs('smooth', CHUNKED, 9000)
+    ref, worst_l, worst_g = {}, 0.0, 0.0
+    for variant in VARIANTS:
+        loss64, grad64 = definition64(pred, target, variant)
+        loss32, grad32 = dense_fp32(pred, target, variant)
+        ref[variant] = (loss64, grad64)
+        worst_l, worst_g = max(worst_l, abs(loss32 - loss64) / abs(loss64)), max(worst_g, rel_grad_err(grad32, grad64))
+    return pred, target, ref, (FACTOR * worst_l, FACTOR * worst_g)
+
+
+@pytest.mark.parametrize('variant', VARIANTS)
+def test_more_partials_than_one_chunk_of_the_last_blocks_sum(variant):
+    """The block that draws the last ticket reads the blocks' partials 256 at a time (sum_partials_in_order, csrc/reduce.h); the
+    shapes above stay within one chunk.  A plane is at least one block of the column pass and one of the focal finish, so 257
+    planes are the fewest with which both launches have more than 256 blocks, and 257 is no multiple of 256: the loop's second
+    pass runs, over one partial, behind its barrier.  The planes are the 5 x 8 of the C = 1 case above (a 1 x 1 plane has one real
+    coefficient: |x| / count leaves the yardstick nothing to err on).  Kept out of reference(): the classes' bars come from the
+    cases they always came from.  The bar is the file's rule on this one case: FACTOR x the largest error of the dense fp32 torch
+    products on the same inputs over the four variants.  Two calls give the same bits"""
+    from mrefsr_amd import _lib
+    b, c, h, w = CHUNKED
+    blocks = _lib.load().mrefsr_freq_loss_blocks(b * c, h, w)
+    assert blocks == 257 and blocks > 256 and blocks % 256 != 0 and max(h, w) <= 64
+    pred, target, ref, (loss_bar, grad_bar) = chunked_reference()
+    loss64, grad64 = ref[variant]
+    (loss, grad), (loss2, grad2) = run_hip(pred, target, variant), run_hip(pred, target, variant)
+    el, eg = abs(float(loss) - loss64) / abs(loss64), rel_grad_err(grad.cpu(), grad64)
+    print(f'  {variant:12s} {CHUNKED} {blocks} blocks  loss64 {loss64:.6e}  loss rel err hip {el:.2e} bar {loss_bar:.2e}   '
+          f'grad rel err hip {eg:.2e} bar {grad_bar:.2e}')
+    assert el <= loss_bar and eg <= grad_bar and bool(torch.isfinite(grad).all())
+    assert torch.equal(loss, loss2) and torch.equal(grad, grad2)

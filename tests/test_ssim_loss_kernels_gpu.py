@@ -175,3 +175,30 @@ def test_equal_images_give_no_loss_and_a_gradient_at_rounding_level(channel):
               f'{float(grad.abs().max()):.2e} torch-fp32 {float(y32.abs().max()):.2e} (bound {64 * 2.0 ** -24 * t:.2e})')
         assert abs(float(loss)) <= bars['generic'][0]
         assert float(grad.abs().max()) <= 64 * 2.0 ** -24 * t and math.isfinite(float(grad.abs().max()))
+
+
+CHUNKED = (43, 43, 43)   # map 33 x 33: six tiles per plane
+
+
+@pytest.mark.parametrize('channel', CHANNELS)
+def test_more_partials_than_one_chunk_of_the_last_blocks_sum(channel):
+    """The block that draws the last ticket reads the blocks' partials 256 at a time (sum_partials_in_order, csrc/reduce.h).  The
+    shapes above stay within one chunk (48 blocks at most); this one has 258 blocks in y mode (one chunk and 2) and 774 in rgb
+    (three chunks and 6), so the loop's later passes run, with the barrier in front of each overwrite of the chunk in LDS.  Kept
+    out of reference(): the classes' bars come from the cases they always came from.  The bar here is the file's rule on this one
+    case: FACTOR x the error of the fp32 torch expression on the same inputs.  Two calls give the same bits (the ticket is back
+    at 0, no pass of the loop reads a chunk that is being replaced)"""
+    from mrefsr_amd import _lib
+    b, h, w = CHUNKED
+    blocks = _lib.load().mrefsr_ssim_loss_blocks(b, h, w, int(channel == 'rgb'))
+    assert blocks == {'y': 258, 'rgb': 774}[channel] and blocks > 256 and blocks % 256 != 0
+    pred, target = make_inputs('smooth', CHUNKED, 5000 + CHANNELS.index(channel))
+    loss64, grad64 = expression(pred, target, channel, torch.float64)
+    loss32, grad32 = expression(pred, target, channel, torch.float32)
+    loss_bar, grad_bar = FACTOR * abs(loss32 - loss64), FACTOR * rel_grad_err(grad32, grad64)
+    (loss, grad), (loss2, grad2) = run_hip(pred, target, channel), run_hip(pred, target, channel)
+    el, eg = abs(float(loss) - loss64), rel_grad_err(grad.cpu(), grad64)
+    print(f'  {channel:3s} {CHUNKED} {blocks} blocks  loss64 {loss64:.6e}  |loss err| hip {el:.2e} bar {loss_bar:.2e}   '
+          f'grad rel err hip {eg:.2e} bar {grad_bar:.2e}')
+    assert el <= loss_bar and eg <= grad_bar and bool(torch.isfinite(grad).all())
+    assert torch.equal(loss, loss2) and torch.equal(grad, grad2)
