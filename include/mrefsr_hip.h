@@ -1136,6 +1136,37 @@ int mrefsr_freq_loss_fwd_f32(const float *pred, const float *target, int planes,
 int mrefsr_freq_loss_bwd_f32(const float *g, const float *grad_loss, int planes, int h, int w, float loss_weight, const float *tab_h,
                              const float *tab_w, float *u, float *grad_pred, mrefsr_stream_t stream);
 
+/* ---- Contextual loss of the training step (csrc/contextual.hip; losses.ContextualLoss, train.contextual_opt; Mechrez
+ * et al., ECCV 2018).  No reference counterpart.  One tap: x (features of the output) and y (of the target), NHWC [B][N][C]
+ * contiguous fp32, N = h w; i runs over positions of x, j over positions of y.  1 <= B <= 65535, 2 <= N <= MREFSR_CX_MAX_N (one N x N
+ * fp32 matrix per sample is materialised in the workspace), C of 64, 128, 256, 512.
+ *   mu[b][c] = mean_p y[b][p][c];  xn = (x - mu) / max(|x - mu|_2, 1e-12) per position, yn the same from y;
+ *   d[i][j] = 1 - <xn_i, yn_j> (v_mfma_f32_16x16x4_f32);  m[i] = min_j d[i][j] at jmin[i] (the lowest j on ties);
+ *   w = exp((1 - d / (m + 1e-5)) / band_width), Z[i] = sum_j w[i][j];
+ *   cxmax[j] = max_i w[i][j] / Z[i] at imax[j] (the lowest i on ties);
+ *   cx[b] = mean_j cxmax[b][j];  tap_loss[0] = mean_b -log(cx[b] + 1e-5).
+ * mrefsr_contextual_workspace_bytes: bytes of `workspace` for the forward (backward = 0) or the backward call; MREFSR_E_INVALID /
+ *   MREFSR_E_UNSUPPORTED for a shape outside the limits (N over the bound: MREFSR_E_UNSUPPORTED).
+ * mrefsr_contextual_fwd_f32: writes xn, yn [B][N][C], rnorm [B][N] (1 / max(|x - mu|, 1e-12)), rowf [2][B][N] = m, Z,
+ *   jmin [B][N], cxmax [B][N], imax [B][N], cx [B], tap_loss [1] -- what the backward call reads -- and the running
+ *   total of a loss over several taps: run[0] = (first ? 0 : run[0]) + tap_loss weight, total[0] = run[0] loss_weight.  x and y are
+ *   only read.  Six launches; every sum in a fixed order (no float atomics), the same bits from call to call.
+ * mrefsr_contextual_bwd_f32: dx [B][N][C] = (accumulate ? dx : 0) + d (gup[0] coef tap_loss) / d x, from the forward's outputs (d is
+ *   recomputed); gup: one float in device memory or NULL (= 1); amax (may be NULL): a zeroed word raised to max |dx|.  The gradient
+ *   passes through the selected element of each column, the row normaliser Z, the row minimum at jmin, the normalisation and the
+ *   centring (mu is a constant of y).  Four launches, fixed orders.
+ * A shape outside the limits is refused before any launch. */
+#define MREFSR_CX_MAX_N 4096
+int64_t mrefsr_contextual_workspace_bytes(int B, int N, int C, int backward);
+int mrefsr_contextual_fwd_f32(const float *x, const float *y, int B, int N, int C, float band_width, float *xn, float *yn, float *rnorm,
+                              float *rowf, int32_t *jmin, float *cxmax, int32_t *imax, float *cx, float *tap_loss, float weight,
+                              float loss_weight, int first, float *run, float *total, void *workspace, int64_t workspace_bytes,
+                              mrefsr_stream_t stream);
+int mrefsr_contextual_bwd_f32(const float *xn, const float *yn, const float *rnorm, int B, int N, int C, float band_width,
+                              const float *rowf, const int32_t *jmin, const float *cxmax, const int32_t *imax, const float *cx,
+                              const float *gup, float coef, float *dx, int accumulate, float *amax, void *workspace,
+                              int64_t workspace_bytes, mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

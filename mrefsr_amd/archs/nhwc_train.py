@@ -24,6 +24,8 @@ same graph is recorded over [N,H,W,C] tensors with one autograd node per FUSED l
   _Pad, _Crop    MRAPAFusion's reflect pad to a multiple of 4 and the crop back (csrc/pad.hip), one pass each way
   _VggLoss       the VGG of PerceptualLoss (losses/): output and GT as one batch forward, input gradients of the output image
                  backward (csrc/percep.hip: pooling, tap criterion, Gram matrices, image packing backward)
+  _VggContextual the same VGG stack for ContextualLoss: per tap the all-pairs similarity, its statistics and their backward on
+                 csrc/contextual.hip
 
 Arithmetic: forward and input-gradient convolutions run the fp16 two-term split (terms 16, three products; FWD_TERMS /
 BWD_TERMS) on weights packed with a cached power-of-two scale (_wscale, watched by check_scales()); an input-gradient launch
@@ -910,6 +912,81 @@ def texture(vgg, x, maps, weights, plan):
     mean = vgg.mean.contiguous() if vgg.use_input_norm else None
     std = vgg.std.contiguous() if vgg.use_input_norm else None
     return _VggTexture.apply(x, plan, mean, std, *coeffs, *gms)
+
+
+# ---- contextual loss (losses.ContextualLoss; Mechrez et al., ECCV 2018) ---------------------------------------------
+KEEP_CX = None   # tests/ set a list: every _VggContextual forward appends, per tap, dict(jmin, imax, CX) of the device's selections
+
+
+_CX_SAVED = ('xn', 'yn', 'rnorm', 'rowf', 'jmin', 'cxmax', 'imax', 'cx')   # what hip.contextual_bwd reads of hip.contextual_fwd's outputs
+
+
+class ContextualLossPlan(VggLossPlan):
+    """VggLossPlan of a ContextualLoss: the taps with their weights, the band width and the loss weight"""
+
+    def __init__(self, vgg_net, layer_weights, band_width, loss_weight, norm_img):
+        super().__init__(vgg_net, layer_weights, 'contextual', 0.0, 0.0, norm_img)
+        self.names = [self.layers[i]['names'][kind] for i, kind, _ in self.taps]   # network order: the summation order
+        self.band_width, self.loss_weight = float(band_width), float(loss_weight)
+
+
+class _VggContextual(Function):
+    """(output x, gt) -> the contextual loss [1]: output and GT as ONE 2B batch through the VGG kernels, per tap the kernels of
+    csrc/contextual.hip (the running total is carried from tap to tap on the device, in network order); the backward adds each
+    tap's gradient where the perceptual term adds its own and runs the input gradients of the first B images back to x."""
+
+    @staticmethod
+    def forward(ctx, x, gt, plan, mean, std):
+        b = x.shape[0]
+        img = torch.cat([x.detach(), gt.detach()]).contiguous()
+        feats, saved = _vgg_stack_forward(plan, img, mean, std)
+        need = ctx.needs_input_grad[0]
+        run, total, keep = None, None, []
+        for (_, _, w), name, f in zip(plan.taps, plan.names, feats):
+            try:
+                total, s = hip.contextual_fwd(f[:b], f[b:], plan.band_width, w, plan.loss_weight, run=run)
+            except NotImplementedError as e:
+                raise NotImplementedError(f'ContextualLoss: tap {name} of {f.shape[1]} x {f.shape[2]} positions: {e}') from None
+            run = s['run']
+            keep.append(s)
+        if KEEP_CX is not None:
+            KEEP_CX.append([dict(jmin=s['jmin'], imax=s['imax'], CX=s['cx']) for s in keep])
+        ctx.plan, ctx.b, ctx.saved = plan, b, saved
+        ctx.save_for_backward(std, *[s[k] for s in (keep if need else []) for k in _CX_SAVED])
+        return total
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_tot):
+        plan, b, saved = ctx.plan, ctx.b, ctx.saved
+        st = ctx.saved_tensors
+        std, nk = st[0], len(_CX_SAVED)
+        keep = [dict(zip(_CX_SAVED, st[1 + j * nk:1 + (j + 1) * nk])) for j in range(len(plan.taps))]
+        g_tot = g_tot.contiguous()
+        tap_of = {(i, k): j for j, (i, k, _) in enumerate(plan.taps)}
+
+        def add_tap(g, i, kind):
+            j = tap_of.get((i, kind))
+            if j is None:
+                return g, None
+            acc = g is not None
+            if g is None:
+                g = torch.empty_like(keep[j]['xn'])
+            return g, hip.contextual_bwd(keep[j], plan.band_width, plan.loss_weight * plan.taps[j][2], g, gup=g_tot, accumulate=acc)
+
+        g_x = _vgg_stack_backward(plan, b, saved, std, add_tap)
+        return g_x, None, None, None, None
+
+
+def contextual(vgg, x, gt, plan):
+    """ContextualLoss.forward on the training engine: -> the loss [1] (a device tensor; autograd reaches x)"""
+    if not (x.is_cuda and gt.is_cuda):
+        raise NotImplementedError('ContextualLoss: mrefsr_amd has no CPU path (HIP kernels only)')
+    if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.shape != gt.shape or x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError(f'ContextualLoss: two float32 [N,3,H,W] images expected, got {tuple(x.shape)} / {tuple(gt.shape)}')
+    mean = vgg.mean.contiguous() if vgg.use_input_norm else None
+    std = vgg.std.contiguous() if vgg.use_input_norm else None
+    return _VggContextual.apply(x, gt, plan, mean, std)
 
 
 def recording(*tensors):

@@ -1962,6 +1962,70 @@ def freq_loss_bwd(g, grad_loss, shape, loss_weight=1.0):
     return grad
 
 
+# ------------------------------------------------------------------ contextual loss of the training step (csrc/contextual.hip)
+CX_MAX_N = 4096   # MREFSR_CX_MAX_N: positions per tap (one N x N fp32 matrix per sample is materialised in scratch)
+
+
+def _cx_workspace(name, b, n, c, backward):
+    need = _lib.load().mrefsr_contextual_workspace_bytes(b, n, c, 1 if backward else 0)
+    if need == -2:
+        raise NotImplementedError(f'{name}: a tap of {n} positions and {c} channels; at most {CX_MAX_N} positions (one N x N matrix per '
+                                  'sample is materialised) and 64, 128, 256 or 512 channels')
+    if need < 0:
+        raise ValueError(f'{name}: B={b} N={n} C={c} (1 <= B <= 65535, N >= 2)')
+    return need
+
+
+def contextual_fwd(x, y, band_width, weight=1.0, loss_weight=1.0, run=None):
+    """one tap of the contextual loss: x (features of the output), y (of the target) [B,h,w,C] contiguous fp32, C of 64 ... 512, h w
+    of 2 ... CX_MAX_N -> (total, saved).  run: None for the first tap of a loss, else the running sum the previous tap's call
+    returned as saved['run'] (updated in place: run += tap loss * weight); total [1] = run * loss_weight.  saved: what
+    contextual_bwd reads (xn, yn, rnorm, rowf = m | Z, jmin, cxmax, imax, cx [B], tap_loss [1], run).  Six
+    launches, fixed summation orders (the same bits from call to call), nothing read back; x and y are only read"""
+    _chk('contextual_fwd', x, y, run)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError(f'contextual_fwd: two [B,h,w,C] maps of one shape expected, got {tuple(x.shape)} and {tuple(y.shape)}')
+    if not (isinstance(band_width, (int, float)) and 0.0 < band_width < float('inf')):
+        raise ValueError(f'contextual_fwd: band_width={band_width!r} is not a finite number > 0')
+    b, h, w, c = x.shape
+    n, dev = h * w, x.device
+    need = _cx_workspace('contextual_fwd', b, n, c, False)
+    f32 = dict(device=dev, dtype=torch.float32)
+    s = dict(xn=torch.empty_like(x), yn=torch.empty_like(x), rnorm=torch.empty((b, n), **f32), rowf=torch.empty((2, b, n), **f32),
+             jmin=torch.empty((b, n), device=dev, dtype=torch.int32), cxmax=torch.empty((b, n), **f32),
+             imax=torch.empty((b, n), device=dev, dtype=torch.int32), cx=torch.empty(b, **f32), tap_loss=torch.empty(1, **f32),
+             run=run if run is not None else torch.empty(1, **f32))
+    total = torch.empty(1, **f32)
+    ws = _scratch(dev, need)
+    with _timed('contextual_fwd', 2.0 * b * n * n * c, detail=True, nbytes=4.0 * (4 * x.numel() + 3 * b * n * n)):
+        _lib.call('mrefsr_contextual_fwd_f32', _p(x), _p(y), b, n, c, C.c_float(band_width), _p(s['xn']), _p(s['yn']), _p(s['rnorm']),
+                  _p(s['rowf']), _p(s['jmin']), _p(s['cxmax']), _p(s['imax']), _p(s['cx']), _p(s['tap_loss']), C.c_float(weight),
+                  C.c_float(loss_weight), 1 if run is None else 0, _p(s['run']), _p(total), _p(ws), C.c_int64(need), _stream())
+    return total, s
+
+
+def contextual_bwd(saved, band_width, coef, dx, gup=None, accumulate=False, want_amax=True):
+    """dx [B,h,w,C] (+)= d (gup * coef * tap loss) / d x of contextual_fwd from its ``saved`` (the distances are recomputed); coef:
+    loss_weight times the tap's weight; gup: a one-element fp32 device tensor or None (= 1).  Four launches, fixed orders.
+    -> max |dx| [1] | None"""
+    names = ('xn', 'yn', 'rnorm', 'rowf', 'cxmax', 'cx')
+    _chk('contextual_bwd', dx, gup, *[saved[k] for k in names])
+    _chk('contextual_bwd', saved['jmin'], saved['imax'], dtype=torch.int32)
+    xn = saved['xn']
+    b, h, w, c = xn.shape
+    n = h * w
+    if tuple(dx.shape) != tuple(xn.shape) or (gup is not None and gup.numel() != 1):
+        raise ValueError(f'contextual_bwd: a gradient buffer of {tuple(xn.shape)} and one upstream value expected, got {tuple(dx.shape)}')
+    need = _cx_workspace('contextual_bwd', b, n, c, True)
+    amax = zeros_f32(dx.device, 1) if want_amax else None
+    ws = _scratch(dx.device, need)
+    with _timed('contextual_bwd', 4.0 * b * n * n * c, detail=True, nbytes=4.0 * (4 * xn.numel() + 3 * b * n * n)):
+        _lib.call('mrefsr_contextual_bwd_f32', _p(xn), _p(saved['yn']), _p(saved['rnorm']), b, n, c, C.c_float(band_width), _p(saved['rowf']),
+                  _p(saved['jmin']), _p(saved['cxmax']), _p(saved['imax']), _p(saved['cx']), _p(gup), C.c_float(coef), _p(dx),
+                  1 if accumulate else 0, _p(amax), _p(ws), C.c_int64(need), _stream())
+    return amax
+
+
 # ------------------------------------------------------------------ second-order degradation (csrc/degrade.hip; degradation.py)
 DEGRADE_MODES = {'area': 0, 'bilinear': 1, 'bicubic': 2}
 

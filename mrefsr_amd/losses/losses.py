@@ -4,6 +4,8 @@ basicsr/losses/losses.py:258-360, 391-405.  LDLLoss is the artifact loss of LDL 
 basicsr/models/realesrgan_model.py:211-226), on the kernels of csrc/ldl_loss.hip.  SSIMLoss has no counterpart in the reference: it is the structural-similarity term the
 validation metric (mrefsr_amd/metrics.py: calculate_ssim) measures, as a criterion, on the kernels of csrc/ssim_loss.hip.  FFTLoss and FocalFrequencyLoss have none either: the L1 distance of the spectra
 (MIMO-UNet, DeepRFT) and the focal frequency loss (Jiang et al., ICCV 2021), on the dense-DFT kernels of csrc/freq_loss.hip.
+ContextualLoss has none either: the contextual loss of Mechrez et al. (ECCV 2018) between VGG features, on the kernels of
+csrc/contextual.hip (archs/nhwc_train.py: _VggContextual).
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
 what the model passes -- reduction='mean', no element weight -- and refuse the rest.  PerceptualLoss runs its VGG19 through ONE
@@ -373,6 +375,99 @@ class FocalFrequencyLoss(nn.Module):
         if not on_gpu:
             return self.loss_weight * focal_frequency_loss_torch(pred, target, self.alpha)
         return _FreqLossFn.apply(pred.contiguous(), target.contiguous(), True, 'ortho', self.alpha, float(self.loss_weight))
+
+
+def _lowest_index_of(hit, dim):
+    """the lowest index along ``dim`` at which the boolean tensor ``hit`` is set (every slice has one)"""
+    n = hit.shape[dim]
+    shape = [1] * hit.dim()
+    shape[dim] = n
+    idx = torch.arange(n, device=hit.device).view(shape)
+    return torch.where(hit, idx, torch.full_like(idx, n)).amin(dim)
+
+
+def contextual_loss_torch(x_feats, y_feats, band_width=0.5, jmin=None, imax=None, parts=False):
+    """The contextual loss of one tap (Mechrez et al., "The Contextual Loss for Image Transformation with Non-Aligned Data", ECCV
+    2018) as torch operations in the tensors' dtype and on their device: the definition ContextualLoss implements.  x_feats
+    (features of the output) and y_feats (of the target, a constant) [B,C,h,w], N = h w; i runs over positions of x, j of y.
+        mu[b,c] = mean_p y[b,c,p] (per sample);  xn = (x - mu) / max(|x - mu|_2, 1e-12) per position, yn the same from y;
+        d[b,i,j] = 1 - <xn[b,:,i], yn[b,:,j]>;  m[b,i] = min_j d at jmin[b,i] (the lowest j on ties);
+        w = exp((1 - d / (m + 1e-5)) / band_width);  cx = w / sum_j w;
+        CX[b] = mean_j max_i cx[b,i,j] (the maximum at imax[b,j], the lowest i on ties);  loss = mean_b -log(CX[b] + 1e-5).
+    The gradient reaches x_feats only: through the selected element of each column, that row's normaliser, the row minimum at jmin,
+    the normalisation and the centring.  jmin [B,N] / imax [B,N] (integer tensors): given selections in place of the computed ones
+    (the values, and so the gradient, route through them).  parts: -> (loss, dict(jmin, imax, CX [B], d [B,N,N], cx [B,N,N]))."""
+    if x_feats.dim() != 4 or x_feats.shape != y_feats.shape:
+        raise ValueError(f'contextual_loss_torch: two [B,C,h,w] feature maps of one shape expected, got {tuple(x_feats.shape)} and '
+                         f'{tuple(y_feats.shape)}')
+    if not (isinstance(band_width, (int, float)) and not isinstance(band_width, bool) and 0.0 < band_width < float('inf')):
+        raise ValueError(f'contextual_loss_torch: band_width={band_width!r} is not a finite number > 0')
+    b, c = x_feats.shape[:2]
+    x, y = x_feats.reshape(b, c, -1), y_feats.detach().reshape(b, c, -1)
+    if x.shape[2] < 2:
+        raise ValueError(f'contextual_loss_torch: at least 2 positions expected, got {tuple(x_feats.shape)}')
+    mu = y.mean(2, keepdim=True)
+    xc, yc = x - mu, y - mu
+    xn = xc / xc.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    yn = yc / yc.norm(dim=1, keepdim=True).clamp_min(1e-12)
+    d = 1.0 - torch.bmm(xn.transpose(1, 2), yn)                                # [B, i, j]
+    if jmin is None:
+        jmin = _lowest_index_of(d == d.amin(2, keepdim=True), 2)
+    m = d.gather(2, jmin.long().unsqueeze(2))                                  # [B, i, 1]
+    w = torch.exp((1.0 - d / (m + 1e-5)) / band_width)
+    cx = w / w.sum(2, keepdim=True)
+    if imax is None:
+        imax = _lowest_index_of(cx == cx.amax(1, keepdim=True), 1)
+    cx_b = cx.gather(1, imax.long().unsqueeze(1)).squeeze(1).mean(1)           # [B]
+    loss = (-torch.log(cx_b + 1e-5)).mean()
+    if parts:
+        return loss, dict(jmin=jmin, imax=imax, CX=cx_b.detach(), d=d.detach(), cx=cx.detach())
+    return loss
+
+
+@LOSS_REGISTRY.register()
+class ContextualLoss(nn.Module):
+    """loss_weight * sum_k layer_weights[k] * contextual_loss(VGG_k(x), VGG_k(gt)) over the named VGG taps in network order: the
+    contextual loss of Mechrez et al. (ECCV 2018) with the cosine distance, the non-local term for targets that are not registered
+    with the output to the pixel (contextual_loss_torch spells one tap out; the feature means are taken per sample, so a sample's
+    loss and gradient are those it would get alone).  gt is a constant (detached); the gradient reaches x, once.  The VGG handling is
+    PerceptualLoss's (taps are the named layers, conv taps before their ReLU; norm_img: (x + 1) * 0.5 on both images first).
+
+    Everything runs on the VGG node of the training engine (archs/nhwc_train.py: _VggContextual) and the kernels of
+    csrc/contextual.hip: the all-pairs similarity and the gradient product on the f32 MFMA, fixed summation orders (the same bits
+    from call to call).  A tap may have at most hip.CX_MAX_N positions (relu3 / conv3 taps of 256^2 images).
+
+    Refused: batch-normalised VGGs, CPU tensors, non-fp32 tensors on the GPU, a tap over the bound (NotImplementedError); inputs that
+    are not [B,3,H,W], differing shapes, a band_width that is not a finite number > 0, empty layer_weights (ValueError)."""
+
+    def __init__(self, layer_weights, vgg_type='vgg19', use_input_norm=True, norm_img=False, band_width=0.5, loss_weight=1.0):
+        super().__init__()
+        if not isinstance(layer_weights, dict) or not layer_weights:
+            raise ValueError(f'ContextualLoss: layer_weights={layer_weights!r}; a non-empty dict of VGG layer names and weights')
+        if isinstance(band_width, bool) or not isinstance(band_width, (int, float)) or not (0.0 < band_width < float('inf')):
+            raise ValueError(f'ContextualLoss: band_width={band_width!r} is not a finite number > 0')
+        if 'bn' in vgg_type:
+            raise NotImplementedError(f'ContextualLoss: vgg_type {vgg_type} (batch-normalised VGGs have no kernel here)')
+        self.layer_weights, self.norm_img = layer_weights, norm_img
+        self.band_width, self.loss_weight = float(band_width), loss_weight
+        self.vgg = VGGFeatureExtractor(layer_name_list=list(layer_weights.keys()), vgg_type=vgg_type, use_input_norm=use_input_norm)
+        self._plan = None
+
+    def forward(self, x, gt):
+        from ..archs import nhwc_train
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f'ContextualLoss: [B,3,H,W] images expected, got {tuple(x.shape)}')
+        if gt.shape != x.shape:
+            raise ValueError(f'ContextualLoss: x {tuple(x.shape)} and gt {tuple(gt.shape)} differ')
+        if not (x.is_cuda and gt.is_cuda):
+            raise NotImplementedError('ContextualLoss: mrefsr_amd has no CPU path (HIP kernels only; contextual_loss_torch is the '
+                                      'definition of one tap in torch)')
+        if not (x.dtype == gt.dtype == torch.float32):
+            raise NotImplementedError(f'ContextualLoss: {x.dtype} / {gt.dtype} images; fp32 only on the GPU')
+        if self._plan is None:
+            self._plan = nhwc_train.ContextualLossPlan(self.vgg.vgg_net, self.layer_weights, self.band_width, self.loss_weight,
+                                                       self.norm_img)
+        return nhwc_train.contextual(self.vgg, x, gt.detach(), self._plan)[0]
 
 
 def _ldl_residuals(gt, out, ema):

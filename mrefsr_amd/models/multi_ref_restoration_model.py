@@ -14,7 +14,9 @@ on the kernels of csrc/texture.hip: _texture_targets), ssim_opt (SSIMLoss: 1 - S
 validation reports, on the kernels of csrc/ssim_loss.hip; no counterpart in the reference), ldl_opt (LDLLoss: the artifact loss of
 LDL between the output, the GT and the output of net_g_ema on the same input, basicsr/models/realesrgan_model.py:211-226, on the
 kernels of csrc/ldl_loss.hip; needs train.ema_decay: _ema_pass), freq_opt (FFTLoss or FocalFrequencyLoss: a distance between the
-spectra of the output and the GT, on the dense-DFT kernels of csrc/freq_loss.hip; no counterpart in the reference), and the adversarial term: network_d
+spectra of the output and the GT, on the dense-DFT kernels of csrc/freq_loss.hip; no counterpart in the reference), contextual_opt
+(ContextualLoss: the non-local contextual loss between the VGG features of the output and of the GT, on the kernels of
+csrc/contextual.hip; no counterpart in the reference), and the adversarial term: network_d
 (ImageDiscriminator, VGGStyleDiscriminator, UNetDiscriminatorSN or StyleGAN2Discriminator, on the kernels of csrc/disc.hip, disc_vgg.hip,
 disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
@@ -226,7 +228,7 @@ class MultiRefRestorationModel:
         return data
 
     def _gt_for(self, which):
-        """the GT of a loss family: 'l1' (pixel, SSIM, LDL, frequency), 'percep' (perceptual, style) or 'gan' (D's real images)"""
+        """the GT of a loss family: 'l1' (pixel, SSIM, LDL, frequency), 'percep' (perceptual, style, contextual) or 'gan' (D's real images)"""
         return self.gt_usm if self._gt_usm[which + '_gt_usm'] and self.gt_usm is not None else self.gt
 
     # ------------------------------------------------------------------ the parameter update: train.hip_adam, train.ema_decay
@@ -316,6 +318,7 @@ class MultiRefRestorationModel:
     cri_texture = None   # TextureLoss of train.texture_opt (init_training_settings)
     cri_ssim = None      # SSIMLoss of train.ssim_opt
     cri_freq = None      # FFTLoss / FocalFrequencyLoss of train.freq_opt
+    cri_contextual = None   # ContextualLoss of train.contextual_opt
     cri_ldl = None       # LDLLoss of train.ldl_opt
     output_ema = None    # net_g_ema's output on this step's input (steps that evaluate the LDL term)
 
@@ -422,6 +425,8 @@ class MultiRefRestorationModel:
         self.cri_ssim = losses.SSIMLoss(**train_opt['ssim_opt']).to(self.device) if train_opt.get('ssim_opt') else None
         self.cri_ldl = self._build_ldl(train_opt)
         self.cri_freq = self._build_freq(train_opt)
+        # ContextualLoss: train.contextual_opt holds its constructor's keys (layer_weights, vgg_type, use_input_norm, norm_img, band_width, loss_weight)
+        self.cri_contextual = losses.ContextualLoss(**train_opt['contextual_opt']).to(self.device) if train_opt.get('contextual_opt') else None
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
         self.net_d_init_steps = train_opt.get('net_d_init_steps', 0)
@@ -764,6 +769,10 @@ class MultiRefRestorationModel:
                 l_g_texture = self.cri_texture(self.output, *self._texture_targets())
                 l_g_total = l_g_total + l_g_texture
                 self.log_dict['l_g_texture'] = l_g_texture.detach()
+            if self.cri_contextual is not None:
+                l_g_contextual = self.cri_contextual(self.output, self._gt_for('percep'))
+                l_g_total = l_g_total + l_g_contextual
+                self.log_dict['l_g_contextual'] = l_g_contextual.detach()
             if self.cri_ssim is not None:
                 l_g_ssim = self.cri_ssim(self.output, self._gt_for('l1'))
                 l_g_total = l_g_total + l_g_ssim
@@ -796,12 +805,12 @@ class MultiRefRestorationModel:
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
         a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
         not with a perceptual, style or texture loss (their VGG node is not captured), an SSIM loss, an LDL loss (its EMA pass is not
-        captured), a frequency-domain loss, nor with a discriminator."""
+        captured), a frequency-domain loss, a contextual loss (a VGG node again), nor with a discriminator."""
         train_opt = self.opt.get('train') or {}
         return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
             and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt') \
             and not train_opt.get('texture_opt') and not train_opt.get('ssim_opt') and not train_opt.get('ldl_opt') \
-            and not train_opt.get('freq_opt') \
+            and not train_opt.get('freq_opt') and not train_opt.get('contextual_opt') \
             and not self.opt.get('network_d')
 
     _TRAIN_INPUTS = ('img_in_lq', 'match_img_in', 'img_ref_stack', 'gt')
