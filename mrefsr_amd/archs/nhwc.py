@@ -104,14 +104,41 @@ def is_nhwc_view(x):
     return x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()
 
 
-AMAX_ATTR = '_mrefsr_amax'   # python attribute of an engine-produced tensor: the device word holding max |tensor| (hip.amax_slot)
+AMAX_ATTR = '_mrefsr_amax'   # python attribute of a tensor: the _Amax handle of the device word holding max |tensor|
+
+
+class _Amax:
+    """max |t| of a tensor t as a one-element device tensor ``word``, and what says whether it still is that: the ``_version`` t
+    had when the word was attached (an in-place op since then makes the word another value's maximum) and, for a slot of
+    hip's ring, the generation its half was issued in (hip.amax_pool_reset() and the ring's re-entry into the half give the slot
+    to another launch).  A measured word (``ring`` None) is a tensor of its own: it has no generation, only a version.  As for
+    packed weights, a write through ``t.data`` moves no version and is not seen."""
+    __slots__ = ('word', 'ring', 'gen', 'version')
+
+
+def attach_amax(t, word, ring=None):
+    """``word`` holds max |t| (or an upper bound within 2x) of t as it is now; ``ring``: the hip.amax_ring() the word is a slot of"""
+    h = _Amax()
+    h.word, h.ring, h.gen, h.version = word, ring, 0 if ring is None else ring.generation(word), t._version
+    setattr(t, AMAX_ATTR, h)
+    return t
+
+
+def _live_amax(t):
+    h = getattr(t, AMAX_ATTR, None)
+    if h is not None and h.version == t._version and (h.ring is None or h.ring.generation(h.word) == h.gen):
+        return h
+
+
+def amax_word(t):
+    """the word attached to t while it is live, else None"""
+    h = _live_amax(t)
+    return None if h is None else h.word
 
 
 def _keep_amax(src, dst):
-    a = getattr(src, AMAX_ATTR, None)
-    if a is not None:
-        setattr(dst, AMAX_ATTR, a)
-    return dst
+    h = _live_amax(src)
+    return dst if h is None else attach_amax(dst, h.word, h.ring)
 
 
 def to_nhwc(x):
@@ -139,11 +166,11 @@ def crop(x, h0, w0):
     if torch.is_grad_enabled() and x.requires_grad:
         from . import nhwc_train
         return nhwc_train.crop(x, h0, w0)
-    slot = hip.amax_slot(x.device) if WINO_INSCALE else None
-    y = hip.crop_nhwc(x, h0, w0, out_amax=slot)
-    if slot is not None:
-        setattr(y, AMAX_ATTR, slot)
-    return y
+    if not WINO_INSCALE:
+        return hip.crop_nhwc(x, h0, w0)
+    ring = hip.amax_ring(x.device)
+    slot = ring.slot()
+    return attach_amax(hip.crop_nhwc(x, h0, w0, out_amax=slot), slot, ring)
 
 
 def image_to_nhwc4(img, mean=None, std=None, range_norm=False):
@@ -203,14 +230,13 @@ def conv(mod, x1, x2=None, slope=None, prelu=None, pre=None, residual=None, epil
     b = mod.bias.detach() if (bias and mod.bias is not None) else None
     # every fp32-equivalent launch measures max |out| in its epilogue (a zeroed device word of hip's pool); the Winograd launch that
     # reads the tensor takes that word as its input scale
-    slot = hip.amax_slot(x1.device) if (amax and terms in (16, 17) and x1.dtype == torch.float32 and WINO_INSCALE) else None
+    ring = hip.amax_ring(x1.device) if (amax and terms in (16, 17) and x1.dtype == torch.float32 and WINO_INSCALE) else None
+    slot = None if ring is None else ring.slot()
     y = hip.conv_nhwc(x1, packed, b, mod.out_channels, mod.kernel_size[0], x2=x2, pre=pre, residual=residual,
                       act=slope is not None or prelu is not None, slope=0.0 if slope is None else slope,
                       slope_ptr=slope_ptr, epilogue=epilogue, out=out,
                       in_amax=wino_in_amax(x1, x2) if (terms == 17 and WINO_INSCALE) else None, out_amax=slot)
-    if slot is not None:
-        setattr(y, AMAX_ATTR, slot)
-    return y
+    return y if slot is None else attach_amax(y, slot, ring)
 
 
 # Input scale of the Winograd launches.  The transform B^T d B is split into fp16 high + low terms AFTER it is formed; the low term
@@ -218,26 +244,24 @@ def conv(mod, x1, x2=None, slope=None, prelu=None, pre=None, residual=None, epil
 # The kernels therefore multiply their input by the power of two that brings max |x| into [2^11, 2^12) and the result by its inverse
 # (csrc/conv_wino.hip: in_amax) -- exact, and the low term is a normal number down to 2^-14 of the maximum.
 # Round 6: max |x| is the CURRENT tensor's, measured by the kernel that produced it (every convolution and DCN launch of the engine
-# writes max |out| into a device word in its epilogue -- hip.amax_slot -- and the word travels with the tensor as a python
-# attribute): no reduction launches, no calibration that could go stale (round 5 measured once per layer on the first batch).  A
-# tensor that did not come out of the engine (a caller's own tensor, the result of a torch op) is measured here, per call; the
-# count of such measurements is AMAX_MEASURED (0 on the benchmark path: tests/test_archs_gpu.py).  MREFSR_WINO_INSCALE=0: no scaling.
+# writes max |out| into a device word in its epilogue -- a slot of hip's ring -- and the word travels with the tensor in an _Amax
+# handle, live for that ring generation and that tensor version): no reduction launches, no calibration that could go stale
+# (round 5 measured once per layer on the first batch).  A tensor without a live word (a caller's own tensor, the result of a torch
+# op, a tensor kept across passes or modified in place) is measured here, once per version; the count of such measurements is
+# AMAX_MEASURED (0 on the benchmark path: tests/test_archs_gpu.py).  MREFSR_WINO_INSCALE=0: no scaling.
 WINO_INSCALE = os.environ.get('MREFSR_WINO_INSCALE', '1') != '0'
 AMAX_MEASURED = [0]
 
 
-def reset_wino_calibration():
-    """(kept for callers of round 5's interface: there is no calibration state any more)"""
-
-
 def amax_of(x):
-    """the device word with max |x|: the producer's, or measured now (two torch launches) for a tensor the engine did not produce"""
-    a = getattr(x, AMAX_ATTR, None)
+    """the device word with max |x|: the live one attached to x, or measured now (two torch launches) and attached for x's
+    current version -- a tensor read by several Winograd launches is measured once"""
+    a = amax_word(x)
     if a is None:
         AMAX_MEASURED[0] += 1
         a = x.detach().abs().amax().float().reshape(1)
         try:
-            setattr(x, AMAX_ATTR, a)
+            attach_amax(x, a)
         except AttributeError:
             pass
     return a
@@ -252,13 +276,9 @@ def wino_in_amax(x1, x2=None):
 def add_(h, x):
     """h += x in place (the skip connections around the trunks, ref_mrapa_restoration_arch.py:228-258) with the bound
     max |h + x| <= max |h| + max |x| as the sum's maximum (a 1-element add: the scale only has to be an upper bound within 2x)"""
-    ah, ax = getattr(h, AMAX_ATTR, None), getattr(x, AMAX_ATTR, None)
-    h.add_(x)
-    if ah is not None and ax is not None:
-        setattr(h, AMAX_ATTR, ah + ax)
-    elif hasattr(h, AMAX_ATTR):
-        delattr(h, AMAX_ATTR)
-    return h
+    ah, ax = amax_word(h), amax_word(x)
+    h.add_(x)   # (moves h's version: a word left on h is dead from here on)
+    return h if ah is None or ax is None else attach_amax(h, ah + ax)
 
 
 def res_chain(blocks, x):

@@ -42,13 +42,16 @@ unfused PReLU in conv(); and for the DCN, as for shapes its fused kernels refuse
 Gradients match the reference's own optimisation step to the fingerprints of tests/golden/e2e_c2.npz
 (tests/test_configs_gpu.py).  ``ENABLED`` is flipped by tests/ only (generic NCHW autograd forms as the comparison).
 """
+import collections
 import os
+import weakref
 
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import hip
+from ..param_cache import Packed, param_stamp
 
 # MIOpen's channels-last kernels for the generic weight gradients of _wgrad (read once by torch, at its first MIOpen convolution)
 os.environ.setdefault('PYTORCH_MIOPEN_SUGGEST_NHWC', '1')
@@ -61,8 +64,8 @@ TERMS = 6
 # launch per step, no synchronisation) raises the library's range flag if a weight has grown past the cached headroom (4x),
 # upon which the model re-runs the step on the range-free kernels and the scales are taken afresh.
 FWD_TERMS = int(os.environ.get('MREFSR_TRAIN_FWD_TERMS', '16'))
-_scales = {}          # (data_ptr, numel) of a weight -> (weakref, scale, limit = 60000 / scale)
-_scale_epoch = [0]
+REFRESH = 50          # steps between full refreshes of the cached scales (one readback of all amaxes)
+_Scale = collections.namedtuple('_Scale', 'ref scale limit')
 
 
 def _scale_of(amax):
@@ -74,59 +77,62 @@ def _scale_of(amax):
     return 2.0 ** (13 - math.floor(math.log2(amax)))
 
 
-def _wscale(weight):
-    import weakref
-    key = (weight.data_ptr(), weight.numel())   # the parameter's storage: the same for every Python handle autograd hands back
-    hit = _scales.get(key)
-    if hit is not None and hit[0]() is not None:
-        return hit[1]
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError('nhwc_train: the fp16 weight scale of a parameter is not cached yet (first use, or its holder was freed) and '
-                           'deriving it needs a readback, which a hipGraph capture cannot contain: run one eager step first')
-    s = _scale_of(float(weight.detach().abs().max().item()))
-    _scales[key] = (weakref.ref(weight), s, 60000.0 / s if s else float('inf'))
-    _scale_epoch[0] += 1
-    return s
+def _scale_entry(weight, amax):
+    s = _scale_of(amax)
+    return _Scale(weakref.ref(weight), s, 60000.0 / s if s else float('inf'))
 
 
-def reset_scales():
-    _scales.clear()
-    _scale_epoch[0] += 1
+class _WeightScales:
+    """The scale of every training weight, its limit 60000 / scale and the cadence of their refresh, by the parameter's storage (the
+    same for every handle autograd hands back).  Of param_stamp() an entry asks only ``alive``: a scale outlives versions on purpose."""
+
+    def __init__(self):
+        self.entries, self.epoch, self.checks, self.lim, self.lim_key = {}, 0, 0, None, None
+
+    def has(self, weight):
+        return (weight.data_ptr(), weight.numel()) in self.entries
+
+    def get(self, weight):
+        key = (weight.data_ptr(), weight.numel())
+        hit = self.entries.get(key)
+        if hit is not None and param_stamp(hit.ref()).alive:
+            return hit.scale
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('nhwc_train: the fp16 weight scale of a parameter is not cached yet (first use, or its holder was freed) and '
+                               'deriving it needs a readback, which a hipGraph capture cannot contain: run one eager step first')
+        hit = self.entries[key] = _scale_entry(weight, float(weight.detach().abs().max().item()))
+        self.epoch += 1
+        return hit.scale
+
+    def reset(self):
+        self.entries.clear()
+        self.epoch += 1
+
+    def check(self):
+        """once per training step, before the forward pass: every cached scale still leaves max|w| * scale inside the fp16 range, else the
+        range flag of hip.conv_range_tripped() is raised (device side: no synchronisation).  Every REFRESH-th call: all scales anew."""
+        live = [(k, w) for k, w in ((k, e.ref()) for k, e in self.entries.items()) if param_stamp(w).alive]
+        self.entries = {k: self.entries[k] for k, _ in live}
+        if not live:
+            return
+        amax = torch.stack(torch._foreach_norm([w.detach() for _, w in live], float('inf')))
+        self.checks += 1
+        if self.checks % REFRESH == 0:
+            fresh = {k: _scale_entry(w, a) for (k, w), a in zip(live, amax.tolist())}
+            self.epoch += any(e.scale != self.entries[k].scale for k, e in fresh.items())
+            self.entries = fresh
+            return
+        if self.lim_key != (self.epoch, len(live)):
+            self.lim_key, self.lim = (self.epoch, len(live)), torch.tensor([self.entries[k].limit for k, _ in live], device=amax.device)
+        hip._range_flag(amax.device).bitwise_or_((amax > self.lim).any().to(torch.int32))
+
+
+_scales = _WeightScales()
+_wscale, reset_scales, check_scales = _scales.get, _scales.reset, _scales.check
 
 
 def scale_epoch():
-    return _scale_epoch[0]
-
-
-_lim_cache = {}
-REFRESH = 50          # steps between full refreshes of the cached scales (one readback of all amaxes)
-_checks = [0]
-
-
-def check_scales():
-    """once per training step, before the forward pass: every cached weight scale still leaves max|w| * scale inside the fp16
-    range, else the range flag of hip.conv_range_tripped() is raised (device side: no synchronisation).  Every REFRESH-th
-    call re-derives all scales from the current weights (one readback)."""
-    import weakref
-    live = [(k, v[0]()) for k, v in _scales.items() if v[0]() is not None]
-    for k in [k for k, v in _scales.items() if v[0]() is None]:
-        del _scales[k]
-    if not live:
-        return
-    amax = torch.stack(torch._foreach_norm([w.detach() for _, w in live], float('inf')))
-    _checks[0] += 1
-    if _checks[0] % REFRESH == 0:
-        changed = False
-        for (k, w), a in zip(live, amax.tolist()):
-            s = _scale_of(a)
-            changed |= s != _scales[k][1]
-            _scales[k] = (weakref.ref(w), s, 60000.0 / s if s else float('inf'))
-        if changed:
-            _scale_epoch[0] += 1
-        return
-    if _lim_cache.get('key') != (_scale_epoch[0], len(live)):
-        _lim_cache.update(key=(_scale_epoch[0], len(live)), lim=torch.tensor([_scales[k][2] for k, _ in live], device=amax.device))
-    hip._range_flag(amax.device).bitwise_or_((amax > _lim_cache['lim']).any().to(torch.int32))
+    return _scales.epoch
 
 
 def _fwd_terms():
@@ -139,83 +145,100 @@ def _fwd_terms():
 BWD_TERMS = int(os.environ.get('MREFSR_TRAIN_BWD_TERMS', '16'))
 
 
-# Packed copies of the training weights.  A parameter changes once per step (optimizer_g.step(), ref
-# multi_ref_restoration_model.py:277) and is used by two launches (forward operator, input-gradient operator): 346 packing
-# launches of ~4 us per step.  The copies live in persistent buffers instead, and ONE multi-tensor launch
-# (mrefsr_conv_pack_weights_multi_f32, a job table in device memory) refreshes all of them: at begin_step() -- called by the
-# model at the top of every optimisation step, also inside the hipGraph capture -- or at the first lookup that finds a copy
-# older than its parameter (``_version``; callers that drive net_g without the model).  A new (weight, slice, arithmetic)
-# is packed by itself once and joins the table of the following refresh.
-_packs = {}        # device index -> {'entries': {key: [weakref, PackedWeight, stamp, job, last refresh it was used in]}, 'table', 'rows', 'dirty', 'refresh'}
 _PACK_KEEP = 4     # refreshes an unused entry survives (validation passes, a second network)
+_PackKey = collections.namedtuple('_PackKey', 'what wscale')   # what: (data_ptr, numel, shape, slice, terms, operator)
 
 
-def _pack_state(device):
-    st = _packs.get(device.index)
-    if st is None:
-        st = _packs[device.index] = dict(entries={}, table=None, rows=[], dirty=True, refresh=0)
-    return st
+class _PackTable:
+    """Packed copies of one device's training weights.  A parameter changes once per step (optimizer_g.step(), ref
+    multi_ref_restoration_model.py:277) and is used by two launches (forward operator, input-gradient operator): 346 packing launches
+    of ~4 us per step.  The copies live in persistent buffers instead (entries: _PackKey -> Packed), and ONE multi-tensor launch
+    (mrefsr_conv_pack_weights_multi_f32, a job table in device memory) refreshes all of them: at begin_step() -- called by the model
+    at the top of every optimisation step, also inside the hipGraph capture -- or at the first lookup that finds a copy older than
+    its parameter (callers that drive net_g without the model).  A new (weight, slice, arithmetic) is packed alone once and joins the
+    next refresh's table.  Keyed by the parameter's STORAGE, not by id() as hip's inference cache: autograd hands back new Python
+    handles.  Stamps carry the capture epoch.  ``frozen``: copies of weights that are never stepped (the perceptual VGG): never
+    in the job table, no _PACK_KEEP, re-made alone when the stamp moves (load_state_dict)."""
+
+    def __init__(self, device):
+        self.device, self.frozen = device, {}
+        self.reset()
+
+    def reset(self):
+        self.entries, self.table, self.rows, self.dirty, self.refreshes = {}, None, [], True, 0
+
+    def refresh(self):
+        """repack every live entry in one launch; False when that takes a new job table (an upload) inside a hipGraph capture"""
+        cap, epoch = hip.capture_epoch()
+        # dead: the parameter is gone, its storage was replaced (`p.data = ...`, `.to()`: the job row still holds the old address),
+        # or nothing has asked for the copy for _PACK_KEEP refreshes
+        now = {k: param_stamp(e.ref()) for k, e in self.entries.items()}
+        dead = [k for k, e in self.entries.items() if not now[k].alive or now[k].ptr != e.stamp.ptr or self.refreshes - e.last_used > _PACK_KEEP]
+        if (dead or self.dirty) and cap:
+            return False
+        for k in dead:
+            del self.entries[k]
+        self.refreshes += 1
+        if dead or self.dirty:
+            self.rows = list(self.entries.values())
+            self.table = hip.conv_pack_table([e.job for e in self.rows], self.device) if self.rows else None
+            self.dirty = False
+        if self.rows:
+            hip.conv_pack_multi(self.table, len(self.rows))
+            for e in self.rows:
+                e.stamp = param_stamp(e.ref(), epoch)
+        return True
+
+    def get(self, weight, cin_slice, terms, dgrad=False, wscale=1.0):
+        """hip.conv_pack_view(weight, cin_slice, terms, dgrad, wscale) from the step's refreshed copies"""
+        cap, epoch = hip.capture_epoch()
+        what = (weight.data_ptr(), weight.numel(), tuple(weight.shape), cin_slice, terms, dgrad)
+        e = self.entries.get((what, wscale))
+        now = None if e is None else param_stamp(e.ref(), epoch)
+        if now is not None and now.alive:
+            e.last_used = self.refreshes
+            if e.stamp != now and not (self.refresh() and e.stamp == now):
+                hip.conv_pack_one(e.job)   # (table being rebuilt under capture, or the entry is not in the table yet): this copy alone
+                e.stamp = now
+            return e.packed
+        pw, job = hip.conv_pack_plan(weight, cin_slice, terms, dgrad, wscale)
+        hip.conv_pack_one(job)
+        if not cap:   # copies of the same (weight, slice, arithmetic, operator) at a superseded scale: nobody reads them again, and a
+            for k in [k for k in self.entries if k.what == what and k.wscale != wscale]:   # repack could raise the range flag for them
+                del self.entries[k]
+        self.entries[_PackKey(what, wscale)] = Packed(weight, pw, param_stamp(weight, epoch), job, self.refreshes)
+        self.dirty = True
+        return pw
+
+    def get_frozen(self, weight, cin_slice, terms, dgrad, wscale):
+        key = (weight.data_ptr(), weight.numel(), cin_slice, terms, dgrad, wscale)
+        e = self.frozen.get(key)
+        if e is None or param_stamp(e.ref()) != e.stamp:
+            for k in [k for k, o in self.frozen.items() if not param_stamp(o.ref()).alive]:
+                del self.frozen[k]
+            pw = hip.conv_pack_view(weight.detach(), cin_slice, terms, dgrad=dgrad, wscale=wscale)
+            e = self.frozen[key] = Packed(weight, pw, param_stamp(weight))
+        return e.packed
 
 
-def _refresh_packs(device):
-    """repack every live entry of ``device`` in one launch; False when the job table would have to be rebuilt (an upload)
-    inside a hipGraph capture"""
-    st = _pack_state(device)
-    cap, epoch = hip.capture_epoch()
-    ent = st['entries']
-    # dead: the parameter is gone, its storage was replaced (`p.data = ...`, `.to()`: the job row still holds the old address),
-    # or nothing has asked for the copy for _PACK_KEEP refreshes
-    dead = [k for k, e in ent.items() if e[0]() is None or e[0]().data_ptr() != k[0] or st['refresh'] - e[4] > _PACK_KEEP]
-    if (dead or st['dirty']) and cap:
-        return False
-    for k in dead:
-        del ent[k]
-    st['refresh'] += 1
-    if dead or st['dirty']:
-        st['rows'] = list(ent.values())
-        st['table'] = hip.conv_pack_table([e[3] for e in st['rows']], device) if st['rows'] else None
-        st['dirty'] = False
-    if st['rows']:
-        hip.conv_pack_multi(st['table'], len(st['rows']))
-        for e in st['rows']:
-            e[2] = (e[0]()._version, epoch)
-    return True
+_packs = {}        # device index -> _PackTable
+
+
+def _packed(weight, cin_slice, terms, dgrad=False, wscale=1.0, frozen=False):
+    t = _packs.get(weight.device.index) or _packs.setdefault(weight.device.index, _PackTable(weight.device))
+    return (t.get_frozen if frozen else t.get)(weight, cin_slice, terms, dgrad, wscale)
 
 
 def begin_step(device=None):
     """top of an optimisation step: refresh every packed weight copy (one launch per device that has any)"""
     for idx in list(_packs) if device is None else [torch.device(device).index]:
-        if idx in _packs and _packs[idx]['entries']:
-            _refresh_packs(torch.device('cuda', idx))
-
-
-def _packed(weight, cin_slice, terms, dgrad=False, wscale=1.0):
-    """hip.conv_pack_view(weight, cin_slice, terms, dgrad, wscale) from the step's refreshed copies"""
-    st = _pack_state(weight.device)
-    cap, epoch = hip.capture_epoch()
-    key = (weight.data_ptr(), weight.numel(), tuple(weight.shape), cin_slice, terms, dgrad, wscale)
-    e = st['entries'].get(key)
-    stamp = (weight._version, epoch)
-    if e is not None and e[0]() is not None:
-        e[4] = st['refresh']
-        if e[2] != stamp:
-            if not (_refresh_packs(weight.device) and e[2] == stamp):
-                hip.conv_pack_one(e[3])   # (table being rebuilt under capture, or the entry is not in the table yet): this copy alone
-                e[2] = stamp
-        return e[1]
-    import weakref
-    pw, job = hip.conv_pack_plan(weight, cin_slice, terms, dgrad, wscale)
-    hip.conv_pack_one(job)
-    if not cap:   # copies of the same (weight, slice, arithmetic, operator) at a superseded scale: nobody reads them again, and a
-        for k in [k for k in st['entries'] if k[:6] == key[:6] and k[6] != wscale]:   # repack could raise the range flag for them
-            del st['entries'][k]
-    st['entries'][key] = [weakref.ref(weight), pw, stamp, job, st['refresh']]
-    st['dirty'] = True
-    return pw
+        if idx in _packs and _packs[idx].entries:
+            _packs[idx].refresh()
 
 
 def reset_packs():
-    _packs.clear()
+    for t in _packs.values():
+        t.reset()
 
 
 def capture_state():
@@ -224,33 +247,32 @@ def capture_state():
     compares the addresses before every replay (a table rebuilt by an eager pass in between, a parameter whose storage was
     replaced: the graph would read freed memory)."""
     objs, ptrs = [], []
-    for idx in sorted(_packs):
-        st = _packs[idx]
-        objs.append((st['table'], list(st['rows'])))
-        ptrs.append(st['table'].data_ptr() if st['table'] is not None else 0)
-        for e in st['rows']:
-            w = e[0]()
-            ptrs.append((e[1].data.data_ptr(), w.data_ptr() if w is not None else -1))
+    for _, t in sorted(_packs.items()):
+        objs.append((t.table, list(t.rows)))
+        ptrs.append(t.table.data_ptr() if t.table is not None else 0)
+        for e in t.rows:
+            now = param_stamp(e.ref())
+            ptrs.append((e.packed.data.data_ptr(), now.ptr if now.alive else -1))
     ptrs.append(hip.capture_ptrs())   # the capture's cached scratch, ticket words and zero chunks: a regrown one has moved
     return objs, tuple(ptrs)
 
 
+def _pack(weight, cin_slice, dgrad=False, frozen=False):
+    """(packed forward / input-gradient operator, terms): the fp16 two-term split with the weight's cached scale (FWD_TERMS /
+    BWD_TERMS 16, outside hip.range_free(), a weight that has a scale), else the range-free split"""
+    want16 = (BWD_TERMS == 16 and not hip.is_range_free()) if dgrad else _fwd_terms() == 16
+    ws = _wscale(weight) if want16 else None
+    if ws is not None:
+        return _packed(weight, cin_slice, 16, dgrad, ws, frozen), 16
+    return _packed(weight, cin_slice, TERMS, dgrad, frozen=frozen), TERMS
+
+
 def _fwd_pack(weight, cin_slice):
-    """(packed forward operator, terms): fp16 two-term with the weight's cached scale, else the range-free split"""
-    if _fwd_terms() == 16:
-        ws = _wscale(weight)
-        if ws is not None:
-            return _packed(weight, cin_slice, 16, wscale=ws), 16
-    return _packed(weight, cin_slice, TERMS), TERMS
+    return _pack(weight, cin_slice)
 
 
 def _bwd_pack(weight, cin_slice):
-    """(packed dgrad operator, terms): fp16 two-term with the weight's cached scale, else the range-free split"""
-    if BWD_TERMS == 16 and not hip.is_range_free():
-        ws = _wscale(weight)
-        if ws is not None:
-            return _packed(weight, cin_slice, 16, dgrad=True, wscale=ws), 16
-    return _packed(weight, cin_slice, TERMS, dgrad=True), TERMS
+    return _pack(weight, cin_slice, dgrad=True)
 
 
 def _unshuffle(t):
@@ -598,35 +620,13 @@ class _Crop(Function):
 
 
 # ---- perceptual / style loss (PerceptualLoss, losses.py:141-238 of the reference model's loss module) ----------------------------
-# Packed copies of the frozen VGG weights: the perceptual VGG is never stepped, so its copies stay out of the per-step multi-tensor
-# refresh (begin_step) and are re-made only when a parameter's version moves (load_state_dict).
-_frozen = {}
 POOL_PLANE = os.environ.get('MREFSR_PERCEP_POOL_PLANE', '0') == '1'   # 1: the forward stores the pool's arg-max plane
 KEEP_TAPS = None   # tests/ set a list: every _VggLoss forward appends its [2B,h,w,c] tap features (sign decisions against fp64)
 
 
-def _frozen_pack(weight, cin_slice, terms, dgrad, wscale):
-    import weakref
-    key = (weight.data_ptr(), weight.numel(), cin_slice, terms, dgrad, wscale)
-    hit = _frozen.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version:
-        return hit[2]
-    for k in [k for k, v in _frozen.items() if v[0]() is None]:
-        del _frozen[k]
-    pw = hip.conv_pack_view(weight.detach(), cin_slice, terms, dgrad=dgrad, wscale=wscale)
-    _frozen[key] = (weakref.ref(weight), weight._version, pw)
-    return pw
-
-
 def _vgg_pack(weight, cin_slice, dgrad):
-    """(packed operator, terms) of a frozen VGG convolution: the engine's training arithmetic (forward: FWD_TERMS, input gradient:
-    BWD_TERMS, both with the cached fp16 weight scale; the range-free split inside hip.range_free())"""
-    want16 = (BWD_TERMS == 16 and not hip.is_range_free()) if dgrad else _fwd_terms() == 16
-    if want16:
-        ws = _wscale(weight)
-        if ws is not None:
-            return _frozen_pack(weight, cin_slice, 16, dgrad, ws), 16
-    return _frozen_pack(weight, cin_slice, TERMS, dgrad, 1.0), TERMS
+    """_pack for a frozen VGG convolution: the engine's training arithmetic on copies that stay out of the per-step refresh"""
+    return _pack(weight, cin_slice, dgrad, frozen=True)
 
 
 class VggLossPlan:

@@ -169,12 +169,12 @@ class DynAgg(nn.Module):
         offset, mask = hip.conv_dynagg(feat, hip.packed_weight(com.weight, None, terms), com.bias.detach(), pre_offset.contiguous(),
                                        self.deform_groups, self._offset_abs_sum)
         self._offset_count += offset.numel()
-        slot = hip.amax_slot(x.device) if (x.dtype == torch.float32 and not nhwc.BF16 and nhwc.WINO_INSCALE) else None
+        ring = hip.amax_ring(x.device) if (x.dtype == torch.float32 and not nhwc.BF16 and nhwc.WINO_INSCALE) else None
+        slot = None if ring is None else ring.slot()
         y = hip.dcn_fwd(x, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation, self.groups,
                         self.deform_groups, act_slope, channels_last=True, bf16_arith=nhwc.BF16, out_amax=slot)
-        if slot is not None:   # (max |out| from the kernel's epilogue: the input scale of MRAPAFusion's 3x3 convolutions)
-            setattr(y, nhwc.AMAX_ATTR, slot)
-        return y
+        # (max |out| from the kernel's epilogue: the input scale of MRAPAFusion's 3x3 convolutions)
+        return y if slot is None else nhwc.attach_amax(y, slot, ring)
 
     def nhwc_ok(self):
         return (self.kernel_size == (3, 3) and self.stride == 1 and self.padding == 1 and self.dilation == 1 and self.groups == 1

@@ -79,7 +79,7 @@ class SingleRefDynamicAggregationRestoration(nn.Module):
             swapped = getattr(self, f'{scale}_dyn_agg').forward_nhwc(ref, off, pre_offset[key], act_slope=0.1)
             h = nhwc.conv(getattr(self, f'head_{scale}')[0], x, x2=swapped, slope=0.1)
             h = nhwc.res_chain(getattr(self, f'body_{scale}'), h)
-            h = h + x if h.requires_grad else nhwc.rnd_(h.add_(x))
+            h = h + x if h.requires_grad else nhwc.rnd_(nhwc.add_(h, x))
             if scale == 'large':
                 return nhwc.conv(self.tail_large[2], nhwc.conv(self.tail_large[0], h, slope=0.1))
             x = nhwc.conv(getattr(self, f'tail_{scale}')[0], h, slope=0.1, epilogue=2)

@@ -5,12 +5,14 @@ gets raw device pointers + ``torch.cuda.current_stream().cuda_stream``.  No CPU 
 tensor raises (the reference's native ops raise NotImplementedError on CPU tensors as well,
 basicsr/ops/dcn/deform_conv.py:61-62).
 """
+import contextlib
 import ctypes as C
 import math
 
 import torch
 
 from . import _lib
+from .param_cache import Packed as _Packed, param_stamp   # (the one liveness rule of everything cached per parameter)
 from ._lib import DcnShape
 
 
@@ -771,9 +773,6 @@ def bias_act_res_(x, bias, slope, residual=None, pre=None):
     return x
 
 
-_PACKED = {}  # (id(weight), slice, terms) -> (weakref, version, packed)
-
-
 _range_flags = {}  # device index -> int32[1]: set by conv_nhwc (terms=16) when an activation leaves the fp16 range
 
 
@@ -814,87 +813,12 @@ def conv_range_tripped(reset=True):
     for f in _range_flags.values():
         v = int(f.item())
         if v & _STALE_BIT:
-            _stale_seen[0] = True
+            _packed.stale = True
         if v & 1:
             hit = True
         if v and reset:
             f.zero_()
     return hit
-
-
-# ---- parameters edited behind autograd's back (`.data` writes bump no version): a device-side fingerprint of every parameter
-# whose packed copy is cached, compared once per forward pass; the verdict travels in the range flag's word (no extra readback)
-_STALE_BIT = 2
-_stale_seen = [False]
-_FP = {'rows': {}, 'order': [], 'dirty': True, 'table': None, 'sums': None, 'done': None, 'ref': None, 'wref': {}}
-
-
-def _fp_register(weight):
-    """remember `weight` (a parameter whose packed copy has just been made) and take its reference fingerprint NOW -- one
-    one-row checksum launch on the stream that has just packed it: a write that bumps no version (`.data`, an EMA, a
-    hipGraph-replayed optimiser step) between this packing and the next verify_packed() is then a mismatch, not part of the
-    reference"""
-    import weakref
-    wid = id(weight)
-    key = (weight.data_ptr(), weight.numel())
-    _FP['rows'][wid] = (weakref.ref(weight), key, weight._version)
-    dev = weight.device
-    tbl = torch.tensor(list(key), dtype=torch.int64).to(dev)
-    ref = torch.zeros(1, dtype=torch.int64, device=dev)
-    done = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.call('mrefsr_weights_checksum', _p(tbl), 1, _p(ref), _p(done), None, None, 0, _stream())
-    _FP.setdefault('wref', {})[wid] = (ref, tbl, done)   # (the table row and counter live as long as the launch may)
-    _FP['dirty'] = True
-
-
-def _fp_table(device):
-    live = [(wid, r) for wid, r in _FP['rows'].items() if r[0]() is not None]
-    if _FP['dirty'] or _FP['table'] is None or len(live) != len(_FP['order']):
-        _FP['rows'] = dict(live)
-        _FP['order'] = [wid for wid, _ in live]
-        wref = _FP.setdefault('wref', {})
-        for wid in [w for w in wref if w not in _FP['rows']]:
-            del wref[wid]
-        flat = [v for _, r in live for v in r[1]]
-        n = len(live)
-        _FP['table'] = torch.tensor(flat, dtype=torch.int64).view(-1, 2).to(device)
-        _FP['sums'] = torch.zeros(n, dtype=torch.int64, device=device)
-        _FP['done'] = torch.zeros(n, dtype=torch.int32, device=device)
-        _FP['ref'] = torch.cat([wref[wid][0] for wid in _FP['order']]) if n else None   # the fingerprints taken at packing time
-        _FP['dirty'] = False
-    return len(_FP['order'])
-
-
-def verify_packed(device=None):
-    """One launch: fingerprint every parameter with a cached packed copy and raise the stale bit where it differs from the
-    fingerprint taken at packing time.  No synchronisation; the bit is read with the range flag (conv_range_tripped(), then
-    packed_stale()).  Call it once per forward pass, before the convolutions."""
-    if not _FP['rows']:
-        return
-    # a parameter modified in a way autograd sees (its version moved: optimiser step, load_state_dict, an in-place op under no_grad)
-    # is re-packed -- and re-fingerprinted -- by the pass that follows: it leaves the check instead of failing it
-    moved = [wid for wid, r in _FP['rows'].items() if r[0]() is not None and (r[0]()._version != r[2] or r[0]().data_ptr() != r[1][0])]
-    if moved:
-        for wid in moved:
-            del _FP['rows'][wid]
-        _FP['dirty'] = True
-        if not _FP['rows']:
-            return
-    device = device or torch.device('cuda', torch.cuda.current_device())
-    n = _fp_table(device)
-    if n == 0:
-        return
-    _lib.call('mrefsr_weights_checksum', _p(_FP['table']), n, _p(_FP['sums']), _p(_FP['done']), _p(_FP['ref']),
-              _p(_range_flag(device)), _STALE_BIT, _stream())
-
-
-def packed_stale(reset=True):
-    """True if verify_packed() found a parameter that no longer matches its packed copy (seen at the last conv_range_tripped()
-    readback); the caller drops the cache (invalidate_packed()) and repeats the pass."""
-    seen = _stale_seen[0]
-    if reset:
-        _stale_seen[0] = False
-    return seen
 
 
 def check_conv_range(reset=True):
@@ -913,41 +837,95 @@ class PackedWeight:
         self.data, self.wscale, self.terms = data, wscale, terms
 
 
-def packed_weight(weight, cin_slice=None, terms=6):
-    """cached conv_pack_weight(weight[:, a:b]): re-packed when the parameter is modified in place through autograd-visible
-    ops (optimizer step, load_state_dict, ``with torch.no_grad(): p.copy_(..)``: they bump ``_version``), re-allocated
-    (``data_ptr``) or replaced.  Writes through ``p.data`` bump nothing; they are caught on the device instead: every cached
-    parameter is fingerprinted when packed and again by ``verify_packed()`` (one launch per forward pass of the model, verdict
-    read with the range flag), and a mismatch makes the model drop the cache and repeat the pass."""
-    import weakref
-    key = (id(weight), cin_slice, terms)
-    hit = _PACKED.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight._version, weight.data_ptr()):
-        return hit[2]
-    if len(_PACKED) > 4096:   # entries of parameters that no longer exist
-        for k in [k for k, v in _PACKED.items() if v[0]() is None]:
-            del _PACKED[k]
-    w = weight.detach()
-    if cin_slice is not None:
-        w = w[:, cin_slice[0]:cin_slice[1]]
-    packed = conv_pack_weight(w.contiguous(), terms)
-    _PACKED[key] = (weakref.ref(weight), (weight._version, weight.data_ptr()), packed)
-    _fp_register(weight)
-    return packed
+_STALE_BIT = 2
 
 
-_packed_epoch = [0]
+class _Fingerprint:
+    """a parameter as verify() checks it: stamp and size, the checksum taken when it was packed (a device word), and the one-row
+    table and counter of that launch (they live as long as the launch may)"""
+    __slots__ = ('ref', 'stamp', 'numel', 'sum', 'row', 'done')
 
 
-def invalidate_packed():
-    """drop every cached packed weight (and let hipGraph captures notice): call after editing parameters through ``.data``"""
-    _PACKED.clear()
-    _packed_epoch[0] += 1
-    _FP.update(rows={}, order=[], dirty=True, table=None, ref=None, wref={})
+class _PackedWeights:
+    """Packed copies of the inference path's convolution weights by (id(parameter), slice, terms), each good for one param_stamp():
+    re-packed when the parameter is modified through autograd-visible ops, re-allocated or replaced.  Unlike the training tables,
+    which key by storage because autograd hands back new Python handles, this cache keys by the parameter object -- and it alone
+    also catches writes through ``p.data``, which move no stamp, on the device: every parameter is fingerprinted when packed (a
+    one-row checksum launch on the stream that has just packed it: such a write between this packing and the next verify() is
+    then a mismatch, not part of the reference) and again by verify(); the verdict travels in the range flag's word (no extra
+    readback), conv_range_tripped() leaves it in ``stale``, and the model then drops the cache and repeats the pass."""
+
+    def __init__(self):
+        self.copies, self.prints = {}, {}        # (id(weight), slice, terms) -> _Packed; id(weight) -> _Fingerprint
+        self.order, self.dirty = [], True        # the device table over self.prints, rebuilt lazily: its rows, out of date
+        self.table = self.sums = self.done = self.ref = None
+        self.stale, self.epoch = False, 0
+
+    def get(self, weight, cin_slice=None, terms=6):
+        """cached conv_pack_weight(weight[:, a:b])"""
+        key = (id(weight), cin_slice, terms)
+        hit = self.copies.get(key)
+        if hit is not None and param_stamp(hit.ref()) == hit.stamp:
+            return hit.packed
+        if len(self.copies) > 4096:   # entries of parameters that no longer exist
+            for k in [k for k, v in self.copies.items() if v.ref() is None]:
+                del self.copies[k]
+        w = weight.detach()
+        if cin_slice is not None:
+            w = w[:, cin_slice[0]:cin_slice[1]]
+        hit = self.copies[key] = _Packed(weight, conv_pack_weight(w.contiguous(), terms), param_stamp(weight))
+        fp = self.prints[id(weight)] = _Fingerprint()
+        fp.ref, fp.stamp, fp.numel, dev = hit.ref, hit.stamp, weight.numel(), weight.device
+        fp.row = torch.tensor([fp.stamp.ptr, fp.numel], dtype=torch.int64).to(dev)
+        fp.sum = torch.zeros(1, dtype=torch.int64, device=dev)
+        fp.done = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.call('mrefsr_weights_checksum', _p(fp.row), 1, _p(fp.sum), _p(fp.done), None, None, 0, _stream())
+        self.dirty = True
+        return hit.packed
+
+    def verify(self, device=None):
+        """One launch: fingerprint every parameter with a cached packed copy and raise the stale bit where it differs from the
+        fingerprint taken at packing time.  No synchronisation; the bit is read with the range flag (conv_range_tripped(), then
+        packed_stale()).  Call it once per forward pass, before the convolutions."""
+        # (a parameter whose stamp moved is re-packed, and re-fingerprinted, by the pass that follows: it leaves the check)
+        moved = [wid for wid, fp in self.prints.items() if fp.ref() is not None and param_stamp(fp.ref()) != fp.stamp]
+        for wid in moved:
+            del self.prints[wid]
+        if not self.prints:
+            self.dirty |= bool(moved)
+            return
+        device = device or torch.device('cuda', torch.cuda.current_device())
+        live = {wid: fp for wid, fp in self.prints.items() if fp.ref() is not None}
+        if moved or self.dirty or self.table is None or len(live) != len(self.order):
+            self.prints, self.order, n = live, list(live.values()), len(live)
+            self.table = torch.tensor([v for fp in self.order for v in (fp.stamp.ptr, fp.numel)], dtype=torch.int64).view(-1, 2).to(device)
+            self.sums = torch.zeros(n, dtype=torch.int64, device=device)
+            self.done = torch.zeros(n, dtype=torch.int32, device=device)
+            self.ref = torch.cat([fp.sum for fp in self.order]) if n else None   # the fingerprints taken at packing time
+            self.dirty = False
+        if self.order:
+            _lib.call('mrefsr_weights_checksum', _p(self.table), len(self.order), _p(self.sums), _p(self.done), _p(self.ref),
+                      _p(_range_flag(device)), _STALE_BIT, _stream())
+
+    def take_stale(self, reset=True):
+        """True if verify() found a parameter that no longer matches its packed copy (seen at the last conv_range_tripped()
+        readback); the caller drops the cache (invalidate_packed()) and repeats the pass."""
+        seen, self.stale = self.stale, self.stale and not reset
+        return seen
+
+    def clear(self):
+        """drop every cached packed weight (and let hipGraph captures notice): call after editing parameters through ``.data``"""
+        self.copies.clear()
+        self.prints, self.order, self.dirty, self.table, self.ref = {}, [], True, None, None
+        self.epoch += 1
+
+
+_packed = _PackedWeights()
+packed_weight, verify_packed, packed_stale, invalidate_packed = _packed.get, _packed.verify, _packed.take_stale, _packed.clear
 
 
 def packed_epoch():
-    return _packed_epoch[0]
+    return _packed.epoch
 
 
 def conv_pack_weight(weight, terms=6):
@@ -1379,44 +1357,66 @@ def crop_bwd_nhwc(g, h, w):
 
 
 # ---- max |out| words of the forward launches (mrefsr_conv_nhwc_amax_f32 / mrefsr_dcn_fwd_amax_f32): one zeroed float per producing
-# launch, handed to the consumer as its in_amax.  A pool per device, two halves: a half is zeroed (one memset) when the slot counter
-# enters it -- its words were handed out >= AMAX_POOL / 2 launches ago, their tensors have long been consumed.  amax_pool_reset()
-# (start of a pass: MultiRefRestorationModel.test / optimize_parameters) zeroes everything and restarts at slot 0, so that a
-# captured graph re-zeroes and re-uses the same words in every replay.
+# launch, handed to the consumer as its in_amax.  A ring per device, two halves: a half is zeroed (one memset) when the slot counter
+# enters it -- its words were handed out >= AMAX_POOL / 2 launches ago.  amax_pool_reset() (start of a pass:
+# MultiRefRestorationModel.test / optimize_parameters) zeroes everything and restarts at slot 0, so that a captured graph re-zeroes
+# and re-uses the same words in every replay.  Either event gives the words of a half to other launches: each half has a generation
+# that moves with it, and the handle a word travels in (archs/nhwc.py) holds the generation it was issued in.
 AMAX_POOL = 8192
-_amax_pool = {}
 
 
-def _amax_state(device):
-    st = _amax_pool.get(device.index)
-    if st is None:
-        buf = torch.zeros(AMAX_POOL, device=device, dtype=torch.float32)
-        st = _amax_pool[device.index] = [buf, 0, list(buf.split(1))]   # (the one-element views are made once: a slice per launch costs microseconds)
-    return st
+class _AmaxRing:
+    HALF = AMAX_POOL // 2
+
+    def __init__(self, device):
+        self.buf = torch.zeros(AMAX_POOL, device=device, dtype=torch.float32)
+        self.views = list(self.buf.split(1))   # (the one-element views are made once: a slice per launch costs microseconds)
+        self.next, self.gen = 0, [0, 0]
+
+    def reset(self):
+        self.buf.zero_()
+        self.next, self.gen = 0, [g + 1 for g in self.gen]
+
+    def slot(self):
+        i = self.next % AMAX_POOL
+        if i % self.HALF == 0:
+            self.buf[i:i + self.HALF].zero_()
+            self.gen[i // self.HALF] += 1
+        self.next = i + 1
+        return self.views[i]
+
+    def generation(self, word):
+        """of the half ``word`` (a slot()) lies in: it has moved once the word may be another launch's"""
+        return self.gen[word.storage_offset() // self.HALF]
+
+    @contextlib.contextmanager
+    def one_half(self, option):
+        """around a pass that takes words BEHIND those of a recorded forward, without a reset: a slot counter that wrapped, or ran
+        into the ring's second half, would zero words in use -- the second half is what the backward pass may still take before the
+        first one, which the recorded graph reads, is handed out again"""
+        start = self.next
+        yield
+        used = self.next
+        if used < start or used > self.HALF:
+            raise RuntimeError(f'{option}: the forward and the EMA pass took {used} max |out| words (the pass from {start} on); a '
+                               f'step has {self.HALF} of them, half of hip.AMAX_POOL = {AMAX_POOL}')
+
+
+_amax_rings = {}
+
+
+def amax_ring(device):
+    return _amax_rings.get(device.index) or _amax_rings.setdefault(device.index, _AmaxRing(device))
 
 
 def amax_pool_reset():
-    for st in _amax_pool.values():
-        st[0].zero_()
-        st[1] = 0
-
-
-def amax_pool_used(device):
-    """the slots handed out on ``device`` since the pool was last reset or wrapped around"""
-    st = _amax_pool.get(device.index)
-    return 0 if st is None else st[1]
+    for ring in _amax_rings.values():
+        ring.reset()
 
 
 def amax_slot(device):
     """a zeroed 1-element float32 device tensor for one launch's max |out|"""
-    st = _amax_state(device)
-    i = st[1]
-    if i == AMAX_POOL:
-        i = 0
-    if i == 0 or i == AMAX_POOL // 2:
-        st[0][i:i + AMAX_POOL // 2].zero_()
-    st[1] = i + 1
-    return st[2][i]
+    return amax_ring(device).slot()
 
 
 def _nhwc_ld(name, t):

@@ -670,15 +670,8 @@ class MultiRefRestorationModel:
         if self.net_g_ema is None:
             raise RuntimeError('train.ldl_opt: there is no net_g_ema (train.ema_decay > 0 is required)')
         args, kwargs = self._net_g_inputs
-        start = hip.amax_pool_used(self.device)
-        with torch.no_grad():
+        with torch.no_grad(), hip.amax_ring(self.device).one_half('train.ldl_opt'):
             out = self.net_g_ema(*args, **kwargs)
-        # a slot counter that wrapped, or ran into the pool's second half, would zero words in use: the second half is what the
-        # backward pass may still take before the first one, which the recorded graph reads, is handed out again
-        used = hip.amax_pool_used(self.device)
-        if used < start or used > hip.AMAX_POOL // 2:
-            raise RuntimeError(f'train.ldl_opt: the forward and the EMA pass took {used} max |out| words (the pass from {start} on); a '
-                               f'step has {hip.AMAX_POOL // 2} of them, half of hip.AMAX_POOL = {hip.AMAX_POOL}')
         return out.detach()
 
     def _match(self, f1, f2, refs):

@@ -39,7 +39,7 @@ def _backward_fused(grad_output, x, offset, mask, weight, with_bias, need_x, dg,
             and cig == c and not hip.is_range_free()):
         return None
     from ...archs import nhwc_train as nt   # (the fp16 weight scale cache of the training engine: one readback per parameter storage)
-    if torch.cuda.is_current_stream_capturing() and (weight.data_ptr(), weight.numel()) not in nt._scales:
+    if torch.cuda.is_current_stream_capturing() and not nt._scales.has(weight):
         return None
     ws = nt._wscale(weight)
     if not ws:   # an (almost) all-zero weight: no fp16 scale

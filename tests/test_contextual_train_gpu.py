@@ -258,7 +258,7 @@ def test_option_absent_the_step_launches_what_it_launched(monkeypatch):
     def traced(contextual_opt=None):
         hip._zero_chunks.entries.clear()   # (a fresh chunk of zeroed words: its one fill launch falls into the untraced first step)
         nhwc_train.reset_scales()
-        monkeypatch.setattr(nhwc_train, '_checks', [0])
+        monkeypatch.setattr(nhwc_train._scales, 'checks', 0)
         model = _built(_opt(deterministic=True, contextual_opt=contextual_opt))
         model.feed_data(data)
         model.optimize_parameters(1)

@@ -982,7 +982,7 @@ def test_winograd_input_scale_is_the_current_batch_s(hip):
             y1 = nhwc.conv(c1, x, bias=False)
             y2 = nhwc.conv(c2, y1, bias=False)
             assert nhwc.AMAX_MEASURED[0] - before == 1          # x is the caller's tensor; y1 carries its producer's word
-            assert getattr(y1, nhwc.AMAX_ATTR).item() == y1.abs().max().item()
+            assert nhwc.amax_word(y1).item() == y1.abs().max().item()
             hip.check_conv_range()
             xd = x.permute(0, 3, 1, 2).double().cpu()
             w1, w2 = c1.weight.double().cpu(), c2.weight.double().cpu()
@@ -992,6 +992,43 @@ def test_winograd_input_scale_is_the_current_batch_s(hip):
             rms, rms32 = (got - want).pow(2).mean().sqrt().item(), (f32 - want).pow(2).mean().sqrt().item()
             print(f'two Winograd layers at input scale {scale:g}: rms error {rms:.2e}, fp32 convolutions {rms32:.2e}')
             assert rms <= 1.75 * rms32, (scale, rms, rms32)
+
+
+def _wino_pair():
+    """c1, c2 and x of the smallest shape nhwc.wino_applies sends to the Winograd kernel: whole 16 x 16 tiles, four 16-channel
+    chunks, couts in whole 64-blocks"""
+    from torch import nn
+    torch.manual_seed(5)
+    return nn.Conv2d(64, 64, 3, 1, 1).cuda(), nn.Conv2d(64, 128, 3, 1, 1).cuda(), torch.randn(1, 16, 16, 64, device='cuda')
+
+
+def test_a_max_word_that_outlived_its_pass_is_not_read(hip):
+    """a tensor kept across hip.amax_pool_reset(): its word is slot 0 of the ring, which the next pass hands to another launch -- here
+    one with a maximum 2^26 larger.  The Winograd launch that reads the kept tensor measures it instead (one measurement), and
+    equals bit for bit the launch over a clone, which carries no word and is measured: both maxima are exact"""
+    from mrefsr_amd.archs import nhwc
+    c1, c2, x = _wino_pair()
+    with torch.no_grad():
+        y1 = nhwc.conv(c1, x * 2.0 ** -16)
+        hip.amax_pool_reset()
+        nhwc.conv(c1, x * 2.0 ** 10)
+        before = nhwc.AMAX_MEASURED[0]
+        got = nhwc.conv(c2, y1)
+        assert nhwc.AMAX_MEASURED[0] - before == 1
+        assert torch.equal(got, nhwc.conv(c2, y1.clone()))
+    hip.check_conv_range()
+
+
+def test_a_static_buffer_is_measured_again_after_copy_(hip):
+    """a caller's tensor refilled in place with a batch 2^12 larger: the maximum cached on it at its first read is not the new
+    batch's (the fp16 range flag would rise); the launch equals the one over a clone bit for bit"""
+    from mrefsr_amd.archs import nhwc
+    c1, _, x = _wino_pair()
+    with torch.no_grad():
+        nhwc.conv(c1, x)
+        x.copy_(x * 2.0 ** 12)
+        assert torch.equal(nhwc.conv(c1, x), nhwc.conv(c1, x.clone()))
+    hip.check_conv_range()
 
 
 def test_conv_wino_epilogues_sources_slices(hip):

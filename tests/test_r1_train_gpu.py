@@ -313,7 +313,7 @@ def test_options_absent_the_step_launches_what_it_launched(data, monkeypatch):
 
     def traced():
         nhwc_train.reset_scales()
-        monkeypatch.setattr(nhwc_train, '_checks', [0])
+        monkeypatch.setattr(nhwc_train._scales, 'checks', 0)
         torch.manual_seed(11)
         model = _small(wgan_gp)
         model.feed_data(data)

@@ -87,7 +87,7 @@ def test_fusion_inference_at_ragged_sizes_is_bit_equal_to_the_f_pad_round_trip(g
         rp = nhwc.to_nhwc(m.spatial_padding(nhwc.as_nchw(refs)))
         want = m.forward_nhwc(tp, rp, t)[:, :h, :w, :].contiguous()
     assert torch.equal(got, want)
-    word = getattr(got, nhwc.AMAX_ATTR)                           # the crop measured the result's own max |x|
+    word = nhwc.amax_word(got)                                    # the crop measured the result's own max |x|
     assert float(word) == float(got.abs().max())
 
 

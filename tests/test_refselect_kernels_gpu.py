@@ -230,8 +230,8 @@ def _gather_case(hip, src, sel, n, misalign=0):
     assert (got[0] == fill).all() and (got[1 + k * b:] == fill).all(), 'a row outside the table was written'
     fresh = hip.ref_gather(dsrc, sel.to(DEV), n)
     assert fresh.shape == want.shape and fresh.is_contiguous() and _same_bits(fresh.cpu(), want)
-    from mrefsr_amd.archs.nhwc import AMAX_ATTR
-    assert getattr(fresh, AMAX_ATTR, None) is None   # (not an engine product: no cached max |out| of another tensor)
+    from mrefsr_amd.archs.nhwc import amax_word
+    assert amax_word(fresh) is None   # (not an engine product: no cached max |out| of another tensor)
 
 
 @pytest.mark.parametrize('shape', [(3, 16, 16), (3, 48, 64), (3, 20, 28)], ids=lambda s: 'x'.join(map(str, s)))
