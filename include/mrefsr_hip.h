@@ -1167,6 +1167,47 @@ int mrefsr_contextual_bwd_f32(const float *xn, const float *yn, const float *rno
                               const float *gup, float coef, float *dx, int accumulate, float *amax, void *workspace,
                               int64_t workspace_bytes, mrefsr_stream_t stream);
 
+/* ---- CoBi, the contextual bilateral loss (Zhang et al., "Zoom to Learn, Learn to Zoom", ICCV 2019; csrc/contextual.hip).
+ * mrefsr_contextual_fwd_sp_f32 / mrefsr_contextual_bwd_sp_f32: the two calls above on a tap whose N = h w positions lie on an h x w
+ *   grid (i = r_i w + c_i), with a spatial term in the distance:
+ *     d[i][j] = (1 - weight_sp) (1 - <xn_i, yn_j>) + weight_sp ((r_i - r_j)^2 + (c_i - c_j)^2) / (h^2 + w^2)
+ *   (raw distances are mixed, then made relative; the squared offset is an integer, divided once in fp32).  Every later statistic runs
+ *   on this d.  With weight_sp > 0 the position norms and the product are taken in double (v_mfma_f64_16x16x4_f64; xn, yn and d each
+ *   rounded to fp32 once): the term leaves row minima of 1e-3 and less on repetitive texture, where fp32 norms and an fp32
+ *   accumulator near 1 cost the loss a digit.  The term is a constant: the backward is that of the plain call on the combined d, times (1 - weight_sp).  Arguments,
+ *   outputs, workspace (mrefsr_contextual_workspace_bytes(B, h w, C, .)), launch counts and checks are those of the plain calls, plus:
+ *   h, w >= 1 (else MREFSR_E_INVALID), h w <= MREFSR_CX_MAX_N (else MREFSR_E_UNSUPPORTED), weight_sp a number in [0, 1) (else
+ *   MREFSR_E_INVALID).  weight_sp = 0 launches the kernels of the plain calls: the same bits.
+ * mrefsr_cx_patch_channels: the channel count Cpad of size x size RGB patches as features, the smallest of 64, 128, 256, 512 that is
+ *   >= 3 size^2; MREFSR_E_INVALID for size < 1, MREFSR_E_UNSUPPORTED for size > 13.
+ * mrefsr_cx_patches_f32: img NCHW [B][3][H][W] -> out NHWC [B][oh ow][Cpad], oh = (H - size) / stride + 1, ow likewise: channel
+ *   (c size + dy) size + dx of patch (pr, pc) is img[b][c][pr stride + dy][pc stride + dx] (F.unfold's order; norm != 0: (v + 1) * 0.5
+ *   first), the channels from 3 size^2 on are zeros.  One launch.
+ * mrefsr_cx_patches_bwd_f32: its adjoint, dimg [B][3][H][W] = (accumulate ? dimg : 0) + scale * the sum of the at most
+ *   ceil(size / stride)^2 entries of g [B][oh ow][Cpad] that cover the pixel, added in ascending (patch row, patch column) order in
+ *   fp32 (gather form: no atomics); a pixel no patch covers gets scale * 0.  One launch.
+ * mrefsr_cx_subsample_f32: f NHWC [B][h][w][C] (C a multiple of 4) -> out [B][hs][ws][C], hs = ceil(h / s), ws = ceil(w / s), the
+ *   positions (r s, c s).  One launch.
+ * mrefsr_cx_subsample_bwd_f32: its adjoint into the tap's gradient buffer g [B][h][w][C]: accumulate = 0 writes gs at the sampled
+ *   positions and zeros elsewhere; accumulate != 0 adds gs at the sampled positions only.  amax (may be NULL): a zeroed word raised to
+ *   max |g| over the whole buffer.  One launch. */
+int mrefsr_contextual_fwd_sp_f32(const float *x, const float *y, int B, int h, int w, int C, float band_width, float weight_sp, float *xn,
+                                 float *yn, float *rnorm, float *rowf, int32_t *jmin, float *cxmax, int32_t *imax, float *cx,
+                                 float *tap_loss, float weight, float loss_weight, int first, float *run, float *total, void *workspace,
+                                 int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_contextual_bwd_sp_f32(const float *xn, const float *yn, const float *rnorm, int B, int h, int w, int C, float band_width,
+                                 float weight_sp, const float *rowf, const int32_t *jmin, const float *cxmax, const int32_t *imax,
+                                 const float *cx, const float *gup, float coef, float *dx, int accumulate, float *amax, void *workspace,
+                                 int64_t workspace_bytes, mrefsr_stream_t stream);
+int mrefsr_cx_patch_channels(int size);
+int mrefsr_cx_patches_f32(const float *img, int B, int H, int W, int size, int stride, int norm, float *out, int Cpad,
+                          mrefsr_stream_t stream);
+int mrefsr_cx_patches_bwd_f32(const float *g, int B, int H, int W, int size, int stride, int Cpad, float scale, float *dimg, int accumulate,
+                              mrefsr_stream_t stream);
+int mrefsr_cx_subsample_f32(const float *f, int B, int h, int w, int C, int s, float *out, mrefsr_stream_t stream);
+int mrefsr_cx_subsample_bwd_f32(const float *gs, int B, int h, int w, int C, int s, float *g, int accumulate, float *amax,
+                                mrefsr_stream_t stream);
+
 /* Fingerprints of n device tensors of 32-bit words: table[2t] = address, table[2t+1] = word count (device memory);
  * sums[t] = sum_i word_i * (2 i + 1) mod 2^64 (exact integer arithmetic: independent of the summation order); `done` is n words
  * of scratch.  With `ref` given, `*flag |= flag_bits` (device memory) where sums[t] != ref[t].  No reference counterpart: the host

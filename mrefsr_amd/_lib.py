@@ -229,6 +229,13 @@ SIGNATURES = {
     'mrefsr_contextual_workspace_bytes': (_i64, [_i, _i, _i, _i]),
     'mrefsr_contextual_fwd_f32': (_i, [_vp, _vp, _i, _i, _i, _f] + [_vp] * 9 + [_f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
     'mrefsr_contextual_bwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _f] + [_vp] * 6 + [_f, _vp, _i, _vp, _vp, _i64, _vp]),
+    'mrefsr_contextual_fwd_sp_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f] + [_vp] * 9 + [_f, _f, _i, _vp, _vp, _vp, _i64, _vp]),
+    'mrefsr_contextual_bwd_sp_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f] + [_vp] * 6 + [_f, _vp, _i, _vp, _vp, _i64, _vp]),
+    'mrefsr_cx_patch_channels': (_i, [_i]),
+    'mrefsr_cx_patches_f32': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    'mrefsr_cx_patches_bwd_f32': (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
+    'mrefsr_cx_subsample_f32': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'mrefsr_cx_subsample_bwd_f32': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'mrefsr_degrade_filter2d_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     'mrefsr_degrade_usm_f32': (_i, [_vp, C.POINTER(C.c_float), _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp]),
     'mrefsr_degrade_resize_f32': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp]),

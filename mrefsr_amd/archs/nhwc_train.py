@@ -25,7 +25,7 @@ same graph is recorded over [N,H,W,C] tensors with one autograd node per FUSED l
   _VggLoss       the VGG of PerceptualLoss (losses/): output and GT as one batch forward, input gradients of the output image
                  backward (csrc/percep.hip: pooling, tap criterion, Gram matrices, image packing backward)
   _VggContextual the same VGG stack for ContextualLoss: per tap the all-pairs similarity, its statistics and their backward on
-                 csrc/contextual.hip
+                 csrc/contextual.hip; with the CoBi options also a tap on RGB patches of the images and taps on a strided sub-grid
 
 Arithmetic: forward and input-gradient convolutions run the fp16 two-term split (terms 16, three products; FWD_TERMS /
 BWD_TERMS) on weights packed with a cached power-of-two scale (_wscale, watched by check_scales()); an input-gradient launch
@@ -915,45 +915,71 @@ def texture(vgg, x, maps, weights, plan):
 
 
 # ---- contextual loss (losses.ContextualLoss; Mechrez et al., ECCV 2018) ---------------------------------------------
-KEEP_CX = None   # tests/ set a list: every _VggContextual forward appends, per tap, dict(jmin, imax, CX) of the device's selections
+KEEP_CX = None   # tests/ set a list: every _VggContextual forward appends, per tap (the RGB tap first), dict(jmin, imax, CX) of the device's selections
 
 
 _CX_SAVED = ('xn', 'yn', 'rnorm', 'rowf', 'jmin', 'cxmax', 'imax', 'cx')   # what hip.contextual_bwd reads of hip.contextual_fwd's outputs
 
 
 class ContextualLossPlan(VggLossPlan):
-    """VggLossPlan of a ContextualLoss: the taps with their weights, the band width and the loss weight"""
+    """VggLossPlan of a ContextualLoss: the taps with their weights and strides, the band width, the weight of the spatial term, the
+    RGB patch tap (rgb: dict(size, stride, weight) or None) and the loss weight.  vgg_net None: no VGG tap (the RGB tap alone)"""
 
-    def __init__(self, vgg_net, layer_weights, band_width, loss_weight, norm_img):
-        super().__init__(vgg_net, layer_weights, 'contextual', 0.0, 0.0, norm_img)
+    def __init__(self, vgg_net, layer_weights, band_width, loss_weight, norm_img, weight_sp=0.0, tap_stride=None, rgb_patch=None):
+        if vgg_net is None:
+            self.layers, self.taps = [], []
+            self.crit, self.pw, self.sw, self.norm_img = 'contextual', 0.0, 0.0, bool(norm_img)
+        else:
+            super().__init__(vgg_net, layer_weights, 'contextual', 0.0, 0.0, norm_img)
         self.names = [self.layers[i]['names'][kind] for i, kind, _ in self.taps]   # network order: the summation order
-        self.band_width, self.loss_weight = float(band_width), float(loss_weight)
+        self.band_width, self.loss_weight, self.weight_sp = float(band_width), float(loss_weight), float(weight_sp)
+        self.strides = [int((tap_stride or {}).get(n, 1)) for n in self.names]
+        self.rgb = dict(rgb_patch) if rgb_patch else None
+        if not self.taps and self.rgb is None:
+            raise ValueError('ContextualLoss: no tap (neither a VGG layer nor rgb_patch)')
 
 
 class _VggContextual(Function):
-    """(output x, gt) -> the contextual loss [1]: output and GT as ONE 2B batch through the VGG kernels, per tap the kernels of
-    csrc/contextual.hip (the running total is carried from tap to tap on the device, in network order); the backward adds each
-    tap's gradient where the perceptual term adds its own and runs the input gradients of the first B images back to x."""
+    """(output x, gt) -> the contextual loss [1]: output and GT as ONE 2B batch; the RGB tap, if any, on the patches of the images
+    (hip.cx_patches), then the batch through the VGG kernels and per tap -- on its positions (r s, c s) when it has a stride
+    (hip.cx_subsample) -- the kernels of csrc/contextual.hip (the running total is carried from tap to tap on the device, the RGB
+    tap first, the VGG taps in network order); the backward adds each tap's gradient where the perceptual term adds its own (a
+    strided tap's scattered by hip.cx_subsample_bwd, which hands max |g| on), runs the input gradients of the first B images back
+    to x and adds the RGB tap's there (hip.cx_patches_bwd)."""
 
     @staticmethod
     def forward(ctx, x, gt, plan, mean, std):
         b = x.shape[0]
         img = torch.cat([x.detach(), gt.detach()]).contiguous()
-        feats, saved = _vgg_stack_forward(plan, img, mean, std)
         need = ctx.needs_input_grad[0]
-        run, total, keep = None, None, []
-        for (_, _, w), name, f in zip(plan.taps, plan.names, feats):
+        state = dict(run=None, total=None)
+        keep = []
+
+        def tap(name, f, w, hint):
+            if f.shape[1] * f.shape[2] > hip.CX_MAX_N:
+                raise NotImplementedError(f'ContextualLoss: tap {name} of {f.shape[1]} x {f.shape[2]} = {f.shape[1] * f.shape[2]} positions; '
+                                          f'at most {hip.CX_MAX_N} (one N x N matrix per sample is materialised): {hint}')
             try:
-                total, s = hip.contextual_fwd(f[:b], f[b:], plan.band_width, w, plan.loss_weight, run=run)
+                state['total'], s = hip.contextual_fwd(f[:b], f[b:], plan.band_width, w, plan.loss_weight, run=state['run'],
+                                                       weight_sp=plan.weight_sp)
             except NotImplementedError as e:
                 raise NotImplementedError(f'ContextualLoss: tap {name} of {f.shape[1]} x {f.shape[2]} positions: {e}') from None
-            run = s['run']
+            state['run'] = s['run']
             keep.append(s)
+
+        if plan.rgb is not None:
+            tap('rgb_patch', hip.cx_patches(img, plan.rgb['size'], plan.rgb['stride'], plan.norm_img), float(plan.rgb['weight']),
+                'raise the stride of rgb_patch')
+        feats, saved = _vgg_stack_forward(plan, img, mean, std) if plan.taps else ([], None)
+        for (_, _, w), name, s, f in zip(plan.taps, plan.names, plan.strides, feats):
+            tap(name, f if s == 1 else hip.cx_subsample(f, s), w,
+                f"evaluate it on a sub-grid with tap_stride = {{'{name}': {max(2, s + 1)}}} or more")
         if KEEP_CX is not None:
             KEEP_CX.append([dict(jmin=s['jmin'], imax=s['imax'], CX=s['cx']) for s in keep])
-        ctx.plan, ctx.b, ctx.saved = plan, b, saved
+        ctx.plan, ctx.b, ctx.saved, ctx.image = plan, b, saved, tuple(x.shape)
+        ctx.tap_shapes = [tuple(f.shape[1:]) for f in feats]
         ctx.save_for_backward(std, *[s[k] for s in (keep if need else []) for k in _CX_SAVED])
-        return total
+        return state['total']
 
     @staticmethod
     @once_differentiable
@@ -961,7 +987,8 @@ class _VggContextual(Function):
         plan, b, saved = ctx.plan, ctx.b, ctx.saved
         st = ctx.saved_tensors
         std, nk = st[0], len(_CX_SAVED)
-        keep = [dict(zip(_CX_SAVED, st[1 + j * nk:1 + (j + 1) * nk])) for j in range(len(plan.taps))]
+        keep = [dict(zip(_CX_SAVED, st[1 + j * nk:1 + (j + 1) * nk])) for j in range(len(plan.taps) + (plan.rgb is not None))]
+        rgb = keep.pop(0) if plan.rgb is not None else None
         g_tot = g_tot.contiguous()
         tap_of = {(i, k): j for j, (i, k, _) in enumerate(plan.taps)}
 
@@ -970,22 +997,35 @@ class _VggContextual(Function):
             if j is None:
                 return g, None
             acc = g is not None
+            coef = plan.loss_weight * plan.taps[j][2]
+            if plan.strides[j] == 1:
+                if g is None:
+                    g = torch.empty_like(keep[j]['xn'])
+                return g, hip.contextual_bwd(keep[j], plan.band_width, coef, g, gup=g_tot, accumulate=acc, weight_sp=plan.weight_sp)
+            gs = torch.empty_like(keep[j]['xn'])
+            hip.contextual_bwd(keep[j], plan.band_width, coef, gs, gup=g_tot, want_amax=False, weight_sp=plan.weight_sp)
             if g is None:
-                g = torch.empty_like(keep[j]['xn'])
-            return g, hip.contextual_bwd(keep[j], plan.band_width, plan.loss_weight * plan.taps[j][2], g, gup=g_tot, accumulate=acc)
+                g = torch.empty((b,) + ctx.tap_shapes[j], device=gs.device, dtype=torch.float32)
+            return g, hip.cx_subsample_bwd(gs, g, plan.strides[j], accumulate=acc)
 
-        g_x = _vgg_stack_backward(plan, b, saved, std, add_tap)
+        g_x = _vgg_stack_backward(plan, b, saved, std, add_tap) if plan.taps else None
+        if rgb is not None:
+            gp = torch.empty_like(rgb['xn'])
+            hip.contextual_bwd(rgb, plan.band_width, plan.loss_weight * float(plan.rgb['weight']), gp, gup=g_tot, want_amax=False,
+                               weight_sp=plan.weight_sp)
+            g_x = hip.cx_patches_bwd(gp, ctx.image, plan.rgb['size'], plan.rgb['stride'], scale=0.5 if plan.norm_img else 1.0, out=g_x)
         return g_x, None, None, None, None
 
 
 def contextual(vgg, x, gt, plan):
-    """ContextualLoss.forward on the training engine: -> the loss [1] (a device tensor; autograd reaches x)"""
+    """ContextualLoss.forward on the training engine: -> the loss [1] (a device tensor; autograd reaches x).  vgg: the loss's
+    VGGFeatureExtractor, None when the plan has no VGG tap"""
     if not (x.is_cuda and gt.is_cuda):
         raise NotImplementedError('ContextualLoss: mrefsr_amd has no CPU path (HIP kernels only)')
     if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.shape != gt.shape or x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f'ContextualLoss: two float32 [N,3,H,W] images expected, got {tuple(x.shape)} / {tuple(gt.shape)}')
-    mean = vgg.mean.contiguous() if vgg.use_input_norm else None
-    std = vgg.std.contiguous() if vgg.use_input_norm else None
+    mean = vgg.mean.contiguous() if vgg is not None and vgg.use_input_norm else None
+    std = vgg.std.contiguous() if vgg is not None and vgg.use_input_norm else None
     return _VggContextual.apply(x, gt, plan, mean, std)
 
 

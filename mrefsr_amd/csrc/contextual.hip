@@ -16,11 +16,22 @@
 // and has no online rescaling, and the column maximum needs Z; with d in scratch (41 MB at B = 4, N = 1600: it stays in the 256 MB
 // of MALL) the three statistics passes are memory-bound sweeps and the product runs once per direction.
 // Every sum has a fixed order; no float atomics; nothing is read back.
+//
+// CoBi (Zhang et al., "Zoom to Learn, Learn to Zoom", ICCV 2019): the *_sp entry points take the tap's grid h x w and weight_sp = ws
+// in [0, 1), and cx_dist stores d = (1 - ws) (1 - <xn_i, yn_j>) + ws ((r_i - r_j)^2 + (c_i - c_j)^2) / (h^2 + w^2), i = r_i w + c_i;
+// every later pass runs on that d as it stands; the norms and the product of such a call are taken in double (cx_normalise<true>,
+// cx_dist<true> on the f64 MFMA).  The spatial term is a constant: the backward is the closed form above on the
+// combined d with coef (1 - ws).  ws = 0 launches the kernels of the plain entry points.  What feeds such taps:
+//   cx_patches       image NCHW [B][3][H][W] -> the size x size RGB patches at a stride as NHWC features [B][oh ow][Cpad], the
+//                    channels in F.unfold's (c, dy, dx) order, zeros past 3 size^2; its adjoint in gather form (no atomics)
+//   cx_subsample     NHWC tap [B][h][w][C] -> the positions (r s, c s); its adjoint scatters into the tap's gradient buffer
 #include "common.h"
+#include <type_traits>
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 constexpr float CX_EPS = 1e-5f;
 constexpr float CX_NORM_FLOOR = 1e-12f;
@@ -46,7 +57,11 @@ __global__ __launch_bounds__(1024) void cx_mean_kernel(const float *__restrict__
     }
 }
 
-// one wave per position: rows [0, BN) are x, rows [BN, 2 BN) are y.  C <= 512: at most two float4 per lane
+// one wave per position: rows [0, BN) are x, rows [BN, 2 BN) are y.  C <= 512: at most two float4 per lane.
+// HI (the CoBi entry points): the squares are added, the root taken and the elements divided in double, each element rounded once.
+// With the spatial term the row minima of repetitive texture are 1e-3 and less, and an fp32 norm -- a common factor 1 + 1e-7 on
+// every distance of a row or a column -- then carries the loss to 1e-6; HI = false is the plain kernel, bit for bit
+template <bool HI>
 __global__ __launch_bounds__(256) void cx_normalise_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ mu,
                                                            float *__restrict__ xn, float *__restrict__ yn, float *__restrict__ rnorm, long BN,
                                                            int N, int C)
@@ -62,6 +77,7 @@ __global__ __launch_bounds__(256) void cx_normalise_kernel(const float *__restri
     float4 *dst = reinterpret_cast<float4 *>((is_x ? xn : yn) + r * C);
     float4 v[2];
     float ss = 0.f;
+    double sd = 0.0;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int k = lane + 64 * q;
@@ -69,17 +85,34 @@ __global__ __launch_bounds__(256) void cx_normalise_kernel(const float *__restri
         if (k < C4) {
             const float4 a = src[k], u = m4[k];
             v[q] = make_float4(a.x - u.x, a.y - u.y, a.z - u.z, a.w - u.w);
-            ss += v[q].x * v[q].x + v[q].y * v[q].y + v[q].z * v[q].z + v[q].w * v[q].w;
+            if constexpr (HI)
+                sd += (double)v[q].x * v[q].x + (double)v[q].y * v[q].y + (double)v[q].z * v[q].z + (double)v[q].w * v[q].w;
+            else
+                ss += v[q].x * v[q].x + v[q].y * v[q].y + v[q].z * v[q].z + v[q].w * v[q].w;
         }
     }
-    ss = __shfl(mrefsr::wave_sum(ss), 0, 64);
-    const float den = fmaxf(sqrtf(ss), CX_NORM_FLOOR);
+    if constexpr (HI) {
+        sd = __shfl(mrefsr::wave_sum(sd), 0, 64);
+        const double root = sqrt(sd);
+        const bool floored = root < (double)CX_NORM_FLOOR;
+        const double den = floored ? (double)CX_NORM_FLOOR : root;
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int k = lane + 64 * q;
-        if (k < C4) dst[k] = make_float4(v[q].x / den, v[q].y / den, v[q].z / den, v[q].w / den);
+        for (int q = 0; q < 2; ++q) {
+            const int k = lane + 64 * q;
+            if (k < C4)
+                dst[k] = make_float4((float)(v[q].x / den), (float)(v[q].y / den), (float)(v[q].z / den), (float)(v[q].w / den));
+        }
+        if (is_x && lane == 0) rnorm[r] = floored ? 1.0f / CX_NORM_FLOOR : (float)(1.0 / den);   // (the floor as cx_grad_finish tests it)
+    } else {
+        ss = __shfl(mrefsr::wave_sum(ss), 0, 64);
+        const float den = fmaxf(sqrtf(ss), CX_NORM_FLOOR);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int k = lane + 64 * q;
+            if (k < C4) dst[k] = make_float4(v[q].x / den, v[q].y / den, v[q].z / den, v[q].w / den);
+        }
+        if (is_x && lane == 0) rnorm[r] = 1.0f / den;
     }
-    if (is_x && lane == 0) rnorm[r] = 1.0f / den;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -89,9 +122,17 @@ __global__ __launch_bounds__(256) void cx_normalise_kernel(const float *__restri
 // channel k0 + 4 (l >> 4) + e on both sides (gram_bwd_kernel's operand trick).  Rows past N load zeros and are not stored.
 // D: column (j) = lane & 15, row (i) = 4 (lane >> 4) + r.
 // ---------------------------------------------------------------------------------------------------------------
+// SP (CoBi): the same tiling on v_mfma_f64_16x16x4_f64 -- the operands converted lane by lane, A / B laid out as in the f32 form,
+// D: column (j) = lane & 15, row (i) = (lane >> 4) + 4 r -- and an epilogue that stores oms (1 - <xn_i, yn_j>) + ws d_sp[i][j],
+// formed in double and rounded once (oms = 1 - ws; gw: the grid's width; diag = h^2 + w^2).  Why double: an f32 accumulator near 1
+// is good to 6e-8, which is 1e-4 of a row minimum of 1e-3 and less -- what the spatial term leaves of repetitive texture -- and the
+// loss then carries 1e-6.  A thread owns the 8 rows i0 + 16 a + (l >> 4) + 4 r and the 2 columns j0 + 16 q + (l & 15): their (r, c)
+// come from one integer division by gw each, before the stores.  SP = false is the plain kernel, bit for bit
+template <bool SP>
 __global__ __launch_bounds__(256) void cx_dist_kernel(const float *__restrict__ xn, const float *__restrict__ yn, float *__restrict__ d, int N,
-                                                      int C, int ld)
+                                                      int C, int ld, int gw, double oms, double ws, double diag)
 {
+    using acc_t = std::conditional_t<SP, f64x4, f32x4>;
     const int b = blockIdx.z;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int kl = lane >> 4, cl = lane & 15;
@@ -106,11 +147,11 @@ __global__ __launch_bounds__(256) void cx_dist_kernel(const float *__restrict__ 
         xr[a] = reinterpret_cast<const float4 *>(xb + (long)(xok[a] ? i : 0) * C) + kl;
         yr[a] = reinterpret_cast<const float4 *>(yb + (long)(yok[a] ? j : 0) * C) + kl;
     }
-    f32x4 acc[2][2];
+    acc_t acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
 #pragma unroll
-        for (int q = 0; q < 2; ++q) acc[a][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int q = 0; q < 2; ++q) acc[a][q] = acc_t{0, 0, 0, 0};
     const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int k4 = 0; k4 < C / 4; k4 += 4) {
         float4 av[2], bv[2];
@@ -123,20 +164,53 @@ __global__ __launch_bounds__(256) void cx_dist_kernel(const float *__restrict__ 
 #pragma unroll
             for (int a = 0; a < 2; ++a)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) acc[a][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(ae[a][e], be[q][e], acc[a][q], 0, 0, 0);
+                for (int q = 0; q < 2; ++q) {
+                    if constexpr (SP)
+                        acc[a][q] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)ae[a][e], (double)be[q][e], acc[a][q], 0, 0, 0);
+                    else
+                        acc[a][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(ae[a][e], be[q][e], acc[a][q], 0, 0, 0);
+                }
     }
     float *db = d + (long)b * N * ld;
+    if constexpr (SP) {
+        int ir[2][4], ic[2][4], jr[2], jc[2];
 #pragma unroll
-    for (int a = 0; a < 2; ++a)
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = i0 + 16 * a + kl + 4 * r;
+                ir[a][r] = i / gw, ic[a][r] = i - ir[a][r] * gw;
+            }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int j = j0 + 16 * q + cl;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = i0 + 16 * a + 4 * kl + r;
-                if (i < N && j < N) db[(long)i * ld + j] = 1.0f - acc[a][q][r];
-            }
+            jr[q] = j / gw, jc[q] = j - jr[q] * gw;
         }
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int j = j0 + 16 * q + cl;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i = i0 + 16 * a + kl + 4 * r;
+                    const int dr = ir[a][r] - jr[q], dc = ic[a][r] - jc[q];
+                    if (i < N && j < N) db[(long)i * ld + j] = (float)(oms * (1.0 - acc[a][q][r]) + ws * ((double)(dr * dr + dc * dc) / diag));
+                }
+            }
+    } else {
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int j = j0 + 16 * q + cl;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i = i0 + 16 * a + 4 * kl + r;
+                    if (i < N && j < N) db[(long)i * ld + j] = 1.0f - acc[a][q][r];
+                }
+            }
+    }
 }
 
 // one wave per row i of d[b]: the minimum with the lowest j on ties, then Z in double over the lane's columns j = l, l + 64, ... and
@@ -361,6 +435,101 @@ __global__ __launch_bounds__(256) void cx_grad_finish_kernel(const float *__rest
     if (amax_bits) mrefsr::publish_amax<true>(amax_bits, amx);   // (one wave per position: thousands of waves on one word)
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// RGB patches as features (CoBi_RGB).  One thread per float4 of out [B][oh ow][Cpad]: channel k = (c size + dy) size + dx of patch
+// (pr, pc) is img[b][c][pr stride + dy][pc stride + dx] (norm: (v + 1) * 0.5 first), zero for k >= 3 size^2
+// ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cx_patches_kernel(const float *__restrict__ img, float *__restrict__ out, long total4, int H, int W,
+                                                         int size, int stride, int oh, int ow, int Cpad, int norm)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total4) return;
+    const int C4 = Cpad >> 2, k4 = (int)(t % C4);
+    const long pos = t / C4;
+    const int pc = (int)(pos % ow), pr = (int)((pos / ow) % oh);
+    const long b = pos / ((long)oh * ow);
+    const int ss = size * size, K = 3 * ss;
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int k = 4 * k4 + e;
+        v[e] = 0.f;
+        if (k < K) {
+            const int c = k / ss, rem = k - c * ss, dy = rem / size, dx = rem - dy * size;
+            const float a = img[((b * 3 + c) * H + pr * stride + dy) * W + pc * stride + dx];
+            v[e] = norm ? (a + 1.0f) * 0.5f : a;
+        }
+    }
+    reinterpret_cast<float4 *>(out)[t] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// the adjoint in gather form, one thread per image element (b, c, y, x): the patches (pr, pc) with pr stride <= y < pr stride + size
+// and the same in x, at most ceil(size / stride)^2 of them, added in ascending (pr, pc) order; times scale; written or added
+__global__ __launch_bounds__(256) void cx_patches_bwd_kernel(const float *__restrict__ g, float *__restrict__ dimg, long total, int H, int W,
+                                                             int size, int stride, int oh, int ow, int Cpad, float scale, int accumulate)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int x = (int)(t % W), y = (int)((t / W) % H);
+    const long bc = t / ((long)H * W);
+    const int c = (int)(bc % 3);
+    const long b = bc / 3;
+    const int r0 = y < size ? 0 : (y - size + stride) / stride, r1 = min(oh - 1, y / stride);
+    const int c0 = x < size ? 0 : (x - size + stride) / stride, c1 = min(ow - 1, x / stride);
+    const float *gb = g + b * oh * ow * Cpad + c * size * size;
+    float s = 0.f;
+    for (int pr = r0; pr <= r1; ++pr) {
+        const int dy = y - pr * stride;
+        for (int pc = c0; pc <= c1; ++pc) s += gb[((long)pr * ow + pc) * Cpad + dy * size + (x - pc * stride)];
+    }
+    s *= scale;
+    dimg[t] = accumulate ? dimg[t] + s : s;
+}
+
+// the positions (r s, c s) of a tap [B][h][w][C] -> [B][hs][ws][C], one thread per float4
+__global__ __launch_bounds__(256) void cx_subsample_kernel(const float *__restrict__ f, float *__restrict__ out, long total4, int h, int w, int C4,
+                                                           int s, int hs, int ws)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total4) return;
+    const int k = (int)(t % C4);
+    const long pos = t / C4;
+    const int c = (int)(pos % ws), r = (int)((pos / ws) % hs);
+    const long b = pos / ((long)hs * ws);
+    reinterpret_cast<float4 *>(out)[t] = reinterpret_cast<const float4 *>(f)[((b * h + (long)r * s) * w + (long)c * s) * C4 + k];
+}
+
+// its adjoint over the float4s of the tap's gradient buffer g [B][h][w][C], CX_SUB_ITEMS per thread a block's width apart (one
+// float4 per thread had 12800 waves peek at the one amax word: 63 us for the 13 MB of a relu2_2 buffer): a sampled position gets
+// (accumulate ? g : 0) + gs, any other keeps its value (accumulate) or is zeroed; max |g| of the whole buffer is published as
+// cx_grad_finish does
+constexpr int CX_SUB_ITEMS = 8;
+__global__ __launch_bounds__(256) void cx_subsample_bwd_kernel(const float *__restrict__ gs, float *__restrict__ g, long total4, int h, int w,
+                                                               int C4, int s, int hs, int ws, int accumulate,
+                                                               unsigned int *__restrict__ amax_bits)
+{
+    float amx = 0.f;
+#pragma unroll
+    for (int it = 0; it < CX_SUB_ITEMS; ++it) {
+        const long t = ((long)blockIdx.x * CX_SUB_ITEMS + it) * 256 + threadIdx.x;
+        if (t >= total4) break;
+        const int k = (int)(t % C4);
+        const long pos = t / C4;
+        const int c = (int)(pos % w), r = (int)((pos / w) % h);
+        const long b = pos / ((long)h * w);
+        float4 *gp = reinterpret_cast<float4 *>(g) + t;
+        float4 v = accumulate ? *gp : make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool hit = r % s == 0 && c % s == 0;
+        if (hit) {
+            const float4 a = reinterpret_cast<const float4 *>(gs)[((b * hs + r / s) * ws + c / s) * C4 + k];
+            v.x += a.x, v.y += a.y, v.z += a.z, v.w += a.w;
+        }
+        if (hit || !accumulate) *gp = v;
+        amx = fmaxf(amx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+    }
+    if (amax_bits) mrefsr::publish_amax<true>(amax_bits, amx);
+}
+
 inline int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 inline int cx_ld(int N) { return (N + 15) / 16 * 16; }
 inline bool cx_shape_ok(int B, int N, int C)
@@ -374,16 +543,115 @@ inline int64_t cx_off_dxn(int B, int N, int C) { return cx_off_d(B, C) + align25
 // null / non-positive sizes are invalid arguments; an N over the bound or another channel count is a shape the kernels do not take
 #define CX_REQUIRE_SHAPE(what)                                                                                                       \
     do {                                                                                                                             \
-        MREFSR_REQUIRE(B >= 1 && B <= 65535 && N >= 2 && C > 0, what ": B=%d N=%d C=%d (1 <= B <= 65535, N >= 2)", B, N, C);          \
+        MREFSR_REQUIRE(B >= 1 && B <= 65535 && N >= 2 && C > 0, "%s: B=%d N=%d C=%d (1 <= B <= 65535, N >= 2)", what, B, N, C);       \
         if (!cx_shape_ok(B, N, C))                                                                                                   \
-            return mrefsr::fail(MREFSR_E_UNSUPPORTED, what ": N=%d C=%d (N <= %d: one N x N matrix per sample is materialised; C of " \
-                                "64, 128, 256, 512)", N, C, MREFSR_CX_MAX_N);                                                         \
+            return mrefsr::fail(MREFSR_E_UNSUPPORTED, "%s: N=%d C=%d (N <= %d: one N x N matrix per sample is materialised; C of "    \
+                                "64, 128, 256, 512)", what, N, C, MREFSR_CX_MAX_N);                                                   \
     } while (0)
 
-void launch_dist(const float *xn, const float *yn, float *d, int B, int N, int C, hipStream_t st)
+// the grid of a *_sp call: h, w >= 1 or the arguments are invalid; h w over the bound is a shape the kernels do not take (N = h w
+// is formed only below it: no overflow)
+#define CX_REQUIRE_GRID(what)                                                                                                        \
+    do {                                                                                                                             \
+        MREFSR_REQUIRE(h >= 1 && w >= 1, "%s: a grid of %d x %d positions", what, h, w);                                              \
+        if ((int64_t)h * w > MREFSR_CX_MAX_N)                                                                                        \
+            return mrefsr::fail(MREFSR_E_UNSUPPORTED, "%s: a grid of %d x %d positions (h w <= %d: one N x N matrix per sample is "   \
+                                "materialised)", what, h, w, MREFSR_CX_MAX_N);                                                        \
+        MREFSR_REQUIRE(weight_sp >= 0.f && weight_sp < 1.f, "%s: weight_sp=%g (a number in [0, 1))", what, (double)weight_sp);        \
+    } while (0)
+
+// the spatial term of a call: gw = 0 is the plain distance
+struct CxSpatial {
+    int gh, gw;
+    float ws;
+};
+
+void launch_dist(const float *xn, const float *yn, float *d, int B, int N, int C, CxSpatial sp, hipStream_t st)
 {
     const int T = (N + 63) / 64;
-    hipLaunchKernelGGL(cx_dist_kernel, dim3(T, T, B), dim3(256), 0, st, xn, yn, d, N, C, cx_ld(N));
+    if (sp.gw > 0 && sp.ws > 0.f)
+        hipLaunchKernelGGL(cx_dist_kernel<true>, dim3(T, T, B), dim3(256), 0, st, xn, yn, d, N, C, cx_ld(N), sp.gw, 1.0 - (double)sp.ws,
+                           (double)sp.ws, (double)(sp.gh * sp.gh + sp.gw * sp.gw));
+    else
+        hipLaunchKernelGGL(cx_dist_kernel<false>, dim3(T, T, B), dim3(256), 0, st, xn, yn, d, N, C, cx_ld(N), 0, 1.0, 0.0, 1.0);
+}
+
+int cx_forward(const char *what, const float *x, const float *y, int B, int N, int C, float band_width, CxSpatial sp, float *xn, float *yn,
+               float *rnorm, float *rowf, int32_t *jmin, float *cxmax, int32_t *imax, float *cx, float *tap_loss, float weight,
+               float loss_weight, int first, float *run, float *total, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(band_width > 0.f && band_width < INFINITY, "%s: band_width=%g (a finite number > 0)", what, (double)band_width);
+    MREFSR_REQUIRE(workspace_bytes >= mrefsr_contextual_workspace_bytes(B, N, C, 0), "%s: workspace of %ld bytes < %ld", what,
+                   (long)workspace_bytes, (long)mrefsr_contextual_workspace_bytes(B, N, C, 0));
+    MREFSR_REQUIRE((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(xn) |
+                    reinterpret_cast<uintptr_t>(yn) | reinterpret_cast<uintptr_t>(workspace)) % 16 == 0,
+                   "%s: pointers must be 16-byte aligned", what);
+    hipStream_t st = (hipStream_t)stream;
+    const long BN = (long)B * N;
+    const int ld = cx_ld(N);
+    float *mu = (float *)workspace, *d = (float *)((char *)workspace + cx_off_d(B, C));
+    hipLaunchKernelGGL(cx_mean_kernel, dim3(C / 16, B), dim3(1024), 0, st, y, mu, N, C);
+    if (sp.gw > 0 && sp.ws > 0.f)
+        hipLaunchKernelGGL(cx_normalise_kernel<true>, dim3((unsigned)((2 * BN + 3) / 4)), dim3(256), 0, st, x, y, (const float *)mu, xn, yn, rnorm,
+                           BN, N, C);
+    else
+        hipLaunchKernelGGL(cx_normalise_kernel<false>, dim3((unsigned)((2 * BN + 3) / 4)), dim3(256), 0, st, x, y, (const float *)mu, xn, yn, rnorm,
+                           BN, N, C);
+    launch_dist(xn, yn, d, B, N, C, sp, st);
+    hipLaunchKernelGGL(cx_row_kernel, dim3((unsigned)((BN + 3) / 4)), dim3(256), 0, st, (const float *)d, rowf, jmin, BN, N, ld, band_width);
+    hipLaunchKernelGGL(cx_col_kernel, dim3((N + 31) / 32, B), dim3(1024), 0, st, (const float *)d, (const float *)rowf, cxmax, imax, BN, N, ld,
+                       band_width);
+    hipLaunchKernelGGL(cx_finish_kernel, dim3(1), dim3(256), 0, st, (const float *)cxmax, cx, tap_loss, run, total, B, N, weight, loss_weight,
+                       first ? 1 : 0);
+    return mrefsr::check_launch(what);
+}
+
+// (the spatial term is a constant of d: every backward quantity is linear in a, so the factor 1 - ws of d d / d <xn_i, yn_j> rides on coef)
+int cx_backward(const char *what, const float *xn, const float *yn, const float *rnorm, int B, int N, int C, float band_width, CxSpatial sp,
+                const float *rowf, const int32_t *jmin, const float *cxmax, const int32_t *imax, const float *cx, const float *gup, float coef,
+                float *dx, int accumulate, float *amax, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(band_width > 0.f && band_width < INFINITY, "%s: band_width=%g (a finite number > 0)", what, (double)band_width);
+    MREFSR_REQUIRE(workspace_bytes >= mrefsr_contextual_workspace_bytes(B, N, C, 1), "%s: workspace of %ld bytes < %ld", what,
+                   (long)workspace_bytes, (long)mrefsr_contextual_workspace_bytes(B, N, C, 1));
+    MREFSR_REQUIRE((reinterpret_cast<uintptr_t>(xn) | reinterpret_cast<uintptr_t>(yn) | reinterpret_cast<uintptr_t>(dx) |
+                    reinterpret_cast<uintptr_t>(workspace)) % 16 == 0,
+                   "%s: pointers must be 16-byte aligned", what);
+    hipStream_t st = (hipStream_t)stream;
+    const long BN = (long)B * N;
+    const int ld = cx_ld(N);
+    float *d = (float *)((char *)workspace + cx_off_d(B, C)), *dxn = (float *)((char *)workspace + cx_off_dxn(B, N, C));
+    if (sp.gw > 0 && sp.ws > 0.f) coef *= (float)(1.0 - (double)sp.ws);
+    launch_dist(xn, yn, d, B, N, C, sp, st);
+    hipLaunchKernelGGL(cx_rowgrad_kernel, dim3((unsigned)BN), dim3(256), 0, st, d, rowf, jmin, cxmax, imax, cx, gup, coef, BN, B, N, ld,
+                       band_width);
+    hipLaunchKernelGGL(cx_grad_gemm_kernel, dim3((N + 63) / 64, C / 64, B), dim3(256), 0, st, (const float *)d, yn, dxn, N, C, ld);
+    hipLaunchKernelGGL(cx_grad_finish_kernel, dim3((unsigned)((BN + 3) / 4)), dim3(256), 0, st, (const float *)dxn, xn, rnorm, dx, BN, C,
+                       accumulate ? 1 : 0, reinterpret_cast<unsigned int *>(amax));
+    return mrefsr::check_launch(what);
+}
+
+inline int cx_patch_channels(int size) { const int k = 3 * size * size; return k <= 64 ? 64 : k <= 128 ? 128 : k <= 256 ? 256 : 512; }
+
+// image, patch and stride of a cx_patches call: -> MREFSR_OK with oh, ow set
+int cx_patch_geometry(const char *what, int B, int H, int W, int size, int stride, int Cpad, int *oh, int *ow)
+{
+    MREFSR_REQUIRE(B >= 1 && H >= 1 && W >= 1 && size >= 1 && stride >= 1, "%s: B=%d H=%d W=%d size=%d stride=%d", what, B, H, W, size, stride);
+    if (size > 13)
+        return mrefsr::fail(MREFSR_E_UNSUPPORTED, "%s: size=%d (3 size^2 <= 512 channels: size <= 13)", what, size);
+    MREFSR_REQUIRE(size <= H && size <= W, "%s: a patch of %d x %d in an image of %d x %d", what, size, size, H, W);
+    MREFSR_REQUIRE(Cpad == cx_patch_channels(size), "%s: Cpad=%d (size %d: %d)", what, Cpad, size, cx_patch_channels(size));
+    MREFSR_REQUIRE((int64_t)B * 3 * H * W < ((int64_t)1 << 31), "%s: an image batch of %d x 3 x %d x %d", what, B, H, W);
+    *oh = (H - size) / stride + 1, *ow = (W - size) / stride + 1;
+    return MREFSR_OK;
+}
+
+int cx_subsample_geometry(const char *what, int B, int h, int w, int C, int s)
+{
+    MREFSR_REQUIRE(B >= 1 && h >= 1 && w >= 1 && C >= 4 && C % 4 == 0 && s >= 1, "%s: B=%d h=%d w=%d C=%d (a multiple of 4) s=%d", what, B, h,
+                   w, C, s);
+    MREFSR_REQUIRE((int64_t)B * h * w * C < ((int64_t)1 << 33), "%s: a tap of %d x %d x %d x %d", what, B, h, w, C);
+    return MREFSR_OK;
 }
 
 }  // namespace
@@ -403,25 +671,8 @@ MREFSR_EXPORT int mrefsr_contextual_fwd_f32(const float *x, const float *y, int 
     MREFSR_REQUIRE(x && y && xn && yn && rnorm && rowf && jmin && cxmax && imax && cx && tap_loss && run && total && workspace,
                    "contextual_fwd: null pointer");
     CX_REQUIRE_SHAPE("contextual_fwd");
-    MREFSR_REQUIRE(band_width > 0.f && band_width < INFINITY, "contextual_fwd: band_width=%g (a finite number > 0)", (double)band_width);
-    MREFSR_REQUIRE(workspace_bytes >= mrefsr_contextual_workspace_bytes(B, N, C, 0), "contextual_fwd: workspace of %ld bytes < %ld",
-                   (long)workspace_bytes, (long)mrefsr_contextual_workspace_bytes(B, N, C, 0));
-    MREFSR_REQUIRE((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(xn) |
-                    reinterpret_cast<uintptr_t>(yn) | reinterpret_cast<uintptr_t>(workspace)) % 16 == 0,
-                   "contextual_fwd: pointers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const long BN = (long)B * N;
-    const int ld = cx_ld(N);
-    float *mu = (float *)workspace, *d = (float *)((char *)workspace + cx_off_d(B, C));
-    hipLaunchKernelGGL(cx_mean_kernel, dim3(C / 16, B), dim3(1024), 0, st, y, mu, N, C);
-    hipLaunchKernelGGL(cx_normalise_kernel, dim3((unsigned)((2 * BN + 3) / 4)), dim3(256), 0, st, x, y, (const float *)mu, xn, yn, rnorm, BN, N, C);
-    launch_dist(xn, yn, d, B, N, C, st);
-    hipLaunchKernelGGL(cx_row_kernel, dim3((unsigned)((BN + 3) / 4)), dim3(256), 0, st, (const float *)d, rowf, jmin, BN, N, ld, band_width);
-    hipLaunchKernelGGL(cx_col_kernel, dim3((N + 31) / 32, B), dim3(1024), 0, st, (const float *)d, (const float *)rowf, cxmax, imax, BN, N, ld,
-                       band_width);
-    hipLaunchKernelGGL(cx_finish_kernel, dim3(1), dim3(256), 0, st, (const float *)cxmax, cx, tap_loss, run, total, B, N, weight, loss_weight,
-                       first ? 1 : 0);
-    return mrefsr::check_launch("contextual_fwd");
+    return cx_forward("contextual_fwd", x, y, B, N, C, band_width, CxSpatial{0, 0, 0.f}, xn, yn, rnorm, rowf, jmin, cxmax, imax, cx, tap_loss,
+                      weight, loss_weight, first, run, total, workspace, workspace_bytes, stream);
 }
 
 MREFSR_EXPORT int mrefsr_contextual_bwd_f32(const float *xn, const float *yn, const float *rnorm, int B, int N, int C, float band_width,
@@ -431,21 +682,90 @@ MREFSR_EXPORT int mrefsr_contextual_bwd_f32(const float *xn, const float *yn, co
 {
     MREFSR_REQUIRE(xn && yn && rnorm && rowf && jmin && cxmax && imax && cx && dx && workspace, "contextual_bwd: null pointer");
     CX_REQUIRE_SHAPE("contextual_bwd");
-    MREFSR_REQUIRE(band_width > 0.f && band_width < INFINITY, "contextual_bwd: band_width=%g (a finite number > 0)", (double)band_width);
-    MREFSR_REQUIRE(workspace_bytes >= mrefsr_contextual_workspace_bytes(B, N, C, 1), "contextual_bwd: workspace of %ld bytes < %ld",
-                   (long)workspace_bytes, (long)mrefsr_contextual_workspace_bytes(B, N, C, 1));
-    MREFSR_REQUIRE((reinterpret_cast<uintptr_t>(xn) | reinterpret_cast<uintptr_t>(yn) | reinterpret_cast<uintptr_t>(dx) |
-                    reinterpret_cast<uintptr_t>(workspace)) % 16 == 0,
-                   "contextual_bwd: pointers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const long BN = (long)B * N;
-    const int ld = cx_ld(N);
-    float *d = (float *)((char *)workspace + cx_off_d(B, C)), *dxn = (float *)((char *)workspace + cx_off_dxn(B, N, C));
-    launch_dist(xn, yn, d, B, N, C, st);
-    hipLaunchKernelGGL(cx_rowgrad_kernel, dim3((unsigned)BN), dim3(256), 0, st, d, rowf, jmin, cxmax, imax, cx, gup, coef, BN, B, N, ld,
-                       band_width);
-    hipLaunchKernelGGL(cx_grad_gemm_kernel, dim3((N + 63) / 64, C / 64, B), dim3(256), 0, st, (const float *)d, yn, dxn, N, C, ld);
-    hipLaunchKernelGGL(cx_grad_finish_kernel, dim3((unsigned)((BN + 3) / 4)), dim3(256), 0, st, (const float *)dxn, xn, rnorm, dx, BN, C,
-                       accumulate ? 1 : 0, reinterpret_cast<unsigned int *>(amax));
-    return mrefsr::check_launch("contextual_bwd");
+    return cx_backward("contextual_bwd", xn, yn, rnorm, B, N, C, band_width, CxSpatial{0, 0, 0.f}, rowf, jmin, cxmax, imax, cx, gup, coef, dx,
+                       accumulate, amax, workspace, workspace_bytes, stream);
+}
+
+MREFSR_EXPORT int mrefsr_contextual_fwd_sp_f32(const float *x, const float *y, int B, int h, int w, int C, float band_width, float weight_sp,
+                                               float *xn, float *yn, float *rnorm, float *rowf, int32_t *jmin, float *cxmax, int32_t *imax,
+                                               float *cx, float *tap_loss, float weight, float loss_weight, int first, float *run, float *total,
+                                               void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(x && y && xn && yn && rnorm && rowf && jmin && cxmax && imax && cx && tap_loss && run && total && workspace,
+                   "contextual_fwd_sp: null pointer");
+    CX_REQUIRE_GRID("contextual_fwd_sp");
+    const int N = h * w;
+    CX_REQUIRE_SHAPE("contextual_fwd_sp");
+    return cx_forward("contextual_fwd_sp", x, y, B, N, C, band_width, CxSpatial{h, w, weight_sp}, xn, yn, rnorm, rowf, jmin, cxmax, imax, cx,
+                      tap_loss, weight, loss_weight, first, run, total, workspace, workspace_bytes, stream);
+}
+
+MREFSR_EXPORT int mrefsr_contextual_bwd_sp_f32(const float *xn, const float *yn, const float *rnorm, int B, int h, int w, int C,
+                                               float band_width, float weight_sp, const float *rowf, const int32_t *jmin, const float *cxmax,
+                                               const int32_t *imax, const float *cx, const float *gup, float coef, float *dx, int accumulate,
+                                               float *amax, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(xn && yn && rnorm && rowf && jmin && cxmax && imax && cx && dx && workspace, "contextual_bwd_sp: null pointer");
+    CX_REQUIRE_GRID("contextual_bwd_sp");
+    const int N = h * w;
+    CX_REQUIRE_SHAPE("contextual_bwd_sp");
+    return cx_backward("contextual_bwd_sp", xn, yn, rnorm, B, N, C, band_width, CxSpatial{h, w, weight_sp}, rowf, jmin, cxmax, imax, cx, gup,
+                       coef, dx, accumulate, amax, workspace, workspace_bytes, stream);
+}
+
+MREFSR_EXPORT int mrefsr_cx_patch_channels(int size)
+{
+    if (size < 1) return MREFSR_E_INVALID;
+    return size > 13 ? MREFSR_E_UNSUPPORTED : cx_patch_channels(size);
+}
+
+MREFSR_EXPORT int mrefsr_cx_patches_f32(const float *img, int B, int H, int W, int size, int stride, int norm, float *out, int Cpad,
+                                        mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(img && out, "cx_patches: null pointer");
+    int oh, ow;
+    if (const int e = cx_patch_geometry("cx_patches", B, H, W, size, stride, Cpad, &oh, &ow)) return e;
+    MREFSR_REQUIRE(reinterpret_cast<uintptr_t>(out) % 16 == 0, "cx_patches: out must be 16-byte aligned");
+    const long total4 = (long)B * oh * ow * (Cpad / 4);
+    hipLaunchKernelGGL(cx_patches_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, out, total4, H, W, size,
+                       stride, oh, ow, Cpad, norm ? 1 : 0);
+    return mrefsr::check_launch("cx_patches");
+}
+
+MREFSR_EXPORT int mrefsr_cx_patches_bwd_f32(const float *g, int B, int H, int W, int size, int stride, int Cpad, float scale, float *dimg,
+                                            int accumulate, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(g && dimg, "cx_patches_bwd: null pointer");
+    int oh, ow;
+    if (const int e = cx_patch_geometry("cx_patches_bwd", B, H, W, size, stride, Cpad, &oh, &ow)) return e;
+    const long total = (long)B * 3 * H * W;
+    hipLaunchKernelGGL(cx_patches_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, dimg, total, H, W, size,
+                       stride, oh, ow, Cpad, scale, accumulate ? 1 : 0);
+    return mrefsr::check_launch("cx_patches_bwd");
+}
+
+MREFSR_EXPORT int mrefsr_cx_subsample_f32(const float *f, int B, int h, int w, int C, int s, float *out, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(f && out, "cx_subsample: null pointer");
+    if (const int e = cx_subsample_geometry("cx_subsample", B, h, w, C, s)) return e;
+    MREFSR_REQUIRE((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(out)) % 16 == 0, "cx_subsample: pointers must be 16-byte aligned");
+    const int hs = (h + s - 1) / s, ws = (w + s - 1) / s;
+    const long total4 = (long)B * hs * ws * (C / 4);
+    hipLaunchKernelGGL(cx_subsample_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, out, total4, h, w, C / 4,
+                       s, hs, ws);
+    return mrefsr::check_launch("cx_subsample");
+}
+
+MREFSR_EXPORT int mrefsr_cx_subsample_bwd_f32(const float *gs, int B, int h, int w, int C, int s, float *g, int accumulate, float *amax,
+                                              mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(gs && g, "cx_subsample_bwd: null pointer");
+    if (const int e = cx_subsample_geometry("cx_subsample_bwd", B, h, w, C, s)) return e;
+    MREFSR_REQUIRE((reinterpret_cast<uintptr_t>(gs) | reinterpret_cast<uintptr_t>(g)) % 16 == 0,
+                   "cx_subsample_bwd: pointers must be 16-byte aligned");
+    const int hs = (h + s - 1) / s, ws = (w + s - 1) / s;
+    const long total4 = (long)B * h * w * (C / 4);
+    hipLaunchKernelGGL(cx_subsample_bwd_kernel, dim3((unsigned)((total4 + 256 * CX_SUB_ITEMS - 1) / (256 * CX_SUB_ITEMS))), dim3(256), 0, (hipStream_t)stream, gs, g, total4, h, w,
+                       C / 4, s, hs, ws, accumulate ? 1 : 0, reinterpret_cast<unsigned int *>(amax));
+    return mrefsr::check_launch("cx_subsample_bwd");
 }

@@ -1976,17 +1976,26 @@ def _cx_workspace(name, b, n, c, backward):
     return need
 
 
-def contextual_fwd(x, y, band_width, weight=1.0, loss_weight=1.0, run=None):
+def _cx_weight_sp(name, weight_sp):
+    if isinstance(weight_sp, bool) or not isinstance(weight_sp, (int, float)) or not (0.0 <= weight_sp < 1.0):
+        raise ValueError(f'{name}: weight_sp={weight_sp!r} is not a number in [0, 1)')
+    return float(weight_sp)
+
+
+def contextual_fwd(x, y, band_width, weight=1.0, loss_weight=1.0, run=None, weight_sp=0.0):
     """one tap of the contextual loss: x (features of the output), y (of the target) [B,h,w,C] contiguous fp32, C of 64 ... 512, h w
     of 2 ... CX_MAX_N -> (total, saved).  run: None for the first tap of a loss, else the running sum the previous tap's call
     returned as saved['run'] (updated in place: run += tap loss * weight); total [1] = run * loss_weight.  saved: what
-    contextual_bwd reads (xn, yn, rnorm, rowf = m | Z, jmin, cxmax, imax, cx [B], tap_loss [1], run).  Six
-    launches, fixed summation orders (the same bits from call to call), nothing read back; x and y are only read"""
+    contextual_bwd reads (xn, yn, rnorm, rowf = m | Z, jmin, cxmax, imax, cx [B], tap_loss [1], run).  weight_sp in [0, 1): CoBi's
+    spatial term, d = (1 - weight_sp) (1 - <xn_i, yn_j>) + weight_sp |p_i - p_j|^2 / (h^2 + w^2) on the map's own h x w grid
+    (0: the plain entry point; > 0: the norms and the product are taken in double, see csrc/contextual.hip).  Six launches, fixed summation orders (the same bits from call to call), nothing read back; x and y
+    are only read"""
     _chk('contextual_fwd', x, y, run)
     if x.dim() != 4 or x.shape != y.shape:
         raise ValueError(f'contextual_fwd: two [B,h,w,C] maps of one shape expected, got {tuple(x.shape)} and {tuple(y.shape)}')
     if not (isinstance(band_width, (int, float)) and 0.0 < band_width < float('inf')):
         raise ValueError(f'contextual_fwd: band_width={band_width!r} is not a finite number > 0')
+    weight_sp = _cx_weight_sp('contextual_fwd', weight_sp)
     b, h, w, c = x.shape
     n, dev = h * w, x.device
     need = _cx_workspace('contextual_fwd', b, n, c, False)
@@ -1997,20 +2006,25 @@ def contextual_fwd(x, y, band_width, weight=1.0, loss_weight=1.0, run=None):
              run=run if run is not None else torch.empty(1, **f32))
     total = torch.empty(1, **f32)
     ws = _scratch(dev, need)
+    outs = (_p(s['xn']), _p(s['yn']), _p(s['rnorm']), _p(s['rowf']), _p(s['jmin']), _p(s['cxmax']), _p(s['imax']), _p(s['cx']),
+            _p(s['tap_loss']), C.c_float(weight), C.c_float(loss_weight), 1 if run is None else 0, _p(s['run']), _p(total), _p(ws),
+            C.c_int64(need), _stream())
     with _timed('contextual_fwd', 2.0 * b * n * n * c, detail=True, nbytes=4.0 * (4 * x.numel() + 3 * b * n * n)):
-        _lib.call('mrefsr_contextual_fwd_f32', _p(x), _p(y), b, n, c, C.c_float(band_width), _p(s['xn']), _p(s['yn']), _p(s['rnorm']),
-                  _p(s['rowf']), _p(s['jmin']), _p(s['cxmax']), _p(s['imax']), _p(s['cx']), _p(s['tap_loss']), C.c_float(weight),
-                  C.c_float(loss_weight), 1 if run is None else 0, _p(s['run']), _p(total), _p(ws), C.c_int64(need), _stream())
+        if weight_sp == 0.0:
+            _lib.call('mrefsr_contextual_fwd_f32', _p(x), _p(y), b, n, c, C.c_float(band_width), *outs)
+        else:
+            _lib.call('mrefsr_contextual_fwd_sp_f32', _p(x), _p(y), b, h, w, c, C.c_float(band_width), C.c_float(weight_sp), *outs)
     return total, s
 
 
-def contextual_bwd(saved, band_width, coef, dx, gup=None, accumulate=False, want_amax=True):
+def contextual_bwd(saved, band_width, coef, dx, gup=None, accumulate=False, want_amax=True, weight_sp=0.0):
     """dx [B,h,w,C] (+)= d (gup * coef * tap loss) / d x of contextual_fwd from its ``saved`` (the distances are recomputed); coef:
-    loss_weight times the tap's weight; gup: a one-element fp32 device tensor or None (= 1).  Four launches, fixed orders.
-    -> max |dx| [1] | None"""
+    loss_weight times the tap's weight; gup: a one-element fp32 device tensor or None (= 1); weight_sp: the forward call's.  Four
+    launches, fixed orders.  -> max |dx| [1] | None"""
     names = ('xn', 'yn', 'rnorm', 'rowf', 'cxmax', 'cx')
     _chk('contextual_bwd', dx, gup, *[saved[k] for k in names])
     _chk('contextual_bwd', saved['jmin'], saved['imax'], dtype=torch.int32)
+    weight_sp = _cx_weight_sp('contextual_bwd', weight_sp)
     xn = saved['xn']
     b, h, w, c = xn.shape
     n = h * w
@@ -2019,10 +2033,95 @@ def contextual_bwd(saved, band_width, coef, dx, gup=None, accumulate=False, want
     need = _cx_workspace('contextual_bwd', b, n, c, True)
     amax = zeros_f32(dx.device, 1) if want_amax else None
     ws = _scratch(dx.device, need)
+    rest = (_p(saved['rowf']), _p(saved['jmin']), _p(saved['cxmax']), _p(saved['imax']), _p(saved['cx']), _p(gup), C.c_float(coef), _p(dx),
+            1 if accumulate else 0, _p(amax), _p(ws), C.c_int64(need), _stream())
     with _timed('contextual_bwd', 4.0 * b * n * n * c, detail=True, nbytes=4.0 * (4 * xn.numel() + 3 * b * n * n)):
-        _lib.call('mrefsr_contextual_bwd_f32', _p(xn), _p(saved['yn']), _p(saved['rnorm']), b, n, c, C.c_float(band_width), _p(saved['rowf']),
-                  _p(saved['jmin']), _p(saved['cxmax']), _p(saved['imax']), _p(saved['cx']), _p(gup), C.c_float(coef), _p(dx),
-                  1 if accumulate else 0, _p(amax), _p(ws), C.c_int64(need), _stream())
+        if weight_sp == 0.0:
+            _lib.call('mrefsr_contextual_bwd_f32', _p(xn), _p(saved['yn']), _p(saved['rnorm']), b, n, c, C.c_float(band_width), *rest)
+        else:
+            _lib.call('mrefsr_contextual_bwd_sp_f32', _p(xn), _p(saved['yn']), _p(saved['rnorm']), b, h, w, c, C.c_float(band_width),
+                      C.c_float(weight_sp), *rest)
+    return amax
+
+
+def cx_patch_channels(size):
+    """the channel count of size x size RGB patches as features of a contextual tap: the smallest of 64, 128, 256, 512 >= 3 size^2"""
+    if isinstance(size, bool) or not isinstance(size, int) or size < 1:
+        raise ValueError(f'cx_patches: size={size!r} is not an integer >= 1')
+    c = _lib.load().mrefsr_cx_patch_channels(size)
+    if c < 0:
+        raise NotImplementedError(f'cx_patches: patches of {size} x {size} have {3 * size * size} channels; at most 512 (size <= 13)')
+    return c
+
+
+def _cx_patch_geometry(name, shape, size, stride):
+    cpad = cx_patch_channels(size)
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+        raise ValueError(f'{name}: stride={stride!r} is not an integer >= 1')
+    if len(shape) != 4 or shape[1] != 3 or shape[0] < 1 or shape[2] < size or shape[3] < size:
+        raise ValueError(f'{name}: a [B,3,H,W] image with H, W >= {size} expected, got {tuple(shape)}')
+    return cpad, (shape[2] - size) // stride + 1, (shape[3] - size) // stride + 1
+
+
+def cx_patches(img, size, stride, norm_img=False):
+    """img [B,3,H,W] -> its size x size patches at ``stride`` as NHWC features [B,oh,ow,Cpad], oh = (H - size) // stride + 1: the
+    channels in F.unfold's (c, dy, dx) order, zeros from 3 size^2 on (Cpad = cx_patch_channels(size)); norm_img: (img + 1) * 0.5
+    first.  One launch"""
+    _chk('cx_patches', img)
+    cpad, oh, ow = _cx_patch_geometry('cx_patches', img.shape, size, stride)
+    b, _, h, w = img.shape
+    out = torch.empty((b, oh, ow, cpad), device=img.device, dtype=torch.float32)
+    with _timed('cx_patches', detail=True, nbytes=4.0 * (img.numel() + out.numel())):
+        _lib.call('mrefsr_cx_patches_f32', _p(img), b, h, w, size, stride, 1 if norm_img else 0, _p(out), cpad, _stream())
+    return out
+
+
+def cx_patches_bwd(g, shape, size, stride, scale=1.0, out=None):
+    """the adjoint of cx_patches: g [B,oh,ow,Cpad] -> d / d img [B,3,H,W] (``shape``) times ``scale``; per pixel the covering patch
+    entries are added in ascending (patch row, patch column) order (a gather: no atomics), a pixel no patch covers gets 0.  out:
+    a gradient image to add into (None: a new one is written).  One launch"""
+    _chk('cx_patches_bwd', g, out)
+    cpad, oh, ow = _cx_patch_geometry('cx_patches_bwd', tuple(shape), size, stride)
+    b, _, h, w = shape
+    if tuple(g.shape) != (b, oh, ow, cpad) or (out is not None and tuple(out.shape) != tuple(shape)):
+        raise ValueError(f'cx_patches_bwd: a gradient of {(b, oh, ow, cpad)} and an image of {tuple(shape)} expected, got {tuple(g.shape)}')
+    acc = out is not None
+    if out is None:
+        out = torch.empty(tuple(shape), device=g.device, dtype=torch.float32)
+    with _timed('cx_patches_bwd', detail=True, nbytes=4.0 * (g.numel() + out.numel())):
+        _lib.call('mrefsr_cx_patches_bwd_f32', _p(g), b, h, w, size, stride, cpad, C.c_float(scale), _p(out), 1 if acc else 0, _stream())
+    return out
+
+
+def _cx_stride(name, f, s):
+    if isinstance(s, bool) or not isinstance(s, int) or s < 1:
+        raise ValueError(f'{name}: stride={s!r} is not an integer >= 1')
+    if f.dim() != 4 or f.shape[3] % 4 or f.numel() == 0:
+        raise ValueError(f'{name}: a [B,h,w,C] map with C a multiple of 4 expected, got {tuple(f.shape)}')
+
+
+def cx_subsample(f, s):
+    """f [B,h,w,C] -> its positions (r s, c s): [B,ceil(h / s),ceil(w / s),C].  One launch"""
+    _chk('cx_subsample', f)
+    _cx_stride('cx_subsample', f, s)
+    b, h, w, c = f.shape
+    out = torch.empty((b, (h + s - 1) // s, (w + s - 1) // s, c), device=f.device, dtype=torch.float32)
+    with _timed('cx_subsample', detail=True, nbytes=8.0 * out.numel()):
+        _lib.call('mrefsr_cx_subsample_f32', _p(f), b, h, w, c, s, _p(out), _stream())
+    return out
+
+
+def cx_subsample_bwd(gs, g, s, accumulate=False, want_amax=True):
+    """the adjoint of cx_subsample into the tap's gradient buffer g [B,h,w,C]: written (gs at the sampled positions, zeros elsewhere)
+    or, with accumulate, gs added at the sampled positions only.  -> max |g| [1] over the whole buffer | None.  One launch"""
+    _chk('cx_subsample_bwd', gs, g)
+    _cx_stride('cx_subsample_bwd', g, s)
+    b, h, w, c = g.shape
+    if tuple(gs.shape) != (b, (h + s - 1) // s, (w + s - 1) // s, c):
+        raise ValueError(f'cx_subsample_bwd: a gradient of {(b, (h + s - 1) // s, (w + s - 1) // s, c)} expected, got {tuple(gs.shape)}')
+    amax = zeros_f32(g.device, 1) if want_amax else None
+    with _timed('cx_subsample_bwd', detail=True, nbytes=4.0 * (gs.numel() + 2 * g.numel())):
+        _lib.call('mrefsr_cx_subsample_bwd_f32', _p(gs), b, h, w, c, s, _p(g), 1 if accumulate else 0, _p(amax), _stream())
     return amax
 
 

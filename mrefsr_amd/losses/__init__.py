@@ -7,11 +7,11 @@ from copy import deepcopy
 from ..utils.registry import LOSS_REGISTRY
 from .losses import (CharbonnierLoss, ContextualLoss, FFTLoss, FocalFrequencyLoss, GANLoss, GradientPenaltyLoss, L1Loss, LDLLoss, MSELoss, PerceptualLoss, SSIMLoss, TextureLoss,
                      gradient_penalty_loss, ldl_artifact_map_torch, ldl_loss_torch, r1_penalty, ssim_loss_torch,
-                     fft_loss_torch, focal_frequency_loss_torch, focal_frequency_weight_torch, contextual_loss_torch)
+                     fft_loss_torch, focal_frequency_loss_torch, focal_frequency_weight_torch, contextual_loss_torch, cx_patches_torch)
 
 __all__ = ['build_loss', 'LOSS_REGISTRY', 'L1Loss', 'MSELoss', 'CharbonnierLoss', 'PerceptualLoss', 'TextureLoss', 'SSIMLoss', 'LDLLoss', 'FFTLoss', 'FocalFrequencyLoss', 'ContextualLoss', 'GANLoss',
            'GradientPenaltyLoss', 'gradient_penalty_loss', 'r1_penalty', 'ssim_loss_torch', 'ldl_artifact_map_torch', 'ldl_loss_torch',
-           'fft_loss_torch', 'focal_frequency_loss_torch', 'focal_frequency_weight_torch', 'contextual_loss_torch']
+           'fft_loss_torch', 'focal_frequency_loss_torch', 'focal_frequency_weight_torch', 'contextual_loss_torch', 'cx_patches_torch']
 
 
 def build_loss(opt):

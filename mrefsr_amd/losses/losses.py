@@ -386,7 +386,11 @@ def _lowest_index_of(hit, dim):
     return torch.where(hit, idx, torch.full_like(idx, n)).amin(dim)
 
 
-def contextual_loss_torch(x_feats, y_feats, band_width=0.5, jmin=None, imax=None, parts=False):
+def _is_weight_sp(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and 0.0 <= v < 1.0
+
+
+def contextual_loss_torch(x_feats, y_feats, band_width=0.5, jmin=None, imax=None, parts=False, weight_sp=0.0):
     """The contextual loss of one tap (Mechrez et al., "The Contextual Loss for Image Transformation with Non-Aligned Data", ECCV
     2018) as torch operations in the tensors' dtype and on their device: the definition ContextualLoss implements.  x_feats
     (features of the output) and y_feats (of the target, a constant) [B,C,h,w], N = h w; i runs over positions of x, j of y.
@@ -394,14 +398,25 @@ def contextual_loss_torch(x_feats, y_feats, band_width=0.5, jmin=None, imax=None
         d[b,i,j] = 1 - <xn[b,:,i], yn[b,:,j]>;  m[b,i] = min_j d at jmin[b,i] (the lowest j on ties);
         w = exp((1 - d / (m + 1e-5)) / band_width);  cx = w / sum_j w;
         CX[b] = mean_j max_i cx[b,i,j] (the maximum at imax[b,j], the lowest i on ties);  loss = mean_b -log(CX[b] + 1e-5).
+    weight_sp = ws in [0, 1) makes it the contextual bilateral loss, CoBi (Zhang et al., "Zoom to Learn, Learn to Zoom", ICCV 2019):
+    with i = r_i w + c_i on the map's own grid,
+        d_sp[i,j] = ((r_i - r_j)^2 + (c_i - c_j)^2) / (h^2 + w^2)   (an integer numerator, one division; in [0, 1));
+        d[b,i,j]  = (1 - ws) (1 - <xn_i, yn_j>) + ws d_sp[i,j],
+    and the row minimum, w, the normaliser, the column maximum and -log run on this d unchanged.  As in the authors' code the RAW
+    distances are mixed and the mix is then made relative -- not a mix of two CX matrices; the normalisation of the squared offset by
+    the grid's squared diagonal is this project's (the term is in [0, 1) like the cosine distance of centred features is in
+    [0, 2], whatever the tap's size).  ws = 0 evaluates the expressions above as they stand.
     The gradient reaches x_feats only: through the selected element of each column, that row's normaliser, the row minimum at jmin,
-    the normalisation and the centring.  jmin [B,N] / imax [B,N] (integer tensors): given selections in place of the computed ones
-    (the values, and so the gradient, route through them).  parts: -> (loss, dict(jmin, imax, CX [B], d [B,N,N], cx [B,N,N]))."""
+    the normalisation and the centring (d_sp is a constant).  jmin [B,N] / imax [B,N] (integer tensors): given selections in place
+    of the computed ones (the values, and so the gradient, route through them).  parts: -> (loss, dict(jmin, imax, CX [B],
+    d [B,N,N], cx [B,N,N]))."""
     if x_feats.dim() != 4 or x_feats.shape != y_feats.shape:
         raise ValueError(f'contextual_loss_torch: two [B,C,h,w] feature maps of one shape expected, got {tuple(x_feats.shape)} and '
                          f'{tuple(y_feats.shape)}')
     if not (isinstance(band_width, (int, float)) and not isinstance(band_width, bool) and 0.0 < band_width < float('inf')):
         raise ValueError(f'contextual_loss_torch: band_width={band_width!r} is not a finite number > 0')
+    if not _is_weight_sp(weight_sp):
+        raise ValueError(f'contextual_loss_torch: weight_sp={weight_sp!r} is not a number in [0, 1)')
     b, c = x_feats.shape[:2]
     x, y = x_feats.reshape(b, c, -1), y_feats.detach().reshape(b, c, -1)
     if x.shape[2] < 2:
@@ -411,6 +426,12 @@ def contextual_loss_torch(x_feats, y_feats, band_width=0.5, jmin=None, imax=None
     xn = xc / xc.norm(dim=1, keepdim=True).clamp_min(1e-12)
     yn = yc / yc.norm(dim=1, keepdim=True).clamp_min(1e-12)
     d = 1.0 - torch.bmm(xn.transpose(1, 2), yn)                                # [B, i, j]
+    if weight_sp != 0:
+        gh, gw = x_feats.shape[2:]
+        p = torch.arange(gh * gw, device=d.device)
+        r, q = p // gw, p % gw
+        num = (r[:, None] - r[None, :]) ** 2 + (q[:, None] - q[None, :]) ** 2   # [i, j], integers
+        d = (1.0 - weight_sp) * d + weight_sp * (num.to(d.dtype) / float(gh * gh + gw * gw))
     if jmin is None:
         jmin = _lowest_index_of(d == d.amin(2, keepdim=True), 2)
     m = d.gather(2, jmin.long().unsqueeze(2))                                  # [B, i, 1]
@@ -425,32 +446,88 @@ def contextual_loss_torch(x_feats, y_feats, band_width=0.5, jmin=None, imax=None
     return loss
 
 
+def cx_patches_torch(img, size, stride):
+    """img [B,3,H,W] -> its size x size patches at ``stride`` as a feature map [B, 3 size^2, oh, ow], oh = (H - size) // stride + 1,
+    ow likewise, the channels in F.unfold's (c, dy, dx) order: what the RGB tap of ContextualLoss (rgb_patch) compares"""
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError(f'cx_patches_torch: a [B,3,H,W] image expected, got {tuple(img.shape)}')
+    for name, v in (('size', size), ('stride', stride)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f'cx_patches_torch: {name}={v!r} is not an integer >= 1')
+    b, _, h, w = img.shape
+    if h < size or w < size:
+        raise ValueError(f'cx_patches_torch: patches of {size} x {size} in an image of {h} x {w}')
+    oh, ow = (h - size) // stride + 1, (w - size) // stride + 1
+    rows = (torch.arange(oh, device=img.device) * stride)[:, None] + torch.arange(size, device=img.device)[None, :]   # [oh, dy]
+    cols = (torch.arange(ow, device=img.device) * stride)[:, None] + torch.arange(size, device=img.device)[None, :]   # [ow, dx]
+    p = img[:, :, rows[:, :, None, None], cols[None, None, :, :]]              # [B, 3, oh, dy, ow, dx]
+    return p.permute(0, 1, 3, 5, 2, 4).reshape(b, 3 * size * size, oh, ow)
+
+
 @LOSS_REGISTRY.register()
 class ContextualLoss(nn.Module):
-    """loss_weight * sum_k layer_weights[k] * contextual_loss(VGG_k(x), VGG_k(gt)) over the named VGG taps in network order: the
-    contextual loss of Mechrez et al. (ECCV 2018) with the cosine distance, the non-local term for targets that are not registered
-    with the output to the pixel (contextual_loss_torch spells one tap out; the feature means are taken per sample, so a sample's
-    loss and gradient are those it would get alone).  gt is a constant (detached); the gradient reaches x, once.  The VGG handling is
-    PerceptualLoss's (taps are the named layers, conv taps before their ReLU; norm_img: (x + 1) * 0.5 on both images first).
+    """loss_weight * (rgb_patch.weight * tap_rgb + sum_k layer_weights[k] * contextual_loss(VGG_k(x), VGG_k(gt))), the RGB tap first,
+    the named VGG taps in network order: the contextual loss of Mechrez et al. (ECCV 2018) with the cosine distance, the non-local
+    term for targets that are not registered with the output to the pixel (contextual_loss_torch spells one tap out; the feature
+    means are taken per sample, so a sample's loss and gradient are those it would get alone).  gt is a constant (detached); the
+    gradient reaches x, once.  The VGG handling is PerceptualLoss's (taps are the named layers, conv taps before their ReLU;
+    norm_img: (x + 1) * 0.5 on both images first).
+
+    The three options of the contextual bilateral loss, CoBi (Zhang et al., "Zoom to Learn, Learn to Zoom", ICCV 2019):
+      weight_sp   in [0, 1): the weight of the spatial term in every tap's distance (contextual_loss_torch), on the grid the tap is
+                  evaluated on -- the strided or the patch grid.  0: the plain loss, on the plain kernels.
+      tap_stride  {layer name: s >= 1}: that tap is evaluated on its positions (r s, c s) only; 1 where a name is absent.  Shallow
+                  taps (relu2_2 of a 160^2 GT: 6400 positions) fit the bound of hip.CX_MAX_N positions that way.
+      rgb_patch   {size, stride, weight}: one more tap, CoBi_RGB: the size x size patches of the images as given (after norm_img,
+                  without the ImageNet mean / std) at that stride as features of 3 size^2 channels (cx_patches_torch).  With it
+                  layer_weights may be empty: no VGG is built then.
 
     Everything runs on the VGG node of the training engine (archs/nhwc_train.py: _VggContextual) and the kernels of
     csrc/contextual.hip: the all-pairs similarity and the gradient product on the f32 MFMA, fixed summation orders (the same bits
-    from call to call).  A tap may have at most hip.CX_MAX_N positions (relu3 / conv3 taps of 256^2 images).
+    from call to call).  A tap may have at most hip.CX_MAX_N positions on the grid it is evaluated on (relu3 / conv3 taps of 256^2
+    images at stride 1).
 
-    Refused: batch-normalised VGGs, CPU tensors, non-fp32 tensors on the GPU, a tap over the bound (NotImplementedError); inputs that
-    are not [B,3,H,W], differing shapes, a band_width that is not a finite number > 0, empty layer_weights (ValueError)."""
+    Refused: batch-normalised VGGs, CPU tensors, non-fp32 tensors on the GPU, a tap over the bound (the message names the tap and
+    suggests a stride), patches of more than 512 channels (size > 13) (NotImplementedError); inputs that are not [B,3,H,W],
+    differing shapes, a band_width that is not a finite number > 0, a weight_sp outside [0, 1), a stride or size that is not an
+    integer >= 1, a tap_stride for a layer that is no tap, empty layer_weights without rgb_patch (ValueError)."""
 
-    def __init__(self, layer_weights, vgg_type='vgg19', use_input_norm=True, norm_img=False, band_width=0.5, loss_weight=1.0):
+    def __init__(self, layer_weights, vgg_type='vgg19', use_input_norm=True, norm_img=False, band_width=0.5, loss_weight=1.0,
+                 weight_sp=0.0, tap_stride=None, rgb_patch=None):
         super().__init__()
-        if not isinstance(layer_weights, dict) or not layer_weights:
-            raise ValueError(f'ContextualLoss: layer_weights={layer_weights!r}; a non-empty dict of VGG layer names and weights')
+        if not isinstance(layer_weights, dict) or (not layer_weights and rgb_patch is None):
+            raise ValueError(f'ContextualLoss: layer_weights={layer_weights!r}; a non-empty dict of VGG layer names and weights (it '
+                             'may be empty with rgb_patch)')
         if isinstance(band_width, bool) or not isinstance(band_width, (int, float)) or not (0.0 < band_width < float('inf')):
             raise ValueError(f'ContextualLoss: band_width={band_width!r} is not a finite number > 0')
-        if 'bn' in vgg_type:
+        if not _is_weight_sp(weight_sp):
+            raise ValueError(f'ContextualLoss: weight_sp={weight_sp!r} is not a number in [0, 1)')
+        if tap_stride is not None:
+            if not isinstance(tap_stride, dict) or any(n not in layer_weights for n in tap_stride):
+                raise ValueError(f'ContextualLoss: tap_stride={tap_stride!r}; a dict of strides for taps of layer_weights '
+                                 f'{sorted(layer_weights)}')
+            for n, s in tap_stride.items():
+                if isinstance(s, bool) or not isinstance(s, int) or s < 1:
+                    raise ValueError(f'ContextualLoss: tap {n}: tap_stride={s!r} is not an integer >= 1')
+        if rgb_patch is not None:
+            if not isinstance(rgb_patch, dict) or 'size' not in rgb_patch or set(rgb_patch) - {'size', 'stride', 'weight'}:
+                raise ValueError(f'ContextualLoss: rgb_patch={rgb_patch!r}; a dict of size, stride (1) and weight (1.0)')
+            rgb_patch = dict(size=rgb_patch['size'], stride=rgb_patch.get('stride', 1), weight=rgb_patch.get('weight', 1.0))
+            for k in ('size', 'stride'):
+                if isinstance(rgb_patch[k], bool) or not isinstance(rgb_patch[k], int) or rgb_patch[k] < 1:
+                    raise ValueError(f'ContextualLoss: tap rgb_patch: {k}={rgb_patch[k]!r} is not an integer >= 1')
+            if isinstance(rgb_patch['weight'], bool) or not isinstance(rgb_patch['weight'], (int, float)):
+                raise ValueError(f'ContextualLoss: tap rgb_patch: weight={rgb_patch["weight"]!r} is not a number')
+            if 3 * rgb_patch['size'] ** 2 > 512:
+                raise NotImplementedError(f'ContextualLoss: tap rgb_patch: patches of size {rgb_patch["size"]} have '
+                                          f'{3 * rgb_patch["size"] ** 2} channels; at most 512 (size <= 13)')
+        if layer_weights and 'bn' in vgg_type:
             raise NotImplementedError(f'ContextualLoss: vgg_type {vgg_type} (batch-normalised VGGs have no kernel here)')
         self.layer_weights, self.norm_img = layer_weights, norm_img
         self.band_width, self.loss_weight = float(band_width), loss_weight
-        self.vgg = VGGFeatureExtractor(layer_name_list=list(layer_weights.keys()), vgg_type=vgg_type, use_input_norm=use_input_norm)
+        self.weight_sp, self.tap_stride, self.rgb_patch = float(weight_sp), dict(tap_stride or {}), rgb_patch
+        self.vgg = VGGFeatureExtractor(layer_name_list=list(layer_weights.keys()), vgg_type=vgg_type,
+                                       use_input_norm=use_input_norm) if layer_weights else None
         self._plan = None
 
     def forward(self, x, gt):
@@ -465,8 +542,9 @@ class ContextualLoss(nn.Module):
         if not (x.dtype == gt.dtype == torch.float32):
             raise NotImplementedError(f'ContextualLoss: {x.dtype} / {gt.dtype} images; fp32 only on the GPU')
         if self._plan is None:
-            self._plan = nhwc_train.ContextualLossPlan(self.vgg.vgg_net, self.layer_weights, self.band_width, self.loss_weight,
-                                                       self.norm_img)
+            self._plan = nhwc_train.ContextualLossPlan(self.vgg.vgg_net if self.vgg is not None else None, self.layer_weights,
+                                                       self.band_width, self.loss_weight, self.norm_img, weight_sp=self.weight_sp,
+                                                       tap_stride=self.tap_stride, rgb_patch=self.rgb_patch)
         return nhwc_train.contextual(self.vgg, x, gt.detach(), self._plan)[0]
 
 

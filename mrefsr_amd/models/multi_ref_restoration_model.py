@@ -425,7 +425,8 @@ class MultiRefRestorationModel:
         self.cri_ssim = losses.SSIMLoss(**train_opt['ssim_opt']).to(self.device) if train_opt.get('ssim_opt') else None
         self.cri_ldl = self._build_ldl(train_opt)
         self.cri_freq = self._build_freq(train_opt)
-        # ContextualLoss: train.contextual_opt holds its constructor's keys (layer_weights, vgg_type, use_input_norm, norm_img, band_width, loss_weight)
+        # ContextualLoss: train.contextual_opt holds its constructor's keys (layer_weights, vgg_type, use_input_norm, norm_img, band_width,
+        # loss_weight, and CoBi's weight_sp, tap_stride = {layer: s}, rgb_patch = {size, stride, weight})
         self.cri_contextual = losses.ContextualLoss(**train_opt['contextual_opt']).to(self.device) if train_opt.get('contextual_opt') else None
         self.net_g_pretrain_steps = train_opt['net_g_pretrain_steps']
         self.net_d_steps = train_opt.get('net_d_steps', 1)
