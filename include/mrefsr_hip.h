@@ -1039,6 +1039,43 @@ int mrefsr_ssim_loss_fwd_f32(const float *pred, const float *target, int batch, 
 int mrefsr_ssim_loss_bwd_f32(const float *pred, const float *target, const float *a, const float *b, const float *c, const float *grad_loss,
                              int batch, int h, int w, int rgb, float loss_weight, float *grad_pred, mrefsr_stream_t stream);
 
+/* ---- Multi-scale SSIM: loss of the training step and metric of validation (csrc/msssim.hip; losses.MSSSIMLoss, train.msssim_opt,
+ * metrics.validation_metrics(msssim=True)) ----------------------------------------------------------------------------
+ * No reference counterpart.  MS-SSIM of Wang, Simoncelli and Bovik (2003) with the window and constants of mrefsr_ssim_loss_* at
+ * every level, in fp32 on the images as they are.  pred, target [batch][3][h][w] contiguous; planes as in the SSIM loss (rgb = 0: Y,
+ * one per image; rgb = 1: 255 x, three per image).  Level 1 is the plane, level j + 1 the 2 x 2 mean of level j with stride 2 (a
+ * trailing odd row or column is dropped): h_j = h >> (j - 1).  F[p][j] = mean of cs = (2 sigma_xy + C2) / (sigma_x^2 + sigma_y^2 +
+ * C2) over level j's (h_j - 10) x (w_j - 10) map for j < levels, mean of l cs (the SSIM map) at j = levels; v[p] = prod_j
+ * F[p][j]^weights[j] when every F[p][j] > 0, otherwise 0 with gradient exactly 0; loss = loss_weight (1 - mean_p v[p]).
+ * Limits: 1 <= levels <= MREFSR_MSSSIM_MAX_LEVELS, min(h, w) >> (levels - 1) >= 11, batch <= 21845, h, w <= 2^19, h w <= 2^30, at
+ * most 2^30 blocks; weights[0 .. levels) (host memory) finite and > 0, used as given.
+ *
+ * mrefsr_msssim_pyramid_floats / _map_floats: the floats of `pyramid` (pred's levels, then target's; level j as [planes][h_j][w_j])
+ *   and of `maps` (the sets a, b, c; level j as [planes][h_j - 10][w_j - 10]); mrefsr_msssim_workspace_bytes: the bytes of the
+ *   forward's (backward = 0) or the backward's (backward = 1; 0 bytes when levels = 1) workspace.  Each -1 for a shape outside the
+ *   limits.  A workspace is dead when the call's launches are enqueued; pyramid, maps and mult carry the forward to the backward.
+ * mrefsr_msssim_loss_fwd_f32: three launches (pyramid; window statistics of all levels, moments about a per-tile reference value,
+ *   one fp32 partial per block; one block that adds each (plane, level)'s partials in double in a fixed order and forms v, the loss
+ *   and the multipliers).  loss[0] = fl32(loss_weight (1 - sum_p v[p] / planes)).  maps and mult [planes][levels] (both or both
+ *   NULL): the coefficient maps d cs/d mu_x, d cs/d E[x^2], d cs/d E[xy] (level `levels`: those of the SSIM map) and mult[p][j] =
+ *   weights[j] v[p] / F[p][j] / count_j (0 under the zero rule).  values (or NULL): v[p] in double, [planes].  No float atomics: the
+ *   same bits from call to call.  pred and target are only read.
+ * mrefsr_msssim_loss_bwd_f32: grad_pred [batch][3][h][w], every element written once.  Level j's own term g_j = mult[p][j] ((G^T a)
+ *   + 2 X_j (G^T b) + Y_j (G^T c)), G^T = the window over the maps zero-extended by 10 (exactly 0 where mult is 0); d_j = g_j +
+ *   d_{j+1}(y >> 1, x >> 1) / 4 inside the pooled region; grad = (-loss_weight / planes) grad_loss[0] d_1 mapped back to R, G, B.
+ *   grad_loss: the upstream gradient, one float in device memory.  Two launches (own terms of the levels 2 .. levels into the
+ *   workspace; level 1 and the sum), one when levels = 1. */
+#define MREFSR_MSSSIM_MAX_LEVELS 5
+int64_t mrefsr_msssim_pyramid_floats(int batch, int h, int w, int rgb, int levels);
+int64_t mrefsr_msssim_map_floats(int batch, int h, int w, int rgb, int levels);
+int64_t mrefsr_msssim_workspace_bytes(int batch, int h, int w, int rgb, int levels, int backward);
+int mrefsr_msssim_loss_fwd_f32(const float *pred, const float *target, int batch, int h, int w, int rgb, int levels, const double *weights,
+                               float loss_weight, float *pyramid, float *maps, float *mult, double *values, void *workspace,
+                               int64_t workspace_bytes, float *loss, mrefsr_stream_t stream);
+int mrefsr_msssim_loss_bwd_f32(const float *pyramid, const float *maps, const float *mult, const float *grad_loss, int batch, int h, int w,
+                               int rgb, int levels, float loss_weight, void *workspace, int64_t workspace_bytes, float *grad_pred,
+                               mrefsr_stream_t stream);
+
 /* ---- LDL artifact loss of the training step (csrc/ldl_loss.hip; losses.LDLLoss, train.ldl_opt) -----------------------
  * basicsr/losses/loss_util.py:99-145 as used by basicsr/models/realesrgan_model.py:211-226, the weight map NOT detached.  pred,
  * target, ema [batch][3][h][w] contiguous fp32; r = sum_c |target - pred|, r_e = sum_c |target - ema| (channels added 0, 1, 2);

@@ -219,6 +219,11 @@ SIGNATURES = {
     'mrefsr_ssim_loss_blocks': (_i, [_i, _i, _i, _i]),
     'mrefsr_ssim_loss_fwd_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _f] + [_vp] * 7),
     'mrefsr_ssim_loss_bwd_f32': (_i, [_vp] * 6 + [_i, _i, _i, _i, _f, _vp, _vp]),
+    'mrefsr_msssim_pyramid_floats': (_i64, [_i] * 5),
+    'mrefsr_msssim_map_floats': (_i64, [_i] * 5),
+    'mrefsr_msssim_workspace_bytes': (_i64, [_i] * 6),
+    'mrefsr_msssim_loss_fwd_f32': (_i, [_vp, _vp] + [_i] * 5 + [C.POINTER(C.c_double), _f] + [_vp] * 5 + [_i64, _vp, _vp]),
+    'mrefsr_msssim_loss_bwd_f32': (_i, [_vp] * 4 + [_i] * 5 + [_f, _vp, _i64, _vp, _vp]),
     'mrefsr_ldl_loss_blocks': (_i, [_i, _i, _i]),
     'mrefsr_ldl_loss_fwd_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _f] + [_vp] * 8),
     'mrefsr_ldl_loss_bwd_f32': (_i, [_vp] * 7 + [_i, _i, _i, _f, _vp, _vp]),

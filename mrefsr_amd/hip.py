@@ -1830,6 +1830,78 @@ def ssim_loss_bwd(pred, target, maps, grad_loss, rgb=False, loss_weight=1.0):
     return grad
 
 
+# ------------------------------------------------------------------ multi-scale SSIM: loss and validation metric (csrc/msssim.hip)
+MSSSIM_MAX_LEVELS = 5   # MREFSR_MSSSIM_MAX_LEVELS
+
+
+def _msssim_shape(name, shape, rgb, levels):
+    """(B, H, W, floats of the two pyramids, floats of the three map sets) of a [B,3,H,W] call, or ValueError"""
+    if len(shape) != 4 or shape[1] != 3:
+        raise ValueError(f'{name}: [B,3,H,W] images expected, got {tuple(shape)}')
+    b, _, h, w = shape
+    lib = _lib.load()
+    pyr = lib.mrefsr_msssim_pyramid_floats(b, h, w, int(bool(rgb)), int(levels))
+    if pyr <= 0:
+        raise ValueError(f'{name}: unsupported shape {tuple(shape)} with {levels} levels (1..{MSSSIM_MAX_LEVELS} levels, '
+                         'min(H, W) >> (levels - 1) >= 11, B <= 21845, H, W <= 2^19, H W <= 2^30)')
+    return b, h, w, pyr, lib.mrefsr_msssim_map_floats(b, h, w, int(bool(rgb)), int(levels))
+
+
+def msssim_loss_fwd(pred, target, weights, rgb=False, loss_weight=1.0, want_grad=False, want_values=False):
+    """pred, target [B,3,H,W] (contiguous fp32) -> (loss, saved, values): loss a 0-dim tensor = loss_weight (1 - mean_p v_p), v_p the
+    MS-SSIM of plane p (Y plane of every image, or with rgb=True its three colour planes at 255 scale) over len(weights) levels
+    with the weights used as given;
+    saved: None, or with want_grad (pyramid, maps, mult), what msssim_loss_bwd reads; values: None, or with want_values v_p
+    [planes] in float64.  Three launches, a fixed summation order (the same bits from call to call), nothing read back; pred and
+    target are only read"""
+    _chk('msssim_loss_fwd', pred, target)
+    if pred.shape != target.shape:
+        raise ValueError(f'msssim_loss_fwd: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
+    levels = len(weights)
+    b, h, w, pyr_floats, map_floats = _msssim_shape('msssim_loss_fwd', pred.shape, rgb, levels)
+    planes = (3 if rgb else 1) * b
+    dev = pred.device
+    ws_bytes = _lib.load().mrefsr_msssim_workspace_bytes(b, h, w, int(bool(rgb)), levels, 0)
+    loss = torch.empty((), device=dev, dtype=torch.float32)
+    values = torch.empty(planes, device=dev, dtype=torch.float64) if want_values else None
+    if want_grad:     # what the backward reads outlives this call: tensors of its own, not scratch
+        pyramid = torch.empty(pyr_floats, device=dev, dtype=torch.float32)
+        maps = torch.empty(map_floats, device=dev, dtype=torch.float32)
+        mult = torch.empty((planes, levels), device=dev, dtype=torch.float32)
+        ws = _scratch(dev, ws_bytes)
+    else:
+        maps = mult = None
+        pyr_bytes = (4 * pyr_floats + 255) // 256 * 256
+        buf = _scratch(dev, pyr_bytes + ws_bytes)
+        pyramid, ws = buf, buf[pyr_bytes:]
+    wts = (C.c_double * MSSSIM_MAX_LEVELS)(*[float(v) for v in weights])
+    with _timed('msssim_loss_fwd', detail=True, nbytes=4.0 * (2 * pred.numel() + 2 * pyr_floats + (map_floats if want_grad else 0))):
+        _lib.call('mrefsr_msssim_loss_fwd_f32', _p(pred), _p(target), b, h, w, int(bool(rgb)), levels, wts, C.c_float(loss_weight),
+                  _p(pyramid), _p(maps), _p(mult), _p(values), _p(ws), C.c_int64(ws_bytes), _p(loss), _stream())
+    return loss, ((pyramid, maps, mult) if want_grad else None), values
+
+
+def msssim_loss_bwd(saved, grad_loss, shape, rgb=False, loss_weight=1.0):
+    """d (grad_loss * loss) / d pred [B,3,H,W] (= shape) of msssim_loss_fwd from what it saved; grad_loss: the upstream gradient, a
+    one-element fp32 device tensor (read by the kernels, not by the host).  Two launches (one for a single level); every element is
+    written once"""
+    pyramid, maps, mult = saved
+    _chk('msssim_loss_bwd', grad_loss, pyramid, maps, mult)
+    levels = mult.shape[1] if mult.dim() == 2 else 0
+    b, h, w, pyr_floats, map_floats = _msssim_shape('msssim_loss_bwd', shape, rgb, levels)
+    planes = (3 if rgb else 1) * b
+    if grad_loss.numel() != 1 or pyramid.numel() != pyr_floats or maps.numel() != map_floats or mult.shape[0] != planes:
+        raise ValueError(f'msssim_loss_bwd: one upstream value, a pyramid of {pyr_floats}, maps of {map_floats} floats and multipliers '
+                         f'[{planes}, {levels}] expected')
+    ws_bytes = _lib.load().mrefsr_msssim_workspace_bytes(b, h, w, int(bool(rgb)), levels, 1)
+    ws = _scratch(pyramid.device, ws_bytes) if ws_bytes else None
+    grad = torch.empty(tuple(shape), device=pyramid.device, dtype=torch.float32)
+    with _timed('msssim_loss_bwd', detail=True, nbytes=4.0 * (grad.numel() + pyr_floats + map_floats)):
+        _lib.call('mrefsr_msssim_loss_bwd_f32', _p(pyramid), _p(maps), _p(mult), _p(grad_loss), b, h, w, int(bool(rgb)), levels,
+                  C.c_float(loss_weight), _p(ws), C.c_int64(ws_bytes), _p(grad), _stream())
+    return grad
+
+
 # ------------------------------------------------------------------ LDL artifact loss of the training step (csrc/ldl_loss.hip)
 LDL_TILE = (16, 32)   # pixels per block of the forward and the backward launch (rows, columns)
 

@@ -5,7 +5,8 @@ basicsr/models/realesrgan_model.py:211-226), on the kernels of csrc/ldl_loss.hip
 validation metric (mrefsr_amd/metrics.py: calculate_ssim) measures, as a criterion, on the kernels of csrc/ssim_loss.hip.  FFTLoss and FocalFrequencyLoss have none either: the L1 distance of the spectra
 (MIMO-UNet, DeepRFT) and the focal frequency loss (Jiang et al., ICCV 2021), on the dense-DFT kernels of csrc/freq_loss.hip.
 ContextualLoss has none either: the contextual loss of Mechrez et al. (ECCV 2018) between VGG features, on the kernels of
-csrc/contextual.hip (archs/nhwc_train.py: _VggContextual).
+csrc/contextual.hip (archs/nhwc_train.py: _VggContextual).  MSSSIMLoss has none either: multi-scale SSIM (Wang, Simoncelli, Bovik 2003) with the
+validation metric's window at every level, on the kernels of csrc/msssim.hip.
 
 The pixel criteria stay element-wise torch operations (at 4 x 3 x 160 x 160 they are noise beside the VGG).  They implement
 what the model passes -- reduction='mean', no element weight -- and refuse the rest.  PerceptualLoss runs its VGG19 through ONE
@@ -14,11 +15,14 @@ kernels, the input-gradient pass of the output image back through the same kerne
 csrc/percep.hip.  GPU tensors only, like the ops.  r1_penalty's per-sample sum of squares and its backward are the kernels of
 csrc/gan_reg.hip for GPU tensors and the torch expression for CPU tensors.
 """
+import math
+
 import torch
 import torch.nn.functional as F
 from torch import nn
 
 from ..archs.vgg_arch import VGGFeatureExtractor
+from ..metrics import MSSSIM_WEIGHTS   # (0.0448, 0.2856, 0.3001, 0.2363, 0.1333): Wang, Simoncelli, Bovik 2003
 from ..utils.registry import LOSS_REGISTRY
 
 
@@ -251,6 +255,136 @@ class SSIMLoss(nn.Module):
         if pred.dtype != torch.float32 or target.dtype != torch.float32:
             raise NotImplementedError(f'SSIMLoss: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
         return _SSIMLossFn.apply(pred.contiguous(), target.contiguous(), self.channel == 'rgb', float(self.loss_weight))
+
+
+MSSSIM_MAX_LEVELS = 5
+
+
+def msssim_levels_allowed(h, w):
+    """the largest number of levels an H x W plane allows: every level at least 11 x 11 (0 when the plane itself is smaller)"""
+    m = 0
+    while m < MSSSIM_MAX_LEVELS and (min(h, w) >> m) >= 11:
+        m += 1
+    return m
+
+
+def _msssim_check_size(name, h, w, levels):
+    allowed = msssim_levels_allowed(h, w)
+    if levels > allowed:
+        raise ValueError(f'{name}: {h} x {w} images with M = {levels} levels: every level must be at least 11 x 11 '
+                         f'(min(H, W) >> (M - 1) >= 11); this shape allows at most M = {allowed}')
+
+
+def msssim_planes_torch(x, y, weights=MSSSIM_WEIGHTS):
+    """v_p [P]: the MS-SSIM of each pair of planes x, y [P,1,H,W] at 255 scale, as torch operations in their dtype.  Level 1 is the
+    plane, level j + 1 = F.avg_pool2d(level j, 2) (a trailing odd row or column is dropped); at every level the 11-tap Gaussian of
+    metrics._gaussian_window on the valid region, C1 = (0.01 255)^2, C2 = (0.03 255)^2; F_j = mean cs for j < M, F_M = mean l cs;
+    v = prod_j F_j^w_j when every F_j > 0, otherwise 0 with gradient exactly 0 (a rule: relu(F)^w would give 0 inf = NaN there)."""
+    from ..metrics import _gaussian_window
+    k = torch.from_numpy(_gaussian_window(11, 1.5)).to(device=x.device, dtype=x.dtype)
+
+    def filt(z):
+        return F.conv2d(F.conv2d(z, k.view(1, 1, 11, 1)), k.view(1, 1, 1, 11))
+    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    fs = []
+    for j in range(len(weights)):
+        if j:
+            x, y = F.avg_pool2d(x, 2), F.avg_pool2d(y, 2)
+        mu1, mu2 = filt(x), filt(y)
+        mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+        s1, s2, s12 = filt(x * x) - mu1_sq, filt(y * y) - mu2_sq, filt(x * y) - mu1_mu2
+        m = (2 * s12 + c2) / (s1 + s2 + c2)
+        if j == len(weights) - 1:
+            m = m * ((2 * mu1_mu2 + c1) / (mu1_sq + mu2_sq + c1))
+        fs.append(m.mean(dim=(1, 2, 3)))
+    fs = torch.stack(fs, dim=1)                                        # [P, M]
+    positive = (fs > 0).all(dim=1)
+    safe = torch.where(positive[:, None], fs, torch.ones_like(fs))     # (no gradient reaches a plane under the zero rule)
+    v = torch.exp((fs.new_tensor(list(weights)) * torch.log(safe)).sum(dim=1))
+    return torch.where(positive, v, torch.zeros_like(v))
+
+
+def msssim_loss_torch(pred, target, channel='y', weights=None):
+    """1 - mean_p MS-SSIM of [B,3,H,W] images in the nominal range [0, 1], as torch operations in the tensors' dtype and on their
+    device: the definition MSSSIMLoss implements (and what it runs for CPU tensors).  Planes as in ssim_loss_torch (channel 'y': one
+    per image, X = 65.481 R + 128.553 G + 24.966 B + 16; 'rgb': three per image, X = 255 x); per plane msssim_planes_torch with
+    weights (w_1 .. w_M), default MSSSIM_WEIGHTS, used as given.  Nothing is clamped or quantised."""
+    weights = MSSSIM_WEIGHTS if weights is None else tuple(weights)
+    if channel == 'y':
+        coef = pred.new_tensor([65.481, 128.553, 24.966]).view(1, 3, 1, 1)
+        x, y = (pred * coef).sum(1, keepdim=True) + 16.0, (target * coef).sum(1, keepdim=True) + 16.0
+    else:
+        x, y = 255.0 * pred, 255.0 * target
+    x, y = x.reshape(-1, 1, *x.shape[2:]), y.reshape(-1, 1, *y.shape[2:])
+    return 1.0 - msssim_planes_torch(x, y, weights).mean()
+
+
+class _MSSSIMLossFn(torch.autograd.Function):
+    """(pred, target) [B,3,H,W] contiguous fp32 on the GPU -> loss_weight (1 - mean MS-SSIM), three launches of csrc/msssim.hip; when
+    pred needs a gradient they also write the pyramid, the coefficient maps and the multipliers the two backward launches read.
+    Differentiable once, towards pred only; the upstream gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, pred, target, rgb, loss_weight, weights):
+        from .. import hip
+        ctx.rgb, ctx.loss_weight, ctx.shape = rgb, loss_weight, tuple(pred.shape)
+        loss, saved, _ = hip.msssim_loss_fwd(pred, target, weights, rgb, loss_weight, want_grad=ctx.needs_input_grad[0])
+        if saved is not None:
+            ctx.save_for_backward(*saved)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        from .. import hip
+        return hip.msssim_loss_bwd(ctx.saved_tensors, grad_loss.contiguous().float(), ctx.shape, ctx.rgb, ctx.loss_weight), None, None, None, None
+
+
+@LOSS_REGISTRY.register()
+class MSSSIMLoss(nn.Module):
+    """loss_weight * (1 - mean MS-SSIM) between [B,3,H,W] images in the nominal range [0, 1]: multi-scale SSIM (Wang, Simoncelli,
+    Bovik 2003) with the window and constants of the validation metric at every level, as a differentiable criterion on the
+    unquantised, unclamped images; msssim_loss_torch spells the definition out.  channel 'y' / 'rgb' as in SSIMLoss.  weights: one
+    per level, M = 1 .. 5 of them, each finite and > 0, used as given (not renormalised); default MSSSIM_WEIGHTS (five levels).
+    Level j + 1 is the 2 x 2 mean of level j; a trailing odd row or column is dropped (implementations differ there; for sides that
+    are multiples of 2^(M-1) there is no odd line).  A plane with a level whose mean is not positive counts 0 and gets gradient 0.
+    target is a constant (detached); the gradient reaches pred, once.
+
+    GPU fp32 tensors run on the kernels of csrc/msssim.hip (three forward and two backward launches, fixed summation orders); CPU
+    tensors of any float dtype take msssim_loss_torch.  Refused: window_size other than 11, sigma other than 1.5, another channel,
+    inputs that are not 3-channel (NotImplementedError); bad weights, differing shapes, and images too small for M levels -- every
+    level must be at least 11 x 11, so five levels need min(H, W) >= 176; fewer levels are never taken silently (ValueError)."""
+
+    def __init__(self, loss_weight=1.0, channel='y', weights=None, window_size=11, sigma=1.5):
+        super().__init__()
+        if window_size != 11 or sigma != 1.5:
+            raise NotImplementedError(f'MSSSIMLoss: window_size={window_size!r}, sigma={sigma!r}; only the 11-tap window with sigma 1.5 of '
+                                      'the validation metric is implemented')
+        if channel not in ('y', 'rgb'):
+            raise NotImplementedError(f"MSSSIMLoss: channel={channel!r}; 'y' or 'rgb'")
+        weights = MSSSIM_WEIGHTS if weights is None else tuple(float(v) for v in weights)
+        if not 1 <= len(weights) <= MSSSIM_MAX_LEVELS:
+            raise ValueError(f'MSSSIMLoss: {len(weights)} weights; one per level, 1 to {MSSSIM_MAX_LEVELS} levels')
+        if not all(math.isfinite(v) and v > 0 for v in weights):
+            raise ValueError(f'MSSSIMLoss: weights={weights!r}; each must be finite and > 0')
+        self.loss_weight, self.channel, self.weights, self.window_size, self.sigma = loss_weight, channel, weights, window_size, sigma
+
+    def check_size(self, h, w):
+        """ValueError when H x W images are too small for this criterion's levels"""
+        _msssim_check_size('MSSSIMLoss', h, w, len(self.weights))
+
+    def forward(self, pred, target, **kwargs):
+        if pred.dim() != 4 or pred.shape[1] != 3:
+            raise NotImplementedError(f'MSSSIMLoss: [B,3,H,W] images expected, got {tuple(pred.shape)}')
+        if target.shape != pred.shape:
+            raise ValueError(f'MSSSIMLoss: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
+        self.check_size(pred.shape[2], pred.shape[3])
+        target = target.detach()
+        if not pred.is_cuda:
+            return self.loss_weight * msssim_loss_torch(pred, target, self.channel, self.weights)
+        if pred.dtype != torch.float32 or target.dtype != torch.float32:
+            raise NotImplementedError(f'MSSSIMLoss: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
+        return _MSSSIMLossFn.apply(pred.contiguous(), target.contiguous(), self.channel == 'rgb', float(self.loss_weight), self.weights)
 
 
 def _freq_residual_spectrum(pred, target, norm):

@@ -93,6 +93,61 @@ def calculate_ssim(img, img2, crop_border, test_y_channel=False):
     return float(np.mean([_ssim(img[..., i], img2[..., i]) for i in range(img.shape[2])]))
 
 
+MSSSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # Wang, Simoncelli, Bovik (Asilomar 2003): five levels
+
+
+def _msssim_size(name, h, w):
+    """every one of the five levels must hold the 11-tap window: min(h, w) >> 4 >= 11"""
+    need = 11 << (len(MSSSIM_WEIGHTS) - 1)
+    if min(h, w) < need:
+        raise ValueError(f'{name}: a {h} x {w} image (after cropping) is too small for {len(MSSSIM_WEIGHTS)}-level MS-SSIM: '
+                         f'both sides must be at least {need}')
+
+
+def _msssim(img, img2, weights=MSSSIM_WEIGHTS):
+    """single-channel MS-SSIM in float64: level j + 1 is the 2 x 2 mean of level j (a trailing odd row or column is dropped), every
+    level with the window and constants of _ssim; prod_j F_j^w_j with F_j = mean cs below the last level and mean l cs there, 0 when
+    an F_j is not positive (the definition of losses.msssim_loss_torch)"""
+    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    k = _gaussian_window()
+    x, y = img, img2
+    value = 1.0
+    for j, wt in enumerate(weights):
+        if j:
+            h2, w2 = x.shape[0] // 2, x.shape[1] // 2
+            x = x[:2 * h2, :2 * w2].reshape(h2, 2, w2, 2).mean(axis=(1, 3))
+            y = y[:2 * h2, :2 * w2].reshape(h2, 2, w2, 2).mean(axis=(1, 3))
+        mu1, mu2 = _filter_valid(x, k), _filter_valid(y, k)
+        mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+        s1 = _filter_valid(x * x, k) - mu1_sq
+        s2 = _filter_valid(y * y, k) - mu2_sq
+        s12 = _filter_valid(x * y, k) - mu1_mu2
+        m = (2 * s12 + c2) / (s1 + s2 + c2)
+        if j == len(weights) - 1:
+            m = m * ((2 * mu1_mu2 + c1) / (mu1_sq + mu2_sq + c1))
+        f = float(m.mean())
+        if not f > 0:
+            return 0.0
+        value *= f ** wt
+    return value
+
+
+def calculate_msssim(img, img2, crop_border, test_y_channel=False):
+    """five-level MS-SSIM of HWC uint8 / [0,255] images with calculate_ssim's cropping and Y plane: per-channel values averaged.
+    The cropped image must be at least 176 x 176 (ValueError otherwise)"""
+    assert img.shape == img2.shape, f'Image shapes are different: {img.shape}, {img2.shape}.'
+    if img.ndim == 2:
+        img, img2 = img[..., None], img2[..., None]
+    if crop_border != 0:
+        img = img[crop_border:-crop_border, crop_border:-crop_border, ...]
+        img2 = img2[crop_border:-crop_border, crop_border:-crop_border, ...]
+    _msssim_size('calculate_msssim', img.shape[0], img.shape[1])
+    if test_y_channel:
+        img, img2 = rgb_to_y(img), rgb_to_y(img2)
+    img, img2 = img.astype(np.float64), img2.astype(np.float64)
+    return float(np.mean([_msssim(img[..., i], img2[..., i]) for i in range(img.shape[2])]))
+
+
 def imwrite(img, path):
     """HWC uint8 RGB image -> PNG (the reference converts to BGR and lets cv2.imwrite convert back: same file)"""
     import os
@@ -165,18 +220,37 @@ def _device_metrics(output, gt, crop_border, sizes, ssim, return_img=False):
     return per, img, single
 
 
-def validation_metrics(output, gt, crop_border, sizes=None, return_img=False):
+def _msssim_y_device(output, gt, crop_border, sizes):
+    """calculate_msssim(..., test_y_channel=True) of each image pair on the forward kernels of csrc/msssim.hip (no coefficient
+    maps): the quantised, cropped images go back into [1,3,h,w] fp32 with torch operations (validation is not the hot path)"""
+    from . import hip
+    imgs = (hip.tensor2img_u8(_device_batch(output)[0]), hip.tensor2img_u8(_device_batch(gt)[0]))
+    vals = []
+    for i in range(imgs[0].shape[0]):
+        oh, ow = (int(v) for v in tuple(sizes[i])[:2]) if sizes is not None else imgs[0].shape[1:3]
+        _msssim_size('validation_metrics', oh - 2 * crop_border, ow - 2 * crop_border)
+        pair = [(im[i, crop_border:oh - crop_border, crop_border:ow - crop_border].permute(2, 0, 1)[None].float() / 255.0).contiguous()
+                for im in imgs]
+        _, _, v = hip.msssim_loss_fwd(pair[0], pair[1], MSSSIM_WEIGHTS, rgb=False, want_values=True)
+        vals.append(float(v[0]))
+    return vals
+
+
+def validation_metrics(output, gt, crop_border, sizes=None, return_img=False, msssim=False):
     """PSNR, PSNR-Y and SSIM-Y of each image pair, as calculate_psnr and calculate_ssim(test_y_channel=True) give them for
     tensor2img(output[i])[:oh, :ow] and tensor2img(gt[i])[:oh, :ow], computed on the GPU.
     output [N,3,H,W], gt [N,3,Hg,Wg] fp32 device tensors; sizes: None (equal shapes, whole images) or N pairs (oh, ow), the valid
     region of each image (the dataset's zero-padding crop).  Returns dict(psnr=[N], psnr_y=[N], ssim_y=[N], finite=[N]); finite is
     False for an image with NaN or inf in its valid region (its numbers are then those of the quantised values, NaN as 0).
-    return_img: also 'img', the uint8 [N,H,W,3] device tensor of tensor2img(output[i]) for every image, uncropped."""
+    return_img: also 'img', the uint8 [N,H,W,3] device tensor of tensor2img(output[i]) for every image, uncropped.
+    msssim: also 'msssim_y' [N], calculate_msssim(test_y_channel=True) of the same images on the kernels of csrc/msssim.hip."""
     if output.dim() != 4:
         raise ValueError(f'validation_metrics: expected [N,3,H,W] batches, got {tuple(output.shape)}')
     per, img, _ = _device_metrics(output, gt, crop_border, sizes, 'y', return_img)
     out = dict(psnr=[p['psnr'] for p in per], psnr_y=[p['psnr_y'] for p in per], ssim_y=[p['ssim'] for p in per],
                finite=[p['finite'] for p in per])
+    if msssim:
+        out['msssim_y'] = _msssim_y_device(output, gt, crop_border, sizes)
     if return_img:
         out['img'] = img
     return out

@@ -11,7 +11,8 @@ Losses (:114-165, :237-279): the pixel criterion (L1Loss, MSELoss, CharbonnierLo
 (PerceptualLoss of losses/, its VGG19 forward and backward on the HIP kernels), texture_opt with use_weights: true (TextureLoss; its
 swapped reference maps and weights, which the reference model reads but never sets, are built from the matcher's indices and values
 on the kernels of csrc/texture.hip: _texture_targets), ssim_opt (SSIMLoss: 1 - SSIM on the Y or the colour planes, the quantity
-validation reports, on the kernels of csrc/ssim_loss.hip; no counterpart in the reference), ldl_opt (LDLLoss: the artifact loss of
+validation reports, on the kernels of csrc/ssim_loss.hip; no counterpart in the reference), msssim_opt (MSSSIMLoss: its multi-scale
+form over up to five levels, on the kernels of csrc/msssim.hip; val.msssim reports it in validation), ldl_opt (LDLLoss: the artifact loss of
 LDL between the output, the GT and the output of net_g_ema on the same input, basicsr/models/realesrgan_model.py:211-226, on the
 kernels of csrc/ldl_loss.hip; needs train.ema_decay: _ema_pass), freq_opt (FFTLoss or FocalFrequencyLoss: a distance between the
 spectra of the output and the GT, on the dense-DFT kernels of csrc/freq_loss.hip; no counterpart in the reference), contextual_opt
@@ -317,6 +318,7 @@ class MultiRefRestorationModel:
     net_g_ema = None
     cri_texture = None   # TextureLoss of train.texture_opt (init_training_settings)
     cri_ssim = None      # SSIMLoss of train.ssim_opt
+    cri_msssim = None    # MSSSIMLoss of train.msssim_opt
     cri_freq = None      # FFTLoss / FocalFrequencyLoss of train.freq_opt
     cri_contextual = None   # ContextualLoss of train.contextual_opt
     cri_ldl = None       # LDLLoss of train.ldl_opt
@@ -423,6 +425,7 @@ class MultiRefRestorationModel:
         self.cri_texture = losses.TextureLoss(**train_opt['texture_opt']).to(self.device) if train_opt.get('texture_opt') else None
         # SSIMLoss: train.ssim_opt holds its constructor's keys (loss_weight, channel, window_size, sigma)
         self.cri_ssim = losses.SSIMLoss(**train_opt['ssim_opt']).to(self.device) if train_opt.get('ssim_opt') else None
+        self.cri_msssim = self._build_msssim(train_opt)
         self.cri_ldl = self._build_ldl(train_opt)
         self.cri_freq = self._build_freq(train_opt)
         # ContextualLoss: train.contextual_opt holds its constructor's keys (layer_weights, vgg_type, use_input_norm, norm_img, band_width,
@@ -443,6 +446,19 @@ class MultiRefRestorationModel:
             raise NotImplementedError(f'Scheduler {stype} is not implemented yet.')
         for optimizer in self.optimizers:
             self.schedulers.append((_CosineAnnealingRestartLR if stype == 'CosineAnnealingRestartLR' else _MultiStepRestartLR)(optimizer, **sched))
+
+    @staticmethod
+    def _build_msssim(train_opt):
+        """train.msssim_opt holds MSSSIMLoss's constructor's keys (loss_weight, channel, weights, window_size, sigma) -> the criterion,
+        or None without the option.  Unknown keys are refused by name."""
+        from .. import losses
+        msssim_opt = train_opt.get('msssim_opt')
+        if not msssim_opt:
+            return None
+        unknown = sorted(set(msssim_opt) - {'loss_weight', 'channel', 'weights', 'window_size', 'sigma'})
+        if unknown:
+            raise ValueError(f'train.msssim_opt: unknown keys {unknown}; loss_weight, channel, weights, window_size, sigma')
+        return losses.MSSSIMLoss(**msssim_opt)
 
     @staticmethod
     def _build_freq(train_opt):
@@ -771,6 +787,10 @@ class MultiRefRestorationModel:
                 l_g_ssim = self.cri_ssim(self.output, self._gt_for('l1'))
                 l_g_total = l_g_total + l_g_ssim
                 self.log_dict['l_g_ssim'] = l_g_ssim.detach()
+            if self.cri_msssim is not None:
+                l_g_msssim = self.cri_msssim(self.output, self._gt_for('l1'))
+                l_g_total = l_g_total + l_g_msssim
+                self.log_dict['l_g_msssim'] = l_g_msssim.detach()
             if self.cri_ldl is not None:   # realesrgan_model.py:211-226
                 self.output_ema = self._ema_pass()
                 l_g_ldl = self.cri_ldl(self.output, self._gt_for('l1'), self.output_ema)
@@ -798,12 +818,13 @@ class MultiRefRestorationModel:
         """opt['train']['hip_graph'] or MREFSR_TRAIN_GRAPH=1 (EXPERIMENTAL, off by default: 1-2 % at the shipped patch size; see the
         fence at the end of _optimize_graphed): forward + backward are captured once per input shape and replayed; the Adam update is
         a second graph, replayed after the fp16-range flag has been read.  Single process only (a DDP all-reduce is not captured), and
-        not with a perceptual, style or texture loss (their VGG node is not captured), an SSIM loss, an LDL loss (its EMA pass is not
+        not with a perceptual, style or texture loss (their VGG node is not captured), an SSIM or MS-SSIM loss, an LDL loss (its EMA pass is not
         captured), a frequency-domain loss, a contextual loss (a VGG node again), nor with a discriminator."""
         train_opt = self.opt.get('train') or {}
         return (bool(train_opt.get('hip_graph')) or os.environ.get('MREFSR_TRAIN_GRAPH', '0') == '1') \
             and not self.opt.get('dist', False) and not train_opt.get('perceptual_opt') and not train_opt.get('style_opt') \
-            and not train_opt.get('texture_opt') and not train_opt.get('ssim_opt') and not train_opt.get('ldl_opt') \
+            and not train_opt.get('texture_opt') and not train_opt.get('ssim_opt') and not train_opt.get('msssim_opt') \
+            and not train_opt.get('ldl_opt') \
             and not train_opt.get('freq_opt') and not train_opt.get('contextual_opt') \
             and not self.opt.get('network_d')
 
@@ -977,6 +998,8 @@ class MultiRefRestorationModel:
 
     def _optimize_parameters(self, step):
         from ..archs import nhwc_train
+        if self.cri_msssim is not None:   # (on the host, before anything is launched: a GT too small for the levels is an error)
+            self.cri_msssim.check_size(*self._gt_for('l1').shape[2:])
         nhwc_train.check_scales()   # cached fp16 weight scales of the training convolutions still valid? (device side)
         if self._train_graph_wanted() and not self._pool_batch('train.hip_graph') and not self._masked_batch('train.hip_graph') \
                 and self._optimize_graphed(step):
@@ -1180,15 +1203,17 @@ class MultiRefRestorationModel:
 
     def _nondist_validation(self, dataloader, current_iter, tb_logger, save_img):
         """per image: feed_data -> test -> uint8 image -> crop the dataset's zero padding -> [PNG] -> PSNR (RGB), PSNR (Y),
-        SSIM (Y) with crop_border from the options (ref :324-386).  save_img writes
+        SSIM (Y) with crop_border from the options (ref :324-386); with val.msssim also five-level MS-SSIM (Y)
+        (metrics.calculate_msssim; logged as MS-SSIM_Y, tb scalar and result key msssim_y).  save_img writes
         path.visualization/<img>/<img>_<iter>.png while training, path.visualization/<dataset>/<img>_<name>[_suffix].png when testing.
         With val.metrics_on_device the metrics run on the GPU and only their scalars (and, for save_img, the image) come back; an
         image with non-finite values in its output or GT takes the numpy path."""
-        from ..metrics import calculate_psnr, calculate_ssim, imwrite, tensor2img, validation_metrics
+        from ..metrics import calculate_msssim, calculate_psnr, calculate_ssim, imwrite, tensor2img, validation_metrics
         logger = logging.getLogger('basicsr')
         dataset_name = getattr(getattr(dataloader, 'dataset', None), 'opt', {}).get('name', 'val')
         on_device = self._metrics_on_device()
-        psnrs, psnrs_y, ssims_y = [], [], []
+        want_msssim = bool((self.opt.get('val') or {}).get('msssim'))
+        psnrs, psnrs_y, ssims_y, msssims_y = [], [], [], []
         for idx, val_data in enumerate(dataloader):
             lq_path = val_data.get('lq_path', [f'{idx:04d}'])
             img_name = os.path.splitext(os.path.basename(lq_path[0] if isinstance(lq_path, (list, tuple)) else lq_path))[0]
@@ -1200,7 +1225,8 @@ class MultiRefRestorationModel:
                 size = [int(v) for v in val_data['original_size']][:2]
             dev = None
             if on_device:
-                dev = validation_metrics(self.output[:1], self.gt[:1], cb, sizes=None if size is None else [size], return_img=save_img)
+                dev = validation_metrics(self.output[:1], self.gt[:1], cb, sizes=None if size is None else [size], return_img=save_img,
+                                         **(dict(msssim=True) if want_msssim else {}))
                 dev = dev if dev['finite'][0] else None
             if dev is not None:
                 sr_img = None
@@ -1208,6 +1234,8 @@ class MultiRefRestorationModel:
                     img = dev['img'][0]
                     sr_img = (img if size is None else img[:size[0], :size[1]]).cpu().numpy()
                 psnr, psnr_y, ssim_y = dev['psnr'][0], dev['psnr_y'][0], dev['ssim_y'][0]
+                if want_msssim:
+                    msssims_y.append(dev['msssim_y'][0])
             else:
                 sr_img = tensor2img(self.output[:1])
                 gt_img = tensor2img(self.gt[:1])
@@ -1217,6 +1245,8 @@ class MultiRefRestorationModel:
                 psnr = calculate_psnr(sr_img, gt_img, crop_border=cb)
                 psnr_y = calculate_psnr(sr_img, gt_img, crop_border=cb, test_y_channel=True)
                 ssim_y = calculate_ssim(sr_img, gt_img, crop_border=cb, test_y_channel=True)
+                if want_msssim:
+                    msssims_y.append(calculate_msssim(sr_img, gt_img, crop_border=cb, test_y_channel=True))
             if save_img:
                 vis = self.opt['path']['visualization']
                 if self.opt['is_train']:
@@ -1229,15 +1259,23 @@ class MultiRefRestorationModel:
             psnrs_y.append(psnr_y)
             ssims_y.append(ssim_y)
             if not self.is_train:
-                logger.info(f'# img {img_name} # PSNR: {psnrs[-1]:.4e} # PSNR_Y: {psnrs_y[-1]:.4e} # SSIM_Y: {ssims_y[-1]:.4e}.')
+                ms = f' # MS-SSIM_Y: {msssims_y[-1]:.4e}' if want_msssim else ''
+                logger.info(f'# img {img_name} # PSNR: {psnrs[-1]:.4e} # PSNR_Y: {psnrs_y[-1]:.4e} # SSIM_Y: {ssims_y[-1]:.4e}{ms}.')
         n = max(len(psnrs), 1)
         avg_psnr, avg_psnr_y, avg_ssim_y = sum(psnrs) / n, sum(psnrs_y) / n, sum(ssims_y) / n
-        logger.info(f'# Validation {dataset_name} # PSNR: {avg_psnr:.4e} # PSNR_Y: {avg_psnr_y:.4e} # SSIM_Y: {avg_ssim_y:.4e}.')
+        avg_msssim_y = sum(msssims_y) / n
+        ms = f' # MS-SSIM_Y: {avg_msssim_y:.4e}' if want_msssim else ''
+        logger.info(f'# Validation {dataset_name} # PSNR: {avg_psnr:.4e} # PSNR_Y: {avg_psnr_y:.4e} # SSIM_Y: {avg_ssim_y:.4e}{ms}.')
         if tb_logger:
             tb_logger.add_scalar('psnr', avg_psnr, current_iter)
             tb_logger.add_scalar('psnr_y', avg_psnr_y, current_iter)
             tb_logger.add_scalar('ssim_y', avg_ssim_y, current_iter)
-        return dict(psnr=avg_psnr, psnr_y=avg_psnr_y, ssim_y=avg_ssim_y)
+            if want_msssim:
+                tb_logger.add_scalar('msssim_y', avg_msssim_y, current_iter)
+        result = dict(psnr=avg_psnr, psnr_y=avg_psnr_y, ssim_y=avg_ssim_y)
+        if want_msssim:
+            result['msssim_y'] = avg_msssim_y
+        return result
 
     def save(self, epoch, current_iter):
         """net_g (and net_d) checkpoints as {'params': state_dict} under path.models (ref :304-308, base_model.py:198-226)"""
