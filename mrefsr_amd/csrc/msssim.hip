@@ -16,13 +16,12 @@
 //   1. pyramid: block (tx, ty, plane) owns the 32 x 32 level-1 pixels from (32 ty, 32 tx) of pred and of target and every pooled
 //      pixel under them (level j: (32 >> (j - 1))^2 of them; 32 is a multiple of 2^4, so a pooled pixel never straddles two blocks).
 //      Pooling: 0.25 ((p00 + p01) + (p10 + p11)) in fp32.
-//   2. statistics, all levels in one grid: block (level, plane, ty, tx) owns 16 x 32 map positions as in ssim_loss_fwd_kernel: the
-//      26 x 42 pixels under them staged in LDS MINUS a per-tile reference value (the level's value at the tile's centre pixel), so
-//      that sigma^2 = E[(x - r)^2] - u^2 does not cancel at 255 scale -- the coarse levels are smooth; 11 taps down the columns
-//      into LDS, then along the rows in registers.  Per position cs = A2 / B2 (levels j < M) or l cs (level M), and, when a
-//      gradient is wanted, the coefficients at fixed RAW second moments
+//   2. statistics, all levels in one grid: block (level, plane, ty, tx) owns 16 x 32 map positions and runs the forward tile body
+//      of ssim_window.h (moments_tile) on the level's planes: the window moments from pixels staged MINUS a per-tile reference
+//      value, so that sigma^2 does not cancel at 255 scale -- the coarse levels are smooth.  Per position cs = A2 / B2 (levels
+//      j < M) or l cs (level M), and, when a gradient is wanted, the coefficients at fixed RAW second moments
 //          j < M:  a = d cs/d mu_x = 2 (mu_x cs - mu_y) / B2,  b = d cs/d E[x^2] = -cs / B2,  c = d cs/d E[xy] = 2 / B2
-//          j = M:  the a, b, c of ssim_loss.hip (m = l cs)
+//          j = M:  the a, b, c of ssim_window.h's ssim_terms (m = l cs)
 //      with A2 = 2 sigma_xy + C2, B2 = sigma_x^2 + sigma_y^2 + C2.  Sum: per thread position k = 0 then 1, the 256 threads by the
 //      LDS tree of reduce.h, one fp32 partial per block.
 //   3. combine, one block: the partials of each (plane, level), which are adjacent, in double: lane l of a wave adds partials
@@ -32,7 +31,7 @@
 //   No float atomics, no ticket, no readback: the same bits from call to call.
 //
 // Backward, two launches (one when M = 1).  Level j's own term is g_j = mult[p][j] (G^T a + 2 X_j G^T b + Y_j G^T c), G^T the same
-// window over the maps zero-extended by 10 (exactly 0 where mult is 0, whatever the maps hold); level j's plane gradient is
+// window over the maps zero-extended by 10 (adjoint_tile; exactly 0 where mult is 0, whatever the maps hold); level j's plane gradient is
 // d_j = g_j + d_{j+1}(y >> 1, x >> 1) / 4 inside the pooled region.  Because H_{j+1} = H_j >> 1, a level-1 pixel lies in level j's
 // pooled region exactly when (y >> (j - 1)) < H_j and (x >> (j - 1)) < W_j, and then in every finer one, so the recursion needs no
 // intermediate planes:
@@ -40,36 +39,15 @@
 //   2. level 1: its own term plus the coarse levels by the recursion's own order, t = g_M; t = g_j + t / 4 for j = M - 1 .. 2;
 //      d_1 = g_1 + t / 4; times (-loss_weight / planes) grad_loss[0] (read from the device), mapped back to R, G, B: every element of
 //      grad_pred is written exactly once.
-#include <math.h>
-
 #include "common.h"
+#include "ssim_window.h"
 
 namespace {
 
-constexpr int TH = 16, TW = 32, HALO = 10, TAPS = 11;
-constexpr int SH = TH + HALO, SW = TW + HALO;   // staged rows / columns: 26 x 42
-constexpr int THREADS = 256;
-constexpr int PER_THREAD = TH * TW / THREADS;   // 2
+using namespace mrefsr::ssim;
+
 constexpr int PT = 32;                          // level-1 pixels per side of a pyramid block
 constexpr int MAXL = MREFSR_MSSSIM_MAX_LEVELS;
-constexpr float C1 = 6.5025f, C2 = 58.5225f;    // (0.01 * 255)^2, (0.03 * 255)^2
-constexpr float YR = 65.481f, YG = 128.553f, YB = 24.966f, Y0 = 16.f;
-
-// (the window helpers are those of ssim_loss.hip, whose kernels stay as they are)
-struct Taps { float g[TAPS]; };
-
-// the taps of metrics._gaussian_window(11, 1.5): exp(-(i - 5)^2 / 4.5) normalised in double, rounded to fp32
-const Taps &gaussian_taps()
-{
-    static const Taps taps = [] {
-        double k[TAPS], s = 0.0;
-        for (int i = 0; i < TAPS; ++i) s += k[i] = exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
-        Taps t;
-        for (int i = 0; i < TAPS; ++i) t.g[i] = (float)(k[i] / s);
-        return t;
-    }();
-    return taps;
-}
 
 // the geometry of one call, passed to every kernel by value (level index j = 0 .. levels - 1 is the text's level j + 1)
 struct Pyr {
@@ -114,49 +92,6 @@ int64_t fwd_partial_bytes(const Pyr &g) { return (g.fblk[g.levels] * 4 + 255) / 
 int64_t fwd_workspace_bytes(const Pyr &g) { return fwd_partial_bytes(g) + (int64_t)g.planes * g.levels * 8; }
 // backward workspace: the own terms of the levels 2 .. M
 int64_t bwd_workspace_bytes(const Pyr &g) { return (g.pix[g.levels] - g.pix[1]) * 4; }
-
-template <bool RGB>
-__device__ __forceinline__ float plane_value(const float *__restrict__ img, const long p, const long hw, const long off)
-{
-    if constexpr (RGB) {
-        return 255.f * img[p * hw + off];
-    } else {
-        const float *px = img + 3 * p * hw + off;
-        return YR * px[0] + YG * px[hw] + YB * px[2 * hw] + Y0;
-    }
-}
-
-// N planes of TH x SW in `v`: the taps down the columns of N planes of SH x SW in `s`; prod(i, val) gives the N values at index i
-template <int N, class F>
-__device__ __forceinline__ void filter_columns(float *__restrict__ v, const Taps &taps, const F &prod)
-{
-    for (int idx = threadIdx.x; idx < TH * SW; idx += THREADS) {
-        float acc[N];
-#pragma unroll
-        for (int q = 0; q < N; ++q) acc[q] = 0.f;
-#pragma unroll
-        for (int i = 0; i < TAPS; ++i) {
-            float val[N];
-            prod(idx + i * SW, val);
-#pragma unroll
-            for (int q = 0; q < N; ++q) acc[q] += taps.g[i] * val[q];
-        }
-#pragma unroll
-        for (int q = 0; q < N; ++q) v[q * TH * SW + idx] = acc[q];
-    }
-}
-
-// the taps along row r of the N planes in `v`, at column c
-template <int N>
-__device__ __forceinline__ void filter_row(const float *__restrict__ v, const Taps &taps, const int r, const int c, float (&out)[N])
-{
-#pragma unroll
-    for (int q = 0; q < N; ++q) out[q] = 0.f;
-#pragma unroll
-    for (int j = 0; j < TAPS; ++j)
-#pragma unroll
-        for (int q = 0; q < N; ++q) out[q] += taps.g[j] * v[q * TH * SW + r * SW + c + j];
-}
 
 // ---- forward 1: the planes and their pooled levels ---------------------------------------------------------------
 template <bool RGB>
@@ -218,60 +153,30 @@ __global__ __launch_bounds__(THREADS) void msssim_stats_kernel(const float *__re
     const int t = (int)(local % tiles);
     const int y0 = (t / g.ftx[j]) * TH, x0 = (t % g.ftx[j]) * TW;
     const float *X = pyramid + g.pix[j] + p * H * W, *Y = X + g.pix[g.levels];
-    const int cy = min(y0 + SH / 2, H - 1), cx = min(x0 + SW / 2, W - 1);
-    const float rx = X[(long)cy * W + cx], ry = Y[(long)cy * W + cx];
-
-    for (int idx = tid; idx < SH * SW; idx += THREADS) {
-        const int gy = y0 + idx / SW, gx = x0 + idx % SW;
-        float xv = 0.f, yv = 0.f;
-        if (gy < H && gx < W) {
-            const long off = (long)gy * W + gx;
-            xv = X[off] - rx;
-            yv = Y[off] - ry;
-        }
-        s[idx] = xv;
-        s[SH * SW + idx] = yv;
-    }
-    __syncthreads();
-    filter_columns<5>(v, taps, [&](const int i, float (&val)[5]) {
-        const float xv = s[i], yv = s[SH * SW + i];
-        val[0] = xv, val[1] = yv, val[2] = xv * xv, val[3] = yv * yv, val[4] = xv * yv;
-    });
-    __syncthreads();
 
     float fsum = 0.f;
-#pragma unroll
-    for (int k = 0; k < PER_THREAD; ++k) {
-        const int idx = k * THREADS + tid, r = idx / TW, c = idx % TW;
-        const int my = y0 + r, mx = x0 + c;
-        float f[5];
-        filter_row<5>(v, taps, r, c, f);
-        const float u = f[0], w = f[1];
-        const float mux = u + rx, muy = w + ry;
-        const float sxx = f[2] - u * u, syy = f[3] - w * w, sxy = f[4] - u * w;
-        const float a2 = 2.f * sxy + C2, b2 = sxx + syy + C2, ib2 = 1.f / b2;
-        if (my >= MH || mx >= MW) continue;
-        const long o = g.map[j] + (p * MH + my) * MW + mx;
-        if (last) {
-            const float a1 = 2.f * mux * muy + C1, b1 = mux * mux + muy * muy + C1;
-            const float ib1 = 1.f / b1, d = ib1 * ib2;
-            const float m = a1 * a2 * d;
-            fsum += m;
-            if constexpr (WANT_GRAD) {
-                maps[o] = 2.f * muy * (a2 - a1) * d + 2.f * mux * m * (ib2 - ib1);
-                maps[g.map[g.levels] + o] = -m * ib2;
-                maps[2 * g.map[g.levels] + o] = 2.f * a1 * d;
+    moments_tile(
+        s, v, taps, H, W, y0, x0, [&](const long off, float &xv, float &yv) { xv = X[off], yv = Y[off]; },
+        [&](const int my, const int mx, const Moments &q) {
+            // (in front of the test and the branches: there the compiler shares A2 and 1 / B2 with ssim_terms, one division per position
+            // for either kind of level; behind them it emits the division a second time)
+            const float a2 = 2.f * q.sxy + C2, b2 = q.sxx + q.syy + C2, ib2 = 1.f / b2;
+            if (my >= MH || mx >= MW) return;
+            const long o = g.map[j] + (p * MH + my) * MW + mx;
+            if (last) {
+                const Terms t = ssim_terms(q);
+                fsum += t.m;
+                if constexpr (WANT_GRAD) maps[o] = t.a, maps[g.map[g.levels] + o] = t.b, maps[2 * g.map[g.levels] + o] = t.c;
+            } else {
+                const float cs = a2 * ib2;
+                fsum += cs;
+                if constexpr (WANT_GRAD) {
+                    maps[o] = 2.f * (q.mux * cs - q.muy) * ib2;
+                    maps[g.map[g.levels] + o] = -cs * ib2;
+                    maps[2 * g.map[g.levels] + o] = 2.f * ib2;
+                }
             }
-        } else {
-            const float cs = a2 * ib2;
-            fsum += cs;
-            if constexpr (WANT_GRAD) {
-                maps[o] = 2.f * (mux * cs - muy) * ib2;
-                maps[g.map[g.levels] + o] = -cs * ib2;
-                maps[2 * g.map[g.levels] + o] = 2.f * ib2;
-            }
-        }
-    }
+        });
     const float bsum = mrefsr::block_sum<THREADS>(v, fsum);   // (meets first: every thread has read v, it becomes the tree)
     if (tid == 0) partial[bid] = bsum;
 }
@@ -318,44 +223,28 @@ __global__ __launch_bounds__(THREADS) void msssim_combine_kernel(const float *__
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------
-// level j's own term mult (G^T a + 2 X G^T b + Y G^T c) of plane p at the block's 16 x 32 pixels from (y0, x0): emit(k, off, value)
-// for the thread's pixels k = 0, 1 inside the level, off = y W + x.  s: 3 SH SW floats of LDS, v: 3 TH SW.
+// level j's own term mult (G^T a + 2 X G^T b + Y G^T c) of plane p at the block's 16 x 32 pixels from (y0, x0), by adjoint_tile of
+// ssim_window.h: emit(off, value) for the thread's pixels inside the level, off = y W + x.  s: 3 SH SW floats of LDS, v: 3 TH SW.
 template <class E>
 __device__ __forceinline__ void own_term(const Pyr &g, const int j, const long p, const int y0, const int x0, const float *__restrict__ pyramid,
                                          const float *__restrict__ maps, const float *__restrict__ mult, const Taps &taps, float *s, float *v,
                                          const E &emit)
 {
-    const int tid = threadIdx.x;
     const int H = g.h[j], W = g.w[j], MH = H - HALO, MW = W - HALO;
     const float m = mult[p * g.levels + j];
     const float *A = maps + g.map[j] + p * MH * MW, *B = A + g.map[g.levels], *C = B + g.map[g.levels];
     const float *X = pyramid + g.pix[j] + p * H * W, *Y = X + g.pix[g.levels];
-
-    for (int idx = tid; idx < SH * SW; idx += THREADS) {
-        const int my = y0 - HALO + idx / SW, mx = x0 - HALO + idx % SW;
-        float av = 0.f, bv = 0.f, cv = 0.f;
-        if (m != 0.f && my >= 0 && my < MH && mx >= 0 && mx < MW) {
+    // (the zero rule: a plane whose multiplier is 0 gets exactly 0, whatever its maps hold -- they are not even read)
+    adjoint_tile(
+        s, v, taps, H, W, y0, x0,
+        [&](const int my, const int mx, float &av, float &bv, float &cv) {
             const long o = (long)my * MW + mx;
-            av = A[o], bv = B[o], cv = C[o];
-        }
-        s[idx] = av;
-        s[SH * SW + idx] = bv;
-        s[2 * SH * SW + idx] = cv;
-    }
-    __syncthreads();
-    filter_columns<3>(v, taps, [&](const int i, float (&val)[3]) { val[0] = s[i], val[1] = s[SH * SW + i], val[2] = s[2 * SH * SW + i]; });
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < PER_THREAD; ++k) {
-        const int idx = k * THREADS + tid, r = idx / TW, c = idx % TW;
-        const int gy = y0 + r, gx = x0 + c;
-        if (gy >= H || gx >= W) continue;
-        float t[3];
-        filter_row<3>(v, taps, r, c, t);
-        const long off = (long)gy * W + gx;
-        // (the zero rule: a plane whose multiplier is 0 gets exactly 0, whatever its maps hold)
-        emit(k, off, m != 0.f ? m * (t[0] + 2.f * X[off] * t[1] + Y[off] * t[2]) : 0.f);
-    }
+            if (m != 0.f) av = A[o], bv = B[o], cv = C[o];
+        },
+        [&](const int gy, const int gx, const float (&t)[3]) {
+            const long off = (long)gy * W + gx;
+            emit(off, m != 0.f ? m * (t[0] + 2.f * X[off] * t[1] + Y[off] * t[2]) : 0.f);
+        });
 }
 
 __global__ __launch_bounds__(THREADS) void msssim_bwd_levels_kernel(const float *__restrict__ pyramid, const float *__restrict__ maps,
@@ -372,7 +261,7 @@ __global__ __launch_bounds__(THREADS) void msssim_bwd_levels_kernel(const float 
     const int t = (int)(local % tiles);
     float *out = own + (g.pix[j] - g.pix[1]) + p * g.h[j] * g.w[j];
     own_term(g, j, p, (t / g.btx[j]) * TH, (t % g.btx[j]) * TW, pyramid, maps, mult, taps, s, v,
-             [&](const int, const long off, const float val) { out[off] = val; });
+             [&](const long off, const float val) { out[off] = val; });
 }
 
 template <bool RGB>
@@ -386,7 +275,7 @@ __global__ __launch_bounds__(THREADS) void msssim_bwd_finish_kernel(const float 
     const int W = g.w[0];
     const long p = blockIdx.z, hw = (long)g.h[0] * W;
     const float f = scale * gup[0];
-    own_term(g, 0, p, blockIdx.y * TH, blockIdx.x * TW, pyramid, maps, mult, taps, s, v, [&](const int, const long off, const float g1) {
+    own_term(g, 0, p, blockIdx.y * TH, blockIdx.x * TW, pyramid, maps, mult, taps, s, v, [&](const long off, const float g1) {
         const int y = (int)(off / W), x = (int)(off % W);
         float t = 0.f;
         for (int j = g.levels - 1; j >= 1; --j) {
@@ -394,13 +283,7 @@ __global__ __launch_bounds__(THREADS) void msssim_bwd_finish_kernel(const float 
             // (outside level j's pooled region the pixel is outside every coarser one: t is still 0)
             t = yy < g.h[j] && xx < g.w[j] ? own[(g.pix[j] - g.pix[1]) + (p * g.h[j] + yy) * g.w[j] + xx] + 0.25f * t : 0.f;
         }
-        const float d = f * (g1 + 0.25f * t);
-        if constexpr (RGB) {
-            grad[p * hw + off] = 255.f * d;
-        } else {
-            float *out = grad + 3 * p * hw + off;
-            out[0] = YR * d, out[hw] = YG * d, out[2 * hw] = YB * d;
-        }
+        store_plane_grad<RGB>(grad, p, hw, off, f * (g1 + 0.25f * t));
     });
 }
 

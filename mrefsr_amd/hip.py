@@ -1787,15 +1787,23 @@ def ref_gather(src, sel, n, out=None):
 SSIM_TILE = (16, 32)   # map positions per forward block / pixels per backward block (rows, columns)
 
 
+def _ssim_planes(name, shape, rgb):
+    """(B, H, W, planes) of a [B,3,H,W] call of the SSIM and MS-SSIM kernels: one plane per image, three with rgb, or ValueError"""
+    if len(shape) != 4 or shape[1] != 3:
+        raise ValueError(f'{name}: [B,3,H,W] images expected, got {tuple(shape)}')
+    b, _, h, w = shape
+    return b, h, w, (3 if rgb else 1) * b
+
+
 def _ssim_shape(name, pred, target, rgb):
     _chk(name, pred, target)
-    if pred.dim() != 4 or pred.shape[1] != 3 or pred.shape != target.shape:
-        raise ValueError(f'{name}: pred and target must be [B,3,H,W] of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}')
-    b, _, h, w = pred.shape
+    if pred.shape != target.shape:
+        raise ValueError(f'{name}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
+    b, h, w, planes = _ssim_planes(name, pred.shape, rgb)
     blocks = _lib.load().mrefsr_ssim_loss_blocks(b, h, w, int(bool(rgb)))
     if blocks <= 0:
         raise ValueError(f'{name}: unsupported shape {tuple(pred.shape)} (B <= 21845, 11 <= H, W <= 2^19, H W <= 2^30)')
-    return b, h, w, blocks
+    return b, h, w, planes, blocks
 
 
 def ssim_loss_fwd(pred, target, rgb=False, loss_weight=1.0, want_grad=False):
@@ -1803,8 +1811,7 @@ def ssim_loss_fwd(pred, target, rgb=False, loss_weight=1.0, want_grad=False):
     plane of every image (rgb=False) or its three colour planes at 255 scale (rgb=True); maps: None, or with want_grad the
     coefficient maps (a, b, c), each [planes,H-10,W-10], that ssim_loss_bwd reads.  One launch, a fixed summation order (the same
     bits from call to call), nothing read back; pred and target are only read"""
-    b, h, w, blocks = _ssim_shape('ssim_loss_fwd', pred, target, rgb)
-    planes = (3 if rgb else 1) * b
+    b, h, w, planes, blocks = _ssim_shape('ssim_loss_fwd', pred, target, rgb)
     maps = tuple(torch.empty((planes, h - 10, w - 10), device=pred.device, dtype=torch.float32) for _ in range(3)) if want_grad else None
     loss = torch.empty((), device=pred.device, dtype=torch.float32)
     part, ticket = _det_scratch(pred.device, 4 * blocks)
@@ -1818,9 +1825,8 @@ def ssim_loss_fwd(pred, target, rgb=False, loss_weight=1.0, want_grad=False):
 def ssim_loss_bwd(pred, target, maps, grad_loss, rgb=False, loss_weight=1.0):
     """d (grad_loss * loss) / d pred [B,3,H,W] of ssim_loss_fwd from its coefficient maps; grad_loss: the upstream gradient, a
     one-element fp32 device tensor (read by the kernel, not by the host).  One launch; every element is written once"""
-    b, h, w, _ = _ssim_shape('ssim_loss_bwd', pred, target, rgb)
+    b, h, w, planes, _ = _ssim_shape('ssim_loss_bwd', pred, target, rgb)
     _chk('ssim_loss_bwd', grad_loss, *maps)
-    planes = (3 if rgb else 1) * b
     if grad_loss.numel() != 1 or len(maps) != 3 or any(m.shape != (planes, h - 10, w - 10) for m in maps):
         raise ValueError(f'ssim_loss_bwd: one upstream value and three maps of {(planes, h - 10, w - 10)} expected')
     grad = torch.empty_like(pred)
@@ -1831,20 +1837,18 @@ def ssim_loss_bwd(pred, target, maps, grad_loss, rgb=False, loss_weight=1.0):
 
 
 # ------------------------------------------------------------------ multi-scale SSIM: loss and validation metric (csrc/msssim.hip)
-MSSSIM_MAX_LEVELS = 5   # MREFSR_MSSSIM_MAX_LEVELS
+MSSSIM_MAX_LEVELS = 5   # MREFSR_MSSSIM_MAX_LEVELS (losses.py takes it from here)
 
 
 def _msssim_shape(name, shape, rgb, levels):
-    """(B, H, W, floats of the two pyramids, floats of the three map sets) of a [B,3,H,W] call, or ValueError"""
-    if len(shape) != 4 or shape[1] != 3:
-        raise ValueError(f'{name}: [B,3,H,W] images expected, got {tuple(shape)}')
-    b, _, h, w = shape
+    """(B, H, W, planes, floats of the two pyramids, floats of the three map sets) of a [B,3,H,W] call, or ValueError"""
+    b, h, w, planes = _ssim_planes(name, shape, rgb)
     lib = _lib.load()
     pyr = lib.mrefsr_msssim_pyramid_floats(b, h, w, int(bool(rgb)), int(levels))
     if pyr <= 0:
         raise ValueError(f'{name}: unsupported shape {tuple(shape)} with {levels} levels (1..{MSSSIM_MAX_LEVELS} levels, '
                          'min(H, W) >> (levels - 1) >= 11, B <= 21845, H, W <= 2^19, H W <= 2^30)')
-    return b, h, w, pyr, lib.mrefsr_msssim_map_floats(b, h, w, int(bool(rgb)), int(levels))
+    return b, h, w, planes, pyr, lib.mrefsr_msssim_map_floats(b, h, w, int(bool(rgb)), int(levels))
 
 
 def msssim_loss_fwd(pred, target, weights, rgb=False, loss_weight=1.0, want_grad=False, want_values=False):
@@ -1858,8 +1862,7 @@ def msssim_loss_fwd(pred, target, weights, rgb=False, loss_weight=1.0, want_grad
     if pred.shape != target.shape:
         raise ValueError(f'msssim_loss_fwd: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
     levels = len(weights)
-    b, h, w, pyr_floats, map_floats = _msssim_shape('msssim_loss_fwd', pred.shape, rgb, levels)
-    planes = (3 if rgb else 1) * b
+    b, h, w, planes, pyr_floats, map_floats = _msssim_shape('msssim_loss_fwd', pred.shape, rgb, levels)
     dev = pred.device
     ws_bytes = _lib.load().mrefsr_msssim_workspace_bytes(b, h, w, int(bool(rgb)), levels, 0)
     loss = torch.empty((), device=dev, dtype=torch.float32)
@@ -1888,8 +1891,7 @@ def msssim_loss_bwd(saved, grad_loss, shape, rgb=False, loss_weight=1.0):
     pyramid, maps, mult = saved
     _chk('msssim_loss_bwd', grad_loss, pyramid, maps, mult)
     levels = mult.shape[1] if mult.dim() == 2 else 0
-    b, h, w, pyr_floats, map_floats = _msssim_shape('msssim_loss_bwd', shape, rgb, levels)
-    planes = (3 if rgb else 1) * b
+    b, h, w, planes, pyr_floats, map_floats = _msssim_shape('msssim_loss_bwd', shape, rgb, levels)
     if grad_loss.numel() != 1 or pyramid.numel() != pyr_floats or maps.numel() != map_floats or mult.shape[0] != planes:
         raise ValueError(f'msssim_loss_bwd: one upstream value, a pyramid of {pyr_floats}, maps of {map_floats} floats and multipliers '
                          f'[{planes}, {levels}] expected')

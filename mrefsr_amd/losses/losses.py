@@ -22,6 +22,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from ..archs.vgg_arch import VGGFeatureExtractor
+from ..hip import MSSSIM_MAX_LEVELS   # (5: the levels the kernels of csrc/msssim.hip take)
 from ..metrics import MSSSIM_WEIGHTS   # (0.0448, 0.2856, 0.3001, 0.2363, 0.1333): Wang, Simoncelli, Bovik 2003
 from ..utils.registry import LOSS_REGISTRY
 
@@ -175,27 +176,58 @@ class TextureLoss(nn.Module):
         return total[0]
 
 
-def ssim_loss_torch(pred, target, channel='y'):
-    """1 - mean SSIM map of [B,3,H,W] images in the nominal range [0, 1], as torch operations in the tensors' dtype and on their
-    device: the definition SSIMLoss implements (and what it runs for CPU tensors).  Planes: channel 'y', X = 65.481 R + 128.553 G +
-    24.966 B + 16 (metrics.rgb_to_y without its float32 round trip); 'rgb', X = 255 x per colour plane.  Per plane the five moments
-    under the normalised 11-tap Gaussian of metrics._gaussian_window, applied separably on the valid region (metrics._filter_valid),
-    and the map of metrics._ssim with C1 = (0.01 255)^2, C2 = (0.03 255)^2.  Nothing is clamped or quantised."""
-    from ..metrics import _gaussian_window
+_SSIM_C1, _SSIM_C2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+
+
+def _ssim_planes(pred, target, channel):
+    """(x, y) [P,1,H,W] at 255 scale of [B,3,H,W] images in the nominal range [0, 1]: channel 'y', one plane per image, X = 65.481 R +
+    128.553 G + 24.966 B + 16 (metrics.rgb_to_y without its float32 round trip); 'rgb', three per image, X = 255 x"""
     if channel == 'y':
         coef = pred.new_tensor([65.481, 128.553, 24.966]).view(1, 3, 1, 1)
         x, y = (pred * coef).sum(1, keepdim=True) + 16.0, (target * coef).sum(1, keepdim=True) + 16.0
     else:
         x, y = 255.0 * pred, 255.0 * target
-    x, y = x.reshape(-1, 1, *x.shape[2:]), y.reshape(-1, 1, *y.shape[2:])
-    k = torch.from_numpy(_gaussian_window(11, 1.5)).to(device=pred.device, dtype=pred.dtype)
+    return x.reshape(-1, 1, *x.shape[2:]), y.reshape(-1, 1, *y.shape[2:])
+
+
+def _ssim_moments(x, y):
+    """(mu1_sq, mu2_sq, mu1_mu2, s1, s2, s12) of planes x, y [P,1,H,W]: the window moments under the normalised 11-tap Gaussian of
+    metrics._gaussian_window, applied separably on the valid region (metrics._filter_valid), in the planes' dtype"""
+    from ..metrics import _gaussian_window
+    k = torch.from_numpy(_gaussian_window(11, 1.5)).to(device=x.device, dtype=x.dtype)
 
     def filt(z):
         return F.conv2d(F.conv2d(z, k.view(1, 1, 11, 1)), k.view(1, 1, 1, 11))
-    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
     mu1, mu2 = filt(x), filt(y)
     mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
-    s1, s2, s12 = filt(x * x) - mu1_sq, filt(y * y) - mu2_sq, filt(x * y) - mu1_mu2
+    return mu1_sq, mu2_sq, mu1_mu2, filt(x * x) - mu1_sq, filt(y * y) - mu2_sq, filt(x * y) - mu1_mu2
+
+
+def _ssim_check_options(name, window_size, sigma, channel):
+    if window_size != 11 or sigma != 1.5:
+        raise NotImplementedError(f'{name}: window_size={window_size!r}, sigma={sigma!r}; only the 11-tap window with sigma 1.5 of '
+                                  'the validation metric is implemented')
+    if channel not in ('y', 'rgb'):
+        raise NotImplementedError(f"{name}: channel={channel!r}; 'y' or 'rgb'")
+
+
+def _ssim_check_images(name, pred, target, check_size):
+    """the input checks of SSIMLoss and MSSSIMLoss in their order: [B,3,H,W], one shape, check_size(H, W), fp32 on the GPU"""
+    if pred.dim() != 4 or pred.shape[1] != 3:
+        raise NotImplementedError(f'{name}: [B,3,H,W] images expected, got {tuple(pred.shape)}')
+    if target.shape != pred.shape:
+        raise ValueError(f'{name}: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
+    check_size(pred.shape[2], pred.shape[3])
+    if pred.is_cuda and (pred.dtype != torch.float32 or target.dtype != torch.float32):
+        raise NotImplementedError(f'{name}: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
+
+
+def ssim_loss_torch(pred, target, channel='y'):
+    """1 - mean SSIM map of [B,3,H,W] images in the nominal range [0, 1], as torch operations in the tensors' dtype and on their
+    device: the definition SSIMLoss implements (and what it runs for CPU tensors).  Per plane of _ssim_planes the moments of
+    _ssim_moments and the map of metrics._ssim with C1 = (0.01 255)^2, C2 = (0.03 255)^2.  Nothing is clamped or quantised."""
+    mu1_sq, mu2_sq, mu1_mu2, s1, s2, s12 = _ssim_moments(*_ssim_planes(pred, target, channel))
+    c1, c2 = _SSIM_C1, _SSIM_C2
     return 1.0 - (((2 * mu1_mu2 + c1) * (2 * s12 + c2)) / ((mu1_sq + mu2_sq + c1) * (s1 + s2 + c2))).mean()
 
 
@@ -235,29 +267,19 @@ class SSIMLoss(nn.Module):
 
     def __init__(self, loss_weight=1.0, channel='y', window_size=11, sigma=1.5):
         super().__init__()
-        if window_size != 11 or sigma != 1.5:
-            raise NotImplementedError(f'SSIMLoss: window_size={window_size!r}, sigma={sigma!r}; only the 11-tap window with sigma 1.5 of '
-                                      'the validation metric is implemented')
-        if channel not in ('y', 'rgb'):
-            raise NotImplementedError(f"SSIMLoss: channel={channel!r}; 'y' or 'rgb'")
+        _ssim_check_options('SSIMLoss', window_size, sigma, channel)
         self.loss_weight, self.channel, self.window_size, self.sigma = loss_weight, channel, window_size, sigma
 
+    def check_size(self, h, w):
+        if h < self.window_size or w < self.window_size:
+            raise ValueError(f'SSIMLoss: {h} x {w} images are smaller than the {self.window_size}-tap window')
+
     def forward(self, pred, target, **kwargs):
-        if pred.dim() != 4 or pred.shape[1] != 3:
-            raise NotImplementedError(f'SSIMLoss: [B,3,H,W] images expected, got {tuple(pred.shape)}')
-        if target.shape != pred.shape:
-            raise ValueError(f'SSIMLoss: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
-        if pred.shape[2] < self.window_size or pred.shape[3] < self.window_size:
-            raise ValueError(f'SSIMLoss: {pred.shape[2]} x {pred.shape[3]} images are smaller than the {self.window_size}-tap window')
+        _ssim_check_images('SSIMLoss', pred, target, self.check_size)
         target = target.detach()
         if not pred.is_cuda:
             return self.loss_weight * ssim_loss_torch(pred, target, self.channel)
-        if pred.dtype != torch.float32 or target.dtype != torch.float32:
-            raise NotImplementedError(f'SSIMLoss: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
         return _SSIMLossFn.apply(pred.contiguous(), target.contiguous(), self.channel == 'rgb', float(self.loss_weight))
-
-
-MSSSIM_MAX_LEVELS = 5
 
 
 def msssim_levels_allowed(h, w):
@@ -277,22 +299,15 @@ def _msssim_check_size(name, h, w, levels):
 
 def msssim_planes_torch(x, y, weights=MSSSIM_WEIGHTS):
     """v_p [P]: the MS-SSIM of each pair of planes x, y [P,1,H,W] at 255 scale, as torch operations in their dtype.  Level 1 is the
-    plane, level j + 1 = F.avg_pool2d(level j, 2) (a trailing odd row or column is dropped); at every level the 11-tap Gaussian of
-    metrics._gaussian_window on the valid region, C1 = (0.01 255)^2, C2 = (0.03 255)^2; F_j = mean cs for j < M, F_M = mean l cs;
+    plane, level j + 1 = F.avg_pool2d(level j, 2) (a trailing odd row or column is dropped); at every level the moments of
+    _ssim_moments, C1 = (0.01 255)^2, C2 = (0.03 255)^2; F_j = mean cs for j < M, F_M = mean l cs;
     v = prod_j F_j^w_j when every F_j > 0, otherwise 0 with gradient exactly 0 (a rule: relu(F)^w would give 0 inf = NaN there)."""
-    from ..metrics import _gaussian_window
-    k = torch.from_numpy(_gaussian_window(11, 1.5)).to(device=x.device, dtype=x.dtype)
-
-    def filt(z):
-        return F.conv2d(F.conv2d(z, k.view(1, 1, 11, 1)), k.view(1, 1, 1, 11))
-    c1, c2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2
+    c1, c2 = _SSIM_C1, _SSIM_C2
     fs = []
     for j in range(len(weights)):
         if j:
             x, y = F.avg_pool2d(x, 2), F.avg_pool2d(y, 2)
-        mu1, mu2 = filt(x), filt(y)
-        mu1_sq, mu2_sq, mu1_mu2 = mu1 * mu1, mu2 * mu2, mu1 * mu2
-        s1, s2, s12 = filt(x * x) - mu1_sq, filt(y * y) - mu2_sq, filt(x * y) - mu1_mu2
+        mu1_sq, mu2_sq, mu1_mu2, s1, s2, s12 = _ssim_moments(x, y)
         m = (2 * s12 + c2) / (s1 + s2 + c2)
         if j == len(weights) - 1:
             m = m * ((2 * mu1_mu2 + c1) / (mu1_sq + mu2_sq + c1))
@@ -306,17 +321,11 @@ def msssim_planes_torch(x, y, weights=MSSSIM_WEIGHTS):
 
 def msssim_loss_torch(pred, target, channel='y', weights=None):
     """1 - mean_p MS-SSIM of [B,3,H,W] images in the nominal range [0, 1], as torch operations in the tensors' dtype and on their
-    device: the definition MSSSIMLoss implements (and what it runs for CPU tensors).  Planes as in ssim_loss_torch (channel 'y': one
-    per image, X = 65.481 R + 128.553 G + 24.966 B + 16; 'rgb': three per image, X = 255 x); per plane msssim_planes_torch with
-    weights (w_1 .. w_M), default MSSSIM_WEIGHTS, used as given.  Nothing is clamped or quantised."""
+    device: the definition MSSSIMLoss implements (and what it runs for CPU tensors).  The planes of _ssim_planes (channel 'y': one
+    per image; 'rgb': three per image), per plane msssim_planes_torch with weights (w_1 .. w_M), default MSSSIM_WEIGHTS, used as
+    given.  Nothing is clamped or quantised."""
     weights = MSSSIM_WEIGHTS if weights is None else tuple(weights)
-    if channel == 'y':
-        coef = pred.new_tensor([65.481, 128.553, 24.966]).view(1, 3, 1, 1)
-        x, y = (pred * coef).sum(1, keepdim=True) + 16.0, (target * coef).sum(1, keepdim=True) + 16.0
-    else:
-        x, y = 255.0 * pred, 255.0 * target
-    x, y = x.reshape(-1, 1, *x.shape[2:]), y.reshape(-1, 1, *y.shape[2:])
-    return 1.0 - msssim_planes_torch(x, y, weights).mean()
+    return 1.0 - msssim_planes_torch(*_ssim_planes(pred, target, channel), weights).mean()
 
 
 class _MSSSIMLossFn(torch.autograd.Function):
@@ -357,11 +366,7 @@ class MSSSIMLoss(nn.Module):
 
     def __init__(self, loss_weight=1.0, channel='y', weights=None, window_size=11, sigma=1.5):
         super().__init__()
-        if window_size != 11 or sigma != 1.5:
-            raise NotImplementedError(f'MSSSIMLoss: window_size={window_size!r}, sigma={sigma!r}; only the 11-tap window with sigma 1.5 of '
-                                      'the validation metric is implemented')
-        if channel not in ('y', 'rgb'):
-            raise NotImplementedError(f"MSSSIMLoss: channel={channel!r}; 'y' or 'rgb'")
+        _ssim_check_options('MSSSIMLoss', window_size, sigma, channel)
         weights = MSSSIM_WEIGHTS if weights is None else tuple(float(v) for v in weights)
         if not 1 <= len(weights) <= MSSSIM_MAX_LEVELS:
             raise ValueError(f'MSSSIMLoss: {len(weights)} weights; one per level, 1 to {MSSSIM_MAX_LEVELS} levels')
@@ -374,16 +379,10 @@ class MSSSIMLoss(nn.Module):
         _msssim_check_size('MSSSIMLoss', h, w, len(self.weights))
 
     def forward(self, pred, target, **kwargs):
-        if pred.dim() != 4 or pred.shape[1] != 3:
-            raise NotImplementedError(f'MSSSIMLoss: [B,3,H,W] images expected, got {tuple(pred.shape)}')
-        if target.shape != pred.shape:
-            raise ValueError(f'MSSSIMLoss: pred {tuple(pred.shape)} and target {tuple(target.shape)} differ')
-        self.check_size(pred.shape[2], pred.shape[3])
+        _ssim_check_images('MSSSIMLoss', pred, target, self.check_size)
         target = target.detach()
         if not pred.is_cuda:
             return self.loss_weight * msssim_loss_torch(pred, target, self.channel, self.weights)
-        if pred.dtype != torch.float32 or target.dtype != torch.float32:
-            raise NotImplementedError(f'MSSSIMLoss: {pred.dtype} / {target.dtype} images; fp32 only on the GPU')
         return _MSSSIMLossFn.apply(pred.contiguous(), target.contiguous(), self.channel == 'rgb', float(self.loss_weight), self.weights)
 
 
