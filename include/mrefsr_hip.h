@@ -305,6 +305,34 @@ int mrefsr_mrattn_fwd_nhwc_masked_f32(const float *q, const float *emb, const fl
                                       int N, int T, int c, int HW, float q_scale, mrefsr_stream_t stream);
 int mrefsr_mrattn_fwd_nhwc_masked_bf16(const void *q, const void *emb, const void *ass, const uint32_t *valid_bits, void *out, int N,
                                        int T, int c, int HW, mrefsr_stream_t stream);
+/* The same head with the blend moved in front of conv_ass (ref_mrapa_restoration_arch.py:321-335).  conv_ass is a plain 3x3
+ * convolution and the softmax weights depend on the output pixel only, so
+ *   sum_t p_t(x) (sum_d W_d s_t(x + d) + b)  =  sum_d W_d (sum_t p_t(x) s_t(x + d))  +  b sum_t p_t(x):
+ * one implicit GEMM over N images instead of a convolution over T * N images and a pass that folds its T results.
+ * mrefsr_mrattn_prob_nhwc_f32 (ref_mrapa_restoration_arch.py:321-335: the softmax of :323-329): prob [N][HW][T] fp32 from
+ * q [N][HW][c] and emb [T*N][HW][c] (t-major), q * q_scale formed on the way in -- the logits, maximum, expf, denominator and
+ * reciprocal of mrefsr_mrattn_fwd_nhwc_scaled_f32 / _masked_f32 in their order.  valid_bits may be NULL (every reference present);
+ * an absent t is never read and gets exactly 0, a sample without a present reference all zeros.  c in {64, 128, 256}, T <= 16. */
+int mrefsr_mrattn_prob_nhwc_f32(const float *q, const float *emb, const uint32_t *valid_bits, float *prob, int N, int T, int c,
+                                int HW, float q_scale, mrefsr_stream_t stream);
+/* mrefsr_mrattn_blend_conv_f32 (ref_mrapa_restoration_arch.py:321-335: conv_ass of :322 and the assembly of :331-335 in one launch):
+ *   refs [T*N][H][W][C] fp32 (t-major)   the warped reference maps conv_ass would read
+ *   prob [N][H][W][T]                    the weights above.  Precondition: prob >= 0 and sum_t prob <= 1 at every pixel; the range
+ *                                        guard checks the staged references, and |blend| <= max |refs| holds only under it
+ *   packed                               conv_ass.weight [2C][C][3][3] packed by mrefsr_conv_pack_weight_f32 with terms = 16 and
+ *                                        the power-of-two scale `wscale`
+ *   bias [2C] or NULL                    enters as bias * sum_t prob_t (the sum in fp32, present t ascending)
+ *   valid_bits [N] or NULL               an absent t is never staged or read (Inf / NaN there reaches nothing)
+ *   in_amax or NULL                      device word with max |refs|: the staged values are scaled by an exact power of two as in
+ *                                        mrefsr_conv_nhwc_scaled_f32
+ *   range_flag or NULL                   bit 0 is set when a staged value leaves the fp16 range (|x| > 65000)
+ *   out [N][H][W][2C] fp32
+ * The blend is an fp32 fma chain over t ascending, split exactly into two fp16 terms; three v_mfma_f32_32x32x16_f16 per product,
+ * fp32 accumulation in the fixed order channel chunk, tap, term: fp32-equivalent and bit-reproducible.  Any H, W >= 1;
+ * C in {64, 128, 256}; T <= 16. */
+int mrefsr_mrattn_blend_conv_f32(const float *refs, const float *prob, const void *packed, const float *bias, const uint32_t *valid_bits,
+                                 const float *in_amax, int *range_flag, float *out, int N, int T, int H, int W, int C, float wscale,
+                                 mrefsr_stream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------

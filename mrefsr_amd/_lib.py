@@ -93,6 +93,8 @@ SIGNATURES = {
     'mrefsr_mrattn_bwd_masked_f32': (_i, [_vp] * 9 + [_i] * 6 + [_vp]),
     'mrefsr_mrattn_fwd_nhwc_masked_f32': (_i, [_vp] * 5 + [_i, _i, _i, _i, _f, _vp]),
     'mrefsr_mrattn_fwd_nhwc_masked_bf16': (_i, [_vp] * 5 + [_i, _i, _i, _i, _vp]),
+    'mrefsr_mrattn_prob_nhwc_f32': (_i, [_vp] * 4 + [_i, _i, _i, _i, _f, _vp]),
+    'mrefsr_mrattn_blend_conv_f32': (_i, [_vp] * 8 + [_i, _i, _i, _i, _i, _f, _vp]),
     'mrefsr_fused_bias_act': (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _f, _f, _i, _vp]),
     'mrefsr_bias_act_res_f32': (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _i, _i64, _f, _vp]),
     'mrefsr_tail_bilinear_add_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -431,6 +431,16 @@ class MRAPAFusion(nn.Module):
         if not fold:
             q = q * self.scale if train else nhwc.rnd_(q.mul_(self.scale))
         emb = nhwc.conv(self.conv_emb2[0], refs, prelu=self.conv_emb2[1], amax=False)
+        if self.blend_first(fold, refs, t):
+            # conv_ass is linear and the softmax weights belong to the output pixel: blend the t references first, convolve n images
+            # instead of t * n (csrc/mrattn_conv.hip).  `ass` is never formed.
+            prob = hip.mrattn_prob_nhwc(q, emb, t, vb, q_scale=float(self.scale))
+            del emb
+            r = hip.mrattn_blend_conv(refs, prob, hip.packed_weight(self.conv_ass.weight, None, 16),
+                                      None if self.conv_ass.bias is None else self.conv_ass.bias.detach(), t, vb,
+                                      in_amax=nhwc.amax_of(refs) if nhwc.WINO_INSCALE else None)   # (the word conv_ass's Winograd launch took)
+            del prob
+            return self._modulate_fuse(target, r, train)
         ass = nhwc.conv(self.conv_ass, refs, amax=False)
         if vb is not None:   # per-sample reference masks: the masked forms of the same three kernels
             if fold:
@@ -442,6 +452,20 @@ class MRAPAFusion(nn.Module):
         else:
             r = nhwc_train.attention(q, emb, ass, t) if train else nhwc.rnd_(hip.mrattn_fwd_nhwc(q, emb, ass, t))
         del emb, ass
+        return self._modulate_fuse(target, r, train)
+
+    # True: inference blends the references in front of conv_ass (hip.mrattn_prob_nhwc + hip.mrattn_blend_conv); False: conv_ass on
+    # every reference, then mrattn_fwd_nhwc -- the form training keeps, and the one tests compare against
+    BLEND_FIRST = True
+
+    def blend_first(self, fold, refs, t):
+        """the blend-then-convolve kernels serve this call: fp32 inference on the fp16 two-term arithmetic (not the range-free re-run),
+        one of the three head widths, t <= 16"""
+        return (self.BLEND_FIRST and fold and nhwc.TERMS == 16 and not hip.is_range_free() and refs.dtype == torch.float32
+                and refs.shape[3] in (64, 128, 256) and self.conv_ass.out_channels == 2 * refs.shape[3] and t <= 16)
+
+    def _modulate_fuse(self, target, r, train):
+        """spatial attention and fusion of :337-348 on the assembled reference features r"""
         attn = nhwc.conv(self.spatial_attn, target, x2=r, slope=0.1)
         attn_mul = nhwc.conv(self.spatial_attn_mul2, nhwc.conv(self.spatial_attn_mul1, attn, slope=0.1), amax=False)   # (modulation terms)
         attn_add = nhwc.conv(self.spatial_attn_add2, nhwc.conv(self.spatial_attn_add1, attn, slope=0.1), amax=False)

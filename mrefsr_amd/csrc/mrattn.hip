@@ -238,6 +238,71 @@ __global__ __launch_bounds__(256) void mrattn_fwd_nhwc_kernel(const typename Io4
     }
 }
 
+// The softmax weights alone (mrattn_conv.hip blends the references with them in front of conv_ass): the logits, maximum, expf,
+// denominator and `inv` of mrattn_fwd_nhwc_kernel in its order, then prob [N][HW][T] = logit[t] * inv (exact 0 for an absent t, all 0
+// for a sample without a present reference), lane `sub` of the pixel's group writing weight t = sub (T <= 16 <= L lanes).
+template <int CH, bool MASKED>
+__global__ __launch_bounds__(256) void mrattn_prob_nhwc_kernel(const float *__restrict__ q, const float *__restrict__ emb, float *__restrict__ prob,
+                                                               int N, int T, long HW, float q_scale, const unsigned int *__restrict__ valid_bits)
+{
+    typedef Io4<false> IO;
+    constexpr int L = CH / 4, PPW = 64 / L;
+    const int lane = threadIdx.x & 63, sub = lane % L, pw = lane / L;
+    const long total = (long)N * HW;
+    const long wave = (blockIdx.x * (long)blockDim.x + threadIdx.x) >> 6, nwave = ((long)gridDim.x * blockDim.x) >> 6;
+    for (long base = wave * PPW; base < total; base += nwave * PPW) {
+        const long gp = base + pw;
+        const bool ok = gp < total;
+        const long g = ok ? gp : total - 1;
+        const long n = g / HW, p = g - n * HW;
+        const unsigned int vb = MASKED ? valid_bits[n] : 0u;
+        float4 qv = IO::ld(q + g * CH + 4 * sub);
+        qv.x *= q_scale, qv.y *= q_scale, qv.z *= q_scale, qv.w *= q_scale;
+        float logit[16];
+        float mx = -3.4e38f;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            if (t < T) {
+                float d = 0.f;
+                if (on<MASKED>(vb, t)) {
+                    const float4 e = IO::ld(emb + (((long)t * N + n) * HW + p) * CH + 4 * sub);
+                    d = qv.x * e.x + qv.y * e.y + qv.z * e.z + qv.w * e.w;
+                }
+#pragma unroll
+                for (int o = L / 2; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+                logit[t] = d;
+                if (on<MASKED>(vb, t)) mx = fmaxf(mx, d);
+            }
+        }
+        float den = 0.f;
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+            if (t < T && on<MASKED>(vb, t)) {
+                logit[t] = expf(logit[t] - mx);
+                den += logit[t];
+            }
+        const float inv = (!MASKED || den > 0.f) ? 1.0f / den : 0.f;
+        float mine = 0.f;
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+            if (t < T && sub == t) mine = on<MASKED>(vb, t) ? logit[t] * inv : 0.f;
+        if (ok && sub < T) prob[g * T + sub] = mine;
+    }
+}
+
+template <bool MASKED>
+int launch_mrattn_prob(const float *q, const float *emb, const unsigned int *vb, float *prob, int N, int T, int c, int HW, float q_scale, hipStream_t st)
+{
+    const long waves = ((long)N * HW * (c / 4) + 63) / 64;
+    const long blocks = (waves + 3) / 4;
+    const dim3 grid((int)(blocks < 65536 ? blocks : 65536));
+    if (c == 256) hipLaunchKernelGGL((mrattn_prob_nhwc_kernel<256, MASKED>), grid, dim3(256), 0, st, q, emb, prob, N, T, (long)HW, q_scale, vb);
+    else if (c == 128) hipLaunchKernelGGL((mrattn_prob_nhwc_kernel<128, MASKED>), grid, dim3(256), 0, st, q, emb, prob, N, T, (long)HW, q_scale, vb);
+    else if (c == 64) hipLaunchKernelGGL((mrattn_prob_nhwc_kernel<64, MASKED>), grid, dim3(256), 0, st, q, emb, prob, N, T, (long)HW, q_scale, vb);
+    else return mrefsr::fail(MREFSR_E_UNSUPPORTED, "mrattn_prob_nhwc: c=%d (64, 128 or 256: the three MRAPAFusion heads)", c);
+    return mrefsr::check_launch("mrattn_prob_nhwc");
+}
+
 template <bool IO16, bool MASKED>
 int launch_mrattn_nhwc(const void *q, const void *emb, const void *ass, const unsigned int *vb, void *out, int N, int T, int c, int HW, float q_scale,
                        hipStream_t st)
@@ -273,6 +338,16 @@ MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_scaled_f32(const float *q, const float 
     MREFSR_REQUIRE(q && emb && ass && out, "mrattn_fwd_nhwc_scaled: null pointer");
     MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_fwd_nhwc_scaled: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
     return launch_mrattn_nhwc<false, false>(q, emb, ass, nullptr, out, N, T, c, HW, q_scale, (hipStream_t)stream);
+}
+
+// the softmax weights of the same attention, prob [N][HW][T], without the assembly (valid_bits may be NULL: every reference present)
+MREFSR_EXPORT int mrefsr_mrattn_prob_nhwc_f32(const float *q, const float *emb, const uint32_t *valid_bits, float *prob, int N, int T, int c,
+                                              int HW, float q_scale, mrefsr_stream_t stream)
+{
+    MREFSR_REQUIRE(q && emb && prob, "mrattn_prob_nhwc: null pointer");
+    MREFSR_REQUIRE(N > 0 && T > 0 && T <= 16 && HW > 0, "mrattn_prob_nhwc: N=%d T=%d HW=%d (T <= 16)", N, T, HW);
+    return valid_bits ? launch_mrattn_prob<true>(q, emb, valid_bits, prob, N, T, c, HW, q_scale, (hipStream_t)stream)
+                      : launch_mrattn_prob<false>(q, emb, nullptr, prob, N, T, c, HW, q_scale, (hipStream_t)stream);
 }
 
 MREFSR_EXPORT int mrefsr_mrattn_fwd_nhwc_bf16(const void *q, const void *emb, const void *ass, void *out, int N, int T, int c, int HW,

@@ -698,6 +698,46 @@ def mrattn_fwd_nhwc_masked(q, emb, ass, t, valid_bits, q_scale=None):
     return out
 
 
+def mrattn_prob_nhwc(q, emb, t, valid_bits=None, q_scale=1.0):
+    """the softmax weights of mrattn_fwd_nhwc / _masked alone: q [N,H,W,c], emb [t*N,H,W,c] (t-major) -> prob [N,H,W,t] fp32; an
+    absent reference (valid_bits) gets exactly 0"""
+    _chk('mrattn_prob_nhwc', q, emb)
+    n, h, w, c = q.shape
+    if tuple(emb.shape) != (n * t, h, w, c):
+        raise ValueError('mrattn_prob_nhwc: inconsistent shapes')
+    if valid_bits is not None:
+        _chk_valid_bits('mrattn_prob_nhwc', valid_bits, n)
+    prob = torch.empty((n, h, w, t), device=q.device, dtype=torch.float32)
+    with _timed('mrattn_prob', ((t + 1.0) * c + t) * h * w * 4.0 * n, detail=True):   # "work" = algorithmic bytes, as mrattn_fwd
+        _lib.call('mrefsr_mrattn_prob_nhwc_f32', _p(q), _p(emb), _p(valid_bits), _p(prob), n, t, c, h * w, C.c_float(q_scale), _stream())
+    return prob
+
+
+def mrattn_blend_conv(refs, prob, packed, bias, t, valid_bits=None, in_amax=None):
+    """conv_ass applied to the softmax blend of the references (= the blend of conv_ass's results: the convolution is linear and the
+    weights belong to the output pixel): refs [t*N,H,W,C] (t-major), prob [N,H,W,t], packed = the terms-16 PackedWeight of the
+    [2C,C,3,3] weight, bias [2C] or None -> [N,H,W,2C].  in_amax: device word with max |refs| (None: no input scaling).
+    Precondition: prob >= 0 and sum_t prob <= 1 at every pixel (softmax weights, mrattn_prob_nhwc): the fp16 range guard
+    (conv_range_tripped) checks the staged references, and the blend stays below their maximum only under it"""
+    _chk('mrattn_blend_conv', refs, prob, bias, in_amax)
+    if packed.terms != 16:
+        raise ValueError('mrattn_blend_conv: weights packed with terms=16 expected')
+    tn, h, w, c = refs.shape
+    n = prob.shape[0]
+    if tn != n * t or tuple(prob.shape) != (n, h, w, t):
+        raise ValueError('mrattn_blend_conv: inconsistent shapes')
+    if packed.data.numel() != _lib.load().mrefsr_conv_packed_bytes(2 * c, c, 3, 16) or (bias is not None and bias.numel() != 2 * c):
+        raise ValueError('mrattn_blend_conv: weight / bias do not belong to a C -> 2C 3x3 convolution')
+    if valid_bits is not None:
+        _chk_valid_bits('mrattn_blend_conv', valid_bits, n)
+    out = torch.empty((n, h, w, 2 * c), device=refs.device, dtype=torch.float32)
+    nby = (refs.numel() + prob.numel() + out.numel()) * 4.0 + 4.0 * c * 2 * c * 9
+    with _timed('mrattn_blend_conv', 2.0 * n * h * w * c * 2 * c * 9, detail=True, nbytes=nby):
+        _lib.call('mrefsr_mrattn_blend_conv_f32', _p(refs), _p(prob), _p(packed.data), _p(bias), _p(valid_bits), _p(in_amax),
+                  _p(_range_flag(refs.device)), _p(out), n, t, h, w, c, C.c_float(packed.wscale), _stream())
+    return out
+
+
 def mrattn_bwd_masked(q, emb, ass, prob, g_out, t, valid_bits, t_major=False, out=None):
     """gradient of mrattn_fwd_masked -> (g_q, g_emb, g_ass); g_emb / g_ass of absent references are exact zeros.  out: the three
     buffers to write into (every element is written)"""
