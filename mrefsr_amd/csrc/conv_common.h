@@ -1,51 +1,14 @@
-// Pieces shared by the convolution kernels (conv_nhwc.hip: direct implicit GEMM; conv_wino.hip: Winograd F(2x2, 3x3)):
-// vector typedefs, the packed 16-bit conversions of the operand splits, the launch arguments and the streaming accessors.
+// Pieces shared by the convolution kernels (conv_nhwc.hip: direct implicit GEMM; conv_wino.hip, conv_wino4.hip: Winograd
+// F(2x2, 3x3)): the launch arguments, the chunk geometry, the streaming accessors and the Winograd entry points.  The vector
+// typedefs, the packed 16-bit conversions and the operand splits are split16.h's, re-exported here.
 #pragma once
 #include "common.h"
+#include "split16.h"
 
 namespace mrefsr_conv {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
+using namespace mrefsr_split16;
 
 constexpr int KC = 16, NB = 64;   // input channels per K chunk, output channels per block column
-
-__device__ __forceinline__ bf16x8 as_bf(u32x4 v) { return __builtin_bit_cast(bf16x8, v); }
-
-// packed round-to-nearest-even bf16 of two floats, and back
-__device__ __forceinline__ unsigned int pk_bf16(float a, float b)
-{
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{a, b}, bf16x2));
-}
-__device__ __forceinline__ float bf_lo(unsigned int p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float bf_hi(unsigned int p) { return __uint_as_float(p & 0xffff0000u); }
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned int pk_f16(float a, float b)   // round-to-nearest-even
-{
-    return __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{a, b}, f16x2));
-}
-__device__ __forceinline__ f32x2 un_f16(unsigned int p) { return __builtin_convertvector(__builtin_bit_cast(f16x2, p), f32x2); }
-
-// WH2 = wh * 2^-11 of 8 packed fp16: exact while the result is a normal fp16, round-to-nearest-even into the
-// denormals exactly like the pack kernel's conversion (plain v_pk_mul_f16: safe next to MFMAs, tools/hazard/)
-__device__ __forceinline__ u32x4 scale_wh(u32x4 v)
-{
-    const f16x2 k = {(_Float16)0.00048828125f, (_Float16)0.00048828125f};
-    u32x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned int d = v[i];
-        r[i] = __builtin_bit_cast(unsigned int, __builtin_bit_cast(f16x2, d) * k);
-    }
-    return r;
-}
 
 struct ConvArgs {
     const float *x1, *x2;
@@ -82,7 +45,6 @@ struct ConvArgs {
 // Output tensors beyond the MALL (256 MB; the 640^2 layers write 0.8-4 GB) are streamed: non-temporal output stores and
 // residual loads do not evict the halo tiles and weight fragments the blocks share (-1 % on those layers; on tensors
 // that fit, the next layer finds its input in the cache and the plain store is 10 % better: 160^2 x 64 channels)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st_f4(float *p, const float4 v, const bool stream)
 {
     if (stream) __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4 *>(p));

@@ -48,13 +48,8 @@ constexpr int DYN_T_LD = 36;                       // DynAgg epilogue: floats pe
 // Arithmetic modes (the `terms` argument of the C ABI):
 //   MODE 0 (terms 6):  bf16, activations and weights as hi + mid + lo, six partial products >= 2^-24
 //   MODE 1 (terms 3):  bf16, hi + lo, three products (~2^-16 relative; experiments only)
-//   MODE 2 (terms 16): fp16 (11-bit significands), two-term split = 22 bits, three products:
-//        a = ah + al,  al stored as AL = fp16(al * 2^11)            (same binade as a: never denormal before a is)
-//        w * S = wh + wl, S = 2^s chosen at pack time so that max|w| * S is in [2^13, 2^14)
-//                         (wl ~ 2^-11 wh stays a normal fp16 for every weight within 2^-17 of the largest);
-//                         a third plane WH2 = wh * 2^-11 (exact) pairs with AL
-//        a * w * S  ~=  ah*wh + ah*wl + AL*WH2        (dropped al*wl: 2^-22 relative), fp32 accumulation,
-//        the epilogue multiplies by 1/S.  Requires |a| < 65504 (fp16 range).
+//   MODE 2 (terms 16): fp16 (11-bit significands), two-term split = 22 bits, three products ah*wh + ah*wl + AL*WH2
+//        (split16.h states the split, its scales and its error); requires |a| < 65504 (fp16 range).
 //   MODE 3 (terms 1):  bf16 ARITHMETIC (BASELINE configs[4]): activations and weights rounded to bf16 (one plane
 //        each, one MFMA per product), fp32 accumulation, the result rounded to bf16 again (kept in an fp32 container)
 template <int MODE> struct ModeTraits;
@@ -72,15 +67,12 @@ __device__ __forceinline__ void split4(const float4 v, u32x2 *out)
 {
     float a = v.x, b = v.y, c = v.z, d = v.w;
     if (MODE == 2) {
-        const unsigned int p0 = pk_f16(a, b), p1 = pk_f16(c, d);
-        out[0] = u32x2{p0, p1};
-        const f32x2 h0 = un_f16(p0), h1 = un_f16(p1);
-        out[1] = u32x2{pk_f16((a - h0[0]) * 2048.f, (b - h0[1]) * 2048.f), pk_f16((c - h1[0]) * 2048.f, (d - h1[1]) * 2048.f)};
+        split_scaled4(a, b, c, d, out[0], out[1]);
         return;
     }
     constexpr int NS = ModeTraits<MODE>::NA;
 #pragma unroll
-    for (int s = 0; s < NS; ++s) {
+    for (int s = 0; s < NS; ++s) {   // (split16.h's peel_bf16, four wide: through the helper the chunk loops are scheduled differently)
         const unsigned int p0 = pk_bf16(a, b), p1 = pk_bf16(c, d);
         out[s] = u32x2{p0, p1};
         if (s + 1 < NS) {
@@ -102,8 +94,8 @@ __device__ __forceinline__ void round4_bf16(float4 &v)
 template <int MODE>
 __device__ __forceinline__ f32x16 mma(u32x4 a, u32x4 b, f32x16 c)
 {
-    if (MODE == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    if (MODE == 2) return mma16(a, b, c);
+    return mma16_bf(a, b, c);
 }
 
 // OIHW fp32 -> [cout block][cin chunk][tap][split][64 cout][16 cin] bf16 (zero padded)
@@ -127,19 +119,11 @@ __device__ __forceinline__ void conv_pack_elements(const float *__restrict__ w, 
         if (MODE == 2) {
             v *= wscale;
             if (range_flag && !(fabsf(v) <= 65000.f)) atomicOr(range_flag, 1);   // a weight that has outgrown its cached power-of-two scale (or is not finite)
-            const unsigned int ph = pk_f16(v, 0.f);
-            const float h = un_f16(ph)[0];
-            wp[base] = (unsigned short)(ph & 0xffffu);
-            wp[base + (size_t)NB * KC] = (unsigned short)(pk_f16(v - h, 0.f) & 0xffffu);
-            wp[base + (size_t)2 * NB * KC] = (unsigned short)(pk_f16(h * (1.0f / 2048.f), 0.f) & 0xffffu);
+            split_weight(v, wp[base], wp[base + (size_t)NB * KC], wp[base + (size_t)2 * NB * KC]);
             continue;
         }
 #pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const unsigned int p = pk_bf16(v, 0.f);
-            wp[base + (size_t)s * NB * KC] = (unsigned short)(p & 0xffffu);
-            v -= bf_lo(p);
-        }
+        for (int s = 0; s < NS; ++s) peel_bf16(v, wp[base + (size_t)s * NB * KC]);
     }
 }
 
@@ -617,15 +601,7 @@ __global__ __launch_bounds__(256, RPW == 4 ? 2 : (RPW == 2 ? 3 : 4)) void conv_n
     const int y0 = by * THB, x0 = (bx / A.n_cb) * TW;
     const int H = A.H, W = A.W;
     float in_s = 1.f, oscale = A.out_scale;
-    if (MODE == 2 && A.in_amax) {
-        const float am = *A.in_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);                      // am = m 2^e, m in [0.5, 1): floor(log2 am) = e - 1
-            in_s = ldexpf(1.f, 14 - e);                // exact powers of two either way
-            oscale = A.out_scale * ldexpf(1.f, e - 14);
-        }
-    }
+    if (MODE == 2) amax_scale<14>(A.in_amax, in_s, oscale);
 
     f32x16 acc[RPW][2];
 #pragma unroll
@@ -975,15 +951,7 @@ __global__ __launch_bounds__(512, 2) void conv_nhwc8_kernel(const ConvArgs A)
     const int y0 = by * TH, x0 = (bx / n_cg) * TW;
     const int H = A.H, W = A.W;
     float in_s = 1.f, oscale = A.out_scale;
-    if (A.in_amax) {
-        const float am = *A.in_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            in_s = ldexpf(1.f, 14 - e);
-            oscale = A.out_scale * ldexpf(1.f, e - 14);
-        }
-    }
+    amax_scale<14>(A.in_amax, in_s, oscale);
     f32x16 acc[RPW][2];
 #pragma unroll
     for (int m = 0; m < RPW; ++m)
@@ -1192,15 +1160,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(const ConvArgs A)
     const int y0 = by * THB, x0 = (bx / A.n_cb) * TW;
     const int H = A.H, W = A.W, n_ch = A.n_ch;
     float in_s = 1.f, oscale = A.out_scale;
-    if (A.in_amax) {
-        const float am = *A.in_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            in_s = ldexpf(1.f, 14 - e);
-            oscale = A.out_scale * ldexpf(1.f, e - 14);
-        }
-    }
+    amax_scale<14>(A.in_amax, in_s, oscale);
     f32x16 acc[RPW][2];
 #pragma unroll
     for (int m = 0; m < RPW; ++m)

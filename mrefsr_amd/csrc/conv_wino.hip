@@ -51,15 +51,6 @@ constexpr int LDS_BYTES = BIAS_OFF + BIAS_MAX * 4;
 static_assert(LDS_BYTES <= 160 * 1024, "conv_wino: LDS budget");
 constexpr int NPF = 3;   // 16-byte pieces of the patch per thread
 
-__device__ __forceinline__ f32x16 mma16(u32x4 a, u32x4 b, f32x16 c)
-{
-#if defined(WINO_ABL) && WINO_ABL == 2
-    c[0] += __uint_as_float(a[0] ^ b[0]);
-    return c;
-#endif
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 
 // OIHW fp32 (strided view, optionally point-mirrored: conv_nhwc.hip's pack) -> U = G g G^T, scaled and split:
 // [cout block][cin chunk][xi 16][plane uh | ul][cout 64][cin 16] fp16, zero padded
@@ -99,11 +90,9 @@ __global__ void wino_pack_kernel(const float *__restrict__ w, unsigned short *__
             for (int b = 0; b < 4; ++b) {
                 const float v = (float)(u4[b] * (double)wscale);
                 if (range_flag && !(fabsf(v) <= 65000.f)) atomicOr(range_flag, 1);
-                const unsigned int ph = pk_f16(v, 0.f);
-                const float h = un_f16(ph)[0];
                 const size_t at = base + (size_t)((a * 4 + b) * 2) * NB * KC;
-                wp[at] = (unsigned short)(ph & 0xffffu);
-                wp[at + (size_t)NB * KC] = (unsigned short)(pk_f16(v - h, 0.f) & 0xffffu);
+                unsigned short uh2;   // (no third plane: the activations' low term is not scaled, conv_wino_common.h)
+                split_weight(v, wp[at], wp[at + (size_t)NB * KC], uh2);
             }
         }
     }
@@ -268,15 +257,7 @@ __global__ __launch_bounds__(512, 2) void conv_wino_kernel(const ConvArgs A)
     // activation, fp16(v - fp16(v)), is a normal number down to |v| = 2^-14 of the maximum instead of a subnormal below |x| = 2^-3
     // (absolute error 2^-25: visible against activations of 1e-2 and less) -- and the result by its inverse.  Exact either way.
     float in_s = 1.f, oscale_in = A.out_scale;
-    if (A.in_amax) {
-        const float am = *A.in_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);                      // am = m 2^e, m in [0.5, 1)
-            in_s = ldexpf(1.f, 12 - e);
-            oscale_in = A.out_scale * ldexpf(1.f, e - 12);
-        }
-    }
+    amax_scale<12>(A.in_amax, in_s, oscale_in);
     in_s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(in_s)));
     auto raw_store = [&](const int slot, const int on) {   // slot = 2 buffer + sub-chunk
         vm_wait3_if(on, pf[0], pf[1], pf[2]);   // younger: the 8 weight fragments requested after this patch

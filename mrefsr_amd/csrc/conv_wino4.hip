@@ -72,11 +72,6 @@ constexpr int NPD = 6, PROWS = 3;                         // thread tid < 216 st
 static_assert(NPD * PROWS == PP && PROWS * PP * 4 <= 256, "conv_wino4: patch piece assignment");
 constexpr unsigned int OOB = 0xffff0000u;                 // (wino_launch: an image of the input is smaller than this)
 
-__device__ __forceinline__ f32x16 mma16(const u32x4 a, const u32x4 b, const f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
 template <int I, int N, class F> __device__ __forceinline__ void sfor(F &&f)
 {
     if constexpr (I < N) {
@@ -303,13 +298,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino4_kernel(const ConvArgs A)
     auto request_piece = [&](const int k) { bload16(pf[k], rq_vo[k], rq_srd, __builtin_amdgcn_readfirstlane(rq_soff)); };
     float in_s = 1.f, oscale_in = A.out_scale;
     if constexpr (SCALED) {   // (conv_wino.hip: max |x| into [2^11, 2^12))
-        const float am = *A.in_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            in_s = ldexpf(1.f, 12 - e);
-            oscale_in = A.out_scale * ldexpf(1.f, e - 12);
-        }
+        amax_scale<12>(*A.in_amax, in_s, oscale_in);
         in_s = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(in_s)));
     }
     auto store_piece = [&](const int slot, const int k) {   // (the caller's counted wait has passed pf through)

@@ -19,7 +19,7 @@ constexpr int RAW_CP = 10, RAW_RS = 20, RAW_Q = PP * RAW_RS + 1, RAW_BYTES = 4 *
 constexpr int BIAS_MAX = 1024;   // bias vector of a launch staged in LDS, zero-padded to whole cout blocks
 constexpr size_t WCH_HALVES = (size_t)16 * 2 * NB * KC;   // packed 16-bit values per (cout block, chunk): [xi][plane][cout 64][cin 16]
 
-// 2 floats -> packed (vh, vl = fp16(v - vh)): one packed conversion, then the exact remainder v - vh formed and rounded by
+// 2 floats -> packed (vh, vl = fp16(v - vh)), the values of split16.h's split_plain by another sequence: one packed conversion, then the exact remainder v - vh formed and rounded by
 // v_fma_mixlo / mixhi_f16 (fp16 source read in place, fp32 accumulate, result rounded to nearest even into one half of the
 // destination): 3 instructions per pair.  vl is NOT scaled into v's binade here (conv_nhwc.hip stores fp16(vl 2^11) and pairs it
 // with a weight plane uh 2^-11): below |v| = 2^-3 it is an fp16 subnormal (the MFMA honours them: tools/hazard/mfma_f16_denorm.hip)

@@ -11,17 +11,12 @@
 //                              on the channels of a pixel they ran 2.4-3x slower).
 //   mrefsr_dcn_bwd_weight_f32  d W = g_out . columns^T with the columns re-gathered tile by tile (as the forward does) instead of
 //                              read back from memory: pixel-K GEMM, both operands transposed through LDS.
-// Arithmetic: the fp16 two-term split of conv_nhwc.hip (three MFMAs per product, fp32-equivalent); the output gradient is scaled
+// Arithmetic: the fp16 two-term split of split16.h (three MFMAs per product, fp32-equivalent); the output gradient is scaled
 // into the fp16 range by the power of two that brings max |g| (device memory, from the activation backward) to [2^13, 2^14).
 #include "conv_common.h"
 
 namespace {
 using namespace mrefsr_conv;
-
-__device__ __forceinline__ f32x16 mma16(u32x4 a, u32x4 b, f32x16 c)
-{
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
 
 struct BwdArgs {
     const float *gy, *x, *offset, *mask;   // g_out [B][H][W][Co], x [B][H][W][C] channels-last; offset [B][18 dg][H][W], mask [B][9 dg][H][W] planar
@@ -72,15 +67,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const BwdArgs A)
     const int b = blockIdx.x / tiles, p0 = (blockIdx.x - b * tiles) * 32;
     const int Co = A.Co, C = A.C, n_ch = A.n_ch;
     float in_s = 1.f, oscale = A.inv_wscale;
-    if (A.g_amax) {
-        const float am = *A.g_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            in_s = ldexpf(1.f, 14 - e);
-            oscale = A.inv_wscale * ldexpf(1.f, e - 14);
-        }
-    }
+    amax_scale<14>(A.g_amax, in_s, oscale);
     // ---- the tile's output gradient -> two fp16 planes in LDS (rows of g_out are contiguous: coalesced 16-byte loads)
     const int q_per_px = Co >> 2;
     for (int i = tid; i < 32 * q_per_px; i += 256) {
@@ -88,9 +75,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const BwdArgs A)
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
         if (p0 + px < HW) v = *reinterpret_cast<const float4 *>(A.gy + ((size_t)b * HW + p0 + px) * Co + co);
         v.x *= in_s, v.y *= in_s, v.z *= in_s, v.w *= in_s;
-        const unsigned int h0 = pk_f16(v.x, v.y), h1 = pk_f16(v.z, v.w);
-        const f32x2 f0 = un_f16(h0), f1 = un_f16(h1);
-        const u32x2 hi = {h0, h1}, lo = {pk_f16((v.x - f0[0]) * 2048.f, (v.y - f0[1]) * 2048.f), pk_f16((v.z - f1[0]) * 2048.f, (v.w - f1[1]) * 2048.f)};
+        u32x2 hi, lo;
+        split_scaled4(v.x, v.y, v.z, v.w, hi, lo);
         unsigned char *d = smem + (co >> 4) * 1024 + ((co >> 3) & 1) * 512 + px * 16 + ((co >> 2) & 1) * 8;
         *reinterpret_cast<u32x2 *>(d) = hi;
         *reinterpret_cast<u32x2 *>(d + n_ch * 1024) = lo;
@@ -196,15 +182,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_kernel(const BwdWArgs A)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, kh = lane >> 5;
     const int HW = A.H * A.W, tiles_img = (HW + 31) / 32, tiles = A.B * tiles_img;
     const int c0 = blockIdx.y * 32, o0 = blockIdx.z * 64, C = A.C, Co = A.Co, cpg = C / A.dg;
-    float gs = 1.f;
-    if (A.g_amax) {
-        const float am = *A.g_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            gs = ldexpf(1.f, 14 - e);
-        }
-    }
+    float gs = 1.f, oscale = 1.f;   // (the inverse scale: dcn_bwd_weight_reduce_kernel's)
+    amax_scale<14>(A.g_amax, gs, oscale);
     const int ot = wv & 1, tg = wv >> 1, t_lo = tg ? 5 : 0, n_t = tg ? 4 : 5;   // wave: cout half, taps [t_lo, t_lo + n_t)
     f32x16 acc[5];
 #pragma unroll
@@ -230,10 +209,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_kernel(const BwdWArgs A)
             unsigned char *d = sg + (((px >> 4) * 2 + ((px >> 3) & 1)) * 1024) + (px & 7) * 2;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const unsigned int h = pk_f16(a0[i], a1[i]);
-                const f32x2 f = un_f16(h);
-                *reinterpret_cast<unsigned int *>(d + (4 * gq + i) * 16) = h;
-                *reinterpret_cast<unsigned int *>(d + 4096 + (4 * gq + i) * 16) = pk_f16(a0[i] - f[0], a1[i] - f[1]);
+                split_plain(a0[i], a1[i], *reinterpret_cast<unsigned int *>(d + (4 * gq + i) * 16), *reinterpret_cast<unsigned int *>(d + 4096 + (4 * gq + i) * 16));
             }
         }
         {   // ---- columns: pixels p0 + 2 cpj, + 1; channels c0 + 4 cq .. + 3; taps of this thread's half
@@ -265,10 +241,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_kernel(const BwdWArgs A)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     xmax = fmaxf(xmax, fmaxf(fabsf(val[0][i]), fabsf(val[1][i])));
-                    const unsigned int h = pk_f16(val[0][i], val[1][i]);
-                    const f32x2 f = un_f16(h);
-                    *reinterpret_cast<unsigned int *>(d + i * 16) = h;
-                    *reinterpret_cast<unsigned int *>(d + 9 * 2048 + i * 16) = pk_f16((val[0][i] - f[0]) * 2048.f, (val[1][i] - f[1]) * 2048.f);
+                    split_scaled(val[0][i], val[1][i], *reinterpret_cast<unsigned int *>(d + i * 16), *reinterpret_cast<unsigned int *>(d + 9 * 2048 + i * 16));
                 }
             }
         }
@@ -309,15 +282,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_kernel(const BwdWArgs A)
 __global__ void dcn_bwd_weight_reduce_kernel(const float *__restrict__ partial, const float *__restrict__ g_amax, float *__restrict__ dw, int splits,
                                              int Co, int C)
 {
-    float oscale = 1.f;
-    if (g_amax) {
-        const float am = *g_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            oscale = ldexpf(1.f, e - 14);
-        }
-    }
+    float gs = 1.f, oscale = 1.f;   // (the input scale: dcn_bwd_weight_kernel's)
+    amax_scale<14>(g_amax, gs, oscale);
     const long total = (long)Co * C * 9;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int tap = (int)(i % 9);
@@ -345,15 +311,8 @@ __global__ __launch_bounds__(256) void conv_wgrad1x1_kernel(const Wg1Args A)
     unsigned char *const sg = smem, *const sx = smem + WG_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, l31 = lane & 31, kh = lane >> 5;
     const int i0 = blockIdx.y * 64, o0 = blockIdx.z * 64;
-    float gs = 1.f;
-    if (A.g_amax) {
-        const float am = *A.g_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            gs = ldexpf(1.f, 14 - e);
-        }
-    }
+    float gs = 1.f, oscale = 1.f;   // (the inverse scale: conv_wgrad1x1_reduce_kernel's)
+    amax_scale<14>(A.g_amax, gs, oscale);
     const int ot = wv & 1, it = wv >> 1;
     f32x16 acc;
 #pragma unroll
@@ -391,15 +350,10 @@ __global__ __launch_bounds__(256) void conv_wgrad1x1_kernel(const Wg1Args A)
         const float x0[4] = {xv[0].x, xv[0].y, xv[0].z, xv[0].w}, x1[4] = {xv[1].x, xv[1].y, xv[1].z, xv[1].w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            unsigned int h = pk_f16(g0[i], g1[i]);
-            f32x2 f = un_f16(h);
-            *reinterpret_cast<unsigned int *>(sg + off + (4 * cq + i) * 16) = h;
-            *reinterpret_cast<unsigned int *>(sg + off + 4096 + (4 * cq + i) * 16) = pk_f16(g0[i] - f[0], g1[i] - f[1]);
+            unsigned char *const dg = sg + off + (4 * cq + i) * 16, *const dx = sx + off + (4 * cq + i) * 16;
+            split_plain(g0[i], g1[i], *reinterpret_cast<unsigned int *>(dg), *reinterpret_cast<unsigned int *>(dg + 4096));
             xmax = fmaxf(xmax, fmaxf(fabsf(x0[i]), fabsf(x1[i])));
-            h = pk_f16(x0[i], x1[i]);
-            f = un_f16(h);
-            *reinterpret_cast<unsigned int *>(sx + off + (4 * cq + i) * 16) = h;
-            *reinterpret_cast<unsigned int *>(sx + off + 4096 + (4 * cq + i) * 16) = pk_f16((x0[i] - f[0]) * 2048.f, (x1[i] - f[1]) * 2048.f);
+            split_scaled(x0[i], x1[i], *reinterpret_cast<unsigned int *>(dx), *reinterpret_cast<unsigned int *>(dx + 4096));
         }
         __syncthreads();
 #pragma unroll
@@ -424,15 +378,8 @@ __global__ __launch_bounds__(256) void conv_wgrad1x1_kernel(const Wg1Args A)
 
 __global__ void conv_wgrad1x1_reduce_kernel(const float *__restrict__ partial, const float *__restrict__ g_amax, float *__restrict__ dw, int splits, long n)
 {
-    float oscale = 1.f;
-    if (g_amax) {
-        const float am = *g_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            oscale = ldexpf(1.f, e - 14);
-        }
-    }
+    float gs = 1.f, oscale = 1.f;   // (the input scale: conv_wgrad1x1_kernel's)
+    amax_scale<14>(g_amax, gs, oscale);
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
         float s = 0.f;
         for (int k = 0; k < splits; ++k) s += partial[(size_t)k * n + i];

@@ -70,15 +70,7 @@ __global__ __launch_bounds__(256) void mrattn_blend_conv_kernel(const BlendArgs 
         tlist[16] = c;
     }
     float in_s = 1.f, oscale = A.out_scale;
-    if (A.in_amax) {   // the input tensor's maximum brought into [2^13, 2^14) by an exact power of two (conv_nhwc.hip)
-        const float am = *A.in_amax;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            in_s = ldexpf(1.f, 14 - e);
-            oscale = A.out_scale * ldexpf(1.f, e - 14);
-        }
-    }
+    amax_scale<14>(A.in_amax, in_s, oscale);   // the input tensor's maximum brought into [2^13, 2^14) by an exact power of two
     __syncthreads();
     const int total = __builtin_amdgcn_readfirstlane(tlist[16]);
     const int n_grp = (total + TG - 1) / TG, n_it = NCH * n_grp;
@@ -194,24 +186,21 @@ __global__ __launch_bounds__(256) void mrattn_blend_conv_kernel(const BlendArgs 
                         u[0] = fmaf(w, s0.x, u[0]), u[1] = fmaf(w, s0.y, u[1]), u[2] = fmaf(w, s0.z, u[2]), u[3] = fmaf(w, s0.w, u[3]);
                         u[4] = fmaf(w, s1.x, u[4]), u[5] = fmaf(w, s1.y, u[5]), u[6] = fmaf(w, s1.z, u[6]), u[7] = fmaf(w, s1.w, u[7]);
                     }
-                // a = ah + al, al kept as fp16(al * 2^11): the split of conv_nhwc.hip
+                // a = ah + al, al kept as fp16(al * 2^11): split16.h
                 u32x4 ah, al;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    ah[c] = pk_f16(u[2 * c], u[2 * c + 1]);
-                    const f32x2 h = un_f16(ah[c]);
-                    al[c] = pk_f16((u[2 * c] - h[0]) * 2048.f, (u[2 * c + 1] - h[1]) * 2048.f);
+                    unsigned int h, l;
+                    split_scaled(u[2 * c], u[2 * c + 1], h, l);
+                    ah[c] = h, al[c] = l;
                 }
                 // partial products smallest first: ah wl, AL WH2 (the third weight plane wh 2^-11 is derived, not loaded), ah wh
 #pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, b[j][1]), acc[m][j], 0, 0, 0);
+                for (int j = 0; j < NJ; ++j) acc[m][j] = mma16(ah, b[j][1], acc[m][j]);
 #pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, al), __builtin_bit_cast(f16x8, scale_wh(b[j][0])), acc[m][j], 0, 0, 0);
+                for (int j = 0; j < NJ; ++j) acc[m][j] = mma16(al, scale_wh(b[j][0]), acc[m][j]);
 #pragma unroll
-                for (int j = 0; j < NJ; ++j)
-                    acc[m][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ah), __builtin_bit_cast(f16x8, b[j][0]), acc[m][j], 0, 0, 0);
+                for (int j = 0; j < NJ; ++j) acc[m][j] = mma16(ah, b[j][0], acc[m][j]);
             }
             if (tap + 1 < TAPS) {
 #pragma unroll

@@ -18,13 +18,10 @@
 //     atomics straight into dW serialise per cache line: 30 M of them per trunk convolution made the first version 6x slower
 //     than MIOpen).
 #include "common.h"
+#include "split16.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace mrefsr_split16;
 
 constexpr int WQ = 32;              // LDS columns per block (two 16-pixel k-steps)
 constexpr int WQV = 30;             // of which input columns: with one halo column either side the gradient row is 32 wide -- 16 pairs
@@ -69,15 +66,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad3x3_kernel(const WgradJobs J
     const int y1 = (y0 + RG < H) ? y0 + RG : H;
 
     float gs = 1.f, oscale = 1.f;
-    {
-        const float am = g_amax ? *g_amax : 0.f;
-        if (am > 1.0e-30f && am < 3.0e38f) {
-            int e;
-            (void)frexpf(am, &e);
-            gs = ldexpf(1.f, 14 - e);
-            oscale = ldexpf(1.f, e - 14);
-        }
-    }
+    amax_scale<14>(g_amax ? *g_amax : 0.f, gs, oscale);
 
     f32x16 acc[9];
 #pragma unroll
@@ -222,12 +211,7 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad3x3_kernel(const WgradJobs J
                 const unsigned char *s = gbuf + tx * G_COPY + (cs * 32 + l31) * ROW_LD + koff;
                 ga[tx][0] = *reinterpret_cast<const u32x4 *>(s);
                 ga[tx][1] = *reinterpret_cast<const u32x4 *>(s + PLANE);
-                const f16x2 k11 = {(_Float16)0.00048828125f, (_Float16)0.00048828125f};
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned int d = ga[tx][0][w];
-                    ga[tx][2][w] = __builtin_bit_cast(unsigned int, __builtin_bit_cast(f16x2, d) * k11);
-                }
+                ga[tx][2] = scale_wh(ga[tx][0]);
             }
 #pragma unroll
             for (int ty = 0; ty < 3; ++ty) {
@@ -240,9 +224,9 @@ __global__ __launch_bounds__(512, 1) void conv_wgrad3x3_kernel(const WgradJobs J
 #pragma unroll
                 for (int tx = 0; tx < 3; ++tx) {
                     f32x16 c = acc[ty * 3 + tx];
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ga[tx][1]), __builtin_bit_cast(f16x8, xb[ty][0]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ga[tx][2]), __builtin_bit_cast(f16x8, xb[ty][1]), c, 0, 0, 0);
-                    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, ga[tx][0]), __builtin_bit_cast(f16x8, xb[ty][0]), c, 0, 0, 0);
+                    c = mma16(ga[tx][1], xb[ty][0], c);
+                    c = mma16(ga[tx][2], xb[ty][1], c);
+                    c = mma16(ga[tx][0], xb[ty][0], c);
                     acc[ty * 3 + tx] = c;
                 }
         }
