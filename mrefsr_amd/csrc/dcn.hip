@@ -15,78 +15,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "dcn_sample.h"
 #include "split16.h"
 
 namespace {
 using namespace mrefsr_split16;
-
-struct Geo {
-    int B, C, H, W, Co, kh, kw, sh, sw, ph, pw, dh, dw, groups, dg, Ho, Wo;
-};
-
-__host__ int make_geo(const mrefsr_dcn_shape *s, Geo &g, const char *who)
-{
-    if (!s) return mrefsr::fail(MREFSR_E_INVALID, "%s: null shape", who);
-    g = Geo{s->B, s->C, s->H, s->W, s->Co, s->kh, s->kw, s->stride_h, s->stride_w, s->pad_h, s->pad_w,
-            s->dil_h, s->dil_w, s->groups, s->dg, 0, 0};
-    if (g.B <= 0 || g.C <= 0 || g.H <= 0 || g.W <= 0 || g.Co <= 0 || g.kh <= 0 || g.kw <= 0 || g.sh <= 0 || g.sw <= 0 ||
-        g.dh <= 0 || g.dw <= 0 || g.groups <= 0 || g.dg <= 0 || g.ph < 0 || g.pw < 0)
-        return mrefsr::fail(MREFSR_E_INVALID, "%s: non-positive dimension in shape", who);
-    if (g.C % g.groups || g.Co % g.groups || g.C % g.dg)
-        return mrefsr::fail(MREFSR_E_INVALID, "%s: C=%d / Co=%d not divisible by groups=%d / dg=%d", who, g.C, g.Co,
-                            g.groups, g.dg);
-    g.Ho = (g.H + 2 * g.ph - (g.dh * (g.kh - 1) + 1)) / g.sh + 1;
-    g.Wo = (g.W + 2 * g.pw - (g.dw * (g.kw - 1) + 1)) / g.sw + 1;
-    if (g.Ho <= 0 || g.Wo <= 0) return mrefsr::fail(MREFSR_E_INVALID, "%s: empty output %dx%d", who, g.Ho, g.Wo);
-    return 0;
-}
-
-// bilinear setup shared by every kernel: 4 clamped corner offsets + 4 weights (0 where the
-// corner is out of range or the sample is outside the validity window)
-struct Tap {
-    int o1, o2, o3, o4;
-    float w1, w2, w3, w4;
-    float lh, lw;
-    bool inside;
-};
-
-// (one rule, three set-ups that move together: this, make_corner in dcn_bwd.hip, Bil in dcn_any.hip -- tests/test_dcn_edges_gpu.py)
-__device__ __forceinline__ Tap make_tap(float hi, float wi, int H, int W)
-{
-    Tap t;
-    t.inside = (hi > -1.f) && (wi > -1.f) && (hi < (float)H) && (wi < (float)W);
-    const float fh = floorf(hi), fw = floorf(wi);
-    const int hl = (int)fh, wl = (int)fw, hh = hl + 1, wh = wl + 1;
-    const float lh = hi - fh, lw = wi - fw, uh = 1.f - lh, uw = 1.f - lw;
-    t.lh = lh;
-    t.lw = lw;
-    const bool okhl = t.inside && hl >= 0, okhh = t.inside && hh <= H - 1;
-    const bool okwl = wl >= 0, okwh = wh <= W - 1;
-    const int chl = min(max(hl, 0), H - 1), chh = min(max(hh, 0), H - 1);
-    const int cwl = min(max(wl, 0), W - 1), cwh = min(max(wh, 0), W - 1);
-    t.o1 = chl * W + cwl;
-    t.o2 = chl * W + cwh;
-    t.o3 = chh * W + cwl;
-    t.o4 = chh * W + cwh;
-    // Four SCALAR products.  Left to itself the SLP vectoriser pairs (uh*lw, lh*uw) into
-    //     v_pk_mul_f32 vD, vA, vB op_sel:[0,1] op_sel_hi:[1,0]          (crossed halves)
-    // and on gfx950 that instruction returned wrong values in lanes 48..63 whenever waves of OTHER workgroups
-    // were issuing bf16 MFMAs on the same SIMD (run-to-run different DCN results at full size, 0.2-2 % of the
-    // pixels; DESIGN 3.2 has the bisection: one workgroup per CU, no MFMA, -fno-slp-vectorize and this form
-    // are clean, the hand-written instruction fails with or without wait states around it).  The empty asm
-    // statements make the products opaque to the vectoriser; tests/test_boundary.py checks the built library
-    // for the instruction form.
-    float p1 = uh * uw, p2 = uh * lw, p3 = lh * uw, p4 = lh * lw;
-    asm volatile("" : "+v"(p1));
-    asm volatile("" : "+v"(p2));
-    asm volatile("" : "+v"(p3));
-    asm volatile("" : "+v"(p4));
-    t.w1 = (okhl && okwl) ? p1 : 0.f;
-    t.w2 = (okhl && okwh) ? p2 : 0.f;
-    t.w3 = (okhh && okwl) ? p3 : 0.f;
-    t.w4 = (okhh && okwh) ? p4 : 0.f;
-    return t;
-}
+using namespace mrefsr_dcn;
 
 // ---------------------------------------------------------------------------------------------
 // weight packing for the MFMA forward:  Wp[chunk = tap*(C/32) + cb][o][kh2][16]
@@ -175,7 +109,7 @@ __global__ __launch_bounds__(256) void dcn_fwd_mfma_kernel(const float *__restri
             for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
 
     float cv[NPT][NCT][4];  // raw corner values of the chunk in flight
-    Tap tp[NPT];
+    Bilinear<float> tp[NPT];
     float mval[NPT];
 
     // three-stage software pipeline: offsets / mask of chunk+2 (tiny loads, one memory latency), bilinear
@@ -198,22 +132,22 @@ __global__ __launch_bounds__(256) void dcn_fwd_mfma_kernel(const float *__restri
 #pragma unroll
         for (int j = 0; j < NPT; ++j) {
             mval[j] = mv_n[j];
-            const float hi = (float)(ho[j] * g.sh - g.ph + ti * g.dh) + oh_n[j];
-            const float wi = (float)(wo[j] * g.sw - g.pw + tj * g.dw) + ow_n[j];
-            tp[j] = make_tap(hi, wi, g.H, g.W);
+            float hi, wi;
+            sample_pos(g, ho[j], wo[j], ti, tj, oh_n[j], ow_n[j], hi, wi);
+            tp[j] = Bilinear<float>(hi, wi, g.H, g.W);
             if (XL == 0) {
                 const float *xc = xb + (size_t)c0 * HWi;
 #pragma unroll
                 for (int i = 0; i < NCT; ++i) {
                     const float *im = xc + (size_t)i * HWi;
-                    cv[j][i][0] = im[tp[j].o1];
-                    cv[j][i][1] = im[tp[j].o2];
-                    cv[j][i][2] = im[tp[j].o3];
-                    cv[j][i][3] = im[tp[j].o4];
+                    cv[j][i][0] = im[tp[j].o[0]];
+                    cv[j][i][1] = im[tp[j].o[1]];
+                    cv[j][i][2] = im[tp[j].o[2]];
+                    cv[j][i][3] = im[tp[j].o[3]];
                 }
             } else {
                 const float *xc = xb + c0;
-                const int offs[4] = {tp[j].o1, tp[j].o2, tp[j].o3, tp[j].o4};
+                const int offs[4] = {tp[j].o[0], tp[j].o[1], tp[j].o[2], tp[j].o[3]};
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
                     const f32x4 v4 = *reinterpret_cast<const f32x4 *>(xc + (size_t)offs[k] * g.C);
@@ -229,7 +163,7 @@ __global__ __launch_bounds__(256) void dcn_fwd_mfma_kernel(const float *__restri
             float v[NCT];
 #pragma unroll
             for (int i = 0; i < NCT; ++i)
-                v[i] = (tp[j].w1 * cv[j][i][0] + tp[j].w2 * cv[j][i][1] + tp[j].w3 * cv[j][i][2] + tp[j].w4 * cv[j][i][3]) * mval[j];
+                v[i] = (tp[j].w[0] * cv[j][i][0] + tp[j].w[1] * cv[j][i][1] + tp[j].w[2] * cv[j][i][2] + tp[j].w[3] * cv[j][i][3]) * mval[j];
             // K row r of the chunk lives at [r & 1][r >> 1] of the pixel's 36-float record
             float *dst = buf + gpx[j] * CL_LD + (gch >> 1);
             if (XL == 0) {
@@ -381,9 +315,9 @@ __global__ void dcn_pack_weight_f16_kernel(const float *__restrict__ w, unsigned
 }
 
 // the bilinear blend as ONE defined operation order (both 16-bit kernels: the same bits whatever the compiler would contract)
-__device__ __forceinline__ float blend4(const Tap &t, const float (&c)[4])
+__device__ __forceinline__ float blend4(const Bilinear<float> &t, const float (&c)[4])
 {
-    return __builtin_fmaf(t.w4, c[3], __builtin_fmaf(t.w3, c[2], __builtin_fmaf(t.w2, c[1], t.w1 * c[0])));
+    return __builtin_fmaf(t.w[3], c[3], __builtin_fmaf(t.w[2], c[2], __builtin_fmaf(t.w[1], c[1], t.w[0] * c[0])));
 }
 // epilogue arithmetic: acc * (1 / S) + bias as one fma (bias 0 when absent), then LeakyReLU
 __device__ __forceinline__ float4 epi4(float4 v, float oscale, const float *bias, int o, float slope)
@@ -464,7 +398,7 @@ __global__ __launch_bounds__(256) void dcn_fwd_bf16_kernel(const float *__restri
             for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
 
     float cv[NJ][NCH][4];
-    Tap tp[NJ];
+    Bilinear<float> tp[NJ];
     float mval[NJ], oh_n[NJ], ow_n[NJ], mv_n[NJ];
     auto offs_issue = [&](int chunk) {
         const int tap = chunk / ncb, cb = chunk - tap * ncb;
@@ -484,9 +418,10 @@ __global__ __launch_bounds__(256) void dcn_fwd_bf16_kernel(const float *__restri
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             mval[j] = mv_n[j];
-            tp[j] = make_tap((float)(ho[j] * g.sh - g.ph + ti * g.dh) + oh_n[j], (float)(wo[j] * g.sw - g.pw + tj * g.dw) + ow_n[j],
-                             g.H, g.W);
-            const int offs[4] = {tp[j].o1, tp[j].o2, tp[j].o3, tp[j].o4};
+            float hi, wi;
+            sample_pos(g, ho[j], wo[j], ti, tj, oh_n[j], ow_n[j], hi, wi);
+            tp[j] = Bilinear<float>(hi, wi, g.H, g.W);
+            const int offs[4] = {tp[j].o[0], tp[j].o[1], tp[j].o[2], tp[j].o[3]};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (IO16) {   // NCH bf16 channels: one 16-byte (NCH = 8) or 8-byte (NCH = 4) load
@@ -810,7 +745,7 @@ __global__ __launch_bounds__(256, T == 2 && MB * NB == 1 ? 3 : 2) void dcn_fwd_p
                 for (int e = 0; e < 16; ++e) acc[t][mi][ni][e] = 0.f;
 
     float cv[NJ][NCH][4];
-    Tap tp[NS];
+    Bilinear<float> tp[NS];
     float mval[NS], oh_n[NS], ow_n[NS], mv_n[NS], amx_run = 0.f;
     const __amdgpu_buffer_rsrc_t x_srd = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<void *>(mrefsr_dcn_scalar_ptr(xb)), 0, PAIR ? (unsigned int)((size_t)g.H * g.W * g.C * 4) : 0u, 0x00020000);
@@ -831,9 +766,9 @@ __global__ __launch_bounds__(256, T == 2 && MB * NB == 1 ? 3 : 2) void dcn_fwd_p
         const int ti = tap / 3, tj = tap - ti * 3;
         if constexpr (PAIR) {
             mval[0] = mv_n[0];
-            tp[0] = make_tap(hbt[0] + (float)(ti * g.dh) + oh_n[0], wbt[0] + (float)(tj * g.dw) + ow_n[0], g.H, g.W);
+            tp[0] = Bilinear<float>(hbt[0] + (float)(ti * g.dh) + oh_n[0], wbt[0] + (float)(tj * g.dw) + ow_n[0], g.H, g.W);
             const unsigned int choff = (unsigned int)(32 * cb + gch) * 4u;
-            const int offs[4] = {tp[0].o1, tp[0].o2, tp[0].o3, tp[0].o4};
+            const int offs[4] = {tp[0].o[0], tp[0].o[1], tp[0].o[2], tp[0].o[3]};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int ob = offs[k] << cshift;   // byte offset of the corner pixel inside the image (< 2^32: checked by the launcher)
@@ -850,8 +785,8 @@ __global__ __launch_bounds__(256, T == 2 && MB * NB == 1 ? 3 : 2) void dcn_fwd_p
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             mval[j] = mv_n[j];
-            tp[j] = make_tap(hbt[j] + (float)(ti * g.dh) + oh_n[j], wbt[j] + (float)(tj * g.dw) + ow_n[j], g.H, g.W);
-            const int offs[4] = {tp[j].o1, tp[j].o2, tp[j].o3, tp[j].o4};
+            tp[j] = Bilinear<float>(hbt[j] + (float)(ti * g.dh) + oh_n[j], wbt[j] + (float)(tj * g.dw) + ow_n[j], g.H, g.W);
+            const int offs[4] = {tp[j].o[0], tp[j].o[1], tp[j].o[2], tp[j].o[3]};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (IO16) {
@@ -888,11 +823,11 @@ __global__ __launch_bounds__(256, T == 2 && MB * NB == 1 ? 3 : 2) void dcn_fwd_p
                 for (int i = 0; i < NCH; ++i) {
                     float a;
                     if (j == 0)
-                        a = __builtin_fmaf(pair_lo(tp[0].w4), cv[j][i][3], __builtin_fmaf(pair_lo(tp[0].w3), cv[j][i][2],
-                            __builtin_fmaf(pair_lo(tp[0].w2), cv[j][i][1], pair_lo(tp[0].w1) * cv[j][i][0]))) * pair_lo(mval[0]);
+                        a = __builtin_fmaf(pair_lo(tp[0].w[3]), cv[j][i][3], __builtin_fmaf(pair_lo(tp[0].w[2]), cv[j][i][2],
+                            __builtin_fmaf(pair_lo(tp[0].w[1]), cv[j][i][1], pair_lo(tp[0].w[0]) * cv[j][i][0]))) * pair_lo(mval[0]);
                     else
-                        a = __builtin_fmaf(pair_hi(tp[0].w4), cv[j][i][3], __builtin_fmaf(pair_hi(tp[0].w3), cv[j][i][2],
-                            __builtin_fmaf(pair_hi(tp[0].w2), cv[j][i][1], pair_hi(tp[0].w1) * cv[j][i][0]))) * pair_hi(mval[0]);
+                        a = __builtin_fmaf(pair_hi(tp[0].w[3]), cv[j][i][3], __builtin_fmaf(pair_hi(tp[0].w[2]), cv[j][i][2],
+                            __builtin_fmaf(pair_hi(tp[0].w[1]), cv[j][i][1], pair_hi(tp[0].w[0]) * cv[j][i][0]))) * pair_hi(mval[0]);
                     v[i] = a;
                 }
             } else {
@@ -1082,140 +1017,6 @@ __global__ __launch_bounds__(256, T == 2 && MB * NB == 1 ? 3 : 2) void dcn_fwd_p
     if (out_amax) mrefsr::publish_amax<true>(out_amax, oamx);
 }
 
-// ---------------------------------------------------------------------------------------------
-// generic forward (any stride / dilation / groups / kernel size / channel count): one thread =
-// one pixel x 16 output channels, sampling on the fly.  Correct everywhere, fast nowhere.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dcn_fwd_generic_kernel(const float *__restrict__ x, const float *__restrict__ offset,
-                                                              const float *__restrict__ mask, const float *__restrict__ w,
-                                                              const float *__restrict__ bias, float *__restrict__ out, Geo g,
-                                                              float slope)
-{
-    const int HWo = g.Ho * g.Wo, HWi = g.H * g.W, KK = g.kh * g.kw;
-    const int cig = g.C / g.groups, cog = g.Co / g.groups, cpg = g.C / g.dg;
-    const int otiles = (cog + 15) / 16;  // 16-wide output tiles never straddle a conv group
-    const long total = (long)g.B * g.groups * otiles * HWo;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int pix = (int)(e % HWo);
-        long t = e / HWo;
-        const int ot = (int)(t % otiles);
-        t /= otiles;
-        const int gr = (int)(t % g.groups), b = (int)(t / g.groups);
-        const int ho = pix / g.Wo, wo = pix - ho * g.Wo;
-        const int o0 = gr * cog + ot * 16;
-        const int no = min(16, gr * cog + cog - o0);
-        float acc[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) acc[k] = 0.f;
-        for (int cc = 0; cc < cig; ++cc) {
-            const int c = gr * cig + cc, dgi = c / cpg;
-            const float *im = x + ((size_t)b * g.C + c) * HWi;
-            for (int tap = 0; tap < KK; ++tap) {
-                const int ti = tap / g.kw, tj = tap - ti * g.kw;
-                const float oh = offset[(((size_t)b * g.dg + dgi) * 2 * KK + 2 * tap) * HWo + pix];
-                const float ow = offset[(((size_t)b * g.dg + dgi) * 2 * KK + 2 * tap + 1) * HWo + pix];
-                const float m = mask ? mask[(((size_t)b * g.dg + dgi) * KK + tap) * HWo + pix] : 1.f;
-                const Tap tp = make_tap((float)(ho * g.sh - g.ph + ti * g.dh) + oh, (float)(wo * g.sw - g.pw + tj * g.dw) + ow,
-                                        g.H, g.W);
-                const float v = (tp.w1 * im[tp.o1] + tp.w2 * im[tp.o2] + tp.w3 * im[tp.o3] + tp.w4 * im[tp.o4]) * m;
-#pragma unroll
-                for (int k = 0; k < 16; ++k)
-                    if (k < no) acc[k] = fmaf(w[((size_t)(o0 + k) * cig + cc) * KK + tap], v, acc[k]);
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k)
-            if (k < no) {
-                float v = acc[k] + (bias ? bias[o0 + k] : 0.f);
-                v = v > 0.f ? v : v * slope;
-                out[((size_t)b * g.Co + o0 + k) * HWo + pix] = v;
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// im2col (for the weight gradient GEMM) and the column -> (offset, mask, input) gradients
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void dcn_im2col_kernel(const float *__restrict__ x, const float *__restrict__ offset,
-                                                         const float *__restrict__ mask, float *__restrict__ col, Geo g)
-{
-    const int HWo = g.Ho * g.Wo, HWi = g.H * g.W, KK = g.kh * g.kw, cpg = g.C / g.dg;
-    const long total = (long)g.B * g.C * HWo;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int pix = (int)(e % HWo);
-        const long t = e / HWo;
-        const int c = (int)(t % g.C), b = (int)(t / g.C);
-        const int ho = pix / g.Wo, wo = pix - ho * g.Wo, dgi = c / cpg;
-        const float *im = x + ((size_t)b * g.C + c) * HWi;
-        for (int tap = 0; tap < KK; ++tap) {
-            const int ti = tap / g.kw, tj = tap - ti * g.kw;
-            const float oh = offset[(((size_t)b * g.dg + dgi) * 2 * KK + 2 * tap) * HWo + pix];
-            const float ow = offset[(((size_t)b * g.dg + dgi) * 2 * KK + 2 * tap + 1) * HWo + pix];
-            const float m = mask ? mask[(((size_t)b * g.dg + dgi) * KK + tap) * HWo + pix] : 1.f;
-            const Tap tp = make_tap((float)(ho * g.sh - g.ph + ti * g.dh) + oh, (float)(wo * g.sw - g.pw + tj * g.dw) + ow,
-                                    g.H, g.W);
-            const float v = (tp.w1 * im[tp.o1] + tp.w2 * im[tp.o2] + tp.w3 * im[tp.o3] + tp.w4 * im[tp.o4]) * m;
-            col[(((size_t)b * g.C + c) * KK + tap) * HWo + pix] = v;
-        }
-    }
-}
-
-// one thread = (b, deformable group, tap, pixel): loops the group's channels; assigns grad_offset
-// (y, x) and grad_mask, scatters grad_x with float atomics (deform_conv_cuda_kernel.cu:635-767)
-__global__ __launch_bounds__(256) void dcn_col2im_kernel(const float *__restrict__ gcol, const float *__restrict__ x,
-                                                         const float *__restrict__ offset, const float *__restrict__ mask,
-                                                         float *__restrict__ gx, float *__restrict__ goff,
-                                                         float *__restrict__ gmask, Geo g)
-{
-    const int HWo = g.Ho * g.Wo, HWi = g.H * g.W, KK = g.kh * g.kw, cpg = g.C / g.dg;
-    const long total = (long)g.B * g.dg * KK * HWo;
-    for (long e = blockIdx.x * (long)blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int pix = (int)(e % HWo);
-        long t = e / HWo;
-        const int tap = (int)(t % KK);
-        t /= KK;
-        const int dgi = (int)(t % g.dg), b = (int)(t / g.dg);
-        const int ho = pix / g.Wo, wo = pix - ho * g.Wo;
-        const int ti = tap / g.kw, tj = tap - ti * g.kw;
-        const size_t oi = (((size_t)b * g.dg + dgi) * 2 * KK + 2 * tap) * HWo + pix;
-        const size_t mi = (((size_t)b * g.dg + dgi) * KK + tap) * HWo + pix;
-        const float oh = offset[oi], ow = offset[oi + HWo];
-        const float m = mask ? mask[mi] : 1.f;
-        const Tap tp = make_tap((float)(ho * g.sh - g.ph + ti * g.dh) + oh, (float)(wo * g.sw - g.pw + tj * g.dw) + ow, g.H,
-                                g.W);
-        // d(sample)/dh, d(sample)/dw as corner coefficient sets (kernel.cu:526-568)
-        const float uh = 1.f - tp.lh, uw = 1.f - tp.lw;
-        float g_oh = 0.f, g_ow = 0.f, g_m = 0.f;
-        // validity of each corner = its position is in range (its weight may still be 0 by value)
-        const float fh = floorf((float)(ho * g.sh - g.ph + ti * g.dh) + oh);
-        const float fw = floorf((float)(wo * g.sw - g.pw + tj * g.dw) + ow);
-        const int hl = (int)fh, wl = (int)fw, hh = hl + 1, wh = wl + 1;
-        const bool v1 = tp.inside && hl >= 0 && wl >= 0, v2 = tp.inside && hl >= 0 && wh <= g.W - 1;
-        const bool v3 = tp.inside && hh <= g.H - 1 && wl >= 0, v4 = tp.inside && hh <= g.H - 1 && wh <= g.W - 1;
-        for (int cc = 0; cc < cpg; ++cc) {
-            const int c = dgi * cpg + cc;
-            const float gc = gcol[(((size_t)b * g.C + c) * KK + tap) * HWo + pix];
-            const float *im = x + ((size_t)b * g.C + c) * HWi;
-            const float x1 = v1 ? im[tp.o1] : 0.f, x2 = v2 ? im[tp.o2] : 0.f, x3 = v3 ? im[tp.o3] : 0.f,
-                        x4 = v4 ? im[tp.o4] : 0.f;
-            g_m = fmaf(gc, tp.w1 * x1 + tp.w2 * x2 + tp.w3 * x3 + tp.w4 * x4, g_m);
-            g_oh = fmaf(gc * m, -uw * x1 - tp.lw * x2 + uw * x3 + tp.lw * x4, g_oh);
-            g_ow = fmaf(gc * m, -uh * x1 + uh * x2 - tp.lh * x3 + tp.lh * x4, g_ow);
-            if (gx) {
-                float *gi = gx + ((size_t)b * g.C + c) * HWi;
-                const float gv = gc * m;
-                if (v1) atomicAdd(gi + tp.o1, gv * tp.w1);
-                if (v2) atomicAdd(gi + tp.o2, gv * tp.w2);
-                if (v3) atomicAdd(gi + tp.o3, gv * tp.w3);
-                if (v4) atomicAdd(gi + tp.o4, gv * tp.w4);
-            }
-        }
-        goff[oi] = g_oh;
-        goff[oi + HWo] = g_ow;
-        if (gmask && mask) gmask[mi] = g_m;
-    }
-}
-
 bool mfma_eligible(const Geo &g)
 {
     const int cpg = g.C / g.dg;
@@ -1382,36 +1183,20 @@ static int dcn_fwd_entry(const float *x, const float *offset, const float *mask,
 #undef MREFSR_DCN_LAUNCH
         return mrefsr::check_launch("dcn_fwd(mfma)");
     }
-    const long total = (long)g.B * g.groups * ((g.Co / g.groups + 15) / 16) * HWo;
-    const long blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(dcn_fwd_generic_kernel, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, x, offset, mask,
-                       weight, bias, out, g, act_slope);
-    return mrefsr::check_launch("dcn_fwd(generic)");
+    // any other stride / dilation / groups / kernel size / channel count: the portable kernel (dcn_any.hip), fp32
+    return mrefsr_dcn_fwd(x, offset, mask, weight, bias, out, s, act_slope, 0, stream);
 }
 
+// im2col (for the weight gradient GEMM) and the column -> (offset, mask, input) gradients: the portable kernels of dcn_any.hip, fp32
 MREFSR_EXPORT int mrefsr_dcn_im2col_f32(const float *x, const float *offset, const float *mask, float *columns,
                                         const mrefsr_dcn_shape *s, mrefsr_stream_t stream)
 {
-    MREFSR_REQUIRE(x && offset && columns, "dcn_im2col: null pointer");
-    Geo g;
-    if (int e = make_geo(s, g, "dcn_im2col")) return e;
-    const long total = (long)g.B * g.C * g.Ho * g.Wo;
-    const long blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(dcn_im2col_kernel, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream, x,
-                       offset, mask, columns, g);
-    return mrefsr::check_launch("dcn_im2col");
+    return mrefsr_dcn_im2col(x, offset, mask, columns, s, 0, stream);
 }
 
 MREFSR_EXPORT int mrefsr_dcn_col2im_f32(const float *grad_col, const float *x, const float *offset, const float *mask,
                                         float *grad_x, float *grad_offset, float *grad_mask, const mrefsr_dcn_shape *s,
                                         mrefsr_stream_t stream)
 {
-    MREFSR_REQUIRE(grad_col && x && offset && grad_offset, "dcn_col2im: null pointer");
-    Geo g;
-    if (int e = make_geo(s, g, "dcn_col2im")) return e;
-    const long total = (long)g.B * g.dg * g.kh * g.kw * g.Ho * g.Wo;
-    const long blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(dcn_col2im_kernel, dim3((int)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, (hipStream_t)stream,
-                       grad_col, x, offset, mask, grad_x, grad_offset, grad_mask, g);
-    return mrefsr::check_launch("dcn_col2im");
+    return mrefsr_dcn_col2im(grad_col, x, offset, mask, grad_x, grad_offset, grad_mask, s, 0, stream);
 }

@@ -14,9 +14,11 @@
 // Arithmetic: the fp16 two-term split of split16.h (three MFMAs per product, fp32-equivalent); the output gradient is scaled
 // into the fp16 range by the power of two that brings max |g| (device memory, from the activation backward) to [2^13, 2^14).
 #include "conv_common.h"
+#include "dcn_sample.h"
 
 namespace {
 using namespace mrefsr_conv;
+using mrefsr_dcn::Bilinear;
 
 struct BwdArgs {
     const float *gy, *x, *offset, *mask;   // g_out [B][H][W][Co], x [B][H][W][C] channels-last; offset [B][18 dg][H][W], mask [B][9 dg][H][W] planar
@@ -26,36 +28,6 @@ struct BwdArgs {
     int B, C, Co, H, W, dg, n_ch;
     float inv_wscale;
 };
-
-// the bilinear set-up of one (pixel, tap, deformable group): deform_conv_cuda_kernel.cu:467-497 (value) and :526-568 (derivatives)
-struct Corner {
-    int o[4];        // pixel index of the four corners, clamped into the image
-    float w[4];      // bilinear weights, 0 where the corner is out of range or the sample outside the validity window
-    float dh[4], dw[4];   // d(sample) / d(h), d(w) coefficients of the four corner values (0 for a corner out of range)
-};
-// (one rule, three set-ups that move together: this, make_tap in dcn.hip, Bil in dcn_any.hip -- tests/test_dcn_edges_gpu.py)
-__device__ __forceinline__ Corner make_corner(const float hi, const float wi, const int H, const int W)
-{
-    Corner c;
-    const bool inside = (hi > -1.f) && (wi > -1.f) && (hi < (float)H) && (wi < (float)W);
-    const float fh = floorf(hi), fw = floorf(wi);
-    const int hl = (int)fh, wl = (int)fw, hh = hl + 1, wh = wl + 1;
-    const float lh = hi - fh, lw = wi - fw, uh = 1.f - lh, uw = 1.f - lw;
-    const bool v1 = inside && hl >= 0 && wl >= 0, v2 = inside && hl >= 0 && wh <= W - 1;
-    const bool v3 = inside && hh <= H - 1 && wl >= 0, v4 = inside && hh <= H - 1 && wh <= W - 1;
-    const int chl = min(max(hl, 0), H - 1), chh = min(max(hh, 0), H - 1), cwl = min(max(wl, 0), W - 1), cwh = min(max(wh, 0), W - 1);
-    c.o[0] = chl * W + cwl, c.o[1] = chl * W + cwh, c.o[2] = chh * W + cwl, c.o[3] = chh * W + cwh;
-    // (four scalar products kept apart: the crossed packed form the vectoriser would build is unsafe beside 16-bit MFMAs, dcn.hip)
-    float p1 = uh * uw, p2 = uh * lw, p3 = lh * uw, p4 = lh * lw;
-    asm volatile("" : "+v"(p1));
-    asm volatile("" : "+v"(p2));
-    asm volatile("" : "+v"(p3));
-    asm volatile("" : "+v"(p4));
-    c.w[0] = v1 ? p1 : 0.f, c.w[1] = v2 ? p2 : 0.f, c.w[2] = v3 ? p3 : 0.f, c.w[3] = v4 ? p4 : 0.f;
-    c.dh[0] = v1 ? -uw : 0.f, c.dh[1] = v2 ? -lw : 0.f, c.dh[2] = v3 ? uw : 0.f, c.dh[3] = v4 ? lw : 0.f;
-    c.dw[0] = v1 ? -uh : 0.f, c.dw[1] = v2 ? uh : 0.f, c.dw[2] = v3 ? -lh : 0.f, c.dw[3] = v4 ? lh : 0.f;
-    return c;
-}
 
 // CPG = channels per deformable group (8, 16 or 32): a 32-channel row block of the GEMM holds 32 / CPG whole groups
 template <int CPG>
@@ -108,7 +80,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const BwdArgs A)
         // ---- epilogue: register e = channel 32 cblk + 8 (e >> 2) + 4 kh + (e & 3) of pixel l31
         const int ti = tap / 3, tj = tap - 3 * ti;
         float g_m = 0.f, g_oh = 0.f, g_ow = 0.f, mval = 1.f;
-        Corner cn;
+        Bilinear<float> cn;
+        float dh[4], dw[4];   // derivative coefficients of the set-up in use, formed with it
         int grp = -1;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -119,7 +92,9 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const BwdArgs A)
                 const size_t oi = (((size_t)b * A.dg + g) * 18 + 2 * tap) * HW + (pok ? p : 0);
                 const float oh = A.offset[oi], ow = A.offset[oi + HW];
                 mval = A.mask ? A.mask[(((size_t)b * A.dg + g) * 9 + tap) * HW + (pok ? p : 0)] : 1.f;
-                cn = make_corner((float)(ph - 1 + ti) + oh, (float)(pw - 1 + tj) + ow, A.H, A.W);
+                cn = Bilinear<float>((float)(ph - 1 + ti) + oh, (float)(pw - 1 + tj) + ow, A.H, A.W);   // (stride 1, pad 1, dilation 1)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) dh[k] = cn.dh(k), dw[k] = cn.dw(k);
                 g_m = g_oh = g_ow = 0.f;
             }
             float4 xc[4];
@@ -134,8 +109,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(const BwdArgs A)
                 const float x4 = j == 0 ? xc[3].x : (j == 1 ? xc[3].y : (j == 2 ? xc[3].z : xc[3].w));
                 g_m = fmaf(gc, cn.w[0] * x1 + cn.w[1] * x2 + cn.w[2] * x3 + cn.w[3] * x4, g_m);
                 const float gv = gc * mval;
-                g_oh = fmaf(gv, cn.dh[0] * x1 + cn.dh[1] * x2 + cn.dh[2] * x3 + cn.dh[3] * x4, g_oh);
-                g_ow = fmaf(gv, cn.dw[0] * x1 + cn.dw[1] * x2 + cn.dw[2] * x3 + cn.dw[3] * x4, g_ow);
+                g_oh = fmaf(gv, dh[0] * x1 + dh[1] * x2 + dh[2] * x3 + dh[3] * x4, g_oh);
+                g_ow = fmaf(gv, dw[0] * x1 + dw[1] * x2 + dw[2] * x3 + dw[3] * x4, g_ow);
                 if (A.gx && pok) {
                     float *gi = A.gx + ((size_t)b * C + c0 + j) * HW;
 #pragma unroll
@@ -228,7 +203,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_kernel(const BwdWArgs A)
                     const size_t oi = (((size_t)b * A.dg + g) * 18 + 2 * tap) * HW + pp;
                     const float oh = A.offset[oi], ow = A.offset[oi + HW];
                     const float m = pok ? (A.mask ? A.mask[(((size_t)b * A.dg + g) * 9 + tap) * HW + pp] : 1.f) : 0.f;
-                    const Corner cn = make_corner((float)(ph - 1 + ti) + oh, (float)(pw - 1 + tj) + ow, A.H, A.W);
+                    const Bilinear<float> cn((float)(ph - 1 + ti) + oh, (float)(pw - 1 + tj) + ow, A.H, A.W);
                     float4 s4 = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {

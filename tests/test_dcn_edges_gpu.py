@@ -1,7 +1,7 @@
 """Every DCN kernel path, forward and backward, on the hostile offset fields of tests/golden/dcn_edge_cases.py: samples exactly on
 the window boundary (-1 and L), on integers, in the two border bands, far outside, and the closed forms (zero offsets = the plain
-convolution, whole-pixel shifts = the convolution of the translated map, all outside / mask 0 = the bias).  The three bilinear
-set-ups -- make_tap (csrc/dcn.hip), make_corner (csrc/dcn_bwd.hip), Bil (csrc/dcn_any.hip) -- are held to one rule here:
+convolution, whole-pixel shifts = the convolution of the translated map, all outside / mask 0 = the bias).  The one bilinear
+set-up of csrc/dcn_sample.h, as the kernels of csrc/dcn.hip, csrc/dcn_bwd.hip and csrc/dcn_any.hip use it, is held to one rule here:
 deform_conv_cuda_kernel.cu:467-497, :526-568 as oracle/mrefsr_oracle.c and oracle/dcn_torch.py restate it
 (tests/test_dcn_edges_cpu.py checks those two against closed forms, each other and a hand evaluation).
 
@@ -265,7 +265,7 @@ ANY_CASES = [(m, dt) for m in E.GEOMETRY_MAPS['g8_dg4'] for dt in (torch.float64
 
 @pytest.mark.parametrize('bhw,dtype', ANY_CASES, ids=[f'{m[0]}x{m[1]}x{m[2]}-{str(d)[6:]}' for m, d in ANY_CASES])
 def test_other_dtypes_forward_im2col_and_col2im_on_every_field(hip, bhw, dtype):
-    """mrefsr_dcn_fwd / _im2col / _col2im (csrc/dcn_any.hip: Bil) in float64 and float16 against oracle/dcn_torch.py in fp64 on the
+    """mrefsr_dcn_fwd / _im2col / _col2im (csrc/dcn_any.hip) in float64 and float16 against oracle/dcn_torch.py in fp64 on the
     values the kernel sees: 1e-11 / 3e-2 of the largest value, gradients four times that; the bias bit for bit and zero columns where
     nothing is sampled; grad_offset / grad_mask exactly 0 on and outside the window boundary"""
     geometry = 'g8_dg4'
@@ -363,7 +363,7 @@ BWD_FIELDS = ('lattice', 'mostly_outside', 'heavy_tail', 'zero', 'shift0', 'shif
 
 @pytest.mark.parametrize('geometry,bhw', COL2IM_CASES, ids=_ids(COL2IM_CASES))
 def test_col2im_on_every_field(hip, geometry, bhw):
-    """hip.dcn_im2col / hip.dcn_col2im in fp32 (make_tap) around the two library GEMMs, against the oracle on every field; exactly 0
+    """hip.dcn_im2col / hip.dcn_col2im in fp32 (csrc/dcn_any.hip) around the two library GEMMs, against the oracle on every field; exactly 0
     on and outside the window boundary; everything exactly 0 when every sample is outside; grad_x / grad_weight of the closed-form
     convolution on zero / whole-pixel offsets"""
     c, co, dg, groups, stride, pad, dil, with_mask = E.GEOMETRIES[geometry]
@@ -407,7 +407,7 @@ GSCALE = 1e-6     # the magnitude of an L1 loss's gradients, as in test_dcn_fuse
 
 @pytest.mark.parametrize('geometry,bhw', FUSED_CASES, ids=_ids(FUSED_CASES))
 def test_fused_backward_on_every_field(hip, geometry, bhw):
-    """hip.dcn_bwd_data / hip.dcn_bwd_weight (make_corner) at 8, 16 and 32 channels per deformable group, with a mask and without one,
+    """hip.dcn_bwd_data / hip.dcn_bwd_weight (csrc/dcn_bwd.hip) at 8, 16 and 32 channels per deformable group, with a mask and without one,
     against the oracle on every field: 2e-4 relative + 2e-4 x max |g|; exactly 0 on and outside the window boundary; everything,
     grad_weight included, exactly 0 when every sample is outside; the closed-form convolution's grad_x / grad_weight"""
     c, co, dg, groups, stride, pad, dil, with_mask = E.GEOMETRIES[geometry]

@@ -1,14 +1,21 @@
 #!/usr/bin/env python3
-"""Bits of the kernels that rest on csrc/split16.h, for a fixed, seeded case list: one case per kernel template that calls the
-header's scale, splits or MFMA wrappers, at the smallest shapes the launchers send there.  Inputs come from a CPU generator and
-mix magnitudes from 1e-6 to 1e3 (low terms in the fp16 subnormals); every scaled case also runs with amax = 0 (the guard's
-unscaled path).  An output above BIG bytes is kept as its SHA-256 (equal digests = equal bits).
+"""Bits of kernels for a fixed, seeded case list (--list, default split16).  An output above BIG bytes is kept as its SHA-256
+(equal digests = equal bits).
 
-    python tools/kernel_bits.py --pin tests/golden/split16_bits.npz     # regenerate the fixture (tools/README.md)
-    python tools/kernel_bits.py out.npz                                 # one run of the list
+  split16     the kernels that rest on csrc/split16.h: one case per kernel template that calls the header's scale, splits or MFMA
+              wrappers, at the smallest shapes the launchers send there.  Inputs come from a CPU generator and mix magnitudes from
+              1e-6 to 1e3 (low terms in the fp16 subnormals); every scaled case also runs with amax = 0 (the guard's unscaled path).
+  dcn_sample  the DCN kernel paths that sample through csrc/dcn_sample.h and the split16 list does not reach, on the lattice and
+              heavy_tail fields of tests/golden/dcn_edge_cases.py (first map of each geometry).  grad_x of dcn_col2im and of
+              dcn_bwd_data, a float-atomic scatter, is not part of the list: the tolerance tests hold it.
 
---pin runs every case twice; an output that does not repeat is left out and named under the key `excluded` with the reason.
-tests/test_split16_bits_gpu.py runs the list on the tree's library and compares per output."""
+    python tools/kernel_bits.py --pin tests/golden/split16_bits.npz                         # regenerate a fixture (tools/README.md)
+    python tools/kernel_bits.py --list dcn_sample --pin tests/golden/dcn_sample_bits.npz [--note 'which library recorded it']
+    python tools/kernel_bits.py [--list NAME] out.npz                                       # one run of the list
+
+--pin runs every case twice; an output that does not repeat is left out and named under the key `excluded` with the reason (at
+most two outputs of the split16 list, none of the dcn_sample list); --note TEXT is stored under the key `note`.  tests/test_split16_bits_gpu.py and tests/test_dcn_sample_bits_gpu.py run the lists on the tree's
+library and compare per output."""
 import hashlib
 import os
 import sys
@@ -116,6 +123,79 @@ def cases():
     return out
 
 
+def dcn_sample_cases():
+    """-> {case name: [outputs as numpy arrays]} (insertion order fixed)"""
+    import torch
+    from mrefsr_amd import hip
+    sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
+    import dcn_edge_cases as E
+    dev = lambda a, dt=None: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda().to(dt or torch.float32)   # noqa: E731
+    nhwc = lambda a, dt=None: dev(a, dt).permute(0, 2, 3, 1).contiguous()   # noqa: E731
+    out = {}
+
+    def fields(geometry, with_mask=None):
+        """(tag, Field, x, weight, bias) for the lattice and the heavy_tail field on the geometry's first map"""
+        c, co, dg, groups, stride, pad, dil, wm = E.GEOMETRIES[geometry]
+        wm = wm if with_mask is None else with_mask
+        bhw = E.GEOMETRY_MAPS[geometry][0]
+        for name in ('lattice', 'heavy_tail'):
+            b = E.covering_batch(bhw[0], dg, bhw[1], bhw[2], stride, pad, dil, wm) if name == 'lattice' else bhw[0]
+            yield (name, E.field(name, b, dg, bhw[1], bhw[2], stride, pad, dil, wm)) + E.inputs(geometry, b, bhw[1], bhw[2])
+
+    def fwd(case, geometry, pt='1', t='2', dt=None, x_dt=None, **kw):
+        c, co, dg, groups, stride, pad, dil, _ = E.GEOMETRIES[geometry]
+        cl = kw.get('channels_last', False)
+        os.environ['MREFSR_DCN_PT'], os.environ['MREFSR_DCN_T'] = pt, t     # (read per call by the launcher)
+        for tag, f, x, wgt, bias in fields(geometry):
+            y = hip.dcn_fwd(nhwc(x, x_dt or dt) if cl else dev(x, x_dt or dt), dev(f.offset, dt), dev(f.mask, dt), dev(wgt, dt), dev(bias, dt), stride, pad, dil,
+                            groups, dg, 0.1, **kw)
+            out[f'{case}.{tag}'] = [y.view(torch.int16).cpu().numpy() if y.dtype == torch.bfloat16 else y.cpu().numpy()]
+
+    def columns(case, geometry, with_mask, dt=None):
+        """dcn_im2col, then dcn_col2im of a seeded column gradient: columns, grad_offset, grad_mask"""
+        c, co, dg, groups, stride, pad, dil, _ = E.GEOMETRIES[geometry]
+        for tag, f, x, wgt, bias in fields(geometry, with_mask):
+            dx, doff, dm = dev(x, dt), dev(f.offset, dt), dev(f.mask, dt)
+            col = hip.dcn_im2col(dx, doff, dm, wgt.shape, stride, pad, dil, groups, dg)
+            gcol = dev(np.random.default_rng(3).standard_normal(tuple(col.shape)), dt)
+            _, goff, gm = hip.dcn_col2im(gcol, dx, doff, dm, wgt.shape, stride, pad, dil, groups, dg)
+            out[f'{case}.{tag}'] = [a.cpu().numpy() for a in (col, goff, gm) if a is not None]
+
+    def fused_bwd(case, geometry):
+        c, co, dg = E.GEOMETRIES[geometry][:3]
+        for tag, f, x, wgt, bias in fields(geometry):
+            g = (np.random.default_rng(4).standard_normal((x.shape[0], co) + f.offset.shape[2:]) * 1e-6).astype(np.float32)
+            pk = hip.conv_pack_view(dev(wgt), None, 16, dgrad='T', wscale=2.0 ** (13 - int(np.floor(np.log2(np.abs(wgt).max())))))
+            _, goff, gm = hip.dcn_bwd_data(nhwc(g), nhwc(x), dev(f.offset), dev(f.mask), pk, dg, g_amax=dev(np.array([np.abs(g).max()])))
+            out[f'{case}.{tag}'] = [goff.cpu().numpy(), gm.cpu().numpy()]
+
+    keep = {k: os.environ.get(k) for k in ('MREFSR_DCN_PT', 'MREFSR_DCN_T')}
+    try:
+        with hip.deterministic(False):   # (the scatter runs; its output is not kept)
+            for geometry in ('g8_dg4', 'g8_4_dg2_groups2_stride2', 'g12_20_dg3_dil2'):     # the portable fp32 forward
+                fwd(f'fwd_portable_{geometry}', geometry)
+            columns('columns_f32_mask', 'g8_dg4', True)
+            columns('columns_f32_nomask', 'g8_dg4', False)
+            fwd('fwd_mfma_nchw_gather', 'c64_dg1_v1', nhwc_gather=False)                   # dcn_fwd_mfma_kernel, DCNv1
+            fwd('fwd_one_tile_c256', 'c256', channels_last=True)                           # dcn_fwd_bf16_kernel
+            fwd('fwd_pt_paired_c128', 'c128', channels_last=True)                          # dcn_fwd_pt_kernel, paired gather
+            fwd('fwd_pt_map8_c128_64', 'c128_64', channels_last=True)                      # ... eight-channel mapping
+            fwd('fwd_bf16_arith_f32_storage', 'c64', channels_last=True, bf16_arith=True)
+            fwd('fwd_bf16_arith_bf16_storage', 'c64', x_dt=torch.bfloat16, channels_last=True, bf16_arith=True)
+            fused_bwd('bwd_data_cpg16', 'c128')
+            fused_bwd('bwd_data_cpg32', 'c256')
+            for tag, dt in (('f64', torch.float64), ('f16', torch.float16)):               # csrc/dcn_any.hip's other dtypes
+                fwd(f'fwd_{tag}', 'g8_dg4', dt=dt)
+                columns(f'columns_{tag}', 'g8_dg4', True, dt=dt)
+    finally:
+        for k, v in keep.items():
+            os.environ.pop(k, None) if v is None else os.environ.__setitem__(k, v)
+    return out
+
+
+LISTS = {'split16': (cases, MAX_EXCLUDED), 'dcn_sample': (dcn_sample_cases, 0)}   # name: (case list, outputs --pin may leave out)
+
+
 def flatten(res):
     """{case: [arrays]} -> {'case/i': array, or its SHA-256 as uint8[32] above BIG bytes}"""
     flat = {}
@@ -131,22 +211,32 @@ def same(a, b):
 
 
 def main(argv):
+    argv, opt = list(argv), {'--list': 'split16', '--note': ''}
+    for name in opt:
+        if name in argv:
+            i = argv.index(name)
+            opt[name] = argv[i + 1]
+            del argv[i:i + 2]
     pin = '--pin' in argv
     paths = [a for a in argv if not a.startswith('--')]
-    if len(paths) != 1:
+    if len(paths) != 1 or opt['--list'] not in LISTS:
         sys.exit(__doc__)
-    first = flatten(cases())
+    run, most = LISTS[opt['--list']]
+    first = flatten(run())
     excluded = []
     if pin:
-        second = flatten(cases())
+        second = flatten(run())
         excluded = [k for k in first if not same(first[k], second[k])]
-        if len(excluded) > MAX_EXCLUDED:
-            sys.exit(f'{len(excluded)} outputs do not repeat (at most {MAX_EXCLUDED} may be left out): {excluded}')
+        if len(excluded) > most:
+            sys.exit(f'{len(excluded)} outputs do not repeat (at most {most} may be left out): {excluded}')
         for k in excluded:
             del first[k]
+    if opt['--note']:
+        first['note'] = np.array([opt['--note']], dtype='U512')
     np.savez_compressed(paths[0], excluded=np.array([f'{k}: did not repeat in two runs of the pinning library' for k in excluded], dtype='U128'),
                         **first)
-    print(f'{len(first)} outputs of {len(set(k.split("/")[0] for k in first))} cases -> {paths[0]} ({os.path.getsize(paths[0])} bytes); excluded: {excluded}')
+    first.pop('note', None)
+    print(f'list {opt["--list"]}: {len(first)} outputs of {len(set(k.split("/")[0] for k in first))} cases -> {paths[0]} ({os.path.getsize(paths[0])} bytes); excluded: {excluded}')
 
 
 if __name__ == '__main__':
