@@ -957,6 +957,37 @@ int64_t mrefsr_r1_sqnorm_workspace_bytes(int batch, int64_t n);
 int mrefsr_r1_sqnorm_f32(const float *g, int batch, int64_t n, float *out, void *workspace, int64_t workspace_bytes, mrefsr_stream_t stream);
 int mrefsr_r1_sqnorm_bwd_f32(const float *g, const float *gs, int batch, int64_t n, float *gg, mrefsr_stream_t stream);
 
+/* ---- differentiable discriminator augmentation (csrc/disc_augment.hip; train.d_augment) -------------------------------------------
+ * No reference counterpart: the colour, translation, cutout and flip operators of DiffAugment (Zhao et al., NeurIPS 2020) and of
+ * ADA's pipeline (Karras et al., NeurIPS 2020), one random transformation T per sample in front of every discriminator call.  For
+ * fixed parameters T(x) = L x + b, L linear.  Images fp32 [B][3][H][W]; fpar [B][4] = {db, s, c, unused}: brightness offset,
+ * saturation factor, contrast factor; ipar [B][8] = {flip, ty, tx, y0, y1, x0, x1, unused}: horizontal flip (0 / 1), integer
+ * translation (any value), cut box [y0,y1) x [x0,x1).  Both tables in device memory.  N = 3 H W.
+ *
+ * mrefsr_disc_augment_f32: output pixel (y, x) of sample b, every line one fp32 operation in this order, nothing fused:
+ *     inside the cut box, or sy = y - ty, sx0 = x - tx outside the image:  out_ch = 0 (selected: a NaN there does not get out)
+ *     sx = flip ? W - 1 - sx0 : sx0;   v_ch = in[b][ch][sy][sx] + db;   mu = ((v_0 + v_1) + v_2) / 3
+ *     u_ch = s v_ch + (1 - s) mu;      m = fl32(sum_b / N) + db;        out_ch = c u_ch + (1 - c) m
+ *   sum_b: the sample's N inputs added in double in a fixed order (a NaN anywhere in the sample reaches every pixel of it through
+ *   m).  Identity parameters (0, 1, 1, no flip, no shift, empty box) return the input's values.  with_bias = 0 takes db as 0 in
+ *   both places: L x, the node of the second derivative.
+ * mrefsr_disc_augment_adj_f32: gx = L^T g.  Source pixel (sy, sx) is read by output pixel y = sy + ty, x = (flip ? W - 1 - sx : sx)
+ *   + tx alone;  G_ch = g[b][ch][y][x] if that pixel is inside the image and outside the cut box, else 0 (selected);
+ *     gx_ch = c (s G_ch + (1 - s) ((G_0 + G_1) + G_2) / 3) + fl32((1 - c) / N) fl32(S_b)
+ *   S_b: g over the sample's kept output pixels, added in double in a fixed order.  The brightness bias has no adjoint term.
+ * contrast = 0 is the caller's statement that c = 1 in every sample: c is taken as 1, m and S_b as 0, the sum launch is skipped and
+ *   workspace / ticket may be NULL (one launch).  Otherwise two launches: per-block double partials and, by the block that arrives
+ *   last, the per-sample sums into `workspace` (mrefsr_disc_augment_workspace_bytes(B, H, W) bytes, 8-byte aligned, the caller's),
+ *   then the apply pass.  `ticket`: one zeroed word that every launch leaves zero again.  No float atomics, no readback, the same
+ *   bits from call to call.  Absolute error against the same formulas in float64: at most 16 * 2^-24 * max(U, |c| U + |1 - c| A) (13 for the adjoint),
+ *   A = max |in| + |db| (max |g| for the adjoint), U = (|s| + |1 - s|) A.
+ * B in 1..65535, H W in 1..2^28 (the -1 of the size query otherwise); out / gx must not alias the input. */
+int64_t mrefsr_disc_augment_workspace_bytes(int B, int H, int W);
+int mrefsr_disc_augment_f32(const float *x, const float *fpar, const int *ipar, int B, int H, int W, int with_bias, int contrast, float *out,
+                            void *workspace, int64_t workspace_bytes, unsigned int *ticket, mrefsr_stream_t stream);
+int mrefsr_disc_augment_adj_f32(const float *g, const float *fpar, const int *ipar, int B, int H, int W, int contrast, float *gx,
+                                void *workspace, int64_t workspace_bytes, unsigned int *ticket, mrefsr_stream_t stream);
+
 /* ---- the x8 geometric self-ensemble of test() (csrc/selfens.hip; val.self_ensemble) ------------------------------------------------
  * No reference counterpart: the "+" evaluation protocol of EDSR and its successors.  Copy j in 0..3 of a group has hf = j & 1,
  * vf = (j >> 1) & 1; a group is untransposed (tr = 0) or transposed (tr = 1).  Copy j of src [..., H, W] is, in torch,

@@ -250,6 +250,9 @@ SIGNATURES = {
     'mrefsr_degrade_levels_workspace_words': (_i64, [_i]),
     'mrefsr_degrade_levels_f32': (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     'mrefsr_degrade_jpeg_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    'mrefsr_disc_augment_workspace_bytes': (_i64, [_i, _i, _i]),
+    'mrefsr_disc_augment_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),
+    'mrefsr_disc_augment_adj_f32': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _vp]),
 }
 
 _lib = None

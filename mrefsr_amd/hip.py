@@ -2483,6 +2483,43 @@ def disc_unpack_image(g4):
     return out
 
 
+# ------------------------------------------------------------------ discriminator augmentation (csrc/disc_augment.hip)
+def _disc_augment(name, entry, x, params, *flags):
+    """params: an archs.d_augment.AugmentParams on x's device -- fpar [B,4] fp32 {db, s, c, -}, ipar [B,8] int32 {flip, ty, tx, y0,
+    y1, x0, x1, -}, and the host's knowledge ``contrast`` (False: c = 1 in every sample, the per-sample sum launch is skipped)"""
+    _chk(name, x, params.fpar)
+    _chk(name, params.ipar, dtype=torch.int32)
+    if x.dim() != 4 or x.shape[1] != 3 or x.numel() == 0:
+        raise NotImplementedError(f'{name}: a non-empty [B,3,H,W] image batch expected, got {tuple(x.shape)}')
+    b, _, h, w = x.shape
+    if tuple(params.fpar.shape) != (b, 4) or tuple(params.ipar.shape) != (b, 8):
+        raise ValueError(f'{name}: parameter tables {tuple(params.fpar.shape)} / {tuple(params.ipar.shape)} for a batch of {b} '
+                         f'([{b},4] fp32 and [{b},8] int32 expected)')
+    out = torch.empty_like(x)
+    ws = ticket = None
+    need = 0
+    if params.contrast:
+        need = _lib.load().mrefsr_disc_augment_workspace_bytes(b, h, w)
+        if need <= 0:
+            raise ValueError(f'{name}: unsupported shape {tuple(x.shape)}')
+        ws, ticket = _det_scratch(x.device, need)
+    _lib.call(entry, _p(x), _p(params.fpar), _p(params.ipar), b, h, w, *flags, 1 if params.contrast else 0, _p(out), _p(ws),
+              C.c_int64(need), _p(ticket), _stream())
+    return out
+
+
+def disc_augment(x, params, bias=True):
+    """x [B,3,H,W] -> T(x) of train.d_augment (archs/d_augment.py: d_augment_torch states the formulas): brightness, saturation,
+    contrast, flip, integer translation and cutout with per-sample parameters; bias=False: its linear part (db taken as 0).  One
+    launch, two when a sample may have contrast; fixed summation order, no atomics"""
+    return _disc_augment('disc_augment', 'mrefsr_disc_augment_f32', x, params, 1 if bias else 0)
+
+
+def disc_augment_adj(g, params):
+    """the adjoint of disc_augment's linear part: g [B,3,H,W] (the gradient of T(x)) -> the gradient of x; launches as disc_augment"""
+    return _disc_augment('disc_augment_adj', 'mrefsr_disc_augment_adj_f32', g, params)
+
+
 def disc_conv_pack_weight(w, cin, dgrad):
     """w [Cout,CinR,3,3] -> [9,cin,Cout] (dgrad False) or [9,Cout,cin] (dgrad True), channels CinR..cin-1 zero"""
     _chk('disc_conv_pack_weight', w)

@@ -23,7 +23,9 @@ disc_unet.hip and disc_sg2.hip)
 with gan_type / gan_weight / grad_penalty_weight, its own Adam (optimizer_d, second in self.optimizers) and scheduler, the D step of :219-245 and l_g_gan of
 :272-276.  gan_type wgan_softplus and the lazily applied R1 penalty on the real images (train.r1_reg_weight, train.net_d_reg_every) are
 those of basicsr/losses/losses.py:284-318, 391-405 and basicsr/models/stylegan2_model.py:75-79, 198-221; lr_d and beta_d are used as
-written (stylegan2_model.py:135-143 rescales them by every / (every + 1): left to the configuration).
+written (stylegan2_model.py:135-143 rescales them by every / (every + 1): left to the configuration).  train.d_augment puts
+DiffAugment / ADA's differentiable colour, translation, cutout and flip operators in front of every discriminator call, on the kernels
+of csrc/disc_augment.hip (_setup_d_augment, _d; no counterpart in the reference; a bad option is a ValueError that names it).
 Refused, not silently skipped: texture_opt without use_weights: true (the reference cannot evaluate it either) and other
 discriminators (NotImplementedError); gan_type without network_d and the
 reverse, r1_reg_weight without network_d (NotImplementedError); an r1_reg_weight that is not a finite number of at least 0, a
@@ -390,6 +392,7 @@ class MultiRefRestorationModel:
         if train_opt.get('r1_reg_weight') and not net_d_opt:
             raise NotImplementedError('train.r1_reg_weight without network_d: R1 regularises a discriminator; give a network_d or drop '
                                       'r1_reg_weight')
+        self._setup_d_augment(train_opt, net_d_opt)   # (a bad train.d_augment is refused before anything is built)
         # R1 on the real images every net_d_reg_every-th D step (stylegan2_model.py:75-79); 0: none
         self.r1_reg_weight = float(train_opt.get('r1_reg_weight') or 0)
         self.net_d_reg_every = int(train_opt.get('net_d_reg_every') or 1)
@@ -446,6 +449,45 @@ class MultiRefRestorationModel:
             raise NotImplementedError(f'Scheduler {stype} is not implemented yet.')
         for optimizer in self.optimizers:
             self.schedulers.append((_CosineAnnealingRestartLR if stype == 'CosineAnnealingRestartLR' else _MultiStepRestartLR)(optimizer, **sched))
+
+    # ------------------------------------------------------------------ train.d_augment: the augmentation in front of every D call
+    d_augment = d_adaptive = _d_aug_gen = None   # (the state of a model without the option)
+
+    def _setup_d_augment(self, train_opt, net_d_opt):
+        """train.d_augment {policy: [color, translation, cutout, flip] (a list or a comma-separated string; color = brightness,
+        saturation and contrast), p: 1.0, brightness: 0.25, saturation: [0, 2], contrast: [0.5, 1.5], translation: 0.125, cutout: 0.5,
+        adaptive: {target: 0.6, interval: 4, speed_kimg: 500}}: DiffAugment / ADA's pixel and colour operators on the kernels of
+        csrc/disc_augment.hip, see archs/d_augment.py (parse_d_augment names what is refused; sample_d_augment the order of draws).
+        The parameters come from a host generator seeded from manual_seed or, without one, from torch's global generator, as
+        _pool_gen is.  No claim about image quality is made: only random-init weights were available offline."""
+        from ..archs import d_augment as da
+        self.d_augment = da.parse_d_augment(train_opt.get('d_augment'), has_net_d=bool(net_d_opt), gan_type=train_opt.get('gan_type'))
+        self.d_adaptive = self._d_aug_gen = None
+        if self.d_augment is None:
+            return
+        seed = self.opt.get('manual_seed')
+        if seed is None:   # (from torch's global generator: reproducible behind torch.manual_seed)
+            seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+        self._d_aug_gen = torch.Generator().manual_seed(seed)
+        if self.d_augment['adaptive'] is not None:
+            self.d_adaptive = da.AdaptiveP(self.d_augment['p'], **self.d_augment['adaptive'])
+
+    @property
+    def _d(self):
+        """what every discriminator call of the training step goes through.  Without train.d_augment it is net_d itself: the same
+        object is called and handed to the gradient penalty.  With it, _d_augmented."""
+        return self.net_d if self.d_augment is None else self._d_augmented
+
+    def _d_augmented(self, x):
+        """net_d(T(x)): a fresh set of parameters per call (one torch.rand on the host generator, one small upload), independently
+        and in program order -- the D step's real images, its fake images, the WGAN-GP interpolate, the R1 real batch on regularised
+        steps (the penalty's gradient is taken with respect to the images before the augmentation, as ADA does), the G step's fake
+        images.  A range-fallback re-run of the G step calls this again and so draws again."""
+        from ..archs import d_augment as da
+        b, _, h, w = x.shape
+        p = self.d_augment['p'] if self.d_adaptive is None else self.d_adaptive.p
+        params = da.sample_d_augment(b, h, w, self.d_augment, p, self._d_aug_gen).to(x.device)
+        return self.net_d(da.d_augment(x, params))
 
     @staticmethod
     def _build_msssim(train_opt):
@@ -801,7 +843,7 @@ class MultiRefRestorationModel:
                 l_g_total = l_g_total + l_g_freq
                 self.log_dict['l_g_freq'] = l_g_freq.detach()
             if self.net_d is not None:   # ref :272-276 (D's parameters are frozen: no weight gradient of D is computed)
-                fake_g_pred = self.net_d(self.output)
+                fake_g_pred = self._d(self.output)
                 l_g_gan = self.cri_gan(fake_g_pred, True, is_disc=False)
                 l_g_total = l_g_total + l_g_gan
                 self.log_dict['l_g_gan'] = l_g_gan.detach()
@@ -938,24 +980,26 @@ class MultiRefRestorationModel:
         for p in self.net_d.parameters():
             p.requires_grad = True
         gan_gt = self._gt_for('gan')
-        real_d_pred = self.net_d(gan_gt)
+        real_d_pred = self._d(gan_gt)
+        if self.d_adaptive is not None:   # (two words on the device; read back every adaptive.interval-th step below)
+            self.d_adaptive.accumulate(real_d_pred)
         l_d_real = self.cri_gan(real_d_pred, True, is_disc=True)
         self.log_dict['l_d_real'] = l_d_real.detach()
         self.log_dict['out_d_real'] = torch.mean(real_d_pred.detach())
-        fake_d_pred = self.net_d(self.output.detach())
+        fake_d_pred = self._d(self.output.detach())
         l_d_fake = self.cri_gan(fake_d_pred, False, is_disc=True)
         self.log_dict['l_d_fake'] = l_d_fake.detach()
         self.log_dict['out_d_fake'] = torch.mean(fake_d_pred.detach())
         l_d_total = l_d_real + l_d_fake
         if self.cri_grad_penalty is not None:
-            l_grad_penalty = self.cri_grad_penalty(self.net_d, gan_gt, self.output)
+            l_grad_penalty = self.cri_grad_penalty(self._d, gan_gt, self.output)
             self.log_dict['l_grad_penalty'] = l_grad_penalty.detach()
             l_d_total = l_d_total + l_grad_penalty
         l_d_total.backward()
         if self.r1_reg_weight > 0 and step % self.net_d_reg_every == 0:
             from ..losses import r1_penalty
             real_img = gan_gt.detach().requires_grad_(True)   # a leaf of its own on the GT's storage (D only reads it)
-            real_pred = self.net_d(real_img)
+            real_pred = self._d(real_img)
             l_d_r1 = r1_penalty(real_pred, real_img)
             # (0 * real_pred[0]: every output of D takes part in this backward, which is what DDP's reducer asks for)
             l_d_r1 = self.r1_reg_weight / 2 * l_d_r1 * self.net_d_reg_every + 0 * real_pred[0]
@@ -964,6 +1008,11 @@ class MultiRefRestorationModel:
         elif self.r1_reg_weight > 0:
             self.log_dict.pop('l_d_r1', None)   # a plain step of the lazy schedule: not the value of an earlier regularised step
         self._step_d()
+        if self.d_adaptive is not None:
+            self.d_adaptive.step()
+            self.log_dict['d_aug_p'] = self.d_adaptive.p
+            if self.d_adaptive.rt is not None:
+                self.log_dict['d_aug_rt'] = self.d_adaptive.rt
         for p in self.net_d.parameters():   # ref :249-251, before the G step
             p.requires_grad = False
 
@@ -1297,6 +1346,8 @@ class MultiRefRestorationModel:
             return
         state = {'epoch': epoch, 'iter': current_iter, 'optimizers': [o.state_dict() for o in self.optimizers],
                  'schedulers': [s.state_dict() for s in self.schedulers]}
+        if self.d_adaptive is not None:   # train.d_augment.adaptive: p and the pending accumulator
+            state['d_augment'] = self.d_adaptive.state_dict()
         os.makedirs(states_dir, exist_ok=True)
         torch.save(state, os.path.join(states_dir, f'{current_iter}.state'))
 
@@ -1309,6 +1360,8 @@ class MultiRefRestorationModel:
             o.load_state_dict(state)
         for sch, state in zip(self.schedulers, resume_schedulers):
             sch.load_state_dict(state)
+        if self.d_adaptive is not None and resume_state.get('d_augment') is not None:   # (a state without it: the option's p)
+            self.d_adaptive.load_state_dict(resume_state['d_augment'], device=self.device)
 
     # ------------------------------------------------------------------ bookkeeping
     def get_current_log(self):
