@@ -742,6 +742,22 @@ def _vgg_stack_backward(plan, b, saved, std, add_tap):
     return None
 
 
+def _tap_slot(plan, g, i, kind, shape, device):
+    """what every add_tap of _vgg_stack_backward starts with -> (j, g, accumulate): j = the index of tap (i, kind) in plan.taps, None
+    when it is none (g as it came); else g is the running gradient (accumulate) or, without one yet, a new buffer of shape(j)"""
+    j = next((j for j, (ti, tk, _) in enumerate(plan.taps) if (ti, tk) == (i, kind)), None)
+    if j is None or g is not None:
+        return j, g, g is not None
+    return j, torch.empty(shape(j), device=device, dtype=torch.float32), False
+
+
+def _vgg_norm(vgg):
+    """(mean, std) of the VGG's input normalisation as the kernels take them, (None, None) without one (or without a VGG)"""
+    if vgg is None or not vgg.use_input_norm:
+        return None, None
+    return vgg.mean.contiguous(), vgg.std.contiguous()
+
+
 class _VggLoss(Function):
     """(output x, gt) -> [perceptual total, style total] of PerceptualLoss with one VGG: the output and the GT run as ONE 2B batch
     through the convolution kernels (the same arithmetic for both feature sets, half the launches); the backward runs the input
@@ -782,17 +798,13 @@ class _VggLoss(Function):
         nt = len(plan.taps)
         feats, grams = st[2:2 + nt], st[2 + nt:]
         g_tot = g_tot.contiguous()
-        tap_of = {(i, k): j for j, (i, k, _) in enumerate(plan.taps)}
 
         def add_tap(g, i, kind):
             """g (None = zero) + the tap's loss gradient; -> (g, max |g|)"""
-            j = tap_of.get((i, kind))
+            j, g, acc = _tap_slot(plan, g, i, kind, lambda j: (b,) + tuple(feats[j].shape[1:]), g_tot.device)
             if j is None:
                 return g, None
             f, w = feats[j], plan.taps[j][2]
-            acc = g is not None
-            if g is None:
-                g = torch.empty((b,) + tuple(f.shape[1:]), device=f.device, dtype=torch.float32)
             amax = None
             if plan.sw > 0:
                 amax = hip.gram_bwd_nhwc(f[:b], grams[j][:b], grams[j][b:], g, plan.sw, w, gup=g_tot[1:2], accumulate=acc,
@@ -813,9 +825,7 @@ def perceptual(vgg, x, gt, plan):
         raise NotImplementedError('PerceptualLoss: mrefsr_amd has no CPU path (HIP kernels only)')
     if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.shape != gt.shape or x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f'PerceptualLoss: two float32 [N,3,H,W] images expected, got {tuple(x.shape)} / {tuple(gt.shape)}')
-    mean = vgg.mean.contiguous() if vgg.use_input_norm else None
-    std = vgg.std.contiguous() if vgg.use_input_norm else None
-    return _VggLoss.apply(x, gt, plan, mean, std)
+    return _VggLoss.apply(x, gt, plan, *_vgg_norm(vgg))
 
 
 # ---- texture loss (TextureLoss, losses.py:430-532 of the reference model's loss module) -----------------------------
@@ -867,16 +877,12 @@ class _VggTexture(Function):
         nt = len(plan.taps)
         fcs, gxs, gms, coeffs = (st[2 + j * nt:2 + (j + 1) * nt] for j in range(4))
         g_tot = g_tot.contiguous()
-        tap_of = {(i, k): j for j, (i, k, _) in enumerate(plan.taps)}
         b = fcs[0].shape[0]
 
         def add_tap(g, i, kind):
-            j = tap_of.get((i, kind))
+            j, g, acc = _tap_slot(plan, g, i, kind, lambda j: fcs[j].shape, g_tot.device)
             if j is None:
                 return g, None
-            acc = g is not None
-            if g is None:
-                g = torch.empty_like(fcs[j])
             scale = plan.loss_weight / 3.0 / 4.0 / ctx.divs[j]
             return g, hip.texture_gram_bwd_nhwc(fcs[j], gxs[j], gms[j], coeffs[j], norms[j:j + 1], g, scale, gup=g_tot, accumulate=acc)
 
@@ -909,9 +915,7 @@ def texture(vgg, x, maps, weights, plan):
             any(maps[n].dtype != torch.float32 or maps[n].dim() != 4 or maps[n].shape[0] != x.shape[0] for n in plan.names):
         raise ValueError(f'TextureLoss: a float32 [N,3,H,W] image, float32 [N,C,h,w] maps and float32 weights expected, got x {tuple(x.shape)}')
     coeffs, gms = texture_targets(plan, maps, weights)
-    mean = vgg.mean.contiguous() if vgg.use_input_norm else None
-    std = vgg.std.contiguous() if vgg.use_input_norm else None
-    return _VggTexture.apply(x, plan, mean, std, *coeffs, *gms)
+    return _VggTexture.apply(x, plan, *_vgg_norm(vgg), *coeffs, *gms)
 
 
 # ---- contextual loss (losses.ContextualLoss; Mechrez et al., ECCV 2018) ---------------------------------------------
@@ -990,22 +994,16 @@ class _VggContextual(Function):
         keep = [dict(zip(_CX_SAVED, st[1 + j * nk:1 + (j + 1) * nk])) for j in range(len(plan.taps) + (plan.rgb is not None))]
         rgb = keep.pop(0) if plan.rgb is not None else None
         g_tot = g_tot.contiguous()
-        tap_of = {(i, k): j for j, (i, k, _) in enumerate(plan.taps)}
 
         def add_tap(g, i, kind):
-            j = tap_of.get((i, kind))
+            j, g, acc = _tap_slot(plan, g, i, kind, lambda j: (b,) + ctx.tap_shapes[j], g_tot.device)
             if j is None:
                 return g, None
-            acc = g is not None
             coef = plan.loss_weight * plan.taps[j][2]
             if plan.strides[j] == 1:
-                if g is None:
-                    g = torch.empty_like(keep[j]['xn'])
                 return g, hip.contextual_bwd(keep[j], plan.band_width, coef, g, gup=g_tot, accumulate=acc, weight_sp=plan.weight_sp)
             gs = torch.empty_like(keep[j]['xn'])
             hip.contextual_bwd(keep[j], plan.band_width, coef, gs, gup=g_tot, want_amax=False, weight_sp=plan.weight_sp)
-            if g is None:
-                g = torch.empty((b,) + ctx.tap_shapes[j], device=gs.device, dtype=torch.float32)
             return g, hip.cx_subsample_bwd(gs, g, plan.strides[j], accumulate=acc)
 
         g_x = _vgg_stack_backward(plan, b, saved, std, add_tap) if plan.taps else None
@@ -1024,9 +1022,7 @@ def contextual(vgg, x, gt, plan):
         raise NotImplementedError('ContextualLoss: mrefsr_amd has no CPU path (HIP kernels only)')
     if x.dtype != torch.float32 or gt.dtype != torch.float32 or x.shape != gt.shape or x.dim() != 4 or x.shape[1] != 3:
         raise ValueError(f'ContextualLoss: two float32 [N,3,H,W] images expected, got {tuple(x.shape)} / {tuple(gt.shape)}')
-    mean = vgg.mean.contiguous() if vgg is not None and vgg.use_input_norm else None
-    std = vgg.std.contiguous() if vgg is not None and vgg.use_input_norm else None
-    return _VggContextual.apply(x, gt, plan, mean, std)
+    return _VggContextual.apply(x, gt, plan, *_vgg_norm(vgg))
 
 
 def recording(*tensors):

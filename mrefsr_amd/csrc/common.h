@@ -47,6 +47,9 @@ inline bool first_use_on_device(unsigned long long &done)
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// blocks of a grid-stride launch: `work` blocks' worth, at least 1 and at most `cap`
+inline int grid_of(long work, int cap) { return (int)(work < 1 ? 1 : (work < cap ? work : cap)); }
+
 // Switches of A/B measurements (tools/; MREFSR_HIP_LIB = a -DMREFSR_AB_KERNELS build): such a build reads them from the environment
 // per call.  In the product they are their defaults at compile time: no getenv, and the branch a switch guards folds away.
 #ifdef MREFSR_AB_KERNELS

@@ -428,7 +428,7 @@ __global__ __launch_bounds__(256) void cx_grad_finish_kernel(const float *__rest
                     v.x += o.x, v.y += o.y, v.z += o.z, v.w += o.w;
                 }
                 gv[k] = v;
-                amx = fmaxf(amx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+                amx = fmaxf(amx, mrefsr::amax4(v));
             }
         }
     }
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(256) void cx_subsample_bwd_kernel(const float *__re
             v.x += a.x, v.y += a.y, v.z += a.z, v.w += a.w;
         }
         if (hit || !accumulate) *gp = v;
-        amx = fmaxf(amx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
+        amx = fmaxf(amx, mrefsr::amax4(v));
     }
     if (amax_bits) mrefsr::publish_amax<true>(amax_bits, amx);
 }

@@ -6,7 +6,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-inline int grid_of(long work, int cap) { return (int)(work < 1 ? 1 : (work < cap ? work : cap)); }
+using mrefsr::grid_of;
 
 __device__ inline float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 

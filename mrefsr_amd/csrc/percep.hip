@@ -5,14 +5,15 @@
 //   maxpool2_bwd_nhwc    its backward fused with the preceding ReLU's mask, + max |g| for the fp16-split dgrad
 //   tap_crit             L1 / Frobenius criterion of several taps: loss partials (fixed order) and / or the gradient
 //   gram_nhwc            G[n] = F^T F / (c h w) (or times a given scale: the texture loss's raw Gram, texture.hip) on v_mfma_f32_16x16x4_f32, upper tiles, split-K, fixed-order second stage
-//   gram_bwd_nhwc        dF += (2 / (c h w)) F S, S = d loss / d G formed inside from G(x) and G(gt), same MFMA
+//   gram_bwd_nhwc        dF += (2 / (c h w)) F S, S = d loss / d G formed inside from G(x) and G(gt), same MFMA (tile body: gram.h)
 //   image_to_nhwc4_bwd   gradient of the image packing + normalisation (fused_act.hip: image_to_nhwc4) -> [N][3][HW]
 // All element-wise / reduction kernels are HBM-bound; the Gram products are a few GFLOP per step.
-#include "common.h"
+#include "gram.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using mrefsr::grid_of;
+using mrefsr::gram::f32x4;
 
 __device__ inline float relu_in(float v, int relu) { return (relu && v < 0.f) ? 0.f : v; }
 
@@ -278,62 +279,20 @@ __global__ __launch_bounds__(256) void gram_finish_kernel(const float *__restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Gram backward: dF[n][p][j] (+)= 2 * sum_k F[n][p][k] S'[n][k][j],  S' = sgn(Gx - Gg) * (coef * inv_chw) (symmetric).
-// Computed transposed, out^T[j][p] = sum_k S'[j][k] F[p][k]: A = S' (rows j), B[k][p] = F[p][k].  A lane holds a float4 of
-// F[p0 + (l & 15)][k0 + 4 (l >> 4) .. + 3] and feeds element e to the e-th MFMA of the 16-channel step, so the MFMA's local
-// k = l >> 4 is channel k0 + 4 (l >> 4) + e -- the S' operand takes the same channel.  Wave = 16 pixels x 64 columns (four
-// accumulators); block = 4 waves = 64 pixels.  D: column (p) = lane & 15, row (j) = 4 (lane >> 4) + r: a float4 of dF's row.
+// Gram backward: dF[n][p][j] (+)= 2 * sum_k F[n][p][k] S'[n][k][j],  S' = sgn(Gx - Gg) * (coef * inv_chw) (symmetric): the tile
+// body of gram.h with the scaled sign as its A operand and the factor 2 behind the sums.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gram_bwd_kernel(const float *__restrict__ f, const float *__restrict__ gx, const float *__restrict__ gg,
                                                        float *__restrict__ df, int HW, int C, const float *__restrict__ gup, float loss_weight,
                                                        float weight, float inv_numel, float inv_chw, int accumulate,
                                                        unsigned int *__restrict__ amax_bits)
 {
-    const int n = blockIdx.z, jb = blockIdx.y * 64;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int p0 = (blockIdx.x * 4 + wave) * 16;
-    const int kl = lane >> 4, cl = lane & 15;
     const float up = gup ? *gup : 1.0f;
     const float coef = __fmul_rn(__fmul_rn(__fmul_rn(up, loss_weight), weight), inv_numel);
     const float sc = __fmul_rn(coef, inv_chw);
-    const float *fn = f + (long)n * HW * C;
-    const float *gxn = gx + (long)n * C * C, *ggn = gg + (long)n * C * C;
-    const int p = p0 + cl;
-    const bool pok = p < HW;
-    f32x4 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < C; k0 += 16) {
-        const int kc = k0 + 4 * kl;
-        const float4 fv = pok ? *reinterpret_cast<const float4 *>(fn + (long)p * C + kc) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float fe[4] = {fv.x, fv.y, fv.z, fv.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const long srow = (long)(kc + e) * C + jb + cl;   // S'[k][j] = S'[j][k]
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const float d = gxn[srow + 16 * b] - ggn[srow + 16 * b];
-                const float sv = d > 0.f ? sc : (d < 0.f ? -sc : 0.f);
-                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(sv, fe[e], acc[b], 0, 0, 0);
-            }
-        }
-    }
-    // lane holds out[p0 + (l & 15)][jb + 16 b + 4 (l >> 4) + r]
-    float amx = 0.f;
-    if (pok) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            float4 *dst = reinterpret_cast<float4 *>(df + ((long)n * HW + p) * C + jb + 16 * b + 4 * kl);
-            float4 v = make_float4(2.f * acc[b][0], 2.f * acc[b][1], 2.f * acc[b][2], 2.f * acc[b][3]);
-            if (accumulate) {
-                const float4 o = *dst;
-                v.x += o.x, v.y += o.y, v.z += o.z, v.w += o.w;
-            }
-            *dst = v;
-            amx = fmaxf(amx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-        }
-    }
-    if (amax_bits) mrefsr::publish_amax<false>(amax_bits, amx);
+    // (the capture is read in front of the selects: read inside them, they compile to 17 more branches instead of v_cndmask)
+    mrefsr::gram::bwd_tile(f, gx, gg, df, HW, C, accumulate, amax_bits,
+                           [sc](const float d) { const float s = sc; return d > 0.f ? s : (d < 0.f ? -s : 0.f); }, [](long) { return 2.f; }, false);
 }
 
 // gradient of image_to_nhwc4: g4 [N][HW][ld] (channels 0..2) -> g_img [N][3][HW] = (g / std) * 0.5 (torch's order: the division's
@@ -358,8 +317,6 @@ __global__ __launch_bounds__(256) void image_bwd_kernel(const float *__restrict_
         }
     }
 }
-
-inline int grid_of(long work, int cap) { return (int)(work < 1 ? 1 : (work < cap ? work : cap)); }
 
 }  // namespace
 
@@ -452,8 +409,8 @@ MREFSR_EXPORT int mrefsr_gram_nhwc_scaled_f32(const float *f, int N, int HW, int
                                               int64_t workspace_bytes, mrefsr_stream_t stream)
 {
     MREFSR_REQUIRE(f && gram && workspace, "gram_nhwc: null pointer");
+    if (const int e = mrefsr::gram::check_gram("gram_nhwc", N, HW, C)) return e;
     const int S = mrefsr_gram_splits(N, HW, C);
-    MREFSR_REQUIRE(S > 0, "gram_nhwc: N=%d HW=%d C=%d (C a multiple of 64)", N, HW, C);
     MREFSR_REQUIRE(workspace_bytes >= mrefsr_gram_workspace_bytes(N, HW, C), "gram_nhwc: workspace of %ld bytes < %ld", (long)workspace_bytes,
                    (long)mrefsr_gram_workspace_bytes(N, HW, C));
     const int T = C / 64, chunk = ((HW + S - 1) / S + 3) / 4 * 4;
@@ -476,7 +433,7 @@ MREFSR_EXPORT int mrefsr_gram_bwd_nhwc_f32(const float *f, const float *gx, cons
                                            float loss_weight, float weight, int accumulate, float *amax, mrefsr_stream_t stream)
 {
     MREFSR_REQUIRE(f && gx && gg && df, "gram_bwd_nhwc: null pointer");
-    MREFSR_REQUIRE(N > 0 && HW > 0 && C > 0 && C % 64 == 0, "gram_bwd_nhwc: N=%d HW=%d C=%d (C a multiple of 64)", N, HW, C);
+    if (const int e = mrefsr::gram::check_gram("gram_bwd_nhwc", N, HW, C)) return e;
     const float inv_numel = 1.0f / ((float)N * (float)C * (float)C), inv_chw = 1.0f / ((float)C * (float)HW);
     hipLaunchKernelGGL(gram_bwd_kernel, dim3((HW + 63) / 64, C / 64, N), dim3(256), 0, (hipStream_t)stream, f, gx, gg, df, HW, C, gup,
                        loss_weight, weight, inv_numel, inv_chw, accumulate ? 1 : 0, reinterpret_cast<unsigned int *>(amax));

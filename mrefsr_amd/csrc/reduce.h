@@ -39,6 +39,9 @@ __device__ __forceinline__ void publish_amax(unsigned int *dst, float m)
         atomicMax(dst, __float_as_uint(m));
 }
 
+// max of the four |components|: what a thread that stores a float4 folds into its running maximum
+__device__ __forceinline__ float amax4(const float4 v) { return fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))); }
+
 // ---- one block ------------------------------------------------------------------------------------------------
 // The halving tree over the THREADS values of a 1-D block of THREADS threads: red[t] = op(red[t], red[t + o]) for all t < o,
 // o = THREADS / 2 .. 1.  Called by ALL threads of the block; every thread gets the result.  `red`: THREADS elements of LDS.

@@ -9,16 +9,15 @@
 //   texture_scale_nhwc  Fc = F (.) coeff (broadcast over the channels)
 //   texture_crit        per layer ||G(x) - G(maps)||_F (fp64 sums in a fixed order, no atomics), the layer terms and the total
 //   texture_gram_bwd    dF (+)= coeff (.) (2 Fc (Gx - Gm)) * sc, sc = gup * loss_weight / 3 / 4 / D / norm (0 where norm == 0),
-//                       on v_mfma_f32_16x16x4_f32 like gram_bwd_nhwc of percep.hip, with max |dF| for the Winograd input scale
+//                       on v_mfma_f32_16x16x4_f32: the tile body of gram.h, which gram_bwd_nhwc of percep.hip runs too, with max |dF|
+//                       for the Winograd input scale
 // The Gram matrices themselves are mrefsr_gram_nhwc_scaled_f32 (percep.hip) with scale 1.
 // Built with -ffp-contract=off: the swap's additions and its division are the roundings the source spells out.
-#include "common.h"
+#include "gram.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-inline int grid_of(long work, int cap) { return (int)(work < 1 ? 1 : (work < cap ? work : cap)); }
+using mrefsr::grid_of;
 
 // ---------------------------------------------------------------------------------------------------------------
 // Selection: one thread per (b, position).  idx, val [K][B][P]; valid_bits [B] (bit k = reference k of sample b present; NULL:
@@ -201,61 +200,21 @@ __global__ __launch_bounds__(64) void crit_finish_kernel(const CritArgs a, const
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Backward of one layer: dF[n][p][j] (+)= coeff[n][p] * sc2 * sum_k Fc[n][p][k] (Gx - Gm)[n][k][j],  sc2 = 2 sc.  The layout of
-// gram_bwd_kernel (percep.hip): computed transposed, A = the Gram difference (rows j; symmetric), B[k][p] = Fc[p][k]; wave = 16
-// pixels x 64 columns, block = 4 waves = 64 pixels; D: column (p) = lane & 15, row (j) = 4 (lane >> 4) + r.  The scalar factor is
-// applied behind the sums (the differences go through the MFMA unscaled: sc is ~1e-20 at the training sizes).
+// Backward of one layer: dF[n][p][j] (+)= coeff[n][p] * sc2 * sum_k Fc[n][p][k] (Gx - Gm)[n][k][j],  sc2 = 2 sc: the tile body of
+// gram.h with the Gram difference itself as its A operand.  The scalar factor is applied behind the sums (the differences go
+// through the MFMA unscaled: sc is ~1e-20 at the training sizes); norm == 0: exactly zero, whatever the sums hold -- torch's norm
+// backward at 0.
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gram_bwd_kernel(const float *__restrict__ fc, const float *__restrict__ gx, const float *__restrict__ gm,
                                                        const float *__restrict__ coeff, const float *__restrict__ norm,
                                                        const float *__restrict__ gup, float *__restrict__ df, int HW, int C, float scale,
                                                        int accumulate, unsigned int *__restrict__ amax_bits)
 {
-    const int n = blockIdx.z, jb = blockIdx.y * 64;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int p0 = (blockIdx.x * 4 + wave) * 16;
-    const int kl = lane >> 4, cl = lane & 15;
     const float nrm = *norm;
     const float up = gup ? *gup : 1.0f;
     const float sc2 = nrm == 0.f ? 0.f : 2.f * ((up * scale) / nrm);
-    const float *fn = fc + (long)n * HW * C;
-    const float *gxn = gx + (long)n * C * C, *gmn = gm + (long)n * C * C;
-    const int p = p0 + cl;
-    const bool pok = p < HW;
-    f32x4 acc[4];
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k0 = 0; k0 < C; k0 += 16) {
-        const int kc = k0 + 4 * kl;
-        const float4 fv = pok ? *reinterpret_cast<const float4 *>(fn + (long)p * C + kc) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float fe[4] = {fv.x, fv.y, fv.z, fv.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const long srow = (long)(kc + e) * C + jb + cl;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const float d = gxn[srow + 16 * b] - gmn[srow + 16 * b];
-                acc[b] = __builtin_amdgcn_mfma_f32_16x16x4f32(d, fe[e], acc[b], 0, 0, 0);
-            }
-        }
-    }
-    float amx = 0.f;
-    if (pok) {
-        const float cs = nrm == 0.f ? 0.f : coeff[(long)n * HW + p] * sc2;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            float4 *dst = reinterpret_cast<float4 *>(df + ((long)n * HW + p) * C + jb + 16 * b + 4 * kl);
-            // (norm == 0: exactly zero, whatever the sums hold -- torch's norm backward at 0)
-            float4 v = nrm == 0.f ? make_float4(0.f, 0.f, 0.f, 0.f) : make_float4(cs * acc[b][0], cs * acc[b][1], cs * acc[b][2], cs * acc[b][3]);
-            if (accumulate) {
-                const float4 o = *dst;
-                v.x += o.x, v.y += o.y, v.z += o.z, v.w += o.w;
-            }
-            *dst = v;
-            amx = fmaxf(amx, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
-        }
-    }
-    if (amax_bits) mrefsr::publish_amax<false>(amax_bits, amx);   // max |dF|
+    mrefsr::gram::bwd_tile(fc, gx, gm, df, HW, C, accumulate, amax_bits, [](const float d) { return d; },
+                           [coeff, sc2](const long px) { return coeff[px] * sc2; }, nrm == 0.f);
 }
 
 }  // namespace
@@ -331,7 +290,7 @@ MREFSR_EXPORT int mrefsr_texture_gram_bwd_nhwc_f32(const float *fc, const float 
                                                    mrefsr_stream_t stream)
 {
     MREFSR_REQUIRE(fc && gx && gm && coeff && norm && df, "texture_gram_bwd_nhwc: null pointer");
-    MREFSR_REQUIRE(N > 0 && N < 65536 && HW > 0 && C > 0 && C % 64 == 0, "texture_gram_bwd_nhwc: N=%d HW=%d C=%d (C a multiple of 64)", N, HW, C);
+    if (const int e = mrefsr::gram::check_gram("texture_gram_bwd_nhwc", N, HW, C)) return e;
     hipLaunchKernelGGL(gram_bwd_kernel, dim3((HW + 63) / 64, C / 64, N), dim3(256), 0, (hipStream_t)stream, fc, gx, gm, coeff, norm, gup, df, HW, C,
                        scale, accumulate ? 1 : 0, reinterpret_cast<unsigned int *>(amax));
     return mrefsr::check_launch("texture_gram_bwd_nhwc");

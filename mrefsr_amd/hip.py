@@ -1714,19 +1714,34 @@ def tap_crit_grad(x, y, grad, weight, group, crit, loss_weights, gup=None, norm=
     return amax
 
 
-def gram_nhwc(f):
-    """f [N,H,W,C] (C a multiple of 64) -> [N,C,C] = F^T F / (C H W) per image (exact f32 MFMA products, fixed summation order)"""
-    _chk('gram_nhwc', f)
+def _gram(name, f, scale):
+    """f [N,H,W,C] -> [N,C,C] = F^T F * scale per image; scale None: 1 / (C H W), which the library forms in fp32"""
+    _chk(name, f)
     n, h, w, c = f.shape
-    lib = _lib.load()
-    need = lib.mrefsr_gram_workspace_bytes(n, h * w, c)
+    need = _lib.load().mrefsr_gram_workspace_bytes(n, h * w, c)
     if need < 0:
-        raise ValueError(f'gram_nhwc: C={c} (a multiple of 64)')
+        raise ValueError(f'{name}: C={c} (a multiple of 64)')
     ws = _scratch(f.device, need)
     g = torch.empty((n, c, c), device=f.device, dtype=torch.float32)
     with _timed('gram_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (f.numel() + g.numel())):
-        _lib.call('mrefsr_gram_nhwc_f32', _p(f), n, h * w, c, _p(g), _p(ws), C.c_int64(need), _stream())
+        if scale is None:
+            _lib.call('mrefsr_gram_nhwc_f32', _p(f), n, h * w, c, _p(g), _p(ws), C.c_int64(need), _stream())
+        else:
+            _lib.call('mrefsr_gram_nhwc_scaled_f32', _p(f), n, h * w, c, C.c_float(scale), _p(g), _p(ws), C.c_int64(need), _stream())
     return g
+
+
+def gram_nhwc(f):
+    """f [N,H,W,C] (C a multiple of 64) -> [N,C,C] = F^T F / (C H W) per image (exact f32 MFMA products, fixed summation order)"""
+    return _gram('gram_nhwc', f, None)
+
+
+def _gram_bwd_shapes(name, f, gx, gy, df):
+    """the shapes gram_bwd_nhwc and texture_gram_bwd_nhwc share: f, df [N,H,W,C]; gx, gy [N,C,C] -> (n, h, w, c)"""
+    n, h, w, c = f.shape
+    if tuple(gx.shape) != (n, c, c) or tuple(gy.shape) != (n, c, c) or tuple(df.shape) != tuple(f.shape):
+        raise ValueError(f'{name}: inconsistent shapes')
+    return n, h, w, c
 
 
 def gram_bwd_nhwc(f, gx, gg, df, loss_weight, weight, gup=None, accumulate=False, want_amax=True):
@@ -1734,9 +1749,7 @@ def gram_bwd_nhwc(f, gx, gg, df, loss_weight, weight, gup=None, accumulate=False
     S = sgn(gx - gg) * ((gup * loss_weight) * weight) / (N C C); gx = gram_nhwc(f).  gup: a device scalar or None (= 1).
     -> max |df| [1] | None"""
     _chk('gram_bwd_nhwc', f, gx, gg, df, gup)
-    n, h, w, c = f.shape
-    if tuple(gx.shape) != (n, c, c) or tuple(gg.shape) != (n, c, c) or tuple(df.shape) != tuple(f.shape):
-        raise ValueError('gram_bwd_nhwc: inconsistent shapes')
+    n, h, w, c = _gram_bwd_shapes('gram_bwd_nhwc', f, gx, gg, df)
     amax = zeros_f32(f.device, 1) if want_amax else None
     with _timed('gram_bwd_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (2 + accumulate) * f.numel()):
         _lib.call('mrefsr_gram_bwd_nhwc_f32', _p(f), _p(gx), _p(gg), _p(df), n, h * w, c, _p(gup), C.c_float(loss_weight), C.c_float(weight),
@@ -2400,17 +2413,7 @@ def texture_scale_nhwc(f, coeff):
 
 def gram_raw_nhwc(f):
     """f [N,H,W,C] (C a multiple of 64) -> [N,C,C] = F^T F per image, not normalised: gram_nhwc's kernels with scale 1"""
-    _chk('gram_raw_nhwc', f)
-    n, h, w, c = f.shape
-    lib = _lib.load()
-    need = lib.mrefsr_gram_workspace_bytes(n, h * w, c)
-    if need < 0:
-        raise ValueError(f'gram_raw_nhwc: C={c} (a multiple of 64)')
-    ws = _scratch(f.device, need)
-    g = torch.empty((n, c, c), device=f.device, dtype=torch.float32)
-    with _timed('gram_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (f.numel() + g.numel())):
-        _lib.call('mrefsr_gram_nhwc_scaled_f32', _p(f), n, h * w, c, C.c_float(1.0), _p(g), _p(ws), C.c_int64(need), _stream())
-    return g
+    return _gram('gram_raw_nhwc', f, 1.0)
 
 
 def texture_crit(gxs, gms, divs, loss_weight):
@@ -2439,9 +2442,8 @@ def texture_gram_bwd_nhwc(fc, gx, gm, coeff, norm, df, scale, gup=None, accumula
     norm == 0.  fc = texture_scale_nhwc(f, coeff), gx = gram_raw_nhwc(fc), norm [1] the layer's entry of texture_crit's norms,
     scale = loss_weight / 3 / 4 / div, gup a device scalar or None (= 1).  -> max |df| [1] | None"""
     _chk('texture_gram_bwd_nhwc', fc, gx, gm, coeff, norm, df, gup)
-    n, h, w, c = fc.shape
-    if tuple(gx.shape) != (n, c, c) or tuple(gm.shape) != (n, c, c) or tuple(df.shape) != tuple(fc.shape) or \
-            tuple(coeff.shape) != (n, h, w) or norm.numel() != 1 or (gup is not None and gup.numel() != 1):
+    n, h, w, c = _gram_bwd_shapes('texture_gram_bwd_nhwc', fc, gx, gm, df)
+    if tuple(coeff.shape) != (n, h, w) or norm.numel() != 1 or (gup is not None and gup.numel() != 1):
         raise ValueError('texture_gram_bwd_nhwc: inconsistent shapes')
     amax = zeros_f32(fc.device, 1) if want_amax else None
     with _timed('texture_gram_bwd_nhwc', 2.0 * n * h * w * c * c, detail=True, nbytes=4.0 * (2 + accumulate) * fc.numel()):

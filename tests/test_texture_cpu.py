@@ -134,3 +134,19 @@ def test_restatement_invariants(s):
     own = torch.arange(gh * gw).view(1, gh, gw).expand(B, gh, gw)
     ident = swap(feat[:1], torch.zeros(B, gh, gw, dtype=torch.long), own, s, h, w)
     assert float(((ident - feat[0]).abs() / feat[0].abs().clamp_min(1e-30)).max()) <= 1e-6
+
+
+def test_library_refuses_a_batch_beyond_the_grid_limit_by_name():
+    """host-side check of the three Gram launchers (no GPU needed): N is gridDim.z, so N = 65536 is an invalid argument with a
+    message that names the function, not a launch failure"""
+    import ctypes
+    from mrefsr_amd import _lib
+    lib = _lib.load()
+    p, n, big = ctypes.c_void_p(16), 65536, ctypes.c_int64(1 << 50)
+    calls = ((b'gram_nhwc', lambda: lib.mrefsr_gram_nhwc_scaled_f32(p, n, 9, 64, 1.0, p, p, big, None)),
+             (b'gram_bwd_nhwc', lambda: lib.mrefsr_gram_bwd_nhwc_f32(p, p, p, p, n, 9, 64, None, 1.0, 1.0, 0, None, None)),
+             (b'texture_gram_bwd_nhwc', lambda: lib.mrefsr_texture_gram_bwd_nhwc_f32(p, p, p, p, p, None, p, n, 9, 64, 1.0, 0, None, None)))
+    for name, call in calls:
+        assert call() == -1, name                       # MREFSR_E_INVALID
+        msg = lib.mrefsr_last_error()
+        assert msg.startswith(name + b':') and b'N=65536' in msg, msg

@@ -8,14 +8,20 @@
   dcn_sample  the DCN kernel paths that sample through csrc/dcn_sample.h and the split16 list does not reach, on the lattice and
               heavy_tail fields of tests/golden/dcn_edge_cases.py (first map of each geometry).  grad_x of dcn_col2im and of
               dcn_bwd_data, a float-atomic scatter, is not part of the list: the tolerance tests hold it.
+  gram        the Gram kernels of the style term and the texture loss (csrc/percep.hip, csrc/texture.hip, whose backward bodies are
+              csrc/gram.h): gram_nhwc, gram_raw_nhwc and both backwards, fresh and accumulated onto a seeded base (texture also with
+              norm == 0), at N = 2 on C = 64, 3 x 3 (one block, 9 of 16 lanes) and C = 128, 9 x 9 (two column blocks, a pixel block
+              with a one-pixel wave and two empty ones, the forward's mirrored tile and split-K).  No float atomic: nothing is left out.
 
     python tools/kernel_bits.py --pin tests/golden/split16_bits.npz                         # regenerate a fixture (tools/README.md)
     python tools/kernel_bits.py --list dcn_sample --pin tests/golden/dcn_sample_bits.npz [--note 'which library recorded it']
+    python tools/kernel_bits.py --list gram --pin tests/golden/gram_bits.npz --note 'which library recorded it'
     python tools/kernel_bits.py [--list NAME] out.npz                                       # one run of the list
 
 --pin runs every case twice; an output that does not repeat is left out and named under the key `excluded` with the reason (at
-most two outputs of the split16 list, none of the dcn_sample list); --note TEXT is stored under the key `note`.  tests/test_split16_bits_gpu.py and tests/test_dcn_sample_bits_gpu.py run the lists on the tree's
-library and compare per output."""
+most two outputs of the split16 list, none of the dcn_sample and gram lists); --note TEXT is stored under the key `note`.
+tests/test_split16_bits_gpu.py, tests/test_dcn_sample_bits_gpu.py and tests/test_gram_bits_gpu.py run the lists on the tree's library
+and compare per output."""
 import hashlib
 import os
 import sys
@@ -193,7 +199,41 @@ def dcn_sample_cases():
     return out
 
 
-LISTS = {'split16': (cases, MAX_EXCLUDED), 'dcn_sample': (dcn_sample_cases, 0)}   # name: (case list, outputs --pin may leave out)
+GRAM_SHAPES = ((64, 3, 3), (128, 9, 9))   # (C, h, w), N = 2
+GRAM_OUTPUTS = ('gram', 'gram_raw', 'bwd_fresh', 'bwd_acc', 'texture_bwd_fresh', 'texture_bwd_acc', 'texture_bwd_norm0')
+
+
+def gram_cases():
+    """-> {case name: [outputs as numpy arrays]} (insertion order fixed).  The backwards give [df, max |df|]; texture_bwd_norm0 gives
+    [df, max |df|, the base it accumulated onto] (df has the base's bits)."""
+    import torch
+    from mrefsr_amd import hip
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
+    out = {}
+    for c, h, w in GRAM_SHAPES:
+        rng = np.random.default_rng(100 + c)
+        f, f2 = dev(mixed(rng, (2, h, w, c))), dev(mixed(rng, (2, h, w, c)))
+        base = mixed(rng, (2, h, w, c))
+        coeff, norm = dev(rng.random((2, h, w)).astype(np.float32)), dev(np.array([7.5], np.float32))
+        gup, zero = dev(np.array([0.37], np.float32)), dev(np.zeros(1, np.float32))
+        gx, gg = hip.gram_nhwc(f), hip.gram_nhwc(f2)          # two different maps: both signs, exact zeros on no diagonal
+        rx, rm = hip.gram_raw_nhwc(f), hip.gram_raw_nhwc(f2)
+
+        def bwd(run, acc):
+            df = dev(base) if acc else torch.empty_like(f)
+            amax = run(df, gup if acc else None, acc)
+            return [df.cpu().numpy(), amax.cpu().numpy()]
+
+        style = lambda df, up, acc: hip.gram_bwd_nhwc(f, gx, gg, df, 0.8, 1.5, gup=up, accumulate=acc)   # noqa: E731
+        tex = lambda nrm: lambda df, up, acc: hip.texture_gram_bwd_nhwc(f, rx, rm, coeff, nrm, df, 1e-3, gup=up, accumulate=acc)   # noqa: E731
+        res = [[gx.cpu().numpy()], [rx.cpu().numpy()], bwd(style, False), bwd(style, True), bwd(tex(norm), False), bwd(tex(norm), True),
+               bwd(tex(zero), True) + [base]]
+        for name, r in zip(GRAM_OUTPUTS, res):
+            out[f'{name}.c{c}_{h}x{w}'] = r
+    return out
+
+
+LISTS = {'split16': (cases, MAX_EXCLUDED), 'dcn_sample': (dcn_sample_cases, 0), 'gram': (gram_cases, 0)}   # name: (case list, outputs --pin may leave out)
 
 
 def flatten(res):
