@@ -7,21 +7,29 @@
 // each product is three v_mfma_f32_32x32x16_f16 with fp32 accumulation against the packed weights of conv_nhwc
 // ([cout block of 64][cin chunk of 16][tap][wh | wl | wh 2^-11][64][16], per-layer power-of-two scale).
 //
-// Block = 256 threads = 4 waves, 8 rows x 32 columns of output pixels x 128 couts; wave w owns rows 2w, 2w + 1 (two A fragments per
-// weight fragment).  Per 16-channel chunk the (10 x 34)-pixel halo tiles of up to TG raw fp32 reference maps are staged in LDS as
-// [t][channel quad][pixel][4 floats] (a lane's `ds_read_b128` walks the pixels at a 16-byte stride: conflict-free); the 3x3 shifts
-// are whole pixels, so the one tile serves the nine taps.  For a tap a lane (pixel lane & 31, channels 8 (lane >> 5) .. + 8 of the
-// chunk) reads its pixel's T references at x + d, blends them with the pixel's weights (registers; fma chain, t ascending, absent t
-// skipped: never staged, never read), splits and multiplies: no column buffer exists.  The next chunk's tiles travel in registers
-// beside the MFMAs.  Accumulation order of every output: channel chunk, (group of TG references when T > TG: u is linear in t, each
-// group's partial blend is split and multiplied on its own), tap, term -- fixed, no atomics but the range flag: bit-reproducible.
+// Block = 256 threads = 4 waves, 4 rows x 32 columns of output pixels x 128 couts; wave w owns row w (one A fragment, four cout
+// columns).  TWO blocks live on a CU (64 KB of LDS and at most 256 registers each: __launch_bounds__(256, 2)): a SIMD holds one
+// wave of each, and while one block fetches and stages its tiles the other one's blend and MFMAs run -- the tiles of a pass are in
+// registers only between their request and their LDS store, never across the tap loop.  The tap loop is straight-line code per
+// number of staged maps, pipelined by one tap: the blend of tap d + 1 issues between the MFMAs of tap d.  Per
+// 16-channel chunk the (6 x 34)-pixel halo tiles of up to TG raw fp32 reference maps are
+// staged in LDS as [t][channel quad][pixel][4 floats] (a lane's `ds_read_b128` walks the pixels at a 16-byte stride:
+// conflict-free), unscaled; the 3x3 shifts are whole pixels, so the one tile serves the nine taps.  For a tap a lane (pixel
+// lane & 31, channels 8 (lane >> 5) .. + 8 of the chunk) reads its pixel's T references at x + d, blends them with the pixel's
+// weights (registers, multiplied once by the power-of-two input scale: fma(p 2^s, v, u) has the bits of fma(p, v 2^s, u); fma
+// chain, t ascending, absent t skipped: never staged, never read), splits and multiplies: no column buffer exists.  The fp16 range
+// guard looks at the values the CENTRE tap reads: every pixel of the image is the centre of exactly one output pixel.
+// Accumulation order of every output: channel chunk, (group of TG references when T > TG: u is linear in t, each group's partial
+// blend is split and multiplied on its own), tap, term -- fixed, no atomics but the range flag: bit-reproducible.
+#include <type_traits>
+
 #include "conv_common.h"
 
 namespace {
 using namespace mrefsr_conv;
 
-constexpr int TG = 5;                       // reference maps staged per pass (5 x 21.25 KB of LDS)
-constexpr int TR = 8, TW = 32;              // output tile
+constexpr int TG = 5;                       // reference maps staged per pass (5 x 12.75 KB of LDS)
+constexpr int TR = 4, TW = 32;              // output tile
 constexpr int PH = TR + 2, PW = TW + 2, NPIX = PH * PW;
 constexpr int QPL = NPIX * 16;              // bytes of one channel quad's plane
 constexpr int TPL = 4 * QPL;                // bytes per staged map
@@ -30,6 +38,7 @@ constexpr int NPK = (NPIECE + 255) / 256;     // pieces of one staged map per th
 constexpr int NJ = 4;                       // 32-cout MFMA columns per wave (128 couts per block)
 constexpr int LDS_RAW = TG * TPL;
 constexpr int LDS_BYTES = LDS_RAW + TR * TW * 4 + 64 + 16;   // + sum_t p per pixel + the list of present references
+static_assert(2 * LDS_BYTES <= 160 * 1024, "two blocks per CU");
 
 struct BlendArgs {
     const float *refs, *prob, *bias, *in_amax;
@@ -42,7 +51,7 @@ struct BlendArgs {
 };
 
 template <int C, bool MASKED>
-__global__ __launch_bounds__(256) void mrattn_blend_conv_kernel(const BlendArgs A)
+__global__ __launch_bounds__(256, 2) void mrattn_blend_conv_kernel(const BlendArgs A)
 {
     constexpr int NCH = C / KC, COUT = 2 * C, TAPS = 9, NW = 3;
     extern __shared__ __align__(16) unsigned char smem[];
@@ -71,161 +80,197 @@ __global__ __launch_bounds__(256) void mrattn_blend_conv_kernel(const BlendArgs 
     }
     float in_s = 1.f, oscale = A.out_scale;
     amax_scale<14>(A.in_amax, in_s, oscale);   // the input tensor's maximum brought into [2^13, 2^14) by an exact power of two
+    // fp16 range guard: |v| in_s > 65000 or NaN  <=>  the bits of |v| above those of 65000 / in_s (a power of two: exact; an
+    // infinite quotient is brought back so that an infinite v still trips)
+    const unsigned int guard_bits = __float_as_uint(fminf(65000.f / in_s, 3.4028234664e38f));
     __syncthreads();
     const int total = __builtin_amdgcn_readfirstlane(tlist[16]);
     const int n_grp = (total + TG - 1) / TG, n_it = NCH * n_grp;
 
     // sum_t p_t of the wave's own pixels (present t ascending, fp32): the weight of the bias
-    const float *prow[2];
-    bool pok[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int gy = y0 + wv * 2 + m, gx = x0 + l31;
-        pok[m] = gy < H && gx < W;
-        prow[m] = A.prob + (((size_t)n * H + (gy < H ? gy : H - 1)) * W + (gx < W ? gx : W - 1)) * T;
+    const int gy_w = y0 + wv, gx_w = x0 + l31;
+    const bool pok = gy_w < H && gx_w < W;
+    const float *prow = A.prob + (((size_t)n * H + (gy_w < H ? gy_w : H - 1)) * W + (gx_w < W ? gx_w : W - 1)) * T;
+    {
         float s = 0.f;
-        for (int k = 0; k < total; ++k) s += prow[m][__builtin_amdgcn_readfirstlane(tlist[k])];
-        if (kh == 0) psum[(wv * 2 + m) * TW + l31] = pok[m] ? s : 0.f;
+        for (int k = 0; k < total; ++k) s += prow[__builtin_amdgcn_readfirstlane(tlist[k])];
+        if (kh == 0) psum[wv * TW + l31] = pok ? s : 0.f;
     }
 
-    f32x16 acc[2][NJ];
+    f32x16 acc[NJ];
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.f;
+        for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-    // the halo tiles of pass `it` (chunk it / n_grp, reference group it % n_grp) -> registers.  A thread owns the same NPK 16-byte
-    // pieces (pixel, channel quad) of every staged map: their offsets inside a map and inside an LDS tile are computed once, a map's
-    // base address is wave-uniform.  A piece outside the map is zero (the convolution's zero padding); a map that is not staged
-    // is not requested.
-    int goff[NPK], loff[NPK];
-    unsigned int in_map = 0u, in_tile = 0u;
+    // the halo tiles of pass `it` (chunk it / n_grp, reference group it % n_grp) -> registers -> LDS.  A thread owns the same NPK
+    // 16-byte pieces (pixel, channel quad) of every staged map: their offsets inside a map and inside an LDS tile are computed once,
+    // a map's base address is wave-uniform.  A piece outside the map is zero in every pass (the convolution's zero padding): it is
+    // written here, once, and its lane stays out of the passes' stores (its request reads the map's first bytes instead); a map that
+    // is not staged is not requested.
+    unsigned int goff[NPK], loff[NPK];
+    bool in_map[NPK];
 #pragma unroll
     for (int k = 0; k < NPK; ++k) {
         const int i = tid + k * 256;
         const int p = i >> 2, q = i & 3;
         const int py = p / PW, px = p - py * PW;
         const int gy = y0 + py - 1, gx = x0 + px - 1;
-        const bool tile = i < NPIECE, ok = tile && gy >= 0 && gy < H && gx >= 0 && gx < W;
-        goff[k] = ok ? (gy * W + gx) * C + 4 * q : 0;
-        loff[k] = q * QPL + p * 16;
-        in_map |= (ok ? 1u : 0u) << k, in_tile |= (tile ? 1u : 0u) << k;
+        const bool tile = i < NPIECE;
+        in_map[k] = tile && gy >= 0 && gy < H && gx >= 0 && gx < W;
+        goff[k] = in_map[k] ? (unsigned int)((gy * W + gx) * C + 4 * q) : 0u;   // floats (below 2^31: the entry checks H W 256)
+        loff[k] = tile ? q * QPL + p * 16 : 0;
+        if (tile && !in_map[k]) {
+#pragma unroll
+            for (int tg = 0; tg < TG; ++tg) *reinterpret_cast<float4 *>(smem + tg * TPL + loff[k]) = make_float4(0.f, 0.f, 0.f, 0.f);
+        }
     }
-    float4 pf[TG][NPK];
-    auto fetch = [&](const int it) {
-        const int ch = it / n_grp, g = it - ch * n_grp;
-        const int cnt = total - g * TG < TG ? total - g * TG : TG;
-#pragma unroll
-        for (int tg = 0; tg < TG; ++tg)
-            if (tg < cnt) {
-                const int t = __builtin_amdgcn_readfirstlane(tlist[g * TG + tg]);
-                const float *base = A.refs + ((size_t)t * N + n) * H * W * C + ch * KC;
-#pragma unroll
-                for (int k = 0; k < NPK; ++k)
-                    pf[tg][k] = ((in_map >> k) & 1u) ? *reinterpret_cast<const float4 *>(base + goff[k]) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-    };
-    if (n_it) fetch(0);
 
-    // B fragments of one tap: NJ columns x (wh, wl); column j sits in cout block 2 cbk + (j >> 1), rows 32 (j & 1) ..
-    const unsigned short *wlane = A.wp + (size_t)l31 * KC + kh * 8;
+    // B fragments of one tap: NJ columns x (wh, wl); column j sits in cout block 2 cbk + (j >> 1), rows 32 (j & 1) ..: a uniform
+    // base per cout block, one lane offset, the rest in the instruction
+    const unsigned int wl_off = (unsigned int)(l31 * KC + kh * 8) * 2u;
     auto bload = [&](const int lin, u32x4 (&b)[NJ][2]) {   // lin = chunk * 9 + tap
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int sp = 0; sp < 2; ++sp)
-                b[j][sp] = *reinterpret_cast<const u32x4 *>(wlane + ((((size_t)(cbk * 2 + (j >> 1)) * NCH * TAPS + lin) * NW + sp) * NB + (j & 1) * 32) * KC);
+            for (int sp = 0; sp < 2; ++sp) {
+                const unsigned short *wu = A.wp + (((size_t)(cbk * 2 + (j >> 1)) * NCH * TAPS + lin) * NW * NB) * KC;
+                b[j][sp] = *reinterpret_cast<const u32x4 *>(reinterpret_cast<const unsigned char *>(wu) + wl_off + (sp * NB + (j & 1) * 32) * KC * 2);
+            }
     };
 
-    bool bad = false;
-    float pr[2][TG];
-    for (int it = 0; it < n_it; ++it) {
-        const int ch = it / n_grp, g = it - ch * n_grp;
-        const int cnt = total - g * TG < TG ? total - g * TG : TG;
-        if (it) __syncthreads();   // the previous pass's tiles have been read
+    unsigned int worst = 0u;   // the largest |v| bits the centre tap has read
+    // The nine taps of a pass over CNT staged maps, straight-line, software-pipelined by one tap: while the 12 MFMAs of tap d run,
+    // the LDS reads of tap d + 1 are in flight and its blend (fma chain, t ascending), range guard and split issue between them, in
+    // 12 slots of one MFMA each (sched_barrier: left to itself the compiler puts the blend in front of the MFMAs).  The products of a
+    // tap, smallest first: ah wl, AL WH2 (the third weight plane wh 2^-11 is derived, not loaded), ah wh.
+    const unsigned char *sp0 = smem + (2 * kh) * QPL + (wv * PW + l31) * 16;
+    auto taps = [&](auto cnt_c, const int cnt, const int ch, u32x4 (&b)[2][NJ][2], const float (&pr)[TG]) {
+        constexpr int CNT = decltype(cnt_c)::value ? decltype(cnt_c)::value : TG;   // (0: the count is `cnt`, known at run time only)
+        constexpr bool FIXED = decltype(cnt_c)::value != 0;
+        f32x4 s[CNT][2];
+        float u[8];
+        u32x4 ah, al, nh, nl, w2[NJ];
+        auto rd = [&](const int tap) {
+            const unsigned char *sp = sp0 + (((tap * 11) >> 5) * (PW - 3) + tap) * 16;   // (dy PW + dx) pixels, tap = 3 dy + dx
 #pragma unroll
-        for (int tg = 0; tg < TG; ++tg)
-            if (tg < cnt) {
-#pragma unroll
-                for (int k = 0; k < NPK; ++k) {
-                    float4 v = pf[tg][k];
-                    v.x *= in_s, v.y *= in_s, v.z *= in_s, v.w *= in_s;
-                    bad = bad || !(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))) <= 65000.f);   // fp16 range guard
-                    if ((in_tile >> k) & 1u) *reinterpret_cast<float4 *>(smem + tg * TPL + loff[k]) = v;
+            for (int k = 0; k < CNT; ++k)
+                if (FIXED || k < cnt) {
+                    s[k][0] = *reinterpret_cast<const f32x4 *>(sp + k * TPL);
+                    s[k][1] = *reinterpret_cast<const f32x4 *>(sp + k * TPL + QPL);
                 }
+        };
+        auto chain = [&](const int k, const bool centre) {
+            if (!FIXED && k >= cnt) return;
+            const float w = pr[k];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) u[c] = fmaf(w, s[k][0][c], k ? u[c] : 0.f), u[4 + c] = fmaf(w, s[k][1][c], k ? u[4 + c] : 0.f);
+            if (centre) {   // the centre tap reads the wave's own output pixels
+                const unsigned int m = 0x7fffffffu;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    worst = max(worst, max(max(__float_as_uint(s[k][h][0]) & m, __float_as_uint(s[k][h][1]) & m),
+                                           max(__float_as_uint(s[k][h][2]) & m, __float_as_uint(s[k][h][3]) & m)));
             }
-        __syncthreads();
-        if (it + 1 < n_it) fetch(it + 1);   // the next pass's tiles travel in registers beside the MFMAs
-        if (n_grp > 1 || it == 0) {
+        };
+        auto split = [&](const int c) {   // a = ah + al, al kept as fp16(al * 2^11): split16.h
+            unsigned int h, l;
+            split_scaled(u[2 * c], u[2 * c + 1], h, l);
+            nh[c] = h, nl[c] = l;
+        };
+        rd(0);
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
+        for (int k = 0; k < CNT; ++k) chain(k, false);
 #pragma unroll
-                for (int k = 0; k < TG; ++k) pr[m][k] = (k < cnt && pok[m]) ? prow[m][__builtin_amdgcn_readfirstlane(tlist[g * TG + k])] : 0.f;
-        }
-        u32x4 b[NJ][2];
-        bload(ch * TAPS, b);
-#pragma nounroll
+        for (int c = 0; c < 4; ++c) split(c);
+        ah = nh, al = nl;
+#pragma unroll
         for (int tap = 0; tap < TAPS; ++tap) {
-            const int dy = (tap * 11) >> 5, dx = tap - 3 * dy;
-            u32x4 bn[NJ][2];
-            if (tap + 1 < TAPS) bload(ch * TAPS + tap + 1, bn);   // the weight fragments run one tap ahead
+            const bool more = tap + 1 < TAPS;
+            u32x4 (&bc)[NJ][2] = b[tap & 1];
+            if (more) {
+                bload(ch * TAPS + tap + 1, b[(tap + 1) & 1]);
+                rd(tap + 1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const unsigned char *sp = smem + (2 * kh) * QPL + ((wv * 2 + m + dy) * PW + l31 + dx) * 16;
-                float u[8];
-#pragma unroll
-                for (int c = 0; c < 8; ++c) u[c] = 0.f;
-#pragma unroll
-                for (int k = 0; k < TG; ++k)   // fma chain, t ascending over the staged (= present) maps
-                    if (k < cnt) {
-                        const float4 s0 = *reinterpret_cast<const float4 *>(sp + k * TPL);
-                        const float4 s1 = *reinterpret_cast<const float4 *>(sp + k * TPL + QPL);
-                        const float w = pr[m][k];
-                        u[0] = fmaf(w, s0.x, u[0]), u[1] = fmaf(w, s0.y, u[1]), u[2] = fmaf(w, s0.z, u[2]), u[3] = fmaf(w, s0.w, u[3]);
-                        u[4] = fmaf(w, s1.x, u[4]), u[5] = fmaf(w, s1.y, u[5]), u[6] = fmaf(w, s1.z, u[6]), u[7] = fmaf(w, s1.w, u[7]);
-                    }
-                // a = ah + al, al kept as fp16(al * 2^11): split16.h
-                u32x4 ah, al;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    unsigned int h, l;
-                    split_scaled(u[2 * c], u[2 * c + 1], h, l);
-                    ah[c] = h, al[c] = l;
+            for (int sl = 0; sl < 12; ++sl) {
+                const int j = sl & 3;
+                if (sl < 4) acc[j] = mma16(ah, bc[j][1], acc[j]);
+                else if (sl < 8) acc[j] = mma16(al, w2[j], acc[j]);
+                else acc[j] = mma16(ah, bc[j][0], acc[j]);
+                if (sl < 2) w2[2 * sl] = scale_wh(bc[2 * sl][0]), w2[2 * sl + 1] = scale_wh(bc[2 * sl + 1][0]);
+                if (more) {
+                    if (sl >= 2 && sl - 2 < CNT) chain(sl - 2, tap + 1 == 4);
+                    if (sl >= 7 && sl < 11) split(sl - 7);
                 }
-                // partial products smallest first: ah wl, AL WH2 (the third weight plane wh 2^-11 is derived, not loaded), ah wh
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[m][j] = mma16(ah, b[j][1], acc[m][j]);
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[m][j] = mma16(al, scale_wh(b[j][0]), acc[m][j]);
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[m][j] = mma16(ah, b[j][0], acc[m][j]);
+                __builtin_amdgcn_sched_barrier(0);
             }
-            if (tap + 1 < TAPS) {
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) b[j][0] = bn[j][0], b[j][1] = bn[j][1];
-            }
+            if (more) ah = nh, al = nl;
         }
+    };
+    float pr[TG];
+    // the passes, specialised on the number of staged maps where every pass of the block has the same (at most TG present references)
+    auto passes = [&](auto cnt_c) {
+        for (int it = 0; it < n_it; ++it) {
+            const int ch = it / n_grp, g = it - ch * n_grp;
+            const int cnt = total - g * TG < TG ? total - g * TG : TG;
+            {
+                f32x4 pf[TG][NPK];
+#pragma unroll
+                for (int tg = 0; tg < TG; ++tg)
+                    if (tg < cnt) {
+                        const int t = __builtin_amdgcn_readfirstlane(tlist[g * TG + tg]);
+                        const float *base = A.refs + ((size_t)t * N + n) * H * W * C + ch * KC;
+#pragma unroll
+                        for (int k = 0; k < NPK; ++k) pf[tg][k] = *reinterpret_cast<const f32x4 *>(base + goff[k]);
+                    } else {   // (defined on every path: no register lives from one pass into the next)
+#pragma unroll
+                        for (int k = 0; k < NPK; ++k) pf[tg][k] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    }
+                if (it) __syncthreads();   // the previous pass's tiles have been read
+#pragma unroll
+                for (int tg = 0; tg < TG; ++tg)
+                    if (tg < cnt) {
+#pragma unroll
+                        for (int k = 0; k < NPK; ++k)
+                            if (in_map[k]) *reinterpret_cast<f32x4 *>(smem + tg * TPL + loff[k]) = pf[tg][k];
+                    }
+            }
+            __builtin_amdgcn_sched_barrier(0);   // the tiles leave the registers before the weight fragments claim theirs
+            if (n_grp > 1 || it == 0) {
+#pragma unroll
+                for (int k = 0; k < TG; ++k) pr[k] = (k < cnt && pok) ? prow[__builtin_amdgcn_readfirstlane(tlist[g * TG + k])] * in_s : 0.f;
+            }
+            u32x4 b[2][NJ][2];   // the weight fragments run one tap ahead: even taps in [0], odd taps in [1]
+            bload(ch * TAPS, b[0]);
+            __syncthreads();
+            taps(cnt_c, cnt, ch, b, pr);
+        }
+    };
+    switch (total <= TG ? total : 0) {
+    case 1: passes(std::integral_constant<int, 1>{}); break;
+    case 2: passes(std::integral_constant<int, 2>{}); break;
+    case 3: passes(std::integral_constant<int, 3>{}); break;
+    case 4: passes(std::integral_constant<int, 4>{}); break;
+    case 5: passes(std::integral_constant<int, 5>{}); break;
+    default: passes(std::integral_constant<int, 0>{}); break;
     }
-    if (bad && A.range_flag) atomicOr(A.range_flag, 1);
+    if (worst > guard_bits && A.range_flag) atomicOr(A.range_flag, 1);
     __syncthreads();   // psum of every row is written (a block without a present reference ran no pass)
 
-    // MFMA result: a lane holds cout 32 j + (lane & 31) of pixels x = (e & 3) + 8 (e >> 2) + 4 kh of row m: a store instruction
+    // MFMA result: a lane holds cout 32 j + (lane & 31) of pixels x = (e & 3) + 8 (e >> 2) + 4 kh of the row: a store instruction
     // writes two pixels' 128 contiguous bytes
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int gy = y0 + wv * 2 + m;
-        if (gy >= H) continue;
+    if (gy_w < H) {
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             const int co = cbk * (NJ * 32) + j * 32 + l31;
             const float bv = A.bias ? A.bias[co] : 0.f;
-            float *orow = A.out + (((size_t)n * H + gy) * W) * COUT + co;
+            float *orow = A.out + (((size_t)n * H + gy_w) * W) * COUT + co;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int x = (e & 3) + 8 * (e >> 2) + 4 * kh, gx = x0 + x;
-                if (gx < W) orow[(size_t)gx * COUT] = acc[m][j][e] * oscale + bv * psum[(wv * 2 + m) * TW + x];
+                if (gx < W) orow[(size_t)gx * COUT] = acc[j][e] * oscale + bv * psum[wv * TW + x];
             }
         }
     }

@@ -12,15 +12,20 @@
               csrc/gram.h): gram_nhwc, gram_raw_nhwc and both backwards, fresh and accumulated onto a seeded base (texture also with
               norm == 0), at N = 2 on C = 64, 3 x 3 (one block, 9 of 16 lanes) and C = 128, 9 x 9 (two column blocks, a pixel block
               with a one-pixel wave and two empty ones, the forward's mirrored tile and split-K).  No float atomic: nothing is left out.
+  blend_conv  mrattn_blend_conv_kernel (csrc/mrattn_conv.hip) at C = 64, 128 and 256, N = 2, on maps of 4 x 4 (smaller than any
+              tile), 12 x 20 (ragged both ways) and 19 x 70 (several tile rows and columns, a tile count that is no multiple of 8):
+              T = 5 without a mask, T = 5 with valid_bits that leave two references to sample 0 and none to sample 1, and at C = 64
+              T = 7 (reference groups of 5 + 2).  References of mixed magnitudes; every case as plain / amax / amax0.  Nothing is left out.
 
     python tools/kernel_bits.py --pin tests/golden/split16_bits.npz                         # regenerate a fixture (tools/README.md)
     python tools/kernel_bits.py --list dcn_sample --pin tests/golden/dcn_sample_bits.npz [--note 'which library recorded it']
     python tools/kernel_bits.py --list gram --pin tests/golden/gram_bits.npz --note 'which library recorded it'
+    python tools/kernel_bits.py --list blend_conv --pin tests/golden/blend_conv_bits.npz --note 'which library recorded it'
     python tools/kernel_bits.py [--list NAME] out.npz                                       # one run of the list
 
 --pin runs every case twice; an output that does not repeat is left out and named under the key `excluded` with the reason (at
-most two outputs of the split16 list, none of the dcn_sample and gram lists); --note TEXT is stored under the key `note`.
-tests/test_split16_bits_gpu.py, tests/test_dcn_sample_bits_gpu.py and tests/test_gram_bits_gpu.py run the lists on the tree's library
+most two outputs of the split16 list, none of the dcn_sample, gram and blend_conv lists); --note TEXT is stored under the key `note`.
+tests/test_split16_bits_gpu.py, tests/test_dcn_sample_bits_gpu.py, tests/test_gram_bits_gpu.py and tests/test_blend_conv_bits_gpu.py run the lists on the tree's library
 and compare per output."""
 import hashlib
 import os
@@ -233,7 +238,56 @@ def gram_cases():
     return out
 
 
-LISTS = {'split16': (cases, MAX_EXCLUDED), 'dcn_sample': (dcn_sample_cases, 0), 'gram': (gram_cases, 0)}   # name: (case list, outputs --pin may leave out)
+BLEND_MAPS = ((4, 4), (12, 20), (19, 70))   # (h, w), N = 2
+BLEND_MASK = (0b10010, 0)                   # valid_bits of the masked cases: references 1 and 4 for sample 0, none for sample 1
+
+
+def blend_inputs(seed, c, t, h, w, n=2):
+    """seeded CPU inputs of one blend_conv case: refs [t*n,h,w,c] of mixed magnitudes and weights prob [n,h,w,t] >= 0 whose sum
+    over t stays below 1 (adds and one division per element: the same bits from every numpy)"""
+    rng = np.random.default_rng(seed)
+    refs = mixed(rng, (t * n, h, w, c))
+    r = rng.random((n, h, w, t), dtype=np.float32) + np.float32(0.01)
+    tot = np.zeros((n, h, w), np.float32)
+    for k in range(t):
+        tot = tot + r[..., k]
+    return refs, (r / (tot * np.float32(1.01))[..., None]).astype(np.float32)
+
+
+def blend_weights(c):
+    """seeded conv_ass weight [2c,c,3,3] and bias [2c] of the blend_conv list"""
+    rng = np.random.default_rng(300 + c)
+    return (rng.standard_normal((2 * c, c, 3, 3)) / (9 * c) ** 0.5).astype(np.float32), rng.standard_normal(2 * c).astype(np.float32)
+
+
+def blend_conv_cases():
+    """-> {case name: [output]} (insertion order fixed).  A masked case multiplies prob by the mask (an absent reference's weight is
+    exactly 0, as mrattn_prob_nhwc leaves it); its sample 1 has no reference at all."""
+    import torch
+    from mrefsr_amd import hip
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()   # noqa: E731
+    out = {}
+    for c in (64, 128, 256):
+        wt, bias = blend_weights(c)
+        pk, bias_d = hip.conv_pack_weight(dev(wt), 16), dev(bias)
+        for h, w in BLEND_MAPS:
+            for tag, t, masked in (('t5', 5, False), ('t5_masked', 5, True)) + ((('t7', 7, False),) if c == 64 else ()):
+                refs, prob = blend_inputs(1000 * c + 10 * h + t + masked, c, t, h, w)
+                vb = None
+                if masked:
+                    present = np.array([[(m >> k) & 1 for k in range(t)] for m in BLEND_MASK], np.float32)
+                    prob = prob * present[:, None, None, :]
+                    vb = dev(np.array(BLEND_MASK, np.int32))
+                refs_d, prob_d = dev(refs), dev(prob)
+                for var, am in (('plain', None), ('amax', dev(np.array([np.abs(refs).max()], np.float32))), ('amax0', dev(np.zeros(1, np.float32)))):
+                    y = hip.mrattn_blend_conv(refs_d, prob_d, pk, bias_d, t, vb, in_amax=am)
+                    out[f'c{c}_{h}x{w}_{tag}.{var}'] = [y.cpu().numpy()]
+    hip.conv_range_tripped(reset=True)   # (values of 1e3 are far inside the fp16 range; the flag is not part of the bits)
+    return out
+
+
+# name: (case list, outputs --pin may leave out)
+LISTS = {'split16': (cases, MAX_EXCLUDED), 'dcn_sample': (dcn_sample_cases, 0), 'gram': (gram_cases, 0), 'blend_conv': (blend_conv_cases, 0)}
 
 
 def flatten(res):
