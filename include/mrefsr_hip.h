@@ -1009,6 +1009,34 @@ int mrefsr_disc_augment_adj_f32(const float *g, const float *fpar, const int *ip
 int mrefsr_dihedral_expand_f32(const float *src, float *dst, int outer, int inner, int C, int H, int W, int tr, mrefsr_stream_t stream);
 int mrefsr_dihedral_merge_f32(const float *a, const float *b, float *out, int N, int C, int H, int W, mrefsr_stream_t stream);
 
+/* ---- colour correction of test() outputs towards the LQ image (csrc/color_fix.hip; val.color_fix) ----------------------------------
+ * No reference counterpart: the "color fix" of StableSR (Wang et al., IJCV 2024).  x the output, s the colour source, out, all fp32
+ * [B][C][H][W] at any 4-byte boundary, every (b, c) plane on its own; out must not alias x or s, which are only read.  sizes: NULL
+ * (whole planes) or [B][2] int32 (h_b, w_b) in DEVICE memory, read by the kernels: the top-left h_b x w_b rectangle of sample b is
+ * the image -- statistics and filters see it alone, with its border as the image border --, and every pixel outside it keeps x's
+ * bits.  The caller checks 1 <= h_b <= H, 1 <= w_b <= W (the kernels clamp the values into that range, so no access leaves the
+ * buffers).  Nothing is clamped to [0, 1].  16-byte accesses when the pointers are 16-byte aligned and W % 4 == 0, 4-byte accesses
+ * otherwise, the same bits either way.  The same bits from call to call.
+ *
+ * mrefsr_color_fix_wavelet_f32: out = x + low_L(s - x), L = levels in 1..5; low_0(v) = v, low_i(v) = low_{i-1}(v) filtered with
+ *   [1,2,1]^T [1,2,1] / 16 at dilation 2^(i-1), reads clamped to the rectangle at every stage (replicate padding).  One launch, one
+ *   block per 64 x 64 tile of a plane; the tile and a halo of 2^L - 1 pixels of s - x in LDS, the 2 L separable passes there in
+ *   place, each  0.25f * (a + c) + 0.5f * b  with two fp32 roundings; where the filtered difference is 0 the output is x's bits (so
+ *   s bit-equal to x returns x).  |out - exact| <= (4 L + 1) 2^-24 max |s - x| + 2^-24 |exact|.
+ *   H, W >= 1, H W <= 2^30, at most 2^31 - 1 tiles; MREFSR_E_INVALID for a null pointer, a non-positive dimension or levels
+ *   outside 1..5.
+ * mrefsr_color_fix_adain_f32: out = (x - mu_x) (sigma_s / sigma_x) + mu_s; mu the mean and sigma = sqrt(var + 1e-5), var the
+ *   unbiased variance, over the plane's rectangle (one pixel has none: MREFSR_E_INVALID for H W = 1 without sizes; with sizes the
+ *   caller checks).  Two launches: per-block (count, mean, M2) of x and of s in double and, by the block that arrives last, their
+ *   merge per plane in ascending block order into `workspace` (mrefsr_color_fix_adain_workspace_bytes(B, C, H, W) bytes, 8-byte
+ *   aligned, the caller's; -1 for a shape outside B C in 1..65535, H W in 1..2^30); then the apply pass, in double with ONE
+ *   rounding to fp32.  `ticket`: one zeroed word that every call leaves zero again.  No float atomics, no readback. */
+int mrefsr_color_fix_wavelet_f32(const float *x, const float *s, float *out, int B, int C, int H, int W, const int32_t *sizes, int levels,
+                                 mrefsr_stream_t stream);
+int64_t mrefsr_color_fix_adain_workspace_bytes(int B, int C, int H, int W);
+int mrefsr_color_fix_adain_f32(const float *x, const float *s, float *out, int B, int C, int H, int W, const int32_t *sizes, void *workspace,
+                               int64_t workspace_bytes, uint32_t *ticket, mrefsr_stream_t stream);
+
 /* ---- the texture loss of the training step and its swapped reference maps (csrc/texture.hip; train.texture_opt) ---------------------
  * TextureLoss.forward(x, maps, weights) of basicsr/models/losses.py:430-532 with use_weights and a tensor `weights`; the maps and
  * weights themselves have no reference counterpart (the reference model reads them, nothing sets them): DESIGN 3.13.

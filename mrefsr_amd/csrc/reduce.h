@@ -107,6 +107,7 @@ __device__ __forceinline__ double block_sum_by_waves(double v, double *wsum)
 // The last block puts the ticket word back to 0, so a launch needs no memset in front of it and can be replayed from a graph.
 // `lds_flag`: one word of the block's LDS that nothing else uses across this call.
 __device__ __forceinline__ void store_partial(float *p, const float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void store_partial(double *p, const double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __device__ __forceinline__ bool last_block_by_ticket(unsigned int *ticket, const unsigned int nblocks, int *lds_flag)
 {

@@ -1246,6 +1246,65 @@ def dihedral_merge(a, b):
     return out
 
 
+# ------------------------------------------------------------------ colour correction of test() outputs (csrc/color_fix.hip)
+COLOR_FIX_MAX_LEVELS = 5
+
+
+def _color_fix_args(name, x, s, sizes, min_pixels=1):
+    """the checks of both colour-fix calls, all on the host before anything is launched -> (B, C, H, W, the [B,2] int32 device table
+    or None).  sizes: None or B pairs (h_b, w_b) of ints with 1 <= h_b <= H, 1 <= w_b <= W"""
+    _chk(name, x, s)
+    if x.dim() != 4 or x.numel() == 0 or s.shape != x.shape:
+        raise ValueError(f'{name}: two non-empty [B,C,H,W] tensors of one shape expected, got {tuple(x.shape)} and {tuple(s.shape)}')
+    b, c, h, w = x.shape
+    rects = [(h, w)] * b
+    table = None
+    if sizes is not None:
+        rects = [tuple(int(v) for v in tuple(r)[:2]) for r in sizes]
+        if len(rects) != b or any(len(r) != 2 for r in rects):
+            raise ValueError(f'{name}: sizes: {b} pairs (h_b, w_b) expected for a batch of {b}, got {sizes!r}')
+        for hb, wb in rects:
+            if not (1 <= hb <= h and 1 <= wb <= w):
+                raise ValueError(f'{name}: sizes: ({hb}, {wb}) is not inside the {h} x {w} planes (1 <= h_b <= H, 1 <= w_b <= W)')
+    for hb, wb in rects:
+        if hb * wb < min_pixels:
+            raise ValueError(f'{name}: a valid rectangle of {hb} x {wb} = {hb * wb} pixel(s) has no unbiased variance '
+                             f'(at least {min_pixels} pixels needed)')
+    if sizes is not None:
+        table = torch.tensor(rects, dtype=torch.int32).to(x.device)
+    return b, c, h, w, table
+
+
+def color_fix_wavelet(x, s, sizes=None, levels=5):
+    """x (the output), s (the colour source) [B,C,H,W] contiguous fp32 -> x + low_L(s - x) = high_L(x) + low_L(s), L = levels in
+    1..5: low_i = low_{i-1} filtered with [1,2,1]^T [1,2,1] / 16 at dilation 2^(i-1), replicate padding at every stage
+    (color_fix.wavelet_color_fix_torch states it).  sizes: None or B pairs (h_b, w_b): the top-left rectangle that is the image of
+    sample b; outside it the result is x's bits.  One launch; the inputs are only read; the same bits from call to call"""
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 1 <= levels <= COLOR_FIX_MAX_LEVELS:
+        raise ValueError(f'color_fix_wavelet: levels {levels!r} is not an int in 1..{COLOR_FIX_MAX_LEVELS}')
+    b, c, h, w, table = _color_fix_args('color_fix_wavelet', x, s, sizes)
+    out = torch.empty_like(x)
+    with _timed('color_fix_wavelet', detail=True, nbytes=12.0 * x.numel()):
+        _lib.call('mrefsr_color_fix_wavelet_f32', _p(x), _p(s), _p(out), b, c, h, w, _p(table), levels, _stream())
+    return out
+
+
+def color_fix_adain(x, s, sizes=None):
+    """x, s [B,C,H,W] contiguous fp32 -> (x - mu_x) (sigma_s / sigma_x) + mu_s per (b, c) plane, mu the mean and sigma = sqrt(var +
+    1e-5) with the unbiased variance over the plane's valid rectangle (color_fix.adain_color_fix_torch states it); sizes as in
+    color_fix_wavelet; a rectangle of one pixel is a ValueError.  Two launches, statistics and the expression in double, one
+    rounding to fp32; fixed summation order, no atomics, nothing read back"""
+    b, c, h, w, table = _color_fix_args('color_fix_adain', x, s, sizes, min_pixels=2)
+    need = _lib.load().mrefsr_color_fix_adain_workspace_bytes(b, c, h, w)
+    if need <= 0:
+        raise ValueError(f'color_fix_adain: unsupported shape {tuple(x.shape)} (B C <= 65535, H W <= 2^30)')
+    ws, ticket = _det_scratch(x.device, need)
+    out = torch.empty_like(x)
+    with _timed('color_fix_adain', detail=True, nbytes=16.0 * x.numel()):
+        _lib.call('mrefsr_color_fix_adain_f32', _p(x), _p(s), _p(out), b, c, h, w, _p(table), _p(ws), C.c_int64(need), _p(ticket), _stream())
+    return out
+
+
 def act_bwd_nhwc(g_out, out, act, slope=0.0, slope_ptr=None, want_bias=True, want_amax=False):
     """Backward of a fused convolution epilogue on [..., C] contiguous tensors: g_pre = g_out * act'(out) with act 0 none,
     1 LeakyReLU(slope) (0 = ReLU), 2 PReLU(slope_ptr).  Returns (g_pre [..., ld] with ld = C rounded up to 4 (extra channels

@@ -49,6 +49,7 @@ import torch
 from torch.nn.parallel import DistributedDataParallel
 
 from ..archs import build_network
+from ..color_fix import color_fix, parse_color_fix
 from ..utils.registry import MODEL_REGISTRY
 
 
@@ -97,6 +98,7 @@ class MultiRefRestorationModel:
         if opt.get('num_gpu', 1) == 0:
             raise NotImplementedError('mrefsr_amd has no CPU path: num_gpu must be >= 1')
         self.check_self_ensemble(opt.get('val'))   # (a bad value is refused before anything is built; test() reads the option)
+        self.color_fix_cfg = parse_color_fix(opt.get('val'))   # None, or the checked val.color_fix configuration (refused likewise)
         self.ref_select = self.check_ref_select(opt)   # None, or (top_k, score) of the ref_select option
         if self.ref_select is not None and not self._REF_POOLS:
             raise ValueError(f'ref_select: {type(self).__name__} takes one reference per sample; reference pools are '
@@ -668,6 +670,7 @@ class MultiRefRestorationModel:
         present candidates on the device (_forward_pool) and restores from those."""
         self.ref_pool = self.ref_selection = self.ref_scores = None
         self.gt_usm = None
+        self.valid_sizes = self._valid_sizes_of(data)
         if self._synthesise:   # opt['degradation'], training batches only: img_in_lq and img_in_up are made from img_in
             data = self._degrade(data)
         if self.ref_select is not None and data['img_ref_list'].shape[1] > self.ref_select[0]:
@@ -1074,12 +1077,45 @@ class MultiRefRestorationModel:
     def test(self):
         run = self._test_self_ensemble if self.check_self_ensemble(self.opt.get('val')) else self._test
         if self.net_g_ema is None:
-            return run()
-        net_g, self.net_g = self.net_g, self.net_g_ema   # sr_model.py:121-125: the EMA weights are the ones tested (and shipped)
-        try:
             run()
-        finally:
-            self.net_g = net_g
+        else:
+            net_g, self.net_g = self.net_g, self.net_g_ema   # sr_model.py:121-125: the EMA weights are the ones tested (and shipped)
+            try:
+                run()
+            finally:
+                self.net_g = net_g
+        self._apply_color_fix()
+
+    # ------------------------------------------------------------------ val.color_fix: the output's colours from the LQ image
+    _color_fix_logged = False
+    color_fix_cfg = valid_sizes = None   # (set by __init__ / feed_data)
+
+    @staticmethod
+    def _valid_sizes_of(data):
+        """the un-padded image sizes of a fed batch: with a truthy ``padding`` and an ``original_size`` -- (h, w[, ...]), each an int
+        or one value per sample, as MultiRefCUFEDSet reports them and a DataLoader collates them -- B pairs [h_b, w_b]; else None"""
+        pad = data.get('padding')
+        if pad is None or data.get('original_size') is None or not bool(torch.as_tensor(pad).any()):
+            return None
+        b = data['img_in_lq'].shape[0]
+        h, w = (torch.as_tensor(v).reshape(-1).tolist() for v in tuple(data['original_size'])[:2])
+        if len(h) not in (1, b) or len(w) not in (1, b):
+            raise ValueError(f'original_size: (h, w) with one value or {b} values each expected for a batch of {b}, got '
+                             f'{data["original_size"]!r}')
+        return [[int(h[i % len(h)]), int(w[i % len(w)])] for i in range(b)]
+
+    def _apply_color_fix(self):
+        """val.color_fix (color_fix.py): the last step of test(), once, on the final output -- behind the range fallback, the
+        packed-weights re-run, the merge of val.self_ensemble and a replayed hipGraph (it is not part of the capture) -- with
+        match_img_in, the bicubic-upsampled LQ, as the colour source and the batch's un-padded sizes as the valid rectangles.
+        Without the option nothing is launched and the output keeps its bits."""
+        if self.color_fix_cfg is None:
+            return
+        if not MultiRefRestorationModel._color_fix_logged:
+            MultiRefRestorationModel._color_fix_logged = True
+            logging.getLogger('basicsr').info(f'val.color_fix: test() takes the colours of its output from the LQ image ({self.color_fix_cfg})')
+        with torch.no_grad():
+            self.output = color_fix(self.output, self.match_img_in, self.color_fix_cfg, self.valid_sizes)
 
     def _test(self):
         self.net_g.eval()
@@ -1428,6 +1464,7 @@ class RefRestorationModel(MultiRefRestorationModel):
     _REF_POOLS = False   # (the ref_select option is refused at construction)
 
     def feed_data(self, data):
+        self.valid_sizes = self._valid_sizes_of(data)
         self.img_in_lq = data['img_in_lq'].to(self.device, non_blocking=True)
         self.img_ref = data['img_ref'].to(self.device, non_blocking=True)
         self.num_refs = 1
