@@ -1037,6 +1037,33 @@ int64_t mrefsr_color_fix_adain_workspace_bytes(int B, int C, int H, int W);
 int mrefsr_color_fix_adain_f32(const float *x, const float *s, float *out, int B, int C, int H, int W, const int32_t *sizes, void *workspace,
                                int64_t workspace_bytes, uint32_t *ticket, mrefsr_stream_t stream);
 
+/* ---- homography views of image batches and the matcher's score against a known homography (csrc/warp.hip; mrefsr_amd/views.py) ---
+ * The reference makes its views on the host (image_pair_generation_perspective of basicsr/data/ref_cufed_dataset.py:190-272:
+ * cv2.warpPerspective, INTER_CUBIC); bit parity with OpenCV is not claimed and its uint8 round trip is not reproduced.
+ *
+ * mrefsr_warp_persp_f32: x [N][C][H][W] fp32 -> y [N][C][Ho][Wo], y not x.  S [N][9] DOUBLE in device memory, row-major: the SAMPLING
+ *   matrix of image n, destination -> source, in integer pixel coordinates (pixel (x, y) is at (x, y)) -- cv2.warpPerspective's
+ *   dst(x, y) = src(M^-1 (x, y, 1)) with S = M^-1.  (u, v, t) = S (xo, yo, 1), sx = u / t, sy = v / t in double; floor and the
+ *   fraction in double, the fraction rounded once to fp32.  interp 1: the 4 x 4 cubic convolution with A = -0.75 (OpenCV's and
+ *   torch.grid_sample's kernel); interp 0: bilinear.  Weights and the separable sum (along x, then along y) in fp32 in the order
+ *   csrc/warp.hip spells out; a fraction of 0 gives the weights exactly [0, 1, 0, 0], of 1 exactly [0, 0, 1, 0].  Taps outside the
+ *   image contribute 0.  The output is exactly 0 where t is not > 0, where a coordinate is not finite and where no tap is inside
+ *   the image.  clamp 1: the result clamped to [0, 1]; 0: not.  For finite inputs the identity returns the input's bits (-0 as +0),
+ *   an integer translation shifted bits and exact zeros, a zero image zeros.  |y - exact| <= 70 2^-24 max |x|, bilinear 7.  One
+ *   launch; coordinate and weights once per pixel for all C channels; no atomics, no readback; the same bits from call to call.
+ *   MREFSR_E_INVALID for a null pointer, y == x, a non-positive size, an interp or clamp that is not 0 or 1, H W or Ho Wo > 2^30, Ho > 524280, N > 65535.
+ * mrefsr_match_stats_f64: max_idx [N][h-2][w-2] int64, the matcher's output (my = idx / (w - 2), mx = idx % (w - 2), as
+ *   mrefsr_offsets_from_idx_f32 decodes it); M [N][9] double in device memory maps a QUERY position to its true REFERENCE position
+ *   in feature coordinates; thr [T] doubles in HOST memory, T in 0..4; stats [N][2 + T] double in device memory.  For the query patch
+ *   with top-left (qx, qy): centre c = (qx + 1, qy + 1), true top-left t = M c - 1 (M's third coordinate at c must be > 0); it
+ *   counts if (qx, qy) and t both satisfy margin <= x <= x_hi - margin and margin <= y <= y_hi - margin (x_hi <= w - 3, y_hi <=
+ *   h - 3: the last top-left of the valid rectangle).  stats[n] = (count, sum of |(mx, my) - t|_2, per threshold the number of
+ *   counted queries with an error <= thr).  All in double; one block per n, the fixed halving tree of reduce.h; no atomics. */
+int mrefsr_warp_persp_f32(const float *x, const double *S, float *y, int N, int C, int H, int W, int Ho, int Wo, int interp, int clamp,
+                          mrefsr_stream_t stream);
+int mrefsr_match_stats_f64(const int64_t *max_idx, const double *M, const double *thr, double *stats, int N, int h, int w, int y_hi, int x_hi,
+                           int margin, int T, mrefsr_stream_t stream);
+
 /* ---- the texture loss of the training step and its swapped reference maps (csrc/texture.hip; train.texture_opt) ---------------------
  * TextureLoss.forward(x, maps, weights) of basicsr/models/losses.py:430-532 with use_weights and a tensor `weights`; the maps and
  * weights themselves have no reference counterpart (the reference model reads them, nothing sets them): DESIGN 3.13.

@@ -212,6 +212,8 @@ SIGNATURES = {
     'mrefsr_color_fix_wavelet_f32': (_i, [_vp, _vp, _vp] + [_i] * 4 + [_vp, _i, _vp]),
     'mrefsr_color_fix_adain_workspace_bytes': (_i64, [_i] * 4),
     'mrefsr_color_fix_adain_f32': (_i, [_vp, _vp, _vp] + [_i] * 4 + [_vp, _vp, _i64, _vp, _vp]),
+    'mrefsr_warp_persp_f32': (_i, [_vp, _vp, _vp] + [_i] * 8 + [_vp]),
+    'mrefsr_match_stats_f64': (_i, [_vp] * 4 + [_i] * 7 + [_vp]),
     'mrefsr_texture_select_f32': (_i, [_vp] * 6 + [_i, _i, _i64, _vp]),
     'mrefsr_texture_swap_nhwc_f32': (_i, [_vp] * 4 + [_i] * 6 + [_vp]),
     'mrefsr_texture_coeff_f32': (_i, [_vp] * 4 + [_i, _i, _i, _vp]),

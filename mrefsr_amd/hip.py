@@ -1305,6 +1305,74 @@ def color_fix_adain(x, s, sizes=None):
     return out
 
 
+# ------------------------------------------------------------------ homography views and the matcher probe (csrc/warp.hip)
+WARP_INTERP = {'bilinear': 0, 'bicubic': 1}
+MATCH_STATS_MAX_THRESHOLDS = 4
+
+
+def _homographies(name, m, n, device):
+    """m: one 3 x 3 matrix or n of them ([3,3], [n,3,3] or [n,9]; a tensor or anything torch.as_tensor takes) -> [n,9] float64 on
+    ``device`` (a host value is one small upload)"""
+    m = torch.as_tensor(m)
+    if not (m.is_floating_point() or m.dtype in (torch.int32, torch.int64)):
+        raise TypeError(f'{name}: a real matrix expected, got {m.dtype}')
+    if m.dim() == 2 and tuple(m.shape) == (3, 3):
+        m = m.expand(n, 3, 3)
+    if tuple(m.shape) not in ((n, 3, 3), (n, 9)):
+        raise ValueError(f'{name}: one 3 x 3 matrix or {n} of them ([{n},3,3] / [{n},9]) expected for a batch of {n}, got {tuple(m.shape)}')
+    return m.reshape(n, 9).to(device=device, dtype=torch.float64).contiguous()
+
+
+def warp_perspective(x, S, out_size=None, interp='bicubic', clamp=False):
+    """x [N,C,H,W] contiguous fp32 -> [N,C,Ho,Wo] (out_size = (Ho, Wo), default (H, W)): the projective view of every image under
+    its SAMPLING matrix S[n] (destination -> source, integer pixel coordinates: out(xo, yo) = x at S (xo, yo, 1), the M^-1 of
+    cv2.warpPerspective; views.py makes such matrices).  S: one 3 x 3 matrix or N of them, float64; a host value is uploaded (one
+    small copy).  interp 'bicubic' (cubic convolution, A = -0.75) or 'bilinear'; taps outside the image are 0; clamp: the result
+    clamped to [0, 1].  One launch; no backward (an input-side operator).  csrc/warp.hip states the arithmetic"""
+    _chk('warp_perspective', x)
+    if x.dim() != 4 or x.numel() == 0:
+        raise ValueError(f'warp_perspective: a non-empty [N,C,H,W] tensor expected, got {tuple(x.shape)}')
+    if interp not in WARP_INTERP:
+        raise ValueError(f'warp_perspective: interp {interp!r} is not one of {", ".join(WARP_INTERP)}')
+    if not isinstance(clamp, bool):
+        raise ValueError(f'warp_perspective: clamp {clamp!r} is not true or false')
+    n, c, h, w = x.shape
+    ho, wo = (h, w) if out_size is None else (int(v) for v in out_size)
+    if ho < 1 or wo < 1:
+        raise ValueError(f'warp_perspective: out_size {out_size!r} is not a pair of positive sizes')
+    s = _homographies('warp_perspective', S, n, x.device)
+    out = torch.empty((n, c, ho, wo), device=x.device, dtype=torch.float32)
+    with _timed('warp_perspective', detail=True, nbytes=4.0 * (x.numel() + out.numel())):
+        _lib.call('mrefsr_warp_persp_f32', _p(x), _p(s), _p(out), n, c, h, w, ho, wo, WARP_INTERP[interp], int(clamp), _stream())
+    return out
+
+
+def match_stats(max_idx, M, thresholds=(1.0, 2.0), margin=0, valid_hw=None):
+    """max_idx [N,h-2,w-2] int64 (the matcher's indices of N query / reference pairs) against the homographies M[n] (one 3 x 3 or N of
+    them, float64) that map a query position to its true reference position in feature coordinates (views.to_feature_coords) ->
+    [N, 2 + T] float64 on the device: per pair the number of counted queries, the sum of their end-point errors in feature pixels
+    and, per threshold, the number of them with an error <= it.  A query counts if its top-left and its true target's both lie
+    ``margin`` inside the valid map; valid_hw = (vh, vw) <= (h, w): the valid part of the feature maps (a zero-padded image),
+    default the whole maps.  One launch, everything in double in a fixed order, nothing read back"""
+    _chk('match_stats', max_idx, dtype=torch.int64)
+    if max_idx.dim() != 3 or max_idx.numel() == 0:
+        raise ValueError(f'match_stats: a non-empty [N,h-2,w-2] index tensor expected, got {tuple(max_idx.shape)}')
+    n, h, w = max_idx.shape[0], max_idx.shape[1] + 2, max_idx.shape[2] + 2
+    thr = [float(t) for t in thresholds]
+    if len(thr) > MATCH_STATS_MAX_THRESHOLDS or any(not t >= 0 for t in thr):
+        raise ValueError(f'match_stats: thresholds {thresholds!r}: at most {MATCH_STATS_MAX_THRESHOLDS} non-negative numbers expected')
+    if isinstance(margin, bool) or not isinstance(margin, int) or margin < 0:
+        raise ValueError(f'match_stats: margin {margin!r} is not a non-negative int')
+    vh, vw = (h, w) if valid_hw is None else (int(v) for v in valid_hw)
+    if not (3 <= vh <= h and 3 <= vw <= w):
+        raise ValueError(f'match_stats: valid_hw ({vh}, {vw}) is not inside the {h} x {w} maps (3 <= vh <= h, 3 <= vw <= w)')
+    m = _homographies('match_stats', M, n, max_idx.device)
+    stats = torch.empty((n, 2 + len(thr)), device=max_idx.device, dtype=torch.float64)
+    _lib.call('mrefsr_match_stats_f64', _p(max_idx), _p(m), (C.c_double * max(len(thr), 1))(*thr), _p(stats), n, h, w, vh - 3, vw - 3, margin,
+              len(thr), _stream())
+    return stats
+
+
 def act_bwd_nhwc(g_out, out, act, slope=0.0, slope_ptr=None, want_bias=True, want_amax=False):
     """Backward of a fused convolution epilogue on [..., C] contiguous tensors: g_pre = g_out * act'(out) with act 0 none,
     1 LeakyReLU(slope) (0 = ReLU), 2 PReLU(slope_ptr).  Returns (g_pre [..., ld] with ld = C rounded up to 4 (extra channels

@@ -26,6 +26,8 @@ those of basicsr/losses/losses.py:284-318, 391-405 and basicsr/models/stylegan2_
 written (stylegan2_model.py:135-143 rescales them by every / (every + 1): left to the configuration).  train.d_augment puts
 DiffAugment / ADA's differentiable colour, translation, cutout and flip operators in front of every discriminator call, on the kernels
 of csrc/disc_augment.hip (_setup_d_augment, _d; no counterpart in the reference; a bad option is a ValueError that names it).
+train.ref_augment, val.ref_perturb and val.match_probe put homography views of the references (views.py, csrc/warp.hip; the view
+generator of ref_cufed_dataset.py:190-272 on the device) into feed_data and validation (_setup_ref_views, _match_probe_stats).
 Refused, not silently skipped: texture_opt without use_weights: true (the reference cannot evaluate it either) and other
 discriminators (NotImplementedError); gan_type without network_d and the
 reverse, r1_reg_weight without network_d (NotImplementedError); an r1_reg_weight that is not a finite number of at least 0, a
@@ -49,6 +51,7 @@ import torch
 from torch.nn.parallel import DistributedDataParallel
 
 from ..archs import build_network
+from .. import views
 from ..color_fix import color_fix, parse_color_fix
 from ..utils.registry import MODEL_REGISTRY
 
@@ -99,6 +102,7 @@ class MultiRefRestorationModel:
             raise NotImplementedError('mrefsr_amd has no CPU path: num_gpu must be >= 1')
         self.check_self_ensemble(opt.get('val'))   # (a bad value is refused before anything is built; test() reads the option)
         self.color_fix_cfg = parse_color_fix(opt.get('val'))   # None, or the checked val.color_fix configuration (refused likewise)
+        self._setup_ref_views(opt)   # train.ref_augment, val.ref_perturb, val.match_probe (refused likewise)
         self.ref_select = self.check_ref_select(opt)   # None, or (top_k, score) of the ref_select option
         if self.ref_select is not None and not self._REF_POOLS:
             raise ValueError(f'ref_select: {type(self).__name__} takes one reference per sample; reference pools are '
@@ -671,10 +675,12 @@ class MultiRefRestorationModel:
         self.ref_pool = self.ref_selection = self.ref_scores = None
         self.gt_usm = None
         self.valid_sizes = self._valid_sizes_of(data)
+        self._gt_fed = 'img_in' in data   # (self.gt may be an earlier batch's)
         if self._synthesise:   # opt['degradation'], training batches only: img_in_lq and img_in_up are made from img_in
             data = self._degrade(data)
         if self.ref_select is not None and data['img_ref_list'].shape[1] > self.ref_select[0]:
             self._feed_pool(data, self.ref_select[0])   # (checked on the host before anything is launched)
+            self.ref_pool['stack'] = self._ref_views(self.ref_pool['stack'], self.ref_pool['n'])
             self.img_in_lq = data['img_in_lq'].to(self.device, non_blocking=True)
             if 'img_in' in data:
                 self.gt = data['img_in'].to(self.device, non_blocking=True)
@@ -693,7 +699,7 @@ class MultiRefRestorationModel:
             valid = ((self.ref_valid_bits[:, None] >> torch.arange(self.num_refs, device=self.device, dtype=torch.int32)) & 1).bool()
             refs = torch.where(valid[:, :, None, None, None], refs, refs.new_zeros(()))
         # k-major stack [K*B,3,H,W]; the reference's list(torch.unbind(dim=1)) is its K slices
-        self.img_ref_stack = refs.transpose(0, 1).reshape(-1, *refs.shape[2:]).contiguous()
+        self.img_ref_stack = self._ref_views(refs.transpose(0, 1).reshape(-1, *refs.shape[2:]).contiguous(), self.num_refs)
         self.img_ref_list = list(self.img_ref_stack.view(self.num_refs, -1, *refs.shape[2:]).unbind(0))
         if 'img_in' in data:
             self.gt = data['img_in'].to(self.device, non_blocking=True)
@@ -1117,6 +1123,145 @@ class MultiRefRestorationModel:
         with torch.no_grad():
             self.output = color_fix(self.output, self.match_img_in, self.color_fix_cfg, self.valid_sizes)
 
+    # ------------------------------------------------------------------ homography views of the references (views.py, csrc/warp.hip)
+    ref_augment = ref_perturb_cfg = match_probe_cfg = _ref_aug_gen = None   # (the state of a model without the options)
+    _validating = False   # inside validation: training-side options are off, validation-side options on
+    _view_index = 0       # images fed since validation began: what the seeded views of val.ref_perturb / val.match_probe count
+    _view_base = 0        # ... and the index of the fed batch's first image
+    _gt_fed = False       # the fed batch had an img_in (feed_data)
+
+    def _setup_ref_views(self, opt):
+        """Three options on hip.warp_perspective; each is parsed here, at construction (views.parse_* name what is refused), and
+        without them no launch of feed_data, test(), validation or the training step changes.
+
+        train.ref_augment {p: 0.5, perturb: [5, 20], window: null, interp: bicubic}: in feed_data of TRAINING batches only
+        (validation leaves it out, the way it puts _synthesise back), each (sample, reference) image is replaced with probability
+        p by its view under a random corner homography (views.sample_corner_homographies: the reference's
+        image_pair_generation_perspective), clamped to [0, 1].  It acts on the k-major stack, or on the pool stack under ref_select,
+        after absent references have been zeroed (a zero image stays zero); one launch and one small upload per batch, none when no
+        image was chosen.  The matrices come from a host generator seeded from manual_seed or, without one, from torch's global
+        generator, as _d_aug_gen is (views.sample_ref_augment states the order of draws).  The input, the GT and img_in_up are
+        untouched.
+
+        val.ref_perturb {scale: 1.0, rotate: 0} or {perturb: [lo, hi], seed: 0, window: null} (either with interp): the references
+        of every validation / test batch (a model that is not training, or validation of one that is) are replaced in feed_data,
+        before anything else runs, by their view scaled and rotated about the image centre (views.similarity; degrees) or under a
+        corner homography that depends on (seed, image index, k) only -- image index counted from 0 since validation began, 0 for
+        the first image of a batch fed outside validation.  Clamped to [0, 1].  Metrics and logs are the usual ones.
+
+        val.match_probe {perturb: [5, 20], window: null, thresholds: [1, 2], margin: 3, source: gt | lq_up, seed: 0, interp: bicubic}
+        (or true): see _match_probe_stats.
+
+        No claim about image or matching quality is made: only random-init weights were available offline."""
+        self.ref_perturb_cfg = views.parse_ref_perturb(opt.get('val'))
+        self.match_probe_cfg = views.parse_match_probe(opt.get('val'))
+        self.ref_augment = views.parse_ref_augment(opt.get('train'))   # (refused in a test-only configuration too ...)
+        if not opt.get('is_train'):
+            self.ref_augment = None   # (... and used by a training model only)
+        self._ref_aug_gen = None
+        if self.ref_augment is not None:
+            seed = opt.get('manual_seed')
+            if seed is None:   # (from torch's global generator: reproducible behind torch.manual_seed)
+                seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+            self._ref_aug_gen = torch.Generator().manual_seed(seed)
+
+    def _ref_views(self, stack, k):
+        """feed_data's reference stack [k*B,3,H,W] (k-major) -> the stack the batch is run on: under train.ref_augment (training
+        batches) or val.ref_perturb (validation / test batches) its views, else the stack itself.  Also notes the batch's place in
+        the count of validation images."""
+        from .. import hip
+        n, _, h, w = stack.shape
+        b = n // k
+        training = bool(self.is_train) and not self._validating
+        self._view_base = self._view_index
+        if self._validating:
+            self._view_index += b
+        if training:
+            if self.ref_augment is None:
+                return stack
+            cfg = self.ref_augment
+            sampling = views.sample_ref_augment(n, h, w, cfg, self._ref_aug_gen)
+            if sampling is None:
+                return stack
+        else:
+            if self.ref_perturb_cfg is None:
+                return stack
+            cfg = self.ref_perturb_cfg
+            if cfg['kind'] == 'similarity':
+                sampling = views.similarity(h, w, cfg['scale'], cfg['rotate'])
+            else:   # image b of the batch: the k matrices of its own generator; entry k' * B + b of the k-major stack
+                per_image = [views.indexed_corner_homographies(cfg['seed'], self._view_base + i, k, h, w, cfg['perturb'], cfg['window'])
+                             for i in range(b)]
+                sampling = torch.stack(per_image, dim=1).reshape(n, 3, 3)
+        with torch.no_grad():
+            return hip.warp_perspective(stack.contiguous(), sampling, interp=cfg['interp'], clamp=True)
+
+    def _extract_pair(self, image1, images2):
+        """the frozen extractor's two stacks: image1 [B,...] through the LR stack, images2 [B,...] through the reference stack"""
+        if hasattr(self.net_extractor, 'forward_stacked'):
+            return self.net_extractor.forward_stacked(image1, images2)
+        f = self.net_extractor(image1, images2)
+        return f['dense_features1'], f['dense_features2']
+
+    def _match_probe_stats(self, cfg, sampling=None):
+        """val.match_probe: the extractor + top-1 matcher pair against a known answer on the fed batch -> [B, 2 + T] float64 ON THE
+        DEVICE (hip.match_stats: count, sum of end-point errors, hits per threshold); nothing is read back.
+        A view V = warp(source, S) is made of every image (clamped to [0, 1]): source the GT, or with source: lq_up match_img_in,
+        the bicubic-upsampled LQ; S from ``sampling`` (one 3 x 3 sampling matrix or B of them) or, without it, the corner
+        homography of (seed, image index) (views.indexed_corner_homographies: checkpoints are compared on the same views).  The
+        extractor's LR stack runs on match_img_in, its reference stack on V, the matcher on both, and the indices are scored
+        against views.to_feature_coords(S) with the batch's un-padded sizes (padding / original_size) bounding the valid maps.
+        The passes do not read the fp16-range flag: match_probe() reads it and repeats the probe on the range-free kernels,
+        validation reads it once behind its loop and reports NaN (_probe_out_of_range)."""
+        from .. import hip
+        src = self.match_img_in if cfg['source'] == 'lq_up' else (self.gt if self._gt_fed else None)
+        if src is None:
+            raise ValueError('val.match_probe.source: gt, but the fed batch has no img_in (use source: lq_up)')
+        b, _, h, w = src.shape
+        if tuple(self.match_img_in.shape[2:]) != (h, w):
+            raise ValueError(f'val.match_probe: the source is {h} x {w}, match_img_in {tuple(self.match_img_in.shape[2:])}')
+        if sampling is None:
+            sampling = torch.stack([views.indexed_corner_homographies(cfg['seed'], self._view_base + i, 1, h, w, cfg['perturb'],
+                                                                      cfg['window'])[0] for i in range(b)])
+        sampling = torch.as_tensor(sampling, dtype=torch.float64).expand(b, 3, 3)
+        to_ref = views.to_feature_coords(sampling)
+        for vh, vw in self.valid_sizes or []:
+            if vh // 4 < 3 or vw // 4 < 3:
+                raise ValueError(f'val.match_probe: the un-padded image of {vh} x {vw} has no 3 x 3 patch of conv3_1 cells '
+                                 '(at least 12 x 12 pixels needed)')
+        hip.amax_pool_reset()
+        with torch.no_grad():
+            view = hip.warp_perspective(src.contiguous(), sampling, interp=cfg['interp'], clamp=True)
+            f1, f2 = self._extract_pair(self.match_img_in, view)
+            idx = self.net_map.match(f1, f2)[0].contiguous()
+            if self.valid_sizes is None:
+                return hip.match_stats(idx, to_ref, cfg['thresholds'], cfg['margin'])
+            # (a padded batch: each image against its own valid rectangle, in conv3_1 cells)
+            return torch.cat([hip.match_stats(idx[i:i + 1], to_ref[i:i + 1], cfg['thresholds'], cfg['margin'], (vh // 4, vw // 4))
+                              for i, (vh, vw) in enumerate(self.valid_sizes)])
+
+    def match_probe(self, sampling=None):
+        """one probe on the fed batch with the val.match_probe configuration (its defaults without the option) -> {count, match_epe,
+        match_pck<t> per threshold}: the number of counted queries, their mean end-point error in feature pixels and the fraction of
+        them within each threshold.  ``sampling``: explicit sampling matrices instead of the seeded ones (_match_probe_stats)"""
+        cfg = self.match_probe_cfg if self.match_probe_cfg is not None else views.parse_match_probe({'match_probe': True})
+        stats = self._match_probe_stats(cfg, sampling)
+        again = self._rerun_range_free('match_probe', lambda: self._match_probe_stats(cfg, sampling), reset_scales=False)
+        stats = stats if again is None else again
+        return views.probe_numbers(stats.sum(0).cpu().tolist(), cfg['thresholds'])
+
+    def _probe_out_of_range(self, probe):
+        """behind validation's loop: the one read of the fp16-range flag for all of the probe's passes.  Set (by a probe, or by one
+        that the next image's test() then took for its own and answered with a re-run): some probe ran on features outside the range
+        of the split kernels, the pooled numbers are not to be trusted and become NaN; said so in the log.  Nothing is re-run."""
+        from .. import hip
+        if not hip.conv_range_tripped():
+            return probe
+        logging.getLogger('basicsr').warning(
+            'val.match_probe: an activation of the extractor left the fp16 range of the split kernels during a probe; the probe is '
+            'not re-run inside validation, its numbers are reported as NaN (model.match_probe() on the batch repeats it range-free)')
+        return {k: (v if k == 'count' else float('nan')) for k, v in probe.items()}
+
     def _test(self):
         self.net_g.eval()
         with torch.no_grad():
@@ -1281,14 +1426,17 @@ class MultiRefRestorationModel:
     def nondist_validation(self, dataloader, current_iter, tb_logger, save_img):
         """validation never synthesises its input (realesrgan_model.py:187-191): the flag is put back behind it"""
         synthesise, self._synthesise = self._synthesise, False
+        self._validating, self._view_index = True, 0   # (train.ref_augment is left out likewise; the views count images from 0)
         try:
             return self._nondist_validation(dataloader, current_iter, tb_logger, save_img)
         finally:
             self._synthesise = synthesise
+            self._validating, self._view_index = False, 0
 
     def _nondist_validation(self, dataloader, current_iter, tb_logger, save_img):
         """per image: feed_data -> test -> uint8 image -> crop the dataset's zero padding -> [PNG] -> PSNR (RGB), PSNR (Y),
-        SSIM (Y) with crop_border from the options (ref :324-386); with val.msssim also five-level MS-SSIM (Y)
+        SSIM (Y) with crop_border from the options (ref :324-386); with val.match_probe also the matcher's score on a known view of
+        every image (_match_probe_stats; logged, sent to tb_logger and returned as match_epe / match_pck<t>); with val.msssim also five-level MS-SSIM (Y)
         (metrics.calculate_msssim; logged as MS-SSIM_Y, tb scalar and result key msssim_y).  save_img writes
         path.visualization/<img>/<img>_<iter>.png while training, path.visualization/<dataset>/<img>_<name>[_suffix].png when testing.
         With val.metrics_on_device the metrics run on the GPU and only their scalars (and, for save_img, the image) come back; an
@@ -1299,11 +1447,15 @@ class MultiRefRestorationModel:
         on_device = self._metrics_on_device()
         want_msssim = bool((self.opt.get('val') or {}).get('msssim'))
         psnrs, psnrs_y, ssims_y, msssims_y = [], [], [], []
+        probe_acc = None   # val.match_probe: the summed statistics, on the device until the loop is over
         for idx, val_data in enumerate(dataloader):
             lq_path = val_data.get('lq_path', [f'{idx:04d}'])
             img_name = os.path.splitext(os.path.basename(lq_path[0] if isinstance(lq_path, (list, tuple)) else lq_path))[0]
             self.feed_data(val_data)
             self.test()
+            if self.match_probe_cfg is not None:
+                stats = self._match_probe_stats(self.match_probe_cfg).sum(0)
+                probe_acc = stats if probe_acc is None else probe_acc + stats
             cb = self.opt['crop_border']
             size = None
             if 'padding' in val_data and val_data['padding']:
@@ -1360,6 +1512,15 @@ class MultiRefRestorationModel:
         result = dict(psnr=avg_psnr, psnr_y=avg_psnr_y, ssim_y=avg_ssim_y)
         if want_msssim:
             result['msssim_y'] = avg_msssim_y
+        if probe_acc is not None:   # the one readback of the probe
+            probe = self._probe_out_of_range(views.probe_numbers(probe_acc.cpu().tolist(), self.match_probe_cfg['thresholds']))
+            count = probe.pop('count')
+            logger.info(f'# Validation {dataset_name} # match probe over {count} queries # '
+                        + ' # '.join(f'{k}: {v:.4e}' for k, v in probe.items()) + '.')
+            if tb_logger:
+                for k, v in probe.items():
+                    tb_logger.add_scalar(k, v, current_iter)
+            result.update(probe)
         return result
 
     def save(self, epoch, current_iter):
@@ -1465,8 +1626,9 @@ class RefRestorationModel(MultiRefRestorationModel):
 
     def feed_data(self, data):
         self.valid_sizes = self._valid_sizes_of(data)
+        self._gt_fed = 'img_in' in data   # (self.gt may be an earlier batch's)
         self.img_in_lq = data['img_in_lq'].to(self.device, non_blocking=True)
-        self.img_ref = data['img_ref'].to(self.device, non_blocking=True)
+        self.img_ref = self._ref_views(data['img_ref'].to(self.device, non_blocking=True), 1)
         self.num_refs = 1
         self.img_ref_stack = self.img_ref
         self.img_ref_list = [self.img_ref]
