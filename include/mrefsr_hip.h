@@ -428,6 +428,16 @@ typedef struct mrefsr_conv_pack_job {
     float wscale;
 } mrefsr_conv_pack_job;
 int mrefsr_conv_pack_weights_multi_f32(const mrefsr_conv_pack_job *jobs, int n_jobs, int *range_flag, mrefsr_stream_t stream);
+/* A 1x1 convolution that follows a 3x3 one with nothing non-linear between them, as ONE 3x3 convolution (csrc/conv_fold.hip) --
+ * spatial_attn_add2 and the reference half of feat_fusion at inference (ref_mrapa_restoration_arch.py:338-347: the 1x1 acts after
+ * the zero padding, so the composition is exact):
+ *   out_w[o][i][tap] = float( sum_m w1x1[o * ld_1x1 + cin_offset + m] * w3x3[m][i][tap] )        [Cout][Cin][3][3]
+ *   out_b[o]         = float( b1x1[o] + sum_m w1x1[o * ld_1x1 + cin_offset + m] * b3x3[m] )      (out_b, b1x1, b3x3 may be NULL)
+ * w1x1 is [Cout][ld_1x1] (columns cin_offset .. cin_offset + Cmid are used), w3x3 [Cmid][Cin][3][3].  The sums run in double in
+ * ascending m (exact products, one rounding per element): two calls give the same bits.  The result is an ordinary weight: it goes
+ * through mrefsr_conv_pack_weight_f32 for any `terms`.  Done once per weight version, not per step. */
+int mrefsr_conv_compose_1x1_3x3_f32(const float *w1x1, int64_t ld_1x1, int cin_offset, const float *w3x3, const float *b3x3,
+                                    const float *b1x1, float *out_w, float *out_b, int Cout, int Cmid, int Cin, mrefsr_stream_t stream);
 int mrefsr_conv_nhwc_f32(const mrefsr_conv_desc *d, const float *x1, const float *x2, const void *packed,
                          const float *bias, const float *slope_ptr, const float *pre, const float *residual,
                          float *out, int *range_flag, mrefsr_stream_t stream);
@@ -484,7 +494,9 @@ int mrefsr_conv_dynagg_f32(const mrefsr_conv_desc *d, const float *x, const void
 
 
 /* Spatial-attention modulation of MRAPAFusion (ref_mrapa_restoration_arch.py:343-345) in one pass:
- * mul_inout[i] = refs[i] * sigmoid(mul_inout[i]) * 2 + add[i]; n a multiple of 4, any (common) layout. */
+ * mul_inout[i] = refs[i] * sigmoid(mul_inout[i]) * 2 + add[i]; n a multiple of 4, any (common) layout.  The f32 entry takes
+ * add = NULL: refs[i] * sigmoid(mul_inout[i]) * 2, the same expression without its last add (the addend then reaches feat_fusion
+ * as the `pre` of its launch, mrefsr_conv_compose_1x1_3x3_f32). */
 int mrefsr_attn_modulate_f32(const float *refs, float *mul_inout, const float *add, int64_t n,
                              mrefsr_stream_t stream);
 int mrefsr_attn_modulate_bf16(const void *refs, void *mul_inout, const void *add, int64_t n, mrefsr_stream_t stream);

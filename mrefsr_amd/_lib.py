@@ -102,6 +102,7 @@ SIGNATURES = {
     'mrefsr_conv_pack_weight_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
     'mrefsr_conv_pack_weight_view_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i64, _i64, _i, _vp]),
     'mrefsr_conv_pack_weights_multi_f32': (_i, [_vp, _i, _vp, _vp]),
+    'mrefsr_conv_compose_1x1_3x3_f32': (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     'mrefsr_act_bwd_blocks': (_i, [_i64, _i]),
     'mrefsr_act_bwd_nhwc_f32': (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _i, _f, _vp, _vp, _vp]),
     'mrefsr_act_bwd_det_workspace_bytes': (_i64, [_i64, _i]),

@@ -220,20 +220,40 @@ def conv(mod, x1, x2=None, slope=None, prelu=None, pre=None, residual=None, epil
         if prelu.weight.numel() != 1:
             raise NotImplementedError('nhwc.conv: per-channel PReLU')
         slope_ptr = prelu.weight.detach()
-    terms = 6 if (TERMS == 16 and hip.is_range_free()) else TERMS   # re-run of a batch that left the fp16 range
-    if terms == 16 and mod.kernel_size[0] == 3 and x1.dtype == torch.float32:
-        nimg = max(x1.shape[0], x2.shape[0] if x2 is not None else 0, residual.shape[0] if residual is not None else 0)
-        cin = x1.shape[3] + (x2.shape[3] if x2 is not None else 0)
-        if wino_applies(nimg, x1.shape[1], x1.shape[2], cin, mod.out_channels, max(x1.stride(2), x2.stride(2) if x2 is not None else 0), epilogue):
-            terms = 17
+    terms = launch_terms(mod.kernel_size[0], mod.out_channels, x1, x2, residual, epilogue)
     packed = hip.packed_weight(mod.weight, cin_slice, terms)
     b = mod.bias.detach() if (bias and mod.bias is not None) else None
+    return _launch(packed, b, mod.out_channels, mod.kernel_size[0], x1, x2, slope, slope_ptr, pre, residual, epilogue, out, amax)
+
+
+def launch_terms(ksize, cout, x1, x2=None, residual=None, epilogue=0):
+    """the descriptor terms of an inference launch over cat([x1, x2]): TERMS, 6 in the re-run of a batch that left the fp16 range,
+    17 (Winograd) where wino_applies()"""
+    terms = 6 if (TERMS == 16 and hip.is_range_free()) else TERMS
+    if terms == 16 and ksize == 3 and x1.dtype == torch.float32:
+        nimg = max(x1.shape[0], x2.shape[0] if x2 is not None else 0, residual.shape[0] if residual is not None else 0)
+        cin = x1.shape[3] + (x2.shape[3] if x2 is not None else 0)
+        if wino_applies(nimg, x1.shape[1], x1.shape[2], cin, cout, max(x1.stride(2), x2.stride(2) if x2 is not None else 0), epilogue):
+            terms = 17
+    return terms
+
+
+def conv_packed(packed, bias, cout, ksize, x1, x2=None, slope=None, pre=None, amax=True):
+    """conv() for weights that are no module's own: ``packed`` a ready hip.PackedWeight for launch_terms() of this launch (a derived
+    entry of hip.packed_fold), ``bias`` a [cout] device tensor or None.  Inference only."""
+    if packed.terms != launch_terms(ksize, cout, x1, x2):
+        raise ValueError(f'nhwc.conv_packed: weights packed with terms {packed.terms}, the launch takes {launch_terms(ksize, cout, x1, x2)}')
+    return _launch(packed, bias, cout, ksize, x1, x2, slope, None, pre, None, 0, None, amax)
+
+
+def _launch(packed, b, cout, ksize, x1, x2, slope, slope_ptr, pre, residual, epilogue, out, amax):
+    terms = packed.terms
     # every fp32-equivalent launch measures max |out| in its epilogue (a zeroed device word of hip's pool); the Winograd launch that
     # reads the tensor takes that word as its input scale
     ring = hip.amax_ring(x1.device) if (amax and terms in (16, 17) and x1.dtype == torch.float32 and WINO_INSCALE) else None
     slot = None if ring is None else ring.slot()
-    y = hip.conv_nhwc(x1, packed, b, mod.out_channels, mod.kernel_size[0], x2=x2, pre=pre, residual=residual,
-                      act=slope is not None or prelu is not None, slope=0.0 if slope is None else slope,
+    y = hip.conv_nhwc(x1, packed, b, cout, ksize, x2=x2, pre=pre, residual=residual,
+                      act=slope is not None or slope_ptr is not None, slope=0.0 if slope is None else slope,
                       slope_ptr=slope_ptr, epilogue=epilogue, out=out,
                       in_amax=wino_in_amax(x1, x2) if (terms == 17 and WINO_INSCALE) else None, out_amax=slot)
     return y if slot is None else attach_amax(y, slot, ring)

@@ -464,10 +464,38 @@ class MRAPAFusion(nn.Module):
         return (self.BLEND_FIRST and fold and nhwc.TERMS == 16 and not hip.is_range_free() and refs.dtype == torch.float32
                 and refs.shape[3] in (64, 128, 256) and self.conv_ass.out_channels == 2 * refs.shape[3] and t <= 16)
 
+    # True: inference folds spatial_attn_add2 into feat_fusion (one 3x3 convolution 2C -> nf with weights composed once per weight
+    # version, hip.packed_fold); False: add2 as a convolution 2C -> 2C of its own -- the form training and the bf16 arithmetic keep,
+    # and the one tests compare against
+    FOLD_ADD2 = True
+
+    def fold_add2(self, train, target):
+        """the folded form serves this call: fp32 inference on the engine, feat_fusion a 1x1 over cat[target, add2's channels],
+        add2 a 3x3 'same' convolution"""
+        ff, add2 = self.feat_fusion, self.spatial_attn_add2
+        return (self.FOLD_ADD2 and not train and not nhwc.BF16 and target.dtype == torch.float32
+                and nhwc._conv_ok(ff) and ff.kernel_size == (1, 1) and nhwc._conv_ok(add2) and add2.kernel_size == (3, 3)
+                and ff.in_channels == target.shape[3] + add2.out_channels)
+
     def _modulate_fuse(self, target, r, train):
         """spatial attention and fusion of :337-348 on the assembled reference features r"""
         attn = nhwc.conv(self.spatial_attn, target, x2=r, slope=0.1)
         attn_mul = nhwc.conv(self.spatial_attn_mul2, nhwc.conv(self.spatial_attn_mul1, attn, slope=0.1), amax=False)   # (modulation terms)
+        if self.fold_add2(train, target):
+            # feat_fusion is linear and pointwise and nothing non-linear stands between it and add2:
+            #   Wf . cat[target, r * 2 sigmoid(mul) + add2(a1)] = Wf . cat[target, r * 2 sigmoid(mul)] + (Wf_r o add2)(a1),
+            # the last term a 3x3 convolution 2C -> nf (exact, padding included: the 1x1 acts after it) that enters the 1x1 launch
+            # as its `pre`; attn_add is never formed (DESIGN 3.21)
+            ff, add2 = self.feat_fusion, self.spatial_attn_add2
+            a1 = nhwc.conv(self.spatial_attn_add1, attn, slope=0.1)
+            del attn
+            w, b = hip.packed_fold(add2.weight, add2.bias, ff.weight, ff.bias, target.shape[3],
+                                   nhwc.launch_terms(3, ff.out_channels, a1))
+            pre = nhwc.conv_packed(w, None, ff.out_channels, 3, a1, amax=False)
+            del a1
+            r = hip.attn_modulate_(r, attn_mul)   # refs * sigmoid(mul) * 2, in place on attn_mul
+            return nhwc.conv_packed(hip.packed_weight(ff.weight, None, nhwc.launch_terms(1, ff.out_channels, target, r)), b,
+                                    ff.out_channels, 1, target, x2=r, slope=0.1, pre=pre)
         attn_add = nhwc.conv(self.spatial_attn_add2, nhwc.conv(self.spatial_attn_add1, attn, slope=0.1), amax=False)
         # refs * sigmoid(mul) * 2 + add, one pass
         r = nhwc_train.modulate(r, attn_mul, attn_add) if train else nhwc.rnd_(hip.attn_modulate_(r, attn_mul, attn_add))

@@ -8,6 +8,7 @@ basicsr/ops/dcn/deform_conv.py:61-62).
 import contextlib
 import ctypes as C
 import math
+import weakref
 
 import torch
 
@@ -886,6 +887,12 @@ class _Fingerprint:
     __slots__ = ('ref', 'stamp', 'numel', 'sum', 'row', 'done')
 
 
+class _Fold:
+    """a derived entry of _PackedWeights: the sources (weak; None where a bias is absent) with their stamps, the packed composed weight
+    and the composed bias"""
+    __slots__ = ('refs', 'stamps', 'packed', 'bias')
+
+
 class _PackedWeights:
     """Packed copies of the inference path's convolution weights by (id(parameter), slice, terms), each good for one param_stamp():
     re-packed when the parameter is modified through autograd-visible ops, re-allocated or replaced.  Unlike the training tables,
@@ -897,6 +904,7 @@ class _PackedWeights:
 
     def __init__(self):
         self.copies, self.prints = {}, {}        # (id(weight), slice, terms) -> _Packed; id(weight) -> _Fingerprint
+        self.folds = {}                          # (ids of w3x3, b3x3, w1x1, b1x1, cin_offset, terms) -> _Fold (get_fold)
         self.order, self.dirty = [], True        # the device table over self.prints, rebuilt lazily: its rows, out of date
         self.table = self.sums = self.done = self.ref = None
         self.stale, self.epoch = False, 0
@@ -914,14 +922,44 @@ class _PackedWeights:
         if cin_slice is not None:
             w = w[:, cin_slice[0]:cin_slice[1]]
         hit = self.copies[key] = _Packed(weight, conv_pack_weight(w.contiguous(), terms), param_stamp(weight))
+        self._fingerprint(weight, hit.ref, hit.stamp)
+        return hit.packed
+
+    def _fingerprint(self, weight, ref, stamp):
+        """take ``weight``'s checksum on the stream that has just read it, as what verify() compares with from now on"""
         fp = self.prints[id(weight)] = _Fingerprint()
-        fp.ref, fp.stamp, fp.numel, dev = hit.ref, hit.stamp, weight.numel(), weight.device
+        fp.ref, fp.stamp, fp.numel, dev = ref, stamp, weight.numel(), weight.device
         fp.row = torch.tensor([fp.stamp.ptr, fp.numel], dtype=torch.int64).to(dev)
         fp.sum = torch.zeros(1, dtype=torch.int64, device=dev)
         fp.done = torch.zeros(1, dtype=torch.int32, device=dev)
         _lib.call('mrefsr_weights_checksum', _p(fp.row), 1, _p(fp.sum), _p(fp.done), None, None, 0, _stream())
         self.dirty = True
-        return hit.packed
+
+    def get_fold(self, w3x3, b3x3, w1x1, b1x1, cin_offset, terms):
+        """(packed W', b') of a 1x1 convolution (columns cin_offset.. of ``w1x1``) applied behind a 3x3 one: conv_compose_1x1_3x3 of
+        the four parameters (either bias may be None), W' packed with ``terms`` -- a DERIVED entry, keyed by its sources and good
+        while every source's param_stamp() stands.  All sources, the biases too, are fingerprinted for verify(): none of them
+        need have a packed copy of its own.  A source that already carries a fingerprint of its current stamp keeps it (the older
+        reference is the stricter one: a ``.data`` write since then still reads as a mismatch)."""
+        srcs = (w3x3, b3x3, w1x1, b1x1)
+        key = tuple(0 if s is None else id(s) for s in srcs) + (cin_offset, terms)
+        hit = self.folds.get(key)
+        if hit is not None and all(r is None or param_stamp(r()) == st for r, st in zip(hit.refs, hit.stamps)):
+            return hit.packed, hit.bias
+        if len(self.folds) > 256:   # entries of parameters that no longer exist
+            for k in [k for k, v in self.folds.items() if any(r is not None and r() is None for r in v.refs)]:
+                del self.folds[k]
+        w, b = conv_compose_1x1_3x3(w1x1.detach(), w3x3.detach(), None if b3x3 is None else b3x3.detach(),
+                                    None if b1x1 is None else b1x1.detach(), cin_offset)
+        hit = self.folds[key] = _Fold()
+        hit.refs = tuple(None if s is None else weakref.ref(s) for s in srcs)
+        hit.stamps = tuple(None if s is None else param_stamp(s) for s in srcs)
+        hit.packed, hit.bias = conv_pack_weight(w, terms), b
+        for s, r, st in zip(srcs, hit.refs, hit.stamps):
+            have = None if s is None else self.prints.get(id(s))
+            if s is not None and not (have is not None and have.ref() is s and have.stamp == st):
+                self._fingerprint(s, r, st)
+        return hit.packed, hit.bias
 
     def verify(self, device=None):
         """One launch: fingerprint every parameter with a cached packed copy and raise the stale bit where it differs from the
@@ -956,12 +994,14 @@ class _PackedWeights:
     def clear(self):
         """drop every cached packed weight (and let hipGraph captures notice): call after editing parameters through ``.data``"""
         self.copies.clear()
+        self.folds.clear()
         self.prints, self.order, self.dirty, self.table, self.ref = {}, [], True, None, None
         self.epoch += 1
 
 
 _packed = _PackedWeights()
 packed_weight, verify_packed, packed_stale, invalidate_packed = _packed.get, _packed.verify, _packed.take_stale, _packed.clear
+packed_fold = _packed.get_fold
 
 
 def packed_epoch():
@@ -989,6 +1029,24 @@ def conv_pack_weight(weight, terms=6):
     packed = torch.empty(nbytes, device=weight.device, dtype=torch.uint8)
     _lib.call('mrefsr_conv_pack_weight_f32', _p(weight), _p(packed), co, ci, kh, terms, C.c_float(wscale), _stream())
     return PackedWeight(packed, wscale, terms)
+
+
+def conv_compose_1x1_3x3(w1x1, w3x3, b3x3=None, b1x1=None, cin_offset=0):
+    """The 3x3 convolution that equals ``w3x3`` [Cmid,Cin,3,3] (+ b3x3) followed by the 1x1 convolution with columns
+    cin_offset .. cin_offset + Cmid of ``w1x1`` [Cout,ld(,1,1)] (+ b1x1): -> (W' [Cout,Cin,3,3], b' [Cout] or None when both biases
+    are None).  fp64 sums in a fixed order, rounded once (csrc/conv_fold.hip); W' packs like any weight (conv_pack_weight)."""
+    _chk('conv_compose_1x1_3x3', w1x1, w3x3, b3x3, b1x1)
+    co, ld = w1x1.shape[0], w1x1.shape[1]
+    cm, ci = w3x3.shape[0], w3x3.shape[1]
+    if w1x1.numel() != co * ld or tuple(w3x3.shape[2:]) != (3, 3) or cin_offset < 0 or cin_offset + cm > ld:
+        raise ValueError(f'conv_compose_1x1_3x3: w1x1 {tuple(w1x1.shape)} (columns from {cin_offset}) behind w3x3 {tuple(w3x3.shape)}')
+    if (b3x3 is not None and b3x3.numel() != cm) or (b1x1 is not None and b1x1.numel() != co):
+        raise ValueError('conv_compose_1x1_3x3: bias sizes')
+    out_w = torch.empty((co, ci, 3, 3), device=w3x3.device, dtype=torch.float32)
+    out_b = None if (b3x3 is None and b1x1 is None) else torch.empty(co, device=w3x3.device, dtype=torch.float32)
+    _lib.call('mrefsr_conv_compose_1x1_3x3_f32', _p(w1x1), C.c_int64(ld), cin_offset, _p(w3x3), _p(b3x3), _p(b1x1), _p(out_w), _p(out_b),
+              co, cm, ci, _stream())
+    return out_w, out_b
 
 
 def conv_pack_view(weight, cin_slice=None, terms=6, dgrad=False, wscale=1.0):
@@ -1723,12 +1781,15 @@ def image_to_nhwc4(img, mean=None, std=None, range_norm=False):
     return out
 
 
-def attn_modulate_(refs, mul, add):
-    """mul <- refs * sigmoid(mul) * 2 + add, in place on ``mul`` (all three contiguous, same shape)"""
+def attn_modulate_(refs, mul, add=None):
+    """mul <- refs * sigmoid(mul) * 2 + add, in place on ``mul`` (all three contiguous, same shape); fp32 with ``add`` None: the same
+    without the last add (the addend travels as the `pre` of feat_fusion's launch)"""
     b16 = mul.dtype == torch.bfloat16
     _chk('attn_modulate', refs, mul, add, dtype=mul.dtype if b16 else torch.float32)
-    if refs.shape != mul.shape or add.shape != mul.shape:
+    if refs.shape != mul.shape or (add is not None and add.shape != mul.shape):
         raise ValueError('attn_modulate: shape mismatch')
+    if add is None and b16:
+        raise NotImplementedError('attn_modulate: the bf16 arithmetic keeps its addend (its rounding points are fixed)')
     _lib.call('mrefsr_attn_modulate_bf16' if b16 else 'mrefsr_attn_modulate_f32', _p(refs), _p(mul), _p(add), C.c_int64(mul.numel()), _stream())
     return mul
 
